@@ -17,9 +17,18 @@ N > 1 (torch.distributed.run, one rank per GPU): per-frame fusion does not shard
 independent replicas, each fusing its own map -> weak scaling, value = all frames / max rank time.
 
 Prints ONE JSON line on rank 0.  `roofline` = the integrate kernel of the timed region, timed live with HIP events
-attached to its dispatch packets on the engine stream, plus (`roofline.stress`) the same kernel on the S-stress map
-(V = 262,144 blocks: 2.15 GB per launch, past the 256 MiB Infinity Cache).  `cpu_baseline` = the CPU oracle built
--O3 -march=native on this box, OpenMP over visible blocks / pixels like upstream's CPU engine, warm-up excluded.
+attached to its dispatch packets on the engine stream.
+
+A plain run does only what that line needs: set up, warm up, time --steps steps, write the outputs (--dump-outputs DIR)
+and print.  Everything else it measures moves behind --full: the two other call disciplines (`config.device_resident_fps`,
+`config.synchronous_fps`), the drop-in mirror loop (`config.dropin_mirror`), the sharded re-integration batch
+(`reintegration`, --reint), the integrate kernel on the S-stress map (`roofline.stress`: V = 262,144 blocks, 2.15 GB per
+launch, past the 256 MiB Infinity Cache) and `cpu_baseline` = the CPU oracle built -O3 -march=native on this box, OpenMP
+over visible blocks / pixels like upstream's CPU engine, warm-up excluded.  The --no-* switches thin out a --full run.
+
+--dump-outputs DIR writes what the timed path hands its caller in the last timed step -- the raycast depth image of the
+last frame, float32 [H, W] metres (0 = no hit) -- as DIR/depth.npy.  The frames are closed-form and the same on every
+run, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import gc
@@ -36,6 +45,16 @@ import __graft_entry__ as ge  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s achievable copy rate
 OUT_RING = 3           # page-locked output images in flight
+MAX_FRAMES = 240       # distinct synthetic frames of a run (~0.5 CPU-s each to make); longer runs play them back and forth
+
+
+def frame_of(i, n):
+    """Frame that step i processes when n distinct frames are played forwards, backwards, forwards ... (0 .. n-1, n-2 .. 1,
+    0 ...): the camera never jumps.  Runs of at most n steps (warm-up included) see every frame once, in order."""
+    if n < 2:
+        return 0
+    j = i % (2 * n - 2)
+    return j if j < n else 2 * n - 2 - j
 
 
 def _gen_frame(args):
@@ -185,6 +204,11 @@ def main():
     ap.add_argument("--workload", default="s_street")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the auxiliary measurements: other call disciplines, drop-in mirror, re-integration batch, "
+                         "S-stress roofline, CPU baseline (off: only the headline figure)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's output (raycast depth image) as DIR/depth.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stress", action="store_true", help="skip the S-stress roofline launch (roofline.stress)")
     ap.add_argument("--no-extra-rates", action="store_true", help="skip the device-resident and synchronous loops")
@@ -197,6 +221,8 @@ def main():
     ap.add_argument("--spawn-dry-run", action="store_true",
                     help="with --gpus N: start the N ranks, let each report its rank / world size and exit before it touches a GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args)   # (this process stays off the GPU; the ranks are children with RANK / LOCAL_RANK / WORLD_SIZE set)
@@ -211,13 +237,13 @@ def main():
     from dslam_amd.harness import synth
     wl = getattr(synth, args.workload)(args.width, args.height)
     K, Wm = args.steps, args.warmup
-    nframes = K + Wm
+    nframes = min(K + Wm, MAX_FRAMES)
     # Synthetic frames first, while this process has not touched the GPU: the worker pool forks, and a forked child
     # of a GPU-initialised process is not safe.  Under a profiler that initialises the GPU before the program starts
     # (rocprofv3 --pmc preloads its tool library) there is no such moment, so no pool is used there.
     preloaded = os.environ.get("LD_PRELOAD", "") + os.environ.get("ROCP_TOOL_LIBRARIES", "")
     workers = 1 if "rocprof" in preloaded.lower() else max(1, min(16, (os.cpu_count() or 2) // max(1, world)))
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     frames_all = generate_frames(args.workload, args.width, args.height, max(nframes, CPU_FRAMES) if want_cpu else nframes, workers)
     frames = tuple(x[:nframes] for x in frames_all)
     rgba_h, depth_h, Ms = frames
@@ -247,7 +273,8 @@ def main():
     cdev = torch.device("cpu") if rehearse else torch.device("cuda", local_rank)   # where the small collectives' tensors live
 
     # pools sized so the un-windowed map of the whole run fits (the reference's default 0x40000-block pool fills
-    # after ~320 KITTI keyframes, memory.txt:320); 288 GB of HBM make a 4 GiB pool a non-issue
+    # after ~320 KITTI keyframes, memory.txt:320); 288 GB of HBM make a 4 GiB pool a non-issue.  Frames played again
+    # add no blocks, so the distinct frames set the size
     need_blocks = 9000 + 600 * nframes
     nlb = 0x40000
     while nlb < need_blocks:
@@ -294,18 +321,19 @@ def main():
         eng.set_async(mode != "sync")
 
         def step(i):
+            f = frame_of(i, nframes)
             if mode == "device":
-                eng.view_update_device(view, rgba_d.data_ptr() + i * rgba_stride, depth_d.data_ptr() + i * depth_stride,
+                eng.view_update_device(view, rgba_d.data_ptr() + f * rgba_stride, depth_d.data_ptr() + f * depth_stride,
                                        timestamp=float(i))
-                eng.process_frame(scene, view, rs, Ms[i], wl.intr)
-                eng.get_image(scene, rs_free, Ms[i], wl.intr, pkg.IMAGE_DEPTH, download=False)
+                eng.process_frame(scene, view, rs, Ms[f], wl.intr)
+                eng.get_image(scene, rs_free, Ms[f], wl.intr, pkg.IMAGE_DEPTH, download=False)
                 return
             slot = i % OUT_RING
             if mode == "pipelined":
                 eng.fence_wait(fences[slot])  # image i - OUT_RING has landed (its consumer may take it) before slot is reused
-            eng.view_update(view, rgba_p[i], depth_p[i], timestamp=float(i))
-            eng.process_frame(scene, view, rs, Ms[i], wl.intr)
-            eng.get_image(scene, rs_free, Ms[i], wl.intr, pkg.IMAGE_DEPTH, out=image_p[slot])
+            eng.view_update(view, rgba_p[f], depth_p[f], timestamp=float(i))
+            eng.process_frame(scene, view, rs, Ms[f], wl.intr)
+            eng.get_image(scene, rs_free, Ms[f], wl.intr, pkg.IMAGE_DEPTH, out=image_p[slot])
             if mode == "pipelined":
                 eng.fence_record(fences[slot])
 
@@ -348,8 +376,11 @@ def main():
     eng.set_async(False)
     st = eng.stats(scene, rs)
     last_image = np.array(image_p[(Wm + K - 1) % OUT_RING]) if args.mode != "device" else \
-        eng.get_image(scene, rs_free, Ms[Wm + K - 1], wl.intr, pkg.IMAGE_DEPTH)
+        eng.get_image(scene, rs_free, Ms[frame_of(Wm + K - 1, nframes)], wl.intr, pkg.IMAGE_DEPTH)
     hits = int((last_image > 0).sum())
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "depth.npy"), np.ascontiguousarray(last_image, dtype=np.float32))
     eng.set_async(args.mode != "sync")
 
     # ---- sharded global re-integration (BASELINE configs[4]): de-integrate + re-integrate the last
@@ -359,12 +390,12 @@ def main():
     #   stored_lists      the same loop, de-integrating from each keyframe's stored visible list (no allocation pass at the old pose)
     #   block_major       dslam_reintegrate_batch: allocation passes first, then every touched block loaded once (the headline)
     reint_out = None
-    if args.reint > 0:
+    if args.full and args.reint > 0:
         try:
             import zlib
             from dslam_amd.harness import reintegrate as reint
             Kre = min(args.reint, K)
-            ids = list(range(Wm + K - Kre, Wm + K))
+            ids = [frame_of(i, nframes) for i in range(Wm + K - Kre, Wm + K)]   # (frame indices)
             new_poses = []
             for n_, i in enumerate(ids):  # a smooth loop-closure correction: small rotation + translation drift
                 T_new = wl.pose(i) @ synth.pose_matrix(synth.look_rotation(0.002 * (n_ + 1), 0.0), [0.01 * (n_ + 1), 0.0, 0.02])
@@ -464,8 +495,9 @@ def main():
                     rs_ref = eng.create_render_state(scene_ref, wl.W, wl.H)
                     eng.set_async(False)
                     for i in range(Wm + K):
-                        eng.view_update_device(view_ref, rgba_d.data_ptr() + i * rgba_stride, depth_d.data_ptr() + i * depth_stride, timestamp=float(i))
-                        eng.process_frame(scene_ref, view_ref, rs_ref, Ms[i], wl.intr)
+                        f = frame_of(i, nframes)
+                        eng.view_update_device(view_ref, rgba_d.data_ptr() + f * rgba_stride, depth_d.data_ptr() + f * depth_stride, timestamp=float(i))
+                        eng.process_frame(scene_ref, view_ref, rs_ref, Ms[f], wl.intr)
                     eng.set_async(args.mode != "sync")
                     saved = barrier
                     barrier = lambda: (eng.synchronize(), torch.cuda.synchronize())  # noqa: E731  (rank-local leg: no collective)
@@ -480,7 +512,7 @@ def main():
 
     # ---- the same frames at the two other call disciplines (rank-local; not `value`)
     extra = {}
-    if not args.no_extra_rates:
+    if args.full and not args.no_extra_rates:
         for mode, key in (("device", "device_resident_fps"), ("sync", "synchronous_fps"), ("pipelined", "pipelined_fps")):
             if mode == args.mode:
                 continue
@@ -494,7 +526,7 @@ def main():
 
     # ---- the same step through the drop-in: the C++ ITMLib mirror driven by the native driver harness (rank 0, N = 1 only)
     mirror_out = None
-    if rank == 0 and world == 1 and not args.no_extra_rates:
+    if args.full and rank == 0 and world == 1 and not args.no_extra_rates:
         try:
             from dslam_amd.harness import mirror_bench
             eng.synchronize()
@@ -511,7 +543,7 @@ def main():
 
     # ---- S-stress: the integrate kernel with every block of a 1 GiB pool visible (rank 0, N = 1 only)
     stress_out = None
-    if rank == 0 and world == 1 and not args.no_stress:
+    if args.full and rank == 0 and world == 1 and not args.no_stress:
         try:
             from dslam_amd.harness import stress
             eng.set_async(False)
@@ -565,6 +597,7 @@ def main():
                        "calls": calls,
                        "parallelism": "replicas" if world > 1 else "single GPU",
                        "voxel_block_pool": nlb,
+                       "distinct_frames": nframes,
                        "visible_blocks_per_frame": blocks / max(1, launches),
                        "allocated_blocks_end": nlb - 1 - st["last_free_block_id"],
                        "raycast_hits_last_frame": hits},
@@ -586,7 +619,7 @@ def main():
                 out["roofline"]["stress_no_push"] = stress_no_push
         if reint_out is not None:
             out["reintegration"] = reint_out
-        if not args.no_cpu_baseline and world == 1:
+        if want_cpu:
             out["cpu_baseline"] = cpu_baseline(pkg, wl, params, frames_all)
             out["cpu_baseline"]["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
         print(json.dumps(out), flush=True)

@@ -1,14 +1,16 @@
 # dispatch-by-dispatch timeline of one dslam_reintegrate_batch call (bench.py's re-integration leg under rocprofv3 --kernel-trace)
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/../.." && pwd)
+export OUT=${PROFILE_RAW:-$R/profiles/raw}
+mkdir -p $OUT
 cd /tmp
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $R/gpurun_out/batch_tl -- python3 $R/bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-stress --no-extra-rates --mode device > $R/gpurun_out/batch_tl.log 2>&1; echo rc=$?
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/batch_tl -- python3 $R/bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-stress --no-extra-rates --mode device > $OUT/batch_tl.log 2>&1; echo rc=$?
 cd $R
 python - <<'P'
-import csv, glob
-f = glob.glob('gpurun_out/batch_tl/**/*kernel_trace.csv', recursive=True)[0]
+import csv, glob, os
+f = glob.glob(os.environ['OUT'] + '/batch_tl/**/*kernel_trace.csv', recursive=True)[0]
 rows = [(int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'].split('(')[0][-40:]) for r in csv.DictReader(open(f))]
-m = glob.glob('gpurun_out/batch_tl/**/*memory_copy_trace.csv', recursive=True)
+m = glob.glob(os.environ['OUT'] + '/batch_tl/**/*memory_copy_trace.csv', recursive=True)
 if m:
     for r in csv.DictReader(open(m[0])):
         rows.append((int(r['Start_Timestamp']), int(r['End_Timestamp']), 'COPY ' + r.get('Direction', '')))

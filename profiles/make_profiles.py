@@ -1,17 +1,17 @@
 #!/usr/bin/env python3
-"""Turn the raw outputs of profiles/collect_profiles.sh (run on the GPU box, merged back under gpurun_out/) into the
-per-round files of this directory.  Usage: python profiles/make_profiles.py r03
+"""Turn the raw outputs of profiles/collect_profiles.sh (run on the GPU box; raw outputs under $PROFILE_RAW, default
+profiles/raw/) into the per-round files of this directory.  Usage: python profiles/make_profiles.py r03
 
-gpurun_out/final_bench.json              <- python bench.py                      (the driver's command)
-gpurun_out/final_bench_sync.json         <- python bench.py --mode sync ...
-gpurun_out/final_stats[_device]/         <- rocprofv3 --kernel-trace --stats ... bench.py [--mode device]
-gpurun_out/final_fetch|final_write/      <- rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace ... bench.py --mode device
-gpurun_out/final_sq/                     <- rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY
-                                            SQ_ACTIVE_INST_VALU SQ_INSTS_SALU --kernel-trace ... bench.py --mode device
-gpurun_out/final_integrate_waves.bin     <- DSLAM_DBG_INTEGRATE dump of k_integrate (per wave: 12 timestamps, clocks, placement)
-gpurun_out/final_wavetime.bin            <- DSLAM_DBG_WAVETIME dump of k_render (per wave: cycles, march length, ...)
-gpurun_out/final_sweep.bin               <- DSLAM_DBG_SWEEP dump of k_alloc_sweep (per tile: 8 timestamps)
-gpurun_out/final_{stress,pipeline,side_bench,quality,maintenance,shard_emulation}.json
+final_bench.json              <- python bench.py --full                     (the headline and the auxiliary legs)
+final_bench_sync.json         <- python bench.py --mode sync ...
+final_stats[_device]/         <- rocprofv3 --kernel-trace --stats ... bench.py [--mode device]
+final_fetch|final_write/      <- rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace ... bench.py --mode device
+final_sq/                     <- rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY
+                                 SQ_ACTIVE_INST_VALU SQ_INSTS_SALU --kernel-trace ... bench.py --mode device
+final_integrate_waves.bin     <- DSLAM_DBG_INTEGRATE dump of k_integrate (per wave: 12 timestamps, clocks, placement)
+final_wavetime.bin            <- DSLAM_DBG_WAVETIME dump of k_render (per wave: cycles, march length, ...)
+final_sweep.bin               <- DSLAM_DBG_SWEEP dump of k_alloc_sweep (per tile: 8 timestamps)
+final_{stress,pipeline,side_bench,quality,maintenance,shard_emulation}.json
 """
 import csv
 import glob
@@ -24,7 +24,7 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "gpurun_out")
+OUT = os.environ.get("PROFILE_RAW", os.path.join(ROOT, "profiles", "raw"))
 HERE = os.path.join(ROOT, "profiles")
 
 
@@ -32,7 +32,7 @@ def newest(pattern, required=True):
     files = sorted(glob.glob(os.path.join(OUT, pattern)), key=os.path.getmtime)
     if not files:
         if required:
-            sys.exit(f"missing {pattern} under gpurun_out/")
+            sys.exit(f"missing {pattern} under {OUT}")
         return None
     return files[-1]
 
@@ -209,7 +209,7 @@ def main():
                 acc[k][r["Counter_Name"]] += float(r["Counter_Value"])
                 disp[k].add(r["Dispatch_Id"])
         out = {"command": "rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_SALU "
-                          "--kernel-trace -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-stress --no-extra-rates --mode device "
+                          "--kernel-trace -- python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-stress --no-extra-rates --mode device "
                           "(the re-integration leg: 32 keyframes of the 110-keyframe map)", "kernels": {}}
         for k, c in acc.items():
             n = len(disp[k])

@@ -25,6 +25,9 @@ def test_library_is_built_and_exports_every_declared_symbol(pkg):
 
 
 def test_library_loads_and_reports_version(pkg):
+    # bind the library to the HIP runtime open_engine() uses (torch's), as open_engine() does: a library first bound to
+    # another libamdhip64 stays bound to it for the rest of the process, and the GPU tests after this one find no device
+    pkg._share_torch_hip_runtime()
     lib = ctypes.CDLL(pkg.LIB_PATH)
     lib.dslam_version.restype = ctypes.c_char_p
     assert b"gfx950" in lib.dslam_version()

@@ -43,7 +43,7 @@ def test_bench_runs_with_two_ranks_sharing_the_gpu():
     import json
     env = dict(os.environ, DSLAM_BENCH_REHEARSE="1")
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4",
-                        "--no-stress", "--no-extra-rates", "--no-cpu-baseline", "--reint", "8"], env=env, capture_output=True, text=True,
+                        "--full", "--no-stress", "--no-extra-rates", "--no-cpu-baseline", "--reint", "8"], env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
