@@ -1,0 +1,512 @@
+"""Float64 references of the hot-path operations, written from SURVEY.md Appendix A and upstream InfiniTAM v2 semantics.
+
+Vectorised numpy, no compiled code.  The rule every function follows:
+  * a threshold predicate (an image bound, a nearest-pixel rounding, the depth cut eta >= -mu, the colour gate, the
+    weight law's rounding, the bounding-box floor / ceil) is evaluated with the spec's float32 expression in the spec's
+    operation order, element-wise in np.float32 (numpy never fuses a multiply-add), so it takes the same branch as a
+    correct float32 kernel;
+  * the values themselves (sdf, colour, positions, depths) are computed in float64.
+Where the float32 and float64 forms of a predicate disagree, the element is a "tie" and is reported: a kernel that
+reordered or contracted that expression could take the other branch there.
+
+The ray march is the exception to the first rule: its predicates (nearest-voxel rounding, the [-0.5, 0.1]
+interpolation window, sdf <= 0, len < lenMax) act on march positions that float32 and float64 reach by different
+rounding, so `cast_rays` evaluates them in float64 and flags every ray that passed within `tie_tol` of one of them.
+"""
+import numpy as np
+
+F = np.float32
+FAR_AWAY, VERY_CLOSE = F(999999.9), F(0.05)
+MEAN_SIGMA_L = 1.2232
+
+
+def mat_vec_f32(M, p):
+    """ORUtils Matrix4f * Vector4f(p, 1) in float32: row r = ((m_r0 x + m_r1 y) + m_r2 z) + m_r3 (no FMA)."""
+    M = np.asarray(M, F)
+    x, y, z = (p[..., k].astype(F) for k in range(3))
+    return np.stack([((M[r, 0] * x + M[r, 1] * y) + M[r, 2] * z) + M[r, 3] for r in range(3)], -1)
+
+
+def mat_vec_f64(M, p):
+    M = np.asarray(M, np.float64)
+    return p @ M[:3, :3].T + M[:3, 3]
+
+
+def project_f32(intr, pc):
+    """u = fx * x / z + cx, v = fy * y / z + cy, float32 in that order."""
+    fx, fy, cx, cy = (F(v) for v in intr)
+    return (fx * pc[..., 0]) / pc[..., 2] + cx, (fy * pc[..., 1]) / pc[..., 2] + cy
+
+
+def project_f64(intr, pc):
+    fx, fy, cx, cy = (float(F(v)) for v in intr)
+    return fx * pc[..., 0] / pc[..., 2] + cx, fy * pc[..., 1] / pc[..., 2] + cy
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# A.3 depth conversion and UpdateView's bilateral filter
+# ---------------------------------------------------------------------------------------------------------------------
+def depth_to_float(mm, a=1.0 / 1000.0, b=0.0):
+    mm = np.asarray(mm, np.int64)
+    return np.where((mm <= 0) | (mm > 32000), -1.0, mm * float(F(a)) + float(F(b)))
+
+
+def filter_depth_pass(src, dst):
+    """Upstream filterDepth over the interior [2, W-3] x [2, H-3] of `dst` (its border is left as it is): a hole
+    (z < 0) stays -1; otherwise the 5x5 weighted mean of the non-negative taps, weight
+    exp(-0.5 ((|i| + |j|) sigma_L^2 + (z' - z)^2 sigma_z^2)), sigma_z = 1 / (0.0012 + 0.0019 (z - 0.4)^2 + 0.0001 / sqrt(z) / 4)."""
+    H, W = src.shape
+    z = src[2:H - 2, 2:W - 2]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sz = 1.0 / (0.0012 + 0.0019 * (z - 0.4) ** 2 + 0.0001 / np.sqrt(z) * 0.25)
+    num = np.zeros_like(z)
+    den = np.zeros_like(z)
+    for i in range(-2, 3):
+        for j in range(-2, 3):
+            t = src[2 + i:H - 2 + i, 2 + j:W - 2 + j]
+            w = np.exp(-0.5 * ((abs(i) + abs(j)) * MEAN_SIGMA_L ** 2 + (t - z) ** 2 * sz ** 2))
+            w = np.where(t < 0.0, 0.0, w)
+            num += w * np.where(t < 0.0, 0.0, t)
+            den += w
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dst[2:H - 2, 2:W - 2] = np.where(z < 0.0, -1.0, num / den)
+
+
+def bilateral_update_view(depth):
+    """ITMViewBuilder::UpdateView with filtering on: five passes alternating between the depth image and floatImage,
+    a zero-initialised image whose border is never written; the result is floatImage (zero border)."""
+    a = np.array(depth, np.float64)
+    b = np.zeros_like(a)
+    filter_depth_pass(a, b)
+    filter_depth_pass(b, a)
+    filter_depth_pass(a, b)
+    filter_depth_pass(b, a)
+    filter_depth_pass(a, b)
+    return b
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# A.5 / A.11 voxel update and de-integration
+# ---------------------------------------------------------------------------------------------------------------------
+LOCAL = np.stack(np.meshgrid(np.arange(8), np.arange(8), np.arange(8), indexing="ij"), -1)[..., ::-1].reshape(512, 3)
+
+
+def round_half_away_f32(x):
+    """roundf on float32 values (exact: the float64 of a float32 plus 0.5 is exact)."""
+    x = x.astype(np.float64)
+    return np.sign(x) * np.floor(np.abs(x) + 0.5)
+
+
+def new_weight(d32, wp):
+    """SURVEY A.11 WeightParams law: depthWeighting ? max(1, (int)roundf(maxNewW (1 - min(d, maxD) / maxD))) : 1."""
+    if wp is None or not wp[0]:
+        return np.ones(d32.shape, np.int64)
+    max_new_w, maxd = F(wp[1]), F(wp[2])
+    dd = np.minimum(d32, maxd)
+    w = round_half_away_f32(max_new_w * (F(1) - dd / maxd)).astype(np.int64)
+    return np.clip(w, 1, int(wp[1]))
+
+
+def bilinear_rgb(rgba, u32, v32, u64, v64):
+    """Bilinear RGB at (u, v): the 2x2 neighbourhood comes from floor of the float32 position, the weights from the
+    float64 one."""
+    W = rgba.shape[1]
+    ix, iy = np.floor(u32).astype(np.int64), np.floor(v32).astype(np.int64)
+    dx, dy = u64 - ix, v64 - iy
+    flat = rgba.reshape(-1, 4)[:, :3].astype(np.float64)
+    a, b = flat[ix + iy * W], flat[ix + 1 + iy * W]
+    c, d = flat[ix + (iy + 1) * W], flat[ix + 1 + (iy + 1) * W]
+    return (a * ((1 - dx) * (1 - dy))[:, None] + b * (dx * (1 - dy))[:, None] + c * ((1 - dx) * dy)[:, None]
+            + d * (dx * dy)[:, None])
+
+
+def integrate(vox, block_pos, depth, rgba, M_d, intr, vs, mu, max_w, M_rgb=None, intr_rgb=None, stop_at_max=False,
+              wp=None, deintegrate=False):
+    """The voxel update of A.5 (or the de-integration of A.11) applied to the blocks `vox` [n, 512] at block
+    positions [n, 3].  `depth` is the view's float32 depth image, `rgba` [H, W, 4].  Returns (new voxels, tie count)."""
+    M_rgb = M_d if M_rgb is None else M_rgb
+    intr_rgb = intr if intr_rgb is None else intr_rgb
+    out = vox.copy()
+    n = len(block_pos)
+    if n == 0:
+        return out, 0
+    Hd, Wd = depth.shape
+    Hr, Wr = rgba.shape[:2]
+    vi = (np.asarray(block_pos, np.int64)[:, None, :] * 8 + LOCAL[None]).reshape(-1, 3)
+    v = out.reshape(-1)
+    pm32 = vi.astype(F) * F(vs)
+    pm64 = vi * float(F(vs))
+    mu32, mu64 = F(mu), float(F(mu))
+    upd = np.ones(len(vi), bool)
+    if stop_at_max and not deintegrate:
+        upd &= v["w_depth"] != max_w
+    # -- depth -----------------------------------------------------------------------------------------------------
+    pc32, pc64 = mat_vec_f32(M_d, pm32), mat_vec_f64(M_d, pm64)
+    ok = pc32[:, 2] > 0
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        u32, w32 = project_f32(intr, pc32)
+        u64, w64 = project_f64(intr, pc64)
+    ok &= (u32 >= 1) & (u32 <= F(Wd - 2)) & (w32 >= 1) & (w32 <= F(Hd - 2))
+    ok64 = (pc64[:, 2] > 0) & (u64 >= 1) & (u64 <= Wd - 2) & (w64 >= 1) & (w64 <= Hd - 2)
+    ties = ok != ok64
+    ui, wi = np.zeros(len(vi), np.int64), np.zeros(len(vi), np.int64)
+    ui[ok] = (u32[ok] + F(0.5)).astype(np.int64)
+    wi[ok] = (w32[ok] + F(0.5)).astype(np.int64)
+    both = ok & ok64
+    ties |= both & (((u64 + 0.5).astype(np.int64) != ui) | ((w64 + 0.5).astype(np.int64) != wi))
+    dm32 = np.where(ok, depth.reshape(-1)[ui + wi * Wd], F(-1))
+    ok &= dm32 > 0
+    eta32 = dm32 - pc32[:, 2]
+    eta64 = dm32.astype(np.float64) - pc64[:, 2]
+    ties |= ok & ((eta32 < -mu32) != (eta64 < -mu64))
+    ok &= eta32 >= -mu32
+    ok &= upd
+    oldF = v["sdf"].astype(np.float64) / 32767.0
+    oldW = v["w_depth"].astype(np.int64)
+    newF = np.minimum(1.0, eta64 / mu64)
+    newW = new_weight(dm32, wp)
+    if not deintegrate:
+        Wsum = oldW + newW
+        Fn = (oldW * oldF + newW * newF) / Wsum
+        sdf = np.trunc(Fn * 32767.0)
+        v["sdf"] = np.where(ok, sdf, v["sdf"]).astype(np.int16)
+        v["w_depth"] = np.where(ok, np.minimum(Wsum, max_w), oldW).astype(np.uint8)
+    else:
+        rem = oldW - newW
+        d_ok = ok & (rem >= 0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            Fn = np.clip((oldW * oldF - newW * newF) / rem, -1.0, 1.0)
+        sdf = np.where(rem == 0, 32767, np.trunc(Fn * 32767.0))
+        v["sdf"] = np.where(d_ok, sdf, v["sdf"]).astype(np.int16)
+        v["w_depth"] = np.where(d_ok, rem, oldW).astype(np.uint8)
+    # -- colour: only where the depth measurement was taken, and only close to the surface --------------------------
+    with np.errstate(divide="ignore", invalid="ignore"):
+        gate32 = (eta32 > mu32) | (np.abs(eta32 / mu32) > F(0.25))
+        gate64 = (eta64 > mu64) | (np.abs(eta64 / mu64) > 0.25)
+    ties |= ok & (gate32 != gate64)
+    c_ok = ok & ~gate32
+    pr32, pr64 = mat_vec_f32(M_rgb, pm32), mat_vec_f64(M_rgb, pm64)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        ru32, rw32 = project_f32(intr_rgb, pr32)
+        ru64, rw64 = project_f64(intr_rgb, pr64)
+    inb32 = (ru32 >= 1) & (ru32 <= F(Wr - 2)) & (rw32 >= 1) & (rw32 <= F(Hr - 2))
+    inb64 = (ru64 >= 1) & (ru64 <= Wr - 2) & (rw64 >= 1) & (rw64 <= Hr - 2)
+    ties |= c_ok & (inb32 != inb64)
+    c_ok &= inb32
+    idx = np.nonzero(c_ok)[0]
+    if len(idx):
+        c = bilinear_rgb(rgba, ru32[idx], rw32[idx], ru64[idx], rw64[idx]) / 255.0
+        oldC = v["clr"][idx].astype(np.float64) / 255.0
+        oWc = v["w_color"][idx].astype(np.float64)[:, None]
+        if not deintegrate:
+            C = (oldC * oWc + c) / (oWc + 1.0)
+            v["clr"][idx] = np.trunc(C * 255.0).astype(np.uint8)
+            v["w_color"][idx] = np.minimum(oWc[:, 0] + 1, max_w).astype(np.uint8)
+        else:
+            has = oWc[:, 0] >= 1
+            rem = oWc - 1.0
+            with np.errstate(divide="ignore", invalid="ignore"):
+                C = np.clip((oldC * oWc - c) / rem, 0.0, 1.0)
+            newc = np.where(rem == 0, 0, np.trunc(C * 255.0))
+            sel = idx[has]
+            v["clr"][sel] = newc[has].astype(np.uint8)
+            v["w_color"][sel] = rem[has, 0].astype(np.uint8)
+    return out, int(ties.sum())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# A.2 / A.7 reads, castRay, the shading normal
+# ---------------------------------------------------------------------------------------------------------------------
+def read_trilinear(m, p):
+    """A.7 read_trilinear at voxel-unit positions p [n, 3]: the 8 corner shorts (missing = 32767), lerped in x, then
+    y, then z, / 32767.  Also returns whether any corner was missing."""
+    p0 = np.floor(p)
+    c = p - p0
+    p0 = p0.astype(np.int64)
+    acc = np.zeros(len(p))
+    miss = np.zeros(len(p), bool)
+    for dz in (0, 1):
+        for dy in (0, 1):
+            for dx in (0, 1):
+                s, _, f = m.lookup(p0 + np.array([dx, dy, dz]))
+                w = (c[:, 0] if dx else 1 - c[:, 0]) * (c[:, 1] if dy else 1 - c[:, 1]) * (c[:, 2] if dz else 1 - c[:, 2])
+                acc += w * s
+                miss |= ~f
+    return acc / 32767.0, miss
+
+
+def read_colour_trilinear(m, p):
+    p0 = np.floor(p)
+    c = p - p0
+    p0 = p0.astype(np.int64)
+    acc = np.zeros((len(p), 3))
+    for dz in (0, 1):
+        for dy in (0, 1):
+            for dx in (0, 1):
+                _, clr, _ = m.lookup(p0 + np.array([dx, dy, dz]))
+                w = (c[:, 0] if dx else 1 - c[:, 0]) * (c[:, 1] if dy else 1 - c[:, 1]) * (c[:, 2] if dz else 1 - c[:, 2])
+                acc += w[:, None] * clr
+    return acc
+
+
+def sdf_normal(m, p):
+    """computeSingleNormalFromSDF: per axis, the trilinear field one voxel ahead minus one voxel behind (the 6 taps,
+    each a trilinear read of 8 corners); normalised.  Also returns whether any tap touched a missing voxel."""
+    g = np.zeros((len(p), 3))
+    miss = np.zeros(len(p), bool)
+    for k in range(3):
+        e = np.zeros(3)
+        e[k] = 1.0
+        a, ma = read_trilinear(m, p + e)
+        b, mb = read_trilinear(m, p - e)
+        g[:, k] = a - b
+        miss |= ma | mb
+    with np.errstate(invalid="ignore", divide="ignore"):  # (no gradient away from the surface: NaN there)
+        return g / np.linalg.norm(g, axis=1, keepdims=True), miss
+
+
+def light_of(M):
+    """The shading light direction: minus the camera's z axis in world coordinates (-invM.getColumn(2))."""
+    return -np.linalg.inv(np.asarray(M, np.float64))[:3, 2]
+
+
+def shaded_grey(angle):
+    """drawPixelGrey: (uchar)((0.8 angle + 0.2) * 255)."""
+    return np.trunc((0.8 * angle + 0.2) * 255.0)
+
+
+def normal_colour(n):
+    """drawPixelNormal (upstream InfiniTAM v2, ITMVisualisationEngine_Shared.h): (uchar)((0.3 + (1 - n) * 0.35) * 255)
+    per channel.  SURVEY A.7's shorthand ((n + 1) / 2) * 255 is not what upstream draws; DESIGN.md 4c records this."""
+    return np.trunc((0.3 + (1.0 - n) * 0.35) * 255.0)
+
+
+def icp_normals(p, hit, tie, vs, light):
+    """processPixelICP<true, false>'s normal from the raycast points p [H, W, 3] (voxel units) and hits [H, W]:
+    pixels within 3 of the image border get none; otherwise the points +-2 pixels away in x and y, unless one of them
+    is no hit or the longer of the two differences exceeds 0.15 m, in which case the points +-1 away, which must all
+    be hits.  n = -(dx x dy), normalised; kept where n . light > 0.  Returns (normals [H, W, 3], found [H, W], tap
+    distance [H, W] (2 or 1), tie [H, W]): tie where a tap pixel is a tie ray or the 0.15 m switch, the
+    angle > 0 cut or a tap's hit depended on a near-threshold value."""
+    H, W = hit.shape
+    n = np.zeros((H, W, 3))
+    found = hit.copy()
+    found[:3] = found[-3:] = False
+    found[:, :3] = found[:, -3:] = False
+    tap = np.full((H, W), 2)
+    t_out = tie.copy()
+
+    def sh(a, dy, dx):  # a[y + dy, x + dx] (wrapping; only used away from the border)
+        return np.roll(a, (-dy, -dx), axis=(0, 1))
+
+    h2 = sh(hit, 0, 2) & sh(hit, 0, -2) & sh(hit, 2, 0) & sh(hit, -2, 0)
+    dx2, dy2 = sh(p, 0, 2) - sh(p, 0, -2), sh(p, 2, 0) - sh(p, -2, 0)
+    ld = np.maximum((dx2 ** 2).sum(-1), (dy2 ** 2).sum(-1)) * vs * vs
+    plus1 = ~h2 | (ld > 0.15 ** 2)
+    t_out |= h2 & (np.abs(ld - 0.15 ** 2) < 1e-6 * 0.15 ** 2)
+    dx1, dy1 = sh(p, 0, 1) - sh(p, 0, -1), sh(p, 1, 0) - sh(p, -1, 0)
+    h1 = sh(hit, 0, 1) & sh(hit, 0, -1) & sh(hit, 1, 0) & sh(hit, -1, 0)
+    found &= ~plus1 | h1
+    tap[plus1] = 1
+    dx = np.where(plus1[..., None], dx1, dx2)
+    dy = np.where(plus1[..., None], dy1, dy2)
+    for dy_, dx_ in ((0, 1), (0, 2), (1, 0), (2, 0), (0, -1), (0, -2), (-1, 0), (-2, 0)):
+        t_out |= sh(tie, dy_, dx_)
+    c = -np.cross(dx, dy)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        c = c / np.linalg.norm(c, axis=-1, keepdims=True)
+    angle = c @ light
+    t_out |= found & (np.abs(angle) < 1e-6)
+    found &= angle > 0
+    n[found] = c[found]
+    return n, found, tap, t_out
+
+
+def visible_blocks(m, M, intr, W, H):
+    """A.6 on every block of the map (no swapping): any of the 8 corners with z >= 1e-10 inside [0, W) x [0, H)."""
+    fac = F(8) * F(m.vs)
+    vis = np.zeros(len(m.block_pos), bool)
+    for dx in (0, 1):
+        for dy in (0, 1):
+            for dz in (0, 1):
+                c = m.block_pos.astype(F) * fac + np.array([dx, dy, dz], F) * fac
+                pc = mat_vec_f32(M, c)
+                with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                    u, v = project_f32(intr, pc)
+                vis |= (pc[:, 2] >= F(1e-10)) & (u >= 0) & (u < W) & (v >= 0) & (v < H)
+    return vis
+
+
+def expected_depths(m, M, intr, W, H):
+    """A.7 CreateExpectedDepths on the visible blocks: per 8x8 tile the (min, max) camera z of the blocks whose
+    projected corner bbox covers it.  Returns [ceil(H/8), ceil(W/8), 2]; no block = (FAR_AWAY, VERY_CLOSE)."""
+    tw, th = -(-W // 8), -(-H // 8)
+    rng = np.empty((th, tw, 2))
+    rng[..., 0], rng[..., 1] = FAR_AWAY, VERY_CLOSE
+    bp = m.block_pos[visible_blocks(m, M, intr, W, H)]
+    if len(bp) == 0:
+        return rng
+    fac = F(8) * F(m.vs)
+    zs, us, vs_, goods = [], [], [], []
+    for corner in range(8):
+        d = np.array([corner & 1, (corner >> 1) & 1, (corner >> 2) & 1])
+        c32 = (bp + d).astype(F) * fac
+        pc = mat_vec_f32(M, c32)
+        good = pc[:, 2] >= F(1e-6)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            u, v = project_f32(intr, pc)
+        zs.append(mat_vec_f64(M, (bp + d) * float(fac))[:, 2])
+        us.append(u / F(8))
+        vs_.append(v / F(8))
+        goods.append(good)
+    z, u, v, g = (np.stack(a, 1) for a in (zs, us, vs_, goods))
+    with np.errstate(invalid="ignore"):
+        ulx = np.minimum(W // 8, np.where(g, np.floor(u), np.inf).min(1))
+        uly = np.minimum(H // 8, np.where(g, np.floor(v), np.inf).min(1))
+        lrx = np.maximum(-1, np.where(g, np.ceil(u), -np.inf).max(1))
+        lry = np.maximum(-1, np.where(g, np.ceil(v), -np.inf).max(1))
+    zmin = np.where(g, z, np.inf).min(1)
+    zmax = np.where(g, z, -np.inf).max(1)
+    ulx, uly = np.maximum(ulx, 0), np.maximum(uly, 0)
+    lrx, lry = np.minimum(lrx, W - 1), np.minimum(lry, H - 1)
+    ok = (ulx <= lrx) & (uly <= lry) & (zmax >= float(VERY_CLOSE))
+    zmin = np.maximum(zmin, float(VERY_CLOSE))
+    for i in np.nonzero(ok)[0]:
+        x0, x1 = int(ulx[i]), min(int(lrx[i]), tw - 1)
+        y0, y1 = int(uly[i]), min(int(lry[i]), th - 1)
+        if x0 > x1 or y0 > y1:
+            continue
+        t = rng[y0:y1 + 1, x0:x1 + 1]
+        t[..., 0] = np.minimum(t[..., 0], zmin[i])
+        t[..., 1] = np.maximum(t[..., 1], zmax[i])
+    return rng
+
+
+def _iround(x):
+    """(int)((x < 0) ? x - 0.5 : x + 0.5)"""
+    return np.trunc(np.where(x < 0, x - 0.5, x + 0.5)).astype(np.int64)
+
+
+def cast_rays(m, M, intr, W, H, tie_tol=1e-4, max_steps=4000):
+    """A.7 castRay for every pixel on map `m`.  Returns dict(p [H, W, 3] hit position in voxel units (world), hit
+    [H, W], tie [H, W], miss_cell [H, W]: a read at the stop point or after either refinement touched a missing voxel, dir: the unit ray,
+    p_stop / sdf_stop: where the march stopped and the read that stopped it, before the two refinement steps)."""
+    vs, mu = float(F(m.vs)), float(F(m.mu))
+    rng = expected_depths(m, M, intr, W, H)
+    fx, fy, cx, cy = (float(F(v)) for v in intr)
+    ys, xs = np.mgrid[0:H, 0:W]
+    xs, ys = xs.reshape(-1).astype(np.float64), ys.reshape(-1).astype(np.float64)
+    r = rng[(ys // 8).astype(int), (xs // 8).astype(int)]
+    invM = np.linalg.inv(np.asarray(M, np.float64))
+
+    def at(z):
+        pc = np.stack([z * ((xs - cx) / fx), z * ((ys - cy) / fy), z], -1)
+        return np.linalg.norm(pc, axis=1) / vs, mat_vec_f64(invM, pc) / vs
+
+    total, ps = at(r[:, 0])
+    total_max, pe = at(r[:, 1])
+    d = pe - ps
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d = d / np.linalg.norm(d, axis=1, keepdims=True)
+    step_scale = mu / vs
+    n = len(xs)
+    p = ps.copy()
+    sdf = np.ones(n)
+    hit = np.zeros(n, bool)
+    tie = np.zeros(n, bool)
+    active = total < total_max
+    tie |= np.abs(total - total_max) < tie_tol
+    for _ in range(max_steps):
+        idx = np.nonzero(active)[0]
+        if len(idx) == 0:
+            break
+        q = p[idx]
+        frac = np.abs(q) - np.floor(np.abs(q))
+        tie[idx] |= np.any(np.abs(frac - 0.5) < tie_tol, axis=1)
+        s16, _, found = m.lookup(_iround(q))
+        s = s16 / 32767.0
+        step = np.full(len(idx), 8.0)
+        win = found & (s <= 0.1) & (s >= -0.5)
+        tie[idx] |= found & ((np.abs(s - 0.1) < tie_tol) | (np.abs(s + 0.5) < tie_tol))
+        if win.any():
+            s[win] = read_trilinear(m, q[win])[0]
+        stop = found & (s <= 0.0)
+        tie[idx] |= found & (np.abs(s) < tie_tol)
+        step[found] = np.maximum(s[found] * step_scale, 1.0)
+        sdf[idx] = s
+        hit[idx[stop]] = True
+        go = idx[~stop]
+        p[go] += step[~stop, None] * d[go]
+        total[go] += step[~stop]
+        active[idx[stop]] = False
+        active[go] = total[go] < total_max[go]
+        tie[go] |= np.abs(total[go] - total_max[go]) < tie_tol
+    else:
+        raise AssertionError("ray march did not terminate")
+    h = np.nonzero(hit)[0]
+    p_stop = p.copy()
+    miss_cell = np.zeros(n, bool)
+    miss_cell[h] = read_trilinear(m, p[h])[1]
+    p[h] += (sdf[h] * step_scale)[:, None] * d[h]
+    s, miss1 = read_trilinear(m, p[h])
+    p[h] += (s * step_scale)[:, None] * d[h]
+    miss_cell[h] |= miss1 | read_trilinear(m, p[h])[1]
+    return dict(p=p.reshape(H, W, 3), hit=hit.reshape(H, W), tie=tie.reshape(H, W), miss_cell=miss_cell.reshape(H, W),
+                dir=d.reshape(H, W, 3), p_stop=p_stop.reshape(H, W, 3),
+                sdf_stop=sdf.reshape(H, W))
+
+
+def camera_depth(M, p_vox, vs):
+    """IMAGE_DEPTH: camera-frame z (metres) of a hit position in voxel units."""
+    return mat_vec_f64(M, p_vox * float(F(vs)))[..., 2]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# marching cubes: the vertex on a cube edge (the case table is csrc/mc_tables.h, validated by test_mc_tables.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def edge_vertex(a, b, v1, v2):
+    """sdfInterp: a + (0 - v1) / (v2 - v1) (b - a), with upstream's early-outs |v1| < 1e-5 -> a, |v2| < 1e-5 -> b,
+    |v1 - v2| < 1e-5 -> a decided on the float32 sdf values."""
+    f1, f2 = v1.astype(F), v2.astype(F)
+    t = np.where(np.abs(F(0) - f1) < F(1e-5), 0.0,
+                 np.where(np.abs(F(0) - f2) < F(1e-5), 1.0,
+                          np.where(np.abs(f1 - f2) < F(1e-5), 0.0, (0.0 - v1) / np.where(v2 == v1, 1.0, v2 - v1))))
+    return a + t[..., None] * (b - a)
+
+
+def mesh(m, corner_offsets, edge_corners, table):
+    """MeshScene on map `m`, in upstream's CPU-engine order: hash entries in index order (those holding a block),
+    their voxels z-major, the table's triangles in order.  A cube is used when its 8 corners are present with
+    sdf != 32767; its case index comes from the corner signs; vertices by `edge_vertex`.  Returns [n, 3, 3] in
+    voxel units."""
+    co = np.asarray(corner_offsets, np.int64)
+    ent = np.nonzero(m.hash["ptr"] >= 0)[0]
+    bpos = m.hash["pos"][ent].astype(np.int64)
+    bases = (bpos[:, None, :] * 8 + LOCAL[None]).reshape(-1, 3)  # LOCAL: x fastest, then y, then z
+    s = np.empty((len(bases), 8), np.int64)
+    ok = np.ones(len(bases), bool)
+    for k in range(8):
+        sk, _, f = m.lookup(bases + co[k])
+        s[:, k] = sk
+        ok &= f & (sk != 32767)
+    bases, s = bases[ok], s[ok]
+    v = s / 32767.0
+    v32 = s.astype(F) / F(32767)
+    cube = ((v32 < 0).astype(np.int64) << np.arange(8)).sum(1)
+    tab = np.full((256, 5, 3), -1, np.int64)
+    cnt = np.zeros(256, np.int64)
+    for c in range(256):
+        row = [e for e in table[c] if e != -1]
+        cnt[c] = len(row) // 3
+        if cnt[c]:
+            tab[c, :cnt[c]] = np.reshape(row, (-1, 3))
+    per = cnt[cube]
+    rep = np.repeat(np.arange(len(cube)), per)
+    slot = np.arange(len(rep)) - np.repeat(np.cumsum(per) - per, per)
+    edges = tab[cube[rep], slot]  # [n, 3]
+    ec = np.asarray(edge_corners, np.int64)
+    ia, ib = ec[edges, 0], ec[edges, 1]
+    b = bases[rep][:, None, :]
+    vr = v[rep]
+    return edge_vertex((b + co[ia]).astype(np.float64), (b + co[ib]).astype(np.float64),
+                       np.take_along_axis(vr, ia, 1), np.take_along_axis(vr, ib, 1))
