@@ -22,6 +22,7 @@ VOXEL_DTYPE = np.dtype(
 
 BLOCK_SIZE3 = 512
 IMAGE_SHADED, IMAGE_COLOUR_FROM_VOLUME, IMAGE_COLOUR_FROM_NORMAL, IMAGE_DEPTH = 0, 1, 2, 3
+MAX_RENDER_MAPS = 64  # DSLAM_MAX_RENDER_MAPS
 
 
 class SceneParams(C.Structure):
@@ -516,6 +517,32 @@ class CApi:
 
     def get_image(self, scene, rs, M, intr, image_type, download=True, out=None):
         return self._image_call("get_image", scene, rs, M, intr, image_type, download, out)
+
+    def get_image_multi(self, scenes, map_poses, rs, M, intr, image_type, download=True, out=None):
+        """dslam_get_image_multi: one raycast over several local maps.  `scenes`: 1 .. MAX_RENDER_MAPS scenes; `map_poses`:
+        one 4x4 world -> map transform per scene (metres, estimatedGlobalPose.GetM()), as a list or an [N, 4, 4] array.
+        Otherwise as get_image."""
+        scenes = list(scenes)
+        T = np.asarray(map_poses, dtype=np.float32)
+        if T.ndim != 3 or T.shape[1:] != (4, 4):
+            raise ValueError("map_poses must be N 4x4 matrices")
+        if len(T) != len(scenes):
+            raise ValueError(f"{len(scenes)} scenes but {len(T)} map poses")
+        n = len(scenes)
+        ptrs = (C.c_void_p * max(n, 1))(*[None if s is None else s.ptr for s in scenes])
+        t_abi = np.ascontiguousarray(np.transpose(T, (0, 2, 1))).reshape(-1) if n else np.zeros(16, np.float32)
+        m, k = self._mi(M, intr)
+        out_rgba = out_f = None
+        if download or out is not None:
+            if image_type == IMAGE_DEPTH:
+                out_f = out if out is not None else np.empty((rs.height, rs.width), dtype=np.float32)
+                assert out_f.dtype == np.float32 and out_f.size == rs.height * rs.width and out_f.flags.c_contiguous
+            else:
+                out_rgba = out if out is not None else np.empty((rs.height, rs.width, 4), dtype=np.uint8)
+                assert out_rgba.dtype == np.uint8 and out_rgba.size == rs.height * rs.width * 4 and out_rgba.flags.c_contiguous
+        self._call("get_image_multi", self._engine, ptrs, _fptr(t_abi), C.c_int(n), rs.ptr, _fptr(m), _fptr(k),
+                   C.c_int(image_type), _vptr(out_rgba), _fptr(out_f))
+        return out_f if image_type == IMAGE_DEPTH else out_rgba
 
     def create_icp_maps(self, scene, rs, M, intr, download=True):
         """trackingController->Prepare.  download=False leaves the maps on the device (all the depth tracker needs)."""

@@ -606,6 +606,7 @@ int dslam_render_state_destroy(dslam_render_state *r) {
   free_dev(r->image_rgba); free_dev(r->image_float); free_dev(r->icp_points); free_dev(r->icp_normals);
   free_dev(r->raycast_image);
   free_dev(r->proj_boxes); free_dev(r->proj_z); free_dev(r->proj_req); free_dev(r->proj_wg_tiles); free_dev(r->counters);
+  free_dev(r->multi_mask); free_dev(r->multi_maps); free_dev(r->multi_counts);
   if (r->vis_hint) (void)hipHostFree(r->vis_hint);
   delete r;
   return DSLAM_OK;
@@ -1499,6 +1500,37 @@ int dslam_get_image(dslam_engine *e, const dslam_scene *s, dslam_render_state *r
     return finish_call(e);
   }
   int rc = get_image_on_device(e, s, r, M, intr, type);
+  if (rc) return rc;
+  return image_out(e, r, type, out_rgba, out_float);
+}
+
+int dslam_get_image_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                          dslam_render_state *r, const float M[16], const float intr[4], int type, uint8_t *out_rgba,
+                          float *out_float) {
+  DSLAM_REQUIRE(e && scenes && T_map_from_world && r && M && intr, "null argument");
+  DSLAM_REQUIRE(num_maps >= 1 && num_maps <= DSLAM_MAX_RENDER_MAPS, "num_maps must be 1 .. DSLAM_MAX_RENDER_MAPS");
+  DSLAM_REQUIRE(type >= 0 && type <= DSLAM_IMAGE_DEPTH, "unknown image type");
+  DSLAM_REQUIRE(r->engine == e, "the render state belongs to another engine");
+  float inv[16];
+  DSLAM_REQUIRE(invert_matrix(M, inv), "pose matrix is singular");
+  for (int i = 0; i < num_maps; i++) {
+    const dslam_scene *s = scenes[i];
+    DSLAM_REQUIRE(s, "a scene in the list is NULL");
+    DSLAM_REQUIRE(s->engine == e, "a scene in the list belongs to another engine");
+    DSLAM_REQUIRE(s->p.voxel_size == scenes[0]->p.voxel_size && s->p.mu == scenes[0]->p.mu,
+                  "all scenes of a composite render need the same voxel_size and mu");
+    DSLAM_REQUIRE(s->p.num_local_blocks <= r->n_local, "the render state's visible-list capacity is below a scene's num_local_blocks");
+    DSLAM_REQUIRE(invert_matrix(T_map_from_world + 16 * i, inv), "a map transform is singular");
+  }
+  r->memo_valid = false;  // raycastResult / range image are about to be rewritten (and never memoised for several maps)
+  void *out = type == DSLAM_IMAGE_DEPTH ? (void *)out_float : (void *)out_rgba;
+  const size_t bytes = (size_t)r->w * r->h * 4;
+  if (out && !(out_rgba && out_float) && in_pinned_range(out, bytes)) {
+    int rc = launch_render_multi(e, scenes, T_map_from_world, num_maps, r, M, intr, type, out);
+    if (rc) return rc;
+    return finish_call(e);
+  }
+  int rc = launch_render_multi(e, scenes, T_map_from_world, num_maps, r, M, intr, type);
   if (rc) return rc;
   return image_out(e, r, type, out_rgba, out_float);
 }

@@ -221,6 +221,11 @@ struct dslam_render_state {
   unsigned long long memo_version = 0;
   int memo_budget = 0;
   float memo_M[16] = {0}, memo_intr[4] = {0};
+  // dslam_get_image_multi (multimap.hip), allocated by its first call: per range cell the maps whose blocks project into
+  // it (bit i = map i), the per-map descriptor table, per map its visible-block count
+  unsigned long long *multi_mask = nullptr;
+  void *multi_maps = nullptr;
+  int *multi_counts = nullptr;
 };
 
 struct dslam_view {
@@ -339,6 +344,9 @@ int launch_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state
                         const float *intr, const dslam_tracker_params *tp, dslam_tracker_result *res);
 int launch_render(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float *M, const float *intr,
                   int type, bool reuse_raycast = false, void *image_out_override = nullptr);
+// scenes / T (N x 16, world -> map) already checked by dslam_get_image_multi
+int launch_render_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T, int n, dslam_render_state *r,
+                        const float *M, const float *intr, int type, void *image_out_override = nullptr);
 int launch_icp_maps(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float *M, const float *intr);
 int launch_mesh_scene(dslam_engine *e, const dslam_scene *s, int max_triangles, int with_colour, int *out_num);
 int launch_decay(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int max_weight, int min_age, int force_all,

@@ -1,0 +1,509 @@
+// multimap.hip -- one raycast over several local maps, each read through its own world -> map transform
+// (dslam_get_image_multi; ITMMainEngine::GetImageAllLocalMaps in the mirror).
+//
+// Reference: the static map is split into local maps (DenseSlam.cpp:133-141, 260-261, 554-565), each a voxel-hash scene
+// with an estimatedGlobalPose (DenseSlam.cpp:190, 577-579); every preview draws currentLocalMap only
+// (InfiniTamDriver.cpp:229-277).  The combination law below is this project's own definition.
+//
+// Front end, 2N + 1 launches for N maps: per map a frustum selection + projection over its alloc_bits (the compaction of
+// FindVisibleBlocks with no list output: the render state's visible list is never written) and a splat of its boxes into
+// the shared range image (per-cell min / max) and the per-cell map mask (bit i: a block of map i projects into the cell);
+// the first selection also resets the range image and the mask.  Then one march launch.
+//
+// March: one wavefront = one 8x8 tile = one range cell, as k_render, so the cell's map mask is wave-uniform.  Every read
+// of the march (nearest voxel, trilinear, 6-tap normal, trilinear colour) is a combined read over the maps of the mask,
+// in ascending map order: a map reports (value v_i, found, confidence w_i); none found -> not found; exactly one ->
+// its value unchanged; more -> sum(w_i v_i) / sum(w_i), accumulated in float32 in map order as
+// num = ((w_0 v_0 + w_1 v_1) + w_2 v_2) + ..., den = ((w_0 + w_1) + w_2) + ..., value = num / den (den == 0: 1.0 for
+// sdf, the first contributor's value for normal / colour).  A map whose transform is exactly the identity reads at
+// the march position itself, so a tile that sees one such map marches and shades bit for bit like k_render.
+#include <cmath>
+#include <cstdio>
+
+#include "dslam_bits.h"
+#include "raycast_device.h"
+
+#pragma clang fp contract(off)
+
+namespace dslam {
+
+// one map of a composite render; T: the first three rows of world -> map, row-major, translation in voxel units
+struct MultiMap {
+  const HashEntry *hash;
+  const uint2 *voxels;
+  unsigned mask;
+  int num_buckets;
+  float T[12];
+  int identity;
+  int pad;
+};
+
+// FindVisibleBlocks + ProjectSingleBlock of one map; the first map's launch also resets the range image and the mask
+struct SelMulti : SelFrustum<true> {
+  unsigned long long *cell_mask;
+  int ncell;
+  __device__ void prologue() const {
+    SelFrustum<true>::prologue();
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ncell; i += gridDim.x * blockDim.x) cell_mask[i] = 0ull;
+  }
+};
+
+// every projected box of one map into the range image (min / max, as k_fill_range_tiles) and the map mask; cells outside
+// the ceil(W/8) x ceil(H/8) corner the march reads are not touched.  A wavefront takes its 64 boxes one after the other,
+// each with all 64 lanes over its cells: a block next to the camera covers thousands of cells, which one lane alone
+// would walk through serially.
+__global__ __launch_bounds__(256) void k_multi_splat(const int *__restrict__ count, const int4 *__restrict__ boxes,
+                                                     const float2 *__restrict__ zr, const int *__restrict__ req,
+                                                     float2 *range, unsigned long long *cell_mask, int W, int cw, int ch,
+                                                     int bit) {
+  const int n = *count;
+  const int lane = threadIdx.x & 63;
+  const unsigned long long b = 1ull << bit;
+  for (int base = blockIdx.x * blockDim.x + (threadIdx.x & ~63); base < n; base += gridDim.x * blockDim.x) {   // (uniform)
+    const int i = base + lane;
+    int x0 = 0, y0 = 0, x1 = -1, y1 = -1, zmin_i = 0, zmax_i = 0;
+    if (i < n && req[i] != 0) {
+      const int4 box = boxes[i];
+      const float2 z = zr[i];
+      x0 = box.x; y0 = box.y;
+      x1 = box.z < cw - 1 ? box.z : cw - 1;
+      y1 = box.w < ch - 1 ? box.w : ch - 1;
+      zmin_i = __float_as_int(z.x); zmax_i = __float_as_int(z.y);
+    }
+    for (int j = 0; j < 64; j++) {
+      const int bx0 = __shfl(x0, j, 64), by0 = __shfl(y0, j, 64), bx1 = __shfl(x1, j, 64), by1 = __shfl(y1, j, 64);
+      const int zmin = __shfl(zmin_i, j, 64), zmax = __shfl(zmax_i, j, 64);
+      if (bx0 > bx1 || by0 > by1) continue;
+      const int w = bx1 - bx0 + 1, cells = w * (by1 - by0 + 1);
+      for (int c = lane; c < cells; c += 64) {
+        const int x = bx0 + c % w, y = by0 + c / w;
+        int *px = reinterpret_cast<int *>(&range[x + (size_t)y * W]);
+        atomicMin(&px[0], zmin);
+        atomicMax(&px[1], zmax);
+        atomicOr(&cell_mask[x + y * cw], b);
+      }
+    }
+  }
+}
+
+struct MultiRenderParams {
+  const MultiMap *maps;
+  const unsigned long long *cell_mask;
+  int cw;
+  Mat4 M, invM;
+  float inv_fx, inv_fy, cx, cy;
+  float one_over_vs, voxel_size, mu, inv_32767;
+  int W, H;
+  const float2 *range;
+  float4 *raycast;
+  uchar4 *out_rgba;
+  float *out_float;
+  int type;
+};
+
+// lowest set bit of a wave-uniform mask, as a scalar
+__device__ __forceinline__ int first_map(unsigned long long mk) {
+  return __builtin_amdgcn_readfirstlane(__builtin_ctzll(mk));
+}
+
+__device__ __forceinline__ VolumeRef volume_of(const MultiMap &m) {
+  VolumeRef v;
+  v.hash = m.hash; v.voxels = m.voxels; v.mask = m.mask; v.num_buckets = m.num_buckets;
+  return v;
+}
+
+// q = T p: ((t0 x + t1 y) + t2 z) + t3 per row; the identity reads at p itself
+__device__ __forceinline__ Vec3 to_map(const MultiMap &m, const Vec3 &p) {
+  if (m.identity) return p;
+  Vec3 q;
+  q.x = ((m.T[0] * p.x + m.T[1] * p.y) + m.T[2] * p.z) + m.T[3];
+  q.y = ((m.T[4] * p.x + m.T[5] * p.y) + m.T[6] * p.z) + m.T[7];
+  q.z = ((m.T[8] * p.x + m.T[9] * p.y) + m.T[10] * p.z) + m.T[11];
+  return q;
+}
+
+// a gradient of the map frame back into the world frame: R^T g
+__device__ __forceinline__ Vec3 to_world_dir(const MultiMap &m, const Vec3 &g) {
+  if (m.identity) return g;
+  Vec3 r;
+  r.x = (m.T[0] * g.x + m.T[4] * g.y) + m.T[8] * g.z;
+  r.y = (m.T[1] * g.x + m.T[5] * g.y) + m.T[9] * g.z;
+  r.z = (m.T[2] * g.x + m.T[6] * g.y) + m.T[10] * g.z;
+  return r;
+}
+
+// trilinear blend of 8 tap values in trilinear_sdf's order (x, then y, then z)
+__device__ __forceinline__ float lerp8(const float s[8], float cx, float cy, float cz) {
+  float res1 = (1.0f - cx) * s[0] + cx * s[1];
+  res1 = (1.0f - cy) * res1 + cy * ((1.0f - cx) * s[2] + cx * s[3]);
+  float res2 = (1.0f - cx) * s[4] + cx * s[5];
+  res2 = (1.0f - cy) * res2 + cy * ((1.0f - cx) * s[6] + cx * s[7]);
+  return (1.0f - cz) * res1 + cz * res2;
+}
+
+// the 8 taps (both voxel words) of the trilinear cell at (x0, y0, z0), as gather_taps_batched; returns whether any tap
+// lies in an allocated block
+__device__ __forceinline__ bool gather_cell(const VolumeRef &vol, int x0, int y0, int z0, uint2 t[8]) {
+  const int bxa[2] = {x0 >> 3, (x0 + 1) >> 3}, bya[2] = {y0 >> 3, (y0 + 1) >> 3}, bza[2] = {z0 >> 3, (z0 + 1) >> 3};
+  int base[8];
+  resolve_cell_blocks(vol, bxa, bya, bza, base);
+  const unsigned lx[2] = {(unsigned)x0 & 7u, (unsigned)(x0 + 1) & 7u};
+  const unsigned ly[2] = {((unsigned)y0 & 7u) << 3, ((unsigned)(y0 + 1) & 7u) << 3};
+  const unsigned lz[2] = {((unsigned)z0 & 7u) << 6, ((unsigned)(z0 + 1) & 7u) << 6};
+  bool any = false;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const unsigned lin = lx[k & 1] | ly[(k >> 1) & 1] | lz[k >> 2];
+    const uint2 v = vol.voxels[(size_t)(base[k] < 0 ? 0 : base[k]) + lin];
+    t[k] = base[k] < 0 ? make_uint2(kEmptyVoxelLo, kEmptyVoxelHi) : v;
+    any |= base[k] >= 0;
+  }
+  return any;
+}
+
+// running state of one combined read
+struct Blend {
+  int n;            // maps that reported found
+  float num, den;   // sum w v, sum w (float32, map order)
+  float first;      // value of the first map that reported found
+  __device__ void add(float v, float w) {
+    if (n == 0) first = v;
+    num += w * v;
+    den += w;
+    n++;
+  }
+  // two or more found: num / den, or `fallback` for den == 0
+  __device__ float value(float fallback) const { return n == 1 ? first : (den > 0.0f ? num / den : fallback); }
+};
+
+// combined trilinear sdf read at world position p; `first_any`: the first candidate's read (all of its taps empty when
+// no map reports found -- what a single-map read returns there)
+__device__ float multi_trilinear(const MultiRenderParams &p, unsigned long long mk, const Vec3 &pt) {
+  Blend b = {0, 0.0f, 0.0f, 0.0f};
+  float first_any = 1.0f;
+  bool have_any = false;
+  while (mk) {
+    const int i = first_map(mk);
+    mk &= mk - 1;
+    const MultiMap &m = p.maps[i];
+    const Vec3 q = to_map(m, pt);
+    const float fx = floorf(q.x), fy = floorf(q.y), fz = floorf(q.z);
+    uint2 t[8];
+    const bool found = gather_cell(volume_of(m), (int)fx, (int)fy, (int)fz, t);
+    unsigned raw[8];
+    float wt[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) { raw[k] = t[k].x; wt[k] = (float)((t[k].x >> 16) & 0xffu); }
+    const float cx = q.x - fx, cy = q.y - fy, cz = q.z - fz;
+    const float v = trilinear_raw(raw, cx, cy, cz);
+    if (!have_any) { first_any = v; have_any = true; }
+    if (found) b.add(v, lerp8(wt, cx, cy, cz));
+  }
+  return b.n == 0 ? first_any : b.value(1.0f);
+}
+
+// castRay (cast_ray<false> in raycast.hip) with every read combined over the maps of the cell's mask
+__device__ __forceinline__ bool cast_ray_multi(Vec4 &out, int x, int y, const MultiRenderParams &p, const float2 minmax,
+                                               const unsigned long long cell_mk) {
+  Vec4 pc;
+  Vec3 ps, pe, dir, res;
+  float sdf = 1.0f;
+  float total, step, total_max;
+  const float step_scale = p.mu * p.one_over_vs;
+
+  pc.z = minmax.x;
+  pc.x = pc.z * (((float)x - p.cx) * p.inv_fx);
+  pc.y = pc.z * (((float)y - p.cy) * p.inv_fy);
+  pc.w = 1.0f;
+  total = sqrtf(pc.x * pc.x + pc.y * pc.y + pc.z * pc.z) * p.one_over_vs;
+  Vec4 q = mul(p.invM, pc);
+  ps.x = q.x * p.one_over_vs; ps.y = q.y * p.one_over_vs; ps.z = q.z * p.one_over_vs;
+
+  pc.z = minmax.y;
+  pc.x = pc.z * (((float)x - p.cx) * p.inv_fx);
+  pc.y = pc.z * (((float)y - p.cy) * p.inv_fy);
+  pc.w = 1.0f;
+  total_max = sqrtf(pc.x * pc.x + pc.y * pc.y + pc.z * pc.z) * p.one_over_vs;
+  q = mul(p.invM, pc);
+  pe.x = q.x * p.one_over_vs; pe.y = q.y * p.one_over_vs; pe.z = q.z * p.one_over_vs;
+
+  dir.x = pe.x - ps.x; dir.y = pe.y - ps.y; dir.z = pe.z - ps.z;
+  const float dn = 1.0f / sqrtf(dir.x * dir.x + dir.y * dir.y + dir.z * dir.z);
+  dir.x *= dn; dir.y *= dn; dir.z *= dn;
+  res = ps;
+  // per-lane block cache: one entry, tagged with its map
+  IndexCache cache = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1};
+  int cache_map = -1;
+  while (total < total_max) {
+    // nearest-voxel read of every map of the cell
+    Blend b = {0, 0.0f, 0.0f, 0.0f};
+    unsigned long long mk = cell_mk;
+    while (mk) {
+      const int i = first_map(mk);
+      mk &= mk - 1;
+      const MultiMap &m = p.maps[i];
+      const Vec3 qm = to_map(m, res);
+      const int vx = iround(qm.x), vy = iround(qm.y), vz = iround(qm.z);
+      if (cache_map != i) { cache.bx = 0x7fffffff; cache_map = i; }
+      const int base = lookup_block(volume_of(m), vx >> 3, vy >> 3, vz >> 3, cache);
+      if (base >= 0) {
+        const unsigned raw = m.voxels[(size_t)base + (unsigned)((vx & 7) | ((vy & 7) << 3) | ((vz & 7) << 6))].x;
+        b.add(div_exact((float)(short)(raw & 0xffffu), 32767.0f, p.inv_32767), (float)((raw >> 16) & 0xffu));
+      }
+    }
+    if (b.n == 0) {
+      sdf = 1.0f;  // empty voxel: 32767 / 32767
+      step = (float)kBlock;
+    } else {
+      sdf = b.value(1.0f);
+      if ((sdf <= 0.1f) && (sdf >= -0.5f)) sdf = multi_trilinear(p, cell_mk, res);
+      if (sdf <= 0.0f) break;
+      step = fmaxf(sdf * step_scale, 1.0f);
+    }
+    res.x += step * dir.x; res.y += step * dir.y; res.z += step * dir.z;
+    total += step;
+  }
+  bool pt_found;
+  if (sdf <= 0.0f) {
+    step = sdf * step_scale;
+    res.x += step * dir.x; res.y += step * dir.y; res.z += step * dir.z;
+    sdf = multi_trilinear(p, cell_mk, res);
+    step = sdf * step_scale;
+    res.x += step * dir.x; res.y += step * dir.y; res.z += step * dir.z;
+    pt_found = true;
+  } else {
+    pt_found = false;
+  }
+  out.x = res.x; out.y = res.y; out.z = res.z; out.w = pt_found ? 1.0f : 0.0f;
+  return pt_found;
+}
+
+// read_colour_interp's arithmetic on gathered taps
+__device__ __forceinline__ Vec4 colour_from_taps(const uint2 t[8], float cx, float cy, float cz) {
+  float rx = 0.0f, ry = 0.0f, rz = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int ox = k & 1, oy = (k >> 1) & 1, oz = (k >> 2) & 1;
+    const uint2 v = t[k];
+    const float wx = ox ? cx : (1.0f - cx), wy = oy ? cy : (1.0f - cy), wz = oz ? cz : (1.0f - cz);
+    const float w = wx * wy * wz;
+    rx += w * (float)(v.x >> 24);
+    ry += w * (float)(v.y & 0xffu);
+    rz += w * (float)((v.y >> 8) & 0xffu);
+  }
+  Vec4 r = {rx / 255.0f, ry / 255.0f, rz / 255.0f, 255.0f / 255.0f};
+  return r;
+}
+
+// one running sum per component (the same law, component by component)
+struct Blend3 {
+  int n;
+  float nx, ny, nz, den;
+  Vec3 first;
+  __device__ void add(const Vec3 &v, float w) {
+    if (n == 0) first = v;
+    nx += w * v.x; ny += w * v.y; nz += w * v.z;
+    den += w;
+    n++;
+  }
+  __device__ Vec3 value() const {
+    if (n == 1 || !(den > 0.0f)) return first;
+    Vec3 r = {nx / den, ny / den, nz / den};
+    return r;
+  }
+};
+
+// k_render<1, SHADE> over several maps: march, depth, and the three shaded types
+template <bool SHADE>
+__global__ __launch_bounds__(64) void k_render_multi(MultiRenderParams p) {
+  const int lane = threadIdx.x & 63;
+  const int x = blockIdx.x * 8 + (lane & 7), y = blockIdx.y * 8 + (lane >> 3);
+  const unsigned long long m0 = p.cell_mask[blockIdx.x + blockIdx.y * p.cw];
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)m0), hi = __builtin_amdgcn_readfirstlane((unsigned)(m0 >> 32));
+  const unsigned long long cell_mk = ((unsigned long long)hi << 32) | lo;
+  if (x >= p.W || y >= p.H) return;
+  const int loc = x + y * p.W;
+  const int loc2 = (int)floorf((float)x / 8.0f) + (int)floorf((float)y / 8.0f) * p.W;
+  Vec4 pr;
+  cast_ray_multi(pr, x, y, p, p.range[loc2], cell_mk);
+  p.raycast[loc] = make_float4(pr.x, pr.y, pr.z, pr.w);
+  if (p.type < 0) return;
+
+  const Vec3 pt = {pr.x, pr.y, pr.z};
+  bool found = pr.w > 0;
+  if (p.type == DSLAM_IMAGE_DEPTH) {
+    float d = 0.0f;
+    if (found) {
+      Vec4 pw = {pt.x * p.voxel_size, pt.y * p.voxel_size, pt.z * p.voxel_size, 1.0f};
+      d = mul(p.M, pw).z;
+    }
+    p.out_float[loc] = d;
+    return;
+  }
+  if (!SHADE) return;
+  Vec3 n = {0, 0, 0};
+  float angle = 0.0f;
+  if (found) {
+    const Vec3 light = {-p.invM.m[8], -p.invM.m[9], -p.invM.m[10]};
+    // combined 6-tap normal: each map's gradient in the world frame, confidence = trilinear w_depth at the point
+    Blend3 b = {0, 0.0f, 0.0f, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f}};
+    Vec3 first_any = {0.0f, 0.0f, 0.0f};
+    bool have_any = false;
+    unsigned long long mk = cell_mk;
+    while (mk) {
+      const int i = first_map(mk);
+      mk &= mk - 1;
+      const MultiMap &m = p.maps[i];
+      const VolumeRef vol = volume_of(m);
+      const Vec3 q = to_map(m, pt);
+      IndexCache c = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1};
+      const Vec3 g = to_world_dir(m, normal_from_sdf(vol, q, c));
+      if (!have_any) { first_any = g; have_any = true; }
+      const float fx = floorf(q.x), fy = floorf(q.y), fz = floorf(q.z);
+      uint2 t[8];
+      if (gather_cell(vol, (int)fx, (int)fy, (int)fz, t)) {
+        float wt[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) wt[k] = (float)((t[k].x >> 16) & 0xffu);
+        b.add(g, lerp8(wt, q.x - fx, q.y - fy, q.z - fz));
+      }
+    }
+    n = b.n == 0 ? first_any : b.value();
+    const float ns = 1.0f / sqrtf(n.x * n.x + n.y * n.y + n.z * n.z);
+    n.x *= ns; n.y *= ns; n.z *= ns;
+    angle = n.x * light.x + n.y * light.y + n.z * light.z;
+    if (!(angle > 0.0f)) found = false;
+  }
+  uchar4 o = make_uchar4(0, 0, 0, 0);
+  if (found) {
+    if (p.type == DSLAM_IMAGE_COLOUR_FROM_VOLUME) {
+      // combined colour: confidence = trilinear w_color
+      Blend3 b = {0, 0.0f, 0.0f, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f}};
+      Vec3 first_any = {0.0f, 0.0f, 0.0f};
+      bool have_any = false;
+      unsigned long long mk = cell_mk;
+      while (mk) {
+        const int i = first_map(mk);
+        mk &= mk - 1;
+        const MultiMap &m = p.maps[i];
+        const Vec3 q = to_map(m, pt);
+        const float fx = floorf(q.x), fy = floorf(q.y), fz = floorf(q.z);
+        uint2 t[8];
+        const bool hit = gather_cell(volume_of(m), (int)fx, (int)fy, (int)fz, t);
+        const float cx = q.x - fx, cy = q.y - fy, cz = q.z - fz;
+        const Vec4 c4 = colour_from_taps(t, cx, cy, cz);
+        const Vec3 c3 = {c4.x, c4.y, c4.z};
+        if (!have_any) { first_any = c3; have_any = true; }
+        if (hit) {
+          float wt[8];
+#pragma unroll
+          for (int k = 0; k < 8; k++) wt[k] = (float)((t[k].y >> 16) & 0xffu);
+          b.add(c3, lerp8(wt, cx, cy, cz));
+        }
+      }
+      const Vec3 clr = b.n == 0 ? first_any : b.value();
+      o = make_uchar4((unsigned char)(clr.x * 255.0f), (unsigned char)(clr.y * 255.0f), (unsigned char)(clr.z * 255.0f),
+                      255);
+    } else if (p.type == DSLAM_IMAGE_COLOUR_FROM_NORMAL) {
+      o = make_uchar4((unsigned char)((0.3f + (-n.x + 1.0f) * 0.35f) * 255.0f),
+                      (unsigned char)((0.3f + (-n.y + 1.0f) * 0.35f) * 255.0f),
+                      (unsigned char)((0.3f + (-n.z + 1.0f) * 0.35f) * 255.0f), 255);
+    } else {
+      const unsigned char g = (unsigned char)((0.8f * angle + 0.2f) * 255.0f);
+      o = make_uchar4(g, g, g, g);
+    }
+  }
+  p.out_rgba[loc] = o;
+}
+
+static bool is_identity(const float *T) {
+  for (int i = 0; i < 16; i++)
+    if (T[i] != ((i % 5) == 0 ? 1.0f : 0.0f)) return false;
+  return true;
+}
+
+static int ensure_multi_buffers(dslam_render_state *r) {
+  if (r->multi_mask) return DSLAM_OK;
+  const size_t ncell = (size_t)((r->w + 7) / 8) * ((r->h + 7) / 8);
+  DSLAM_HIP(hipMalloc(&r->multi_mask, ncell * sizeof(unsigned long long)));
+  DSLAM_HIP(hipMalloc(&r->multi_maps, DSLAM_MAX_RENDER_MAPS * sizeof(MultiMap)));
+  DSLAM_HIP(hipMalloc(&r->multi_counts, DSLAM_MAX_RENDER_MAPS * sizeof(int)));
+  return DSLAM_OK;
+}
+
+// scenes / T_map_from_world (column-major, metres) are checked by the caller (dslam_get_image_multi)
+int launch_render_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T, int n, dslam_render_state *r,
+                        const float *M, const float *intr, int type, void *image_out_override) {
+  int rc = ensure_multi_buffers(r);
+  if (rc) return rc;
+  const float vs = scenes[0]->p.voxel_size;
+  const int cw = (r->w + 7) / 8, ch = (r->h + 7) / 8;
+  MultiMap maps[DSLAM_MAX_RENDER_MAPS];
+  for (int i = 0; i < n; i++) {
+    const dslam_scene *s = scenes[i];
+    const float *Ti = T + 16 * i;
+    MultiMap &m = maps[i];
+    memset(&m, 0, sizeof(m));
+    m.hash = s->hash; m.voxels = s->voxels; m.mask = (unsigned)(s->p.num_buckets - 1); m.num_buckets = s->p.num_buckets;
+    m.identity = is_identity(Ti) ? 1 : 0;
+    for (int row = 0; row < 3; row++) {
+      for (int col = 0; col < 3; col++) m.T[row * 4 + col] = Ti[col * 4 + row];
+      m.T[row * 4 + 3] = Ti[12 + row] / vs;   // translation in voxel units
+    }
+  }
+  DSLAM_HIP(hipMemcpyAsync(r->multi_maps, maps, (size_t)n * sizeof(MultiMap), hipMemcpyHostToDevice, e->stream));
+  // front end: map i seen from M is a camera at M T_i^-1 (the identity keeps M bit for bit)
+  for (int i = 0; i < n; i++) {
+    const dslam_scene *s = scenes[i];
+    const float *Ti = T + 16 * i;
+    float Mi[16];
+    if (maps[i].identity) {
+      memcpy(Mi, M, sizeof(Mi));
+    } else {
+      float Tinv[16];
+      if (!invert_matrix(Ti, Tinv)) { set_last_error("map transform is singular"); return DSLAM_ERR_INVALID; }
+      for (int col = 0; col < 4; col++)
+        for (int row = 0; row < 4; row++) {
+          double acc = 0.0;
+          for (int k = 0; k < 4; k++) acc += (double)M[k * 4 + row] * (double)Tinv[col * 4 + k];
+          Mi[col * 4 + row] = (float)acc;
+        }
+    }
+    if ((rc = ensure_scratch(e, s->n_entries, s->p.num_local_blocks))) return rc;
+    SelMulti sel;
+    sel.hash = s->hash;
+    sel.fp = make_frustum_params(s, r, Mi, intr);
+    sel.boxes = r->proj_boxes; sel.zr_out = r->proj_z; sel.req_out = r->proj_req; sel.range = r->range;
+    sel.npix = i == 0 ? r->w * r->h : 0;
+    sel.cell_mask = r->multi_mask;
+    sel.ncell = i == 0 ? cw * ch : 0;
+    launch_bits_select(e, s->alloc_bits, s->n_entries, sel, nullptr, r->n_local, r->multi_counts + i, s->counters);
+    hipLaunchKernelGGL(k_multi_splat, dim3(256), dim3(256), 0, e->stream, r->multi_counts + i, r->proj_boxes, r->proj_z,
+                       r->proj_req, r->range, r->multi_mask, r->w, cw, ch, i);
+    DSLAM_HIP(hipGetLastError());
+  }
+  MultiRenderParams rp;
+  rp.maps = static_cast<const MultiMap *>(r->multi_maps);
+  rp.cell_mask = r->multi_mask;
+  rp.cw = cw;
+  memcpy(rp.M.m, M, 64);
+  if (!invert_matrix(M, rp.invM.m)) { set_last_error("pose matrix is singular"); return DSLAM_ERR_INVALID; }
+  rp.inv_fx = 1.0f / intr[0]; rp.inv_fy = 1.0f / intr[1]; rp.cx = intr[2]; rp.cy = intr[3];
+  rp.voxel_size = vs; rp.one_over_vs = 1.0f / vs; rp.mu = scenes[0]->p.mu;
+  rp.inv_32767 = 1.0f / 32767.0f;
+  rp.W = r->w; rp.H = r->h;
+  rp.range = r->range; rp.raycast = r->raycast; rp.out_rgba = r->image_rgba; rp.out_float = r->image_float;
+  rp.type = type;
+  if (image_out_override) {
+    if (type == DSLAM_IMAGE_DEPTH) rp.out_float = static_cast<float *>(image_out_override);
+    else rp.out_rgba = static_cast<uchar4 *>(image_out_override);
+  }
+  if (type == DSLAM_IMAGE_DEPTH || type < 0)
+    hipLaunchKernelGGL(k_render_multi<false>, dim3(cw, ch), dim3(64), 0, e->stream, rp);
+  else
+    hipLaunchKernelGGL(k_render_multi<true>, dim3(cw, ch), dim3(64), 0, e->stream, rp);
+  DSLAM_HIP(hipGetLastError());
+  return DSLAM_OK;
+}
+
+}  // namespace dslam

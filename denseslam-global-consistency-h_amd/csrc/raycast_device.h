@@ -1,0 +1,417 @@
+// raycast_device.h -- the device side of the ray march shared by raycast.hip (one map) and multimap.hip (several
+// maps): block frustum test and projection (FindVisibleBlocks / CreateExpectedDepths) and the voxel reads of castRay
+// and the shading pass.  Moved here unchanged from raycast.hip.
+#pragma once
+#include <cstring>
+
+#include "dslam_bits.h"
+
+#pragma clang fp contract(off)
+
+namespace dslam {
+
+// ---------------------------------------------------------------------------------------------------------
+// FindVisibleBlocks: ordered compaction of entries with ptr >= 0 that pass the 8-corner frustum test
+// ---------------------------------------------------------------------------------------------------------
+// An ordered selection over the scene's alloc_bits (dslam_bits.h): only entries that hold a block are read and tested
+// (round 2: a frustum-flag sweep over all 1.18 M entries and a compaction sweep over 1.18 M byte flags).
+struct FrustumParams {
+  Mat4 M;
+  float fx, fy, cx, cy, voxel_size;
+  int W, H;
+};
+
+// ---------------------------------------------------------------------------------------------------------
+// CreateExpectedDepths
+// ---------------------------------------------------------------------------------------------------------
+struct ProjParams {
+  Mat4 M;
+  float fx, fy, cx, cy, voxel_size;
+  int W, H;
+};
+
+// ProjectSingleBlock: bbox (in 1/8-resolution cells) and z-range of one block; returns the number of 16x16 render
+// tiles it needs (0 = nothing to render)
+__device__ __forceinline__ int project_single_block(const HashEntry &e, const ProjParams &p, int4 &box, float2 &zr) {
+  if (e.ptr < 0) return 0;
+  int ulx = p.W / 8, uly = p.H / 8, lrx = -1, lry = -1;
+  float zmin = kFarAway, zmax = kVeryClose;
+#pragma unroll
+  for (int corner = 0; corner < 8; corner++) {
+    short tx = e.pos[0], ty = e.pos[1], tz = e.pos[2];
+    tx += (corner & 1) ? 1 : 0; ty += (corner & 2) ? 1 : 0; tz += (corner & 4) ? 1 : 0;
+    Vec4 q;
+    q.x = (float)tx * (float)kBlock * p.voxel_size;
+    q.y = (float)ty * (float)kBlock * p.voxel_size;
+    q.z = (float)tz * (float)kBlock * p.voxel_size;
+    q.w = 1.0f;
+    q = mul(p.M, q);
+    if (q.z < 1e-6f) continue;
+    const float px = (p.fx * q.x / q.z + p.cx) / 8.0f;
+    const float py = (p.fy * q.y / q.z + p.cy) / 8.0f;
+    if ((float)ulx > floorf(px)) ulx = (int)floorf(px);
+    if ((float)lrx < ceilf(px)) lrx = (int)ceilf(px);
+    if ((float)uly > floorf(py)) uly = (int)floorf(py);
+    if ((float)lry < ceilf(py)) lry = (int)ceilf(py);
+    if (zmin > q.z) zmin = q.z;
+    if (zmax < q.z) zmax = q.z;
+  }
+  if (ulx < 0) ulx = 0;
+  if (uly < 0) uly = 0;
+  if (lrx >= p.W) lrx = p.W - 1;
+  if (lry >= p.H) lry = p.H - 1;
+  bool valid = !(ulx > lrx) && !(uly > lry);
+  if (zmin < kVeryClose) zmin = kVeryClose;
+  if (zmax < kVeryClose) valid = false;
+  if (!valid) return 0;
+  const int rx = (int)ceilf((float)(lrx - ulx + 1) / 16.0f), ry = (int)ceilf((float)(lry - uly + 1) / 16.0f);
+  box = make_int4(ulx, uly, lrx, lry);
+  zr = make_float2(zmin, zmax);
+  return rx * ry;
+}
+
+// PROJECT: the lane that lists visible entry number r also projects it (CreateExpectedDepths' ProjectSingleBlock; GetImage
+// runs both with one pose), the compaction launch resets the range image, and every compaction tile leaves its
+// render-tile total for k_fill_range_tiles.
+template <bool PROJECT>
+struct SelFrustum {
+  const HashEntry *hash;
+  FrustumParams fp;
+  int4 *boxes;
+  float2 *zr_out;
+  int *req_out;
+  float2 *range;
+  int npix;
+  __device__ void prologue() const {
+    if (PROJECT)   // (independent job) reset the range image to (FAR_AWAY, VERY_CLOSE)
+      for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) range[i] = make_float2(kFarAway, kVeryClose);
+  }
+  typedef HashEntry Payload;
+  __device__ HashEntry load(int t) const { return load_entry(hash, t); }
+  __device__ bool test(int, const HashEntry &e) const {
+    if (e.ptr < 0) return false;
+    bool vis, vis_enl;
+    check_block_vis<false>(vis, vis_enl, e.pos[0], e.pos[1], e.pos[2], fp.M, fp.fx, fp.fy, fp.cx, fp.cy, fp.voxel_size, fp.W, fp.H);
+    return vis;
+  }
+  struct Staged { int4 box; float2 zr; int req; };
+  __device__ Staged stage(int, const HashEntry &e) const {
+    Staged s;
+    s.req = 0;
+    if (!PROJECT) return s;
+    ProjParams pp;
+    pp.M = fp.M; pp.fx = fp.fx; pp.fy = fp.fy; pp.cx = fp.cx; pp.cy = fp.cy; pp.voxel_size = fp.voxel_size; pp.W = fp.W; pp.H = fp.H;
+    s.req = project_single_block(e, pp, s.box, s.zr);
+    return s;
+  }
+  __device__ int emit(int, int r, bool listed, const Staged &s) const {
+    if (!PROJECT || !listed) return 0;
+    if (s.req) { boxes[r] = s.box; zr_out[r] = s.zr; }
+    req_out[r] = s.req;
+    return s.req;
+  }
+  __device__ void finish(int) const {}
+};
+
+static FrustumParams make_frustum_params(const dslam_scene *s, const dslam_render_state *r, const float *M, const float *intr) {
+  FrustumParams fp;
+  memcpy(fp.M.m, M, 64);
+  fp.fx = intr[0]; fp.fy = intr[1]; fp.cx = intr[2]; fp.cy = intr[3]; fp.voxel_size = s->p.voxel_size;
+  fp.W = r->w; fp.H = r->h;
+  return fp;
+}
+
+static ProjParams make_proj_params(const dslam_scene *s, const dslam_render_state *r, const float *M, const float *intr) {
+  ProjParams pp;
+  memcpy(pp.M.m, M, 64);
+  pp.fx = intr[0]; pp.fy = intr[1]; pp.cx = intr[2]; pp.cy = intr[3]; pp.voxel_size = s->p.voxel_size;
+  pp.W = r->w; pp.H = r->h;
+  return pp;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// voxel access
+// ---------------------------------------------------------------------------------------------------------
+struct VolumeRef {
+  const HashEntry *hash;
+  const uint2 *voxels;
+  unsigned mask;
+  int num_buckets;
+};
+
+struct IndexCache {
+  int bx, by, bz, block_ptr;
+};
+
+__device__ __forceinline__ uint2 read_voxel(const VolumeRef &vol, int px, int py, int pz, bool &found, IndexCache &c) {
+  const int bx = ((px < 0) ? px - kBlock + 1 : px) / kBlock;
+  const int by = ((py < 0) ? py - kBlock + 1 : py) / kBlock;
+  const int bz = ((pz < 0) ? pz - kBlock + 1 : pz) / kBlock;
+  const int lin = (px - bx * kBlock) + (py - by * kBlock) * kBlock + (pz - bz * kBlock) * kBlock * kBlock;
+  if (bx == c.bx && by == c.by && bz == c.bz) {
+    found = true;
+    return vol.voxels[(size_t)c.block_ptr + lin];
+  }
+  int h = hash_index(bx, by, bz, vol.mask);
+  while (true) {
+    const HashEntry e = load_entry(vol.hash, h);
+    if (e.pos[0] == bx && e.pos[1] == by && e.pos[2] == bz && e.ptr >= 0) {
+      found = true;
+      c.bx = bx; c.by = by; c.bz = bz;
+      c.block_ptr = e.ptr * kBlock3;
+      return vol.voxels[(size_t)c.block_ptr + lin];
+    }
+    if (e.offset < 1) break;
+    h = vol.num_buckets + e.offset - 1;
+  }
+  found = false;
+  return make_uint2(kEmptyVoxelLo, kEmptyVoxelHi);
+}
+
+__device__ __forceinline__ float rd_sdf(const VolumeRef &vol, int x, int y, int z, bool &found, IndexCache &c) {
+  return (float)(short)(read_voxel(vol, x, y, z, found, c).x & 0xffffu);
+}
+
+// (int)(x < 0 ? x - 0.5f : x + 0.5f); copysign folds the compare + select into one bit-field insert (-0.0 gives 0
+// either way)
+__device__ __forceinline__ int iround(float x) { return (int)(x + __builtin_copysignf(0.5f, x)); }
+
+__device__ __forceinline__ float read_sdf_uninterp(const VolumeRef &vol, const Vec3 &pt, bool &found, IndexCache &c) {
+  return rd_sdf(vol, iround(pt.x), iround(pt.y), iround(pt.z), found, c) / 32767.0f;
+}
+
+// block base pointer (voxel index of the block's first voxel) or -1; refreshes the per-lane cache on a hit
+__device__ __forceinline__ int lookup_block(const VolumeRef &vol, int bx, int by, int bz, IndexCache &c) {
+  if (bx == c.bx && by == c.by && bz == c.bz) return c.block_ptr;
+  int h = hash_index(bx, by, bz, vol.mask);
+  while (true) {
+    const HashEntry e = load_entry(vol.hash, h);
+    if (e.pos[0] == bx && e.pos[1] == by && e.pos[2] == bz && e.ptr >= 0) {
+      c.bx = bx; c.by = by; c.bz = bz;
+      c.block_ptr = e.ptr * kBlock3;
+      return c.block_ptr;
+    }
+    if (e.offset < 1) return -1;
+    h = vol.num_buckets + e.offset - 1;
+  }
+}
+
+// Block base pointers (voxel index of the block's first voxel, or -1) of the 8 corners of a trilinear cell whose
+// per-axis block coordinates are bxa/bya/bza[0..1]; corner k = (k & 1, (k >> 1) & 1, k >> 2).  All eight bucket heads
+// are loaded in ONE round trip (equal blocks hit the same address); corners whose head holds another block follow
+// their excess chains together, one round trip per link.
+__device__ __forceinline__ void resolve_cell_blocks(const VolumeRef &vol, const int bxa[2], const int bya[2],
+                                                    const int bza[2], int base[8]) {
+  const unsigned hx[2] = {(unsigned)bxa[0] * 73856093u, (unsigned)bxa[1] * 73856093u};
+  const unsigned hy[2] = {(unsigned)bya[0] * 19349669u, (unsigned)bya[1] * 19349669u};
+  const unsigned hz[2] = {(unsigned)bza[0] * 83492791u, (unsigned)bza[1] * 83492791u};
+  // packed position words of an entry: x = pos0 | pos1 << 16, y = pos2 (| pad); a block coordinate outside the
+  // short range can never be stored, so it never matches
+  const unsigned tx[2] = {(unsigned)bxa[0] & 0xffffu, (unsigned)bxa[1] & 0xffffu};
+  const unsigned ty[2] = {(unsigned)bya[0] << 16, (unsigned)bya[1] << 16};
+  const unsigned tz[2] = {(unsigned)bza[0] & 0xffffu, (unsigned)bza[1] & 0xffffu};
+  const bool okx[2] = {bxa[0] == (short)bxa[0], bxa[1] == (short)bxa[1]};
+  const bool oky[2] = {bya[0] == (short)bya[0], bya[1] == (short)bya[1]};
+  const bool okz[2] = {bza[0] == (short)bza[0], bza[1] == (short)bza[1]};
+  int h[8];
+  u32x4 e[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    h[k] = (int)((hx[k & 1] ^ hy[(k >> 1) & 1] ^ hz[k >> 2]) & vol.mask);
+    e[k] = *reinterpret_cast<const u32x4 *>(vol.hash + h[k]);
+  }
+  unsigned pending = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const bool ok = okx[k & 1] && oky[(k >> 1) & 1] && okz[k >> 2];
+    const bool match = ok && e[k].x == (tx[k & 1] | ty[(k >> 1) & 1]) && (e[k].y & 0xffffu) == tz[k >> 2] && (int)e[k].w >= 0;
+    base[k] = match ? (int)e[k].w * kBlock3 : -1;
+    if (!match && (int)e[k].z >= 1) { pending |= 1u << k; h[k] = vol.num_buckets + (int)e[k].z - 1; }
+  }
+  // excess chains: all unresolved corners advance one link per round trip.  Branch-free on purpose -- a wave64
+  // executes every instruction any of its lanes needs, and eight predicated blocks with a branch each cost five
+  // times the instructions of selects (resolved corners just re-read their last entry and ignore it).
+  while (pending) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) e[k] = *reinterpret_cast<const u32x4 *>(vol.hash + h[k]);
+    unsigned still = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const bool pk = (pending & (1u << k)) != 0;
+      const bool ok = okx[k & 1] && oky[(k >> 1) & 1] && okz[k >> 2];
+      const bool match = ok && e[k].x == (tx[k & 1] | ty[(k >> 1) & 1]) && (e[k].y & 0xffffu) == tz[k >> 2] && (int)e[k].w >= 0;
+      const bool cont = pk && !match && (int)e[k].z >= 1;
+      base[k] = (pk && match) ? (int)e[k].w * kBlock3 : base[k];
+      h[k] = cont ? vol.num_buckets + (int)e[k].z - 1 : h[k];
+      still |= cont ? (1u << k) : 0u;
+    }
+    pending = still;
+  }
+}
+
+// The 8 taps of a trilinear read.  Tap k = (dx, dy, dz) = (k & 1, (k >> 1) & 1, k >> 2) relative to (x, y, z).  The
+// kernel is bound by the NUMBER of scattered load instructions (measured: prefetching or speculative variants that
+// add loads are slower), so the <= 8 (usually 1 or 2) distinct voxel blocks are resolved with as few probes as
+// possible -- de-duplicated per axis, per-lane block cache first -- and then the 8 voxel loads are issued together.
+// A tap whose block is not allocated reads the empty voxel, exactly like readVoxel.
+__device__ __forceinline__ void gather_taps(const VolumeRef &vol, int x, int y, int z, IndexCache &c, uint2 t[8]) {
+  const int bx0 = x >> 3, by0 = y >> 3, bz0 = z >> 3;  // arithmetic shift = floor division, as pointToVoxelBlockPos
+  const int bx1 = (x + 1) >> 3, by1 = (y + 1) >> 3, bz1 = (z + 1) >> 3;
+  const bool sx = bx1 == bx0, sy = by1 == by0, sz = bz1 == bz0;
+  int p[8];
+  p[0] = lookup_block(vol, bx0, by0, bz0, c);
+  p[1] = sx ? p[0] : lookup_block(vol, bx1, by0, bz0, c);
+  p[2] = sy ? p[0] : lookup_block(vol, bx0, by1, bz0, c);
+  p[3] = sx ? p[2] : (sy ? p[1] : lookup_block(vol, bx1, by1, bz0, c));
+  p[4] = sz ? p[0] : lookup_block(vol, bx0, by0, bz1, c);
+  p[5] = sz ? p[1] : (sx ? p[4] : lookup_block(vol, bx1, by0, bz1, c));
+  p[6] = sz ? p[2] : (sy ? p[4] : lookup_block(vol, bx0, by1, bz1, c));
+  p[7] = sz ? p[3] : (sx ? p[6] : (sy ? p[5] : lookup_block(vol, bx1, by1, bz1, c)));
+  const int lx0 = x & 7, lx1 = (x + 1) & 7, ly0 = (y & 7) * kBlock, ly1 = ((y + 1) & 7) * kBlock;
+  const int lz0 = (z & 7) * kBlock * kBlock, lz1 = ((z + 1) & 7) * kBlock * kBlock;
+  const int lin[8] = {lx0 + ly0 + lz0, lx1 + ly0 + lz0, lx0 + ly1 + lz0, lx1 + ly1 + lz0,
+                      lx0 + ly0 + lz1, lx1 + ly0 + lz1, lx0 + ly1 + lz1, lx1 + ly1 + lz1};
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    // clamp the address so the load is unconditional (and therefore batched); select afterwards
+    const uint2 v = vol.voxels[(size_t)(p[k] >= 0 ? p[k] : 0) + lin[k]];
+    t[k] = (p[k] >= 0) ? v : make_uint2(kEmptyVoxelLo, kEmptyVoxelHi);
+  }
+}
+
+// a / b via the correctly rounded reciprocal y = RN(1/b): exactly RN(a/b) for b = 32767 (0 mismatches over every
+// finite float a, tests/tools/verify_exact_div.cpp); 3 instructions instead of the ~10 of an IEEE division
+__device__ __forceinline__ float div_exact(float a, float b, float y) {
+  const float q = a * y;
+  const float r = __fmaf_rn(-b, q, a);
+  return __fmaf_rn(r, y, q);
+}
+
+__device__ __forceinline__ float trilinear_sdf(const uint2 t[8], float cx, float cy, float cz) {
+  float s[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) s[k] = (float)(short)(t[k].x & 0xffffu);
+  float res1 = (1.0f - cx) * s[0] + cx * s[1];
+  res1 = (1.0f - cy) * res1 + cy * ((1.0f - cx) * s[2] + cx * s[3]);
+  float res2 = (1.0f - cx) * s[4] + cx * s[5];
+  res2 = (1.0f - cy) * res2 + cy * ((1.0f - cx) * s[6] + cx * s[7]);
+  return div_exact((1.0f - cz) * res1 + cz * res2, 32767.0f, 1.0f / 32767.0f);
+}
+
+// The 8 taps (low voxel words) of the trilinear cell at (x0, y0, z0) in two load round trips: every block of the
+// cell resolved together, then the 8 taps together; a tap whose block is not allocated reads the empty voxel.
+__device__ __forceinline__ void gather_taps_batched(const VolumeRef &vol, int x0, int y0, int z0, unsigned raw[8]) {
+  const int bxa[2] = {x0 >> 3, (x0 + 1) >> 3}, bya[2] = {y0 >> 3, (y0 + 1) >> 3}, bza[2] = {z0 >> 3, (z0 + 1) >> 3};
+  int base[8];
+  resolve_cell_blocks(vol, bxa, bya, bza, base);
+  const unsigned lx[2] = {(unsigned)x0 & 7u, (unsigned)(x0 + 1) & 7u};
+  const unsigned ly[2] = {((unsigned)y0 & 7u) << 3, ((unsigned)(y0 + 1) & 7u) << 3};
+  const unsigned lz[2] = {((unsigned)z0 & 7u) << 6, ((unsigned)(z0 + 1) & 7u) << 6};
+  const char *vbytes = reinterpret_cast<const char *>(vol.voxels);
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const unsigned lin = lx[k & 1] | ly[(k >> 1) & 1] | lz[k >> 2];
+    const unsigned off = (base[k] < 0) ? 0u : ((unsigned)base[k] + lin) * 8u;
+    raw[k] = *reinterpret_cast<const unsigned *>(vbytes + off);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; k++) raw[k] = (base[k] < 0) ? kEmptyVoxelLo : raw[k];
+}
+
+__device__ __forceinline__ float trilinear_raw(const unsigned raw[8], float cx, float cy, float cz) {
+  uint2 t[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) t[k] = make_uint2(raw[k], 0u);
+  return trilinear_sdf(t, cx, cy, cz);
+}
+
+// readFromSDF_float_interpolated; same values as read_sdf_interp, two round trips instead of up to nine
+__device__ __forceinline__ float read_sdf_interp_batched(const VolumeRef &vol, const Vec3 &pt) {
+  const float fx = floorf(pt.x), fy = floorf(pt.y), fz = floorf(pt.z);
+  unsigned raw[8];
+  gather_taps_batched(vol, (int)fx, (int)fy, (int)fz, raw);
+  return trilinear_raw(raw, pt.x - fx, pt.y - fy, pt.z - fz);
+}
+
+__device__ __forceinline__ float read_sdf_interp(const VolumeRef &vol, const Vec3 &pt, bool &found, IndexCache &c) {
+  const float fx = floorf(pt.x), fy = floorf(pt.y), fz = floorf(pt.z);
+  const int x = (int)fx, y = (int)fy, z = (int)fz;
+  const float cx = pt.x - fx, cy = pt.y - fy, cz = pt.z - fz;
+  uint2 t[8];
+  gather_taps(vol, x, y, z, c, t);
+  found = true;
+  return trilinear_sdf(t, cx, cy, cz);
+}
+
+__device__ __forceinline__ Vec4 read_colour_interp(const VolumeRef &vol, const Vec3 &pt, IndexCache &c) {
+  const float fx = floorf(pt.x), fy = floorf(pt.y), fz = floorf(pt.z);
+  const int x = (int)fx, y = (int)fy, z = (int)fz;
+  const float cx = pt.x - fx, cy = pt.y - fy, cz = pt.z - fz;
+  float rx = 0.0f, ry = 0.0f, rz = 0.0f;
+  uint2 t[8];
+  gather_taps(vol, x, y, z, c, t);
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int ox = k & 1, oy = (k >> 1) & 1, oz = (k >> 2) & 1;
+    const uint2 v = t[k];
+    const float wx = ox ? cx : (1.0f - cx), wy = oy ? cy : (1.0f - cy), wz = oz ? cz : (1.0f - cz);
+    const float w = wx * wy * wz;
+    rx += w * (float)(v.x >> 24);
+    ry += w * (float)(v.y & 0xffu);
+    rz += w * (float)((v.y >> 8) & 0xffu);
+  }
+  Vec4 r = {rx / 255.0f, ry / 255.0f, rz / 255.0f, 255.0f / 255.0f};
+  return r;
+}
+
+// computeSingleNormalFromSDF (un-normalised gradient)
+__device__ __forceinline__ Vec3 normal_from_sdf(const VolumeRef &vol, const Vec3 &pt, IndexCache &c) {
+  bool f;
+  Vec3 ret;
+  const float flx = floorf(pt.x), fly = floorf(pt.y), flz = floorf(pt.z);
+  const int x = (int)flx, y = (int)fly, z = (int)flz;
+  const float cx = pt.x - flx, cy = pt.y - fly, cz = pt.z - flz;
+  const float nx = 1.0f - cx, ny = 1.0f - cy, nz = 1.0f - cz;
+  Vec4 front, back, tmp;
+  front.x = rd_sdf(vol, x, y, z, f, c); front.y = rd_sdf(vol, x + 1, y, z, f, c);
+  front.z = rd_sdf(vol, x, y + 1, z, f, c); front.w = rd_sdf(vol, x + 1, y + 1, z, f, c);
+  back.x = rd_sdf(vol, x, y, z + 1, f, c); back.y = rd_sdf(vol, x + 1, y, z + 1, f, c);
+  back.z = rd_sdf(vol, x, y + 1, z + 1, f, c); back.w = rd_sdf(vol, x + 1, y + 1, z + 1, f, c);
+  float p1, p2, v1;
+  // gradient x
+  p1 = front.x * ny * nz + front.z * cy * nz + back.x * ny * cz + back.z * cy * cz;
+  tmp.x = rd_sdf(vol, x - 1, y, z, f, c); tmp.y = rd_sdf(vol, x - 1, y + 1, z, f, c);
+  tmp.z = rd_sdf(vol, x - 1, y, z + 1, f, c); tmp.w = rd_sdf(vol, x - 1, y + 1, z + 1, f, c);
+  p2 = tmp.x * ny * nz + tmp.y * cy * nz + tmp.z * ny * cz + tmp.w * cy * cz;
+  v1 = p1 * cx + p2 * nx;
+  p1 = front.y * ny * nz + front.w * cy * nz + back.y * ny * cz + back.w * cy * cz;
+  tmp.x = rd_sdf(vol, x + 2, y, z, f, c); tmp.y = rd_sdf(vol, x + 2, y + 1, z, f, c);
+  tmp.z = rd_sdf(vol, x + 2, y, z + 1, f, c); tmp.w = rd_sdf(vol, x + 2, y + 1, z + 1, f, c);
+  p2 = tmp.x * ny * nz + tmp.y * cy * nz + tmp.z * ny * cz + tmp.w * cy * cz;
+  ret.x = (p1 * nx + p2 * cx - v1) / 32767.0f;
+  // gradient y
+  p1 = front.x * nx * nz + front.y * cx * nz + back.x * nx * cz + back.y * cx * cz;
+  tmp.x = rd_sdf(vol, x, y - 1, z, f, c); tmp.y = rd_sdf(vol, x + 1, y - 1, z, f, c);
+  tmp.z = rd_sdf(vol, x, y - 1, z + 1, f, c); tmp.w = rd_sdf(vol, x + 1, y - 1, z + 1, f, c);
+  p2 = tmp.x * nx * nz + tmp.y * cx * nz + tmp.z * nx * cz + tmp.w * cx * cz;
+  v1 = p1 * cy + p2 * ny;
+  p1 = front.z * nx * nz + front.w * cx * nz + back.z * nx * cz + back.w * cx * cz;
+  tmp.x = rd_sdf(vol, x, y + 2, z, f, c); tmp.y = rd_sdf(vol, x + 1, y + 2, z, f, c);
+  tmp.z = rd_sdf(vol, x, y + 2, z + 1, f, c); tmp.w = rd_sdf(vol, x + 1, y + 2, z + 1, f, c);
+  p2 = tmp.x * nx * nz + tmp.y * cx * nz + tmp.z * nx * cz + tmp.w * cx * cz;
+  ret.y = (p1 * ny + p2 * cy - v1) / 32767.0f;
+  // gradient z
+  p1 = front.x * nx * ny + front.y * cx * ny + front.z * nx * cy + front.w * cx * cy;
+  tmp.x = rd_sdf(vol, x, y, z - 1, f, c); tmp.y = rd_sdf(vol, x + 1, y, z - 1, f, c);
+  tmp.z = rd_sdf(vol, x, y + 1, z - 1, f, c); tmp.w = rd_sdf(vol, x + 1, y + 1, z - 1, f, c);
+  p2 = tmp.x * nx * ny + tmp.y * cx * ny + tmp.z * nx * cy + tmp.w * cx * cy;
+  v1 = p1 * cz + p2 * nz;
+  p1 = back.x * nx * ny + back.y * cx * ny + back.z * nx * cy + back.w * cx * cy;
+  tmp.x = rd_sdf(vol, x, y, z + 2, f, c); tmp.y = rd_sdf(vol, x + 1, y, z + 2, f, c);
+  tmp.z = rd_sdf(vol, x, y + 1, z + 2, f, c); tmp.w = rd_sdf(vol, x + 1, y + 1, z + 2, f, c);
+  p2 = tmp.x * nx * ny + tmp.y * cx * ny + tmp.z * nx * cy + tmp.w * cx * cy;
+  ret.z = (p1 * nz + p2 * cz - v1) / 32767.0f;
+  return ret;
+}
+
+}  // namespace dslam

@@ -304,7 +304,8 @@ class ITMMainEngine {
   };
 
   ITMMainEngine(const ITMLibSettings *settings_, const ITMRGBDCalib *calib, Vector2i imgSize_rgb, Vector2i imgSize_d = Vector2i(-1, -1))
-      : settings(settings_), view(nullptr), engine_(nullptr), freeviewScene_(nullptr), renderState_freeview_(nullptr) {
+      : settings(settings_), view(nullptr), engine_(nullptr), freeviewScene_(nullptr), renderState_freeview_(nullptr),
+        renderState_allmaps_(nullptr) {
     if (imgSize_d.x == -1 || imgSize_d.y == -1) imgSize_d = imgSize_rgb;
     dslam_check(dslam_engine_create(settings->hipDeviceIndex, &engine_), "dslam_engine_create");
     // calls enqueue; the calls that hand data to the host wait (see the head of this file)
@@ -320,6 +321,7 @@ class ITMMainEngine {
   }
   virtual ~ITMMainEngine() {
     delete renderState_freeview_;
+    delete renderState_allmaps_;
     delete mActiveDataManger; delete mapManager; delete visualisationEngine; delete trackingController;
     delete viewBuilder; delete denseMapper; delete view;
     dslam_engine_destroy(engine_);
@@ -374,6 +376,47 @@ class ITMMainEngine {
     if (deferred_) dslam_check(dslam_engine_synchronize(engine_), "dslam_engine_synchronize");
   }
 
+  /// (extension) The whole reconstruction in one image: every local map of mapManager drawn through its
+  /// estimatedGlobalPose.GetM() (Tdw, DenseSlam.cpp:190,577-579) from `pose` in the global frame -- the reference's
+  /// previews draw currentLocalMap only (DenseSlam.h:146-164).  FREECAMERA_* types as GetImage; other types and a call
+  /// before the first local map do nothing.  dslam_get_image_multi, combination law in DESIGN.md section 10.
+  void GetImageAllLocalMaps(ITMUChar4Image *out, ITMFloatImage *outFloat, GetImageType type, ITMPose *pose,
+                            ITMIntrinsics *intrinsics) {
+    const int n = mapManager->numLocalMaps();
+    if (n == 0 || pose == nullptr || intrinsics == nullptr) return;
+    if (n > DSLAM_MAX_RENDER_MAPS)
+      throw std::runtime_error("GetImageAllLocalMaps: " + std::to_string(n) + " local maps, at most " +
+                               std::to_string(DSLAM_MAX_RENDER_MAPS) + " can be drawn in one image");
+    int t;
+    switch (type) {
+      case InfiniTAM_IMAGE_FREECAMERA_SHADED: t = DSLAM_IMAGE_SHADED; break;
+      case InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME: t = DSLAM_IMAGE_COLOUR_FROM_VOLUME; break;
+      case InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL: t = DSLAM_IMAGE_COLOUR_FROM_NORMAL; break;
+      case InfiniTAM_IMAGE_FREECAMERA_DEPTH: t = DSLAM_IMAGE_DEPTH; break;
+      default: return;
+    }
+    const Vector2i sz = (t == DSLAM_IMAGE_DEPTH) ? (outFloat ? outFloat->noDims : Vector2i(0, 0)) : (out ? out->noDims : Vector2i(0, 0));
+    if (sz.x <= 0) return;
+    const ITMLocalMap *first = mapManager->getLocalMap(0);
+    if (renderState_allmaps_ == nullptr || allmapsSize_.x != sz.x || allmapsSize_.y != sz.y) {
+      delete renderState_allmaps_;
+      renderState_allmaps_ = visualisationEngine->CreateRenderState(first->scene, sz);
+      allmapsSize_ = sz;
+    }
+    std::vector<const dslam_scene *> scenes(n);
+    std::vector<float> T((size_t)n * 16);
+    for (int i = 0; i < n; i++) {
+      const ITMLocalMap *m = mapManager->getLocalMap(i);
+      scenes[i] = m->scene->handle;
+      memcpy(&T[(size_t)i * 16], m->estimatedGlobalPose.GetM().m, 16 * sizeof(float));
+    }
+    dslam_check(dslam_get_image_multi(engine_, scenes.data(), T.data(), n, renderState_allmaps_->handle, pose->GetM().m,
+                                      intrinsics->projectionParamsSimple.all.v, t,
+                                      t == DSLAM_IMAGE_DEPTH ? nullptr : &out->GetData(MEMORYDEVICE_CPU)->x,
+                                      t == DSLAM_IMAGE_DEPTH ? outFloat->GetData(MEMORYDEVICE_CPU) : nullptr), "dslam_get_image_multi");
+    if (deferred_) dslam_check(dslam_engine_synchronize(engine_), "dslam_engine_synchronize");
+  }
+
   /// SaveCurrSceneToMesh(objFileName, scene) (DenseSlam.cpp:641): meshingEngine->MeshScene(mesh, scene), then
   /// mesh->WriteOBJ(objFileName).  The marching cubes run on the device; the triangle list comes back in the order
   /// of upstream's CPU engine, so the file is the same from run to run.
@@ -413,6 +456,8 @@ class ITMMainEngine {
   const ITMScene<ITMVoxel, ITMVoxelIndex> *freeviewScene_;
   ITMRenderState *renderState_freeview_;
   Vector2i freeviewSize_;
+  ITMRenderState *renderState_allmaps_;   ///< GetImageAllLocalMaps' own render state
+  Vector2i allmapsSize_;
 };
 
 }  // namespace Engine

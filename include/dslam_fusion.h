@@ -45,6 +45,8 @@ extern "C" {
 #define DSLAM_DEFAULT_EXCESS_LIST_SIZE 0x20000 /* SDF_EXCESS_LIST_SIZE */
 #define DSLAM_TRANSFER_BLOCK_NUM 0x1000       /* SDF_TRANSFER_BLOCK_NUM */
 #define DSLAM_MAX_RENDERING_BLOCKS (65536 * 4)
+/* local maps one dslam_get_image_multi call can draw (a bit each in a 64-bit mask per 8x8 pixel tile) */
+#define DSLAM_MAX_RENDER_MAPS 64
 
 typedef enum {
   DSLAM_OK = 0,
@@ -419,6 +421,23 @@ int dslam_render_image(dslam_engine *e, const dslam_scene *s, dslam_render_state
 int dslam_get_image(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
                     const float intrinsics[4], int image_type, uint8_t *out_rgba_host,
                     float *out_float_host);
+/* A view of the whole reconstruction: every local map of the map graph in one raycast, each read through its
+ * estimatedGlobalPose.  The reference creates local maps (createNewLocalMap, DenseSlam.cpp:133-141; shouldStartNewLocalMap,
+ * :260-261, :554-565) and counts them in the GUI (DenseSLAMGUI.cpp:290), but every preview draws currentLocalMap only
+ * (DenseSlam.h:146-164, InfiniTamDriver.cpp:229-277) and the export writes one mesh per map (SystemEntry.cpp:365-369).
+ * scenes[i] is seen through T_map_from_world[16 i .. 16 i + 15] (column-major, metres: the Tdw = estimatedGlobalPose.GetM()
+ * of DenseSlam.cpp:190, 577-579), i.e. from the camera M T_i^-1.  Every read of the march at a world point p goes to each
+ * map whose blocks project into p's 8x8 tile, at T_i p; the maps that hold the voxel are combined: one -> its value
+ * unchanged, several -> sum(w_i v_i) / sum(w_i) in list order, w = w_depth (sdf, normal) or w_color (colour), trilinear
+ * where the read is.  A list of one map at the identity draws exactly what dslam_get_image draws.
+ * Same image types, outputs (host, dslam_host_alloc, both NULL: the device image) and async behaviour as dslam_get_image;
+ * the render-tile budget (MAX_RENDERING_BLOCKS) is not applied.  The render state's visible list is not touched; its
+ * GetImage memo is dropped.  DSLAM_ERR_INVALID: num_maps outside 1 .. DSLAM_MAX_RENDER_MAPS, a NULL scene, a scene of
+ * another engine or with another voxel_size / mu than scenes[0], a singular M or T_i, or a scene whose num_local_blocks
+ * exceeds the render state's visible-list capacity. */
+int dslam_get_image_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world,
+                          int num_maps, dslam_render_state *r, const float M[16], const float intrinsics[4],
+                          int image_type, uint8_t *out_rgba_host, float *out_float_host);
 /* trackingController->Prepare(trackingState, scene, view, renderState) (InfiniTamDriver.h:208-220):
  * CreateExpectedDepths + CreateICPMaps from the render state's own visible list.  Outputs are
  * Vector4f per pixel (points: metres, world frame, w = 1 or -1; normals: w = 0 or -1); may be NULL. */
