@@ -354,6 +354,12 @@ class CApi:
         self._call("debug_stream_launches", self._engine, C.byref(n))
         return n.value
 
+    def debug_front_end_counts(self):
+        """(fusion launches that computed GetImage's front end, GetImage calls that took it)"""
+        computed, adopted = C.c_longlong(0), C.c_longlong(0)
+        self._call("debug_front_end_counts", self._engine, C.byref(computed), C.byref(adopted))
+        return computed.value, adopted.value
+
     def reintegrate_batch_stats(self, scene):
         """(blocks the last batch loaded, its block-operations: (block, keyframe) pairs de-integrated or re-fused) -- HIP engine"""
         b, o = C.c_int32(0), C.c_int32(0)

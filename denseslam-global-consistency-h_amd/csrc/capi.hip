@@ -252,6 +252,7 @@ int dslam_engine_create(int device_index, dslam_engine **out) {
   DSLAM_HIP(hipSetDevice(device_index));
   dslam_engine *e = new dslam_engine();
   e->device = device_index;
+  if (const char *v = getenv("DSLAM_SPECULATIVE_FRONT_END")) e->speculate_front = atoi(v) != 0;
   const int rc = engine_allocate(e);
   if (rc) {
     (void)dslam_engine_destroy(e);
@@ -322,6 +323,12 @@ int dslam_debug_stream_launches(dslam_engine *e, long long *count_out) {
   return DSLAM_OK;
 }
 
+int dslam_debug_front_end_counts(dslam_engine *e, long long *computed_out, long long *adopted_out) {
+  DSLAM_REQUIRE(e && computed_out && adopted_out, "null argument");
+  *computed_out = e->front_launches;
+  *adopted_out = e->front_adoptions;
+  return DSLAM_OK;
+}
 int dslam_debug_inject_device_error(dslam_engine *e, dslam_scene *s, int bits) {
   DSLAM_REQUIRE(e && s && s->engine == e && (bits == 1 || bits == 2 || bits == 3), "bad argument");
   int rc = launch_inject_error(e, s, bits);
@@ -460,6 +467,48 @@ int dslam_scene_create(dslam_engine *e, const dslam_scene_params *p, void *ext_v
   return DSLAM_OK;
 }
 
+static void free_front_end(FrontEndRecord *&f) {
+  if (f) {
+    free_dev(f->visible_ids); free_dev(f->proj_boxes); free_dev(f->proj_z); free_dev(f->proj_req); free_dev(f->proj_wg_tiles);
+    free_dev(f->range); free_dev(f->counters);
+    delete f;
+    f = nullptr;
+  }
+}
+
+static int front_end_allocate(dslam_engine *e, FrontEndRecord *f) {
+  DSLAM_HIP(hipMalloc(&f->visible_ids, (size_t)f->n_local * sizeof(int)));
+  DSLAM_HIP(hipMalloc(&f->proj_boxes, (size_t)f->n_local * sizeof(int4)));
+  DSLAM_HIP(hipMalloc(&f->proj_z, (size_t)f->n_local * sizeof(float2)));
+  DSLAM_HIP(hipMalloc(&f->proj_req, (size_t)f->n_local * sizeof(int)));
+  DSLAM_HIP(hipMalloc(&f->proj_wg_tiles, (size_t)(f->n_entries / 1024 + 1024) * sizeof(int)));
+  DSLAM_HIP(hipMalloc(&f->range, (size_t)f->w * f->h * sizeof(float2)));
+  DSLAM_HIP(hipMalloc(&f->counters, sizeof(RenderCounters)));
+  DSLAM_HIP(hipMemsetAsync(f->counters, 0, sizeof(RenderCounters), e->stream));
+  return DSLAM_OK;
+}
+
+// the scene's FrontEndRecord with buffers the size of r's (GetImage adopts them by exchanging pointers with its render
+// state, so they are sized like a render state's: render_state_allocate)
+static int front_end_for(dslam_engine *e, dslam_scene *s, const dslam_render_state *r, FrontEndRecord **out) {
+  FrontEndRecord *f = s->front;
+  if (f && f->w == r->w && f->h == r->h && f->n_local == r->n_local && f->n_entries == r->n_entries) {
+    *out = f;
+    return DSLAM_OK;
+  }
+  DSLAM_HIP(hipStreamSynchronize(e->stream));   // (the old buffers may still be in use)
+  free_front_end(s->front);
+  // attached to the scene only complete: a failed allocation leaves the scene without a record, never with part of one
+  f = new FrontEndRecord();
+  f->w = r->w; f->h = r->h; f->n_local = r->n_local; f->n_entries = r->n_entries;
+  if (const int rc = front_end_allocate(e, f)) {
+    free_front_end(f);
+    return rc;
+  }
+  *out = s->front = f;
+  return DSLAM_OK;
+}
+
 int dslam_scene_destroy(dslam_scene *s) {
   if (!s) return DSLAM_OK;
   (void)hipStreamSynchronize(s->engine->stream);
@@ -477,6 +526,7 @@ int dslam_scene_destroy(dslam_scene *s) {
   for (uint4 *slab : s->slabs) (void)hipHostFree(slab);
   if (s->next_slot_host) (void)hipHostFree(s->next_slot_host);
   free_dev(s->slot_dev);
+  free_front_end(s->front);
   delete s;
   return DSLAM_OK;
 }
@@ -1318,8 +1368,17 @@ int dslam_process_frame(dslam_engine *e, dslam_scene *s, const dslam_view *v, ds
   if (rc) return rc;
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   if (r) r->memo_valid = false;
+  // GetImage's front end for this pose (FrontEndRecord): not with swapping, whose passes change the table behind the fusion
+  FrontEndRecord *front = nullptr;
+  if (s->front) s->front->valid = false;
+  if (e->speculate_front && !s->p.use_swapping && r->n_entries == s->n_entries && (rc = front_end_for(e, s, r, &front))) return rc;
   if ((rc = launch_allocate(e, s, v, r, M_d, intr_d, only_visible))) return rc;
-  if ((rc = launch_integrate(e, s, v, r, M_d, intr_d, M_rgb, intr_rgb, false, is_defusion ? 1 : 0))) return rc;
+  if ((rc = launch_integrate(e, s, v, r, M_d, intr_d, M_rgb, intr_rgb, false, is_defusion ? 1 : 0, front))) return rc;
+  if (front && front->valid) {
+    front->version = s->version;
+    memcpy(front->M, M_d, sizeof(front->M));
+    memcpy(front->intr, intr_d, sizeof(front->intr));
+  }
   if (s->p.use_swapping) {
     if ((rc = launch_swap_in(e, s, r))) return rc;
     if ((rc = launch_swap_out(e, s, r, false))) return rc;

@@ -127,20 +127,28 @@ inline TileChain next_chain(dslam_engine *e, int n_tiles, int *grid_out, bool se
 // FindVisibleBlocks where this one takes 12.8: merely fused, with the look-back in place of the boundary, it took 14.4; the
 // staging is what the fusion made possible.  Other shapes measured: 512 threads x 4096 entries
 // 15.2 us (twice the tickets), 1024 x 4096 20.7 us (two 1024-thread workgroups do not share a CU).
-template <class Sel>
-__global__ __launch_bounds__(kSelThreads) void k_bits_select(const unsigned *__restrict__ src_bits, Sel sel, int *__restrict__ out,
-                                                             int capacity, int *total_out, int *tile_sum_out, TileChain ch,
-                                                             SceneCounters *err_cnt) {
+// The LDS of one selection tile (a struct, so that a kernel whose workgroups run other jobs too can lay it over its own LDS)
+struct SelLds {
+  static constexpr int kTileEntries = kSelTileWords * 32;
+  int red[kSelThreads / 64];
+  int ticket;
+  unsigned short list[kTileEntries];
+  unsigned pick[kTileEntries / 32];   // verdicts by list position
+  int pref[kTileEntries / 32];
+};
+
+// One workgroup of kSelThreads threads: one tile of the selection (k_bits_select below, and the front-end tiles that ride
+// at the front of the fusion launch, integrate.hip)
+template <class Sel, int BATCH = kSelBatch>
+__device__ __forceinline__ void bits_select_tile(const unsigned *__restrict__ src_bits, Sel sel, int *__restrict__ out,
+                                                 int capacity, int *total_out, int *tile_sum_out, TileChain ch,
+                                                 SceneCounters *err_cnt, int *red, int *s_ticket, unsigned short *s_list,
+                                                 unsigned *s_pick, int *s_pref) {
   constexpr int kWaves = kSelThreads / 64;
-  constexpr int kTileEntries = kSelTileWords * 32;
-  constexpr int kRounds = (kTileEntries + kSelThreads * kSelBatch - 1) / (kSelThreads * kSelBatch);
-  __shared__ int red[kWaves];
-  __shared__ int s_ticket;
-  __shared__ unsigned short s_list[kTileEntries];
-  __shared__ unsigned s_pick[kTileEntries / 32];   // verdicts by list position
-  __shared__ int s_pref[kTileEntries / 32];
+  constexpr int kTileEntries = SelLds::kTileEntries;
+  constexpr int kRounds = (kTileEntries + kSelThreads * BATCH - 1) / (kSelThreads * BATCH);
   const unsigned long long t_start = ch.dbg ? __builtin_amdgcn_s_memtime() : 0ull;
-  const int b = take_ticket(ch.ticket, ch.ticket_base, &s_ticket);
+  const int b = take_ticket(ch.ticket, ch.ticket_base, s_ticket);
   if ((unsigned)b >= (unsigned)ch.n_tiles) return;   // (unsigned: a ticket in front of the host's base must not index anything)
 #define DSLAM_SEL_STAMP(i) do { if (ch.dbg && threadIdx.x == 0) ch.dbg[(size_t)b * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
   if (ch.dbg && threadIdx.x == 0) ch.dbg[(size_t)b * 8] = t_start;
@@ -166,37 +174,37 @@ __global__ __launch_bounds__(kSelThreads) void k_bits_select(const unsigned *__r
   DSLAM_SEL_STAMP(3);
   const int t0 = b * kTileEntries;
   // ---- test: four candidates per lane in flight; the first round's payloads stay in registers for the emit --------------
-  typename Sel::Payload pl0[kSelBatch];
-  int tt0[kSelBatch];
+  typename Sel::Payload pl0[BATCH];
+  int tt0[BATCH];
   unsigned pass0 = 0;
 #pragma unroll
-  for (int q = 0; q < kSelBatch; q++) {
+  for (int q = 0; q < BATCH; q++) {
     const int j = tid + q * kSelThreads;
     tt0[q] = j < tot ? t0 + (int)s_list[j] : -1;
     if (tt0[q] >= 0) pl0[q] = sel.load(tt0[q]);
   }
 #pragma unroll
-  for (int q = 0; q < kSelBatch; q++) {
+  for (int q = 0; q < BATCH; q++) {
     const bool ok = tt0[q] >= 0 && sel.test(tt0[q], pl0[q]);
     pass0 |= ok ? (1u << q) : 0u;
     const unsigned long long m = __ballot(ok);
     if (lane == 0 && m) { const int wi = (tid + q * kSelThreads) >> 5; s_pick[wi] = (unsigned)m; s_pick[wi + 1] = (unsigned)(m >> 32); }
   }
   for (int rd = 1; rd < kRounds; rd++) {
-    if (rd * kSelThreads * kSelBatch >= tot) break;   // (uniform)
-    typename Sel::Payload pl[kSelBatch];
-    int tt[kSelBatch];
+    if (rd * kSelThreads * BATCH >= tot) break;   // (uniform)
+    typename Sel::Payload pl[BATCH];
+    int tt[BATCH];
 #pragma unroll
-    for (int q = 0; q < kSelBatch; q++) {
-      const int j = tid + (rd * kSelBatch + q) * kSelThreads;
+    for (int q = 0; q < BATCH; q++) {
+      const int j = tid + (rd * BATCH + q) * kSelThreads;
       tt[q] = j < tot ? t0 + (int)s_list[j] : -1;
       if (tt[q] >= 0) pl[q] = sel.load(tt[q]);
     }
 #pragma unroll
-    for (int q = 0; q < kSelBatch; q++) {
+    for (int q = 0; q < BATCH; q++) {
       const bool ok = tt[q] >= 0 && sel.test(tt[q], pl[q]);
       const unsigned long long m = __ballot(ok);
-      if (lane == 0 && m) { const int wi = (tid + (rd * kSelBatch + q) * kSelThreads) >> 5; s_pick[wi] = (unsigned)m; s_pick[wi + 1] = (unsigned)(m >> 32); }
+      if (lane == 0 && m) { const int wi = (tid + (rd * BATCH + q) * kSelThreads) >> 5; s_pick[wi] = (unsigned)m; s_pick[wi + 1] = (unsigned)(m >> 32); }
     }
   }
   __syncthreads();
@@ -212,10 +220,10 @@ __global__ __launch_bounds__(kSelThreads) void k_bits_select(const unsigned *__r
   __syncthreads();   // (s_pref)
   DSLAM_SEL_STAMP(5);
   // what an emit can work out without its rank is worked out while the counts travel
-  typename Sel::Staged st0[kSelBatch];
-  int rk0[kSelBatch];
+  typename Sel::Staged st0[BATCH];
+  int rk0[BATCH];
 #pragma unroll
-  for (int q = 0; q < kSelBatch; q++) {
+  for (int q = 0; q < BATCH; q++) {
     const int j = tid + q * kSelThreads;
     rk0[q] = 0;
     if ((pass0 >> q) & 1u) {
@@ -229,17 +237,17 @@ __global__ __launch_bounds__(kSelThreads) void k_bits_select(const unsigned *__r
   // ---- emit -----------------------------------------------------------------------------------------------------------------
   int sum = 0;
 #pragma unroll
-  for (int q = 0; q < kSelBatch; q++) {
+  for (int q = 0; q < BATCH; q++) {
     if (!((pass0 >> q) & 1u)) continue;
     const int r = before + rk0[q];
     if (r < capacity && out) out[r] = tt0[q];
     sum += sel.emit(tt0[q], r, r < capacity, st0[q]);
   }
   for (int rd = 1; rd < kRounds; rd++) {
-    if (rd * kSelThreads * kSelBatch >= tot) break;
+    if (rd * kSelThreads * BATCH >= tot) break;
 #pragma unroll
-    for (int q = 0; q < kSelBatch; q++) {
-      const int j = tid + (rd * kSelBatch + q) * kSelThreads;
+    for (int q = 0; q < BATCH; q++) {
+      const int j = tid + (rd * BATCH + q) * kSelThreads;
       if (j >= tot || !((s_pick[j >> 5] >> (j & 31)) & 1u)) continue;
       const int t = t0 + (int)s_list[j];
       const int r = before + s_pref[j >> 5] + __popc(s_pick[j >> 5] & ((1u << (j & 31)) - 1u));
@@ -268,6 +276,18 @@ __global__ __launch_bounds__(kSelThreads) void k_bits_select(const unsigned *__r
     }
   }
 #undef DSLAM_SEL_STAMP
+}
+
+template <class Sel>
+__global__ __launch_bounds__(kSelThreads) void k_bits_select(const unsigned *__restrict__ src_bits, Sel sel, int *__restrict__ out,
+                                                             int capacity, int *total_out, int *tile_sum_out, TileChain ch,
+                                                             SceneCounters *err_cnt) {
+  __shared__ int red[kSelThreads / 64];
+  __shared__ int s_ticket;
+  __shared__ unsigned short s_list[SelLds::kTileEntries];
+  __shared__ unsigned s_pick[SelLds::kTileEntries / 32];
+  __shared__ int s_pref[SelLds::kTileEntries / 32];
+  bits_select_tile(src_bits, sel, out, capacity, total_out, tile_sum_out, ch, err_cnt, red, &s_ticket, s_list, s_pick, s_pref);
 }
 
 // out[0 .. min(total, capacity)) = the selected entries, ascending; *total_out = min(total, capacity).

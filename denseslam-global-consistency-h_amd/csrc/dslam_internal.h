@@ -47,6 +47,8 @@ struct dslam_engine {
                                        // event a view still waits on (they go when the last such view lets go)
   hipStream_t copy_stream = nullptr;  // pipelined uploads (async mode, page-locked sources): H2D of frame i + 1 under frame i's kernels
   bool async_mode = false;
+  // ProcessFrame computes GetImage's front end for its own pose (FrontEndRecord); DSLAM_SPECULATIVE_FRONT_END=0 turns it off
+  bool speculate_front = true;
   dslam_weight_params wp{0, 1, 1.0f};
   // scratch shared by all scenes of this engine (sized for the largest scene seen)
   int scratch_entries = 0;
@@ -115,6 +117,8 @@ struct dslam_engine {
   // dslam_render_state::vis_hint).  Lowered only by the parity test of those paths.
   int push_job_min = 65536;
   long long stream_launches = 0;      // fusion / de-integration launches that took the streaming instantiation (test hook)
+  long long front_launches = 0;       // fusion launches that computed GetImage's front end (FrontEndRecord; test hook)
+  long long front_adoptions = 0;      // GetImage front ends taken from such a record instead of computed (test hook)
   int render_tile_budget = DSLAM_MAX_RENDERING_BLOCKS;  // MAX_RENDERING_BLOCKS; lowered only by the budget test
   double *icp_partials_host = nullptr;  // depth tracker: per-workgroup partial sums in mapped pinned host memory
   double *icp_partials = nullptr;       // ... and the device address of the same buffer
@@ -126,6 +130,24 @@ struct dslam_engine {
   int mesh_triangles = 0;
   bool mesh_has_colour = false;
   bool mesh_table_ready = false;      // the case table sits in this device's constant memory
+};
+
+// GetImage's front end for the pose of the last ProcessFrame: FindVisibleBlocks with the projections of its blocks and a reset
+// range image, computed by workgroups at the front of that ProcessFrame's fusion launch (they read the table, not the
+// voxels).  A GetImage of the same scene version, pose, intrinsics and image size adopts the buffers -- their pointers
+// are exchanged with the render state's -- and runs only the range pass and the march (raycast.hip).
+struct FrontEndRecord {
+  bool valid = false;
+  unsigned long long version = 0;     // the scene's version after the ProcessFrame
+  float M[16] = {0}, intr[4] = {0};
+  int w = 0, h = 0, n_local = 0, n_entries = 0;   // the sizes of the buffers (= those of the render states they may go to)
+  int *visible_ids = nullptr;
+  int4 *proj_boxes = nullptr;
+  float2 *proj_z = nullptr;
+  int *proj_req = nullptr;
+  int *proj_wg_tiles = nullptr;
+  float2 *range = nullptr;
+  dslam::RenderCounters *counters = nullptr;
 };
 
 struct dslam_scene {
@@ -182,6 +204,7 @@ struct dslam_scene {
   int *alloc_born = nullptr;
   int alloc_born_stamp = 0;
   int dirty_shards = 0, dirty_chunk = 0;  // the layout of the last dslam_shard_dirty_plan
+  FrontEndRecord *front = nullptr;        // allocated by the first ProcessFrame that computes it
 };
 
 struct dslam_render_state {
@@ -313,9 +336,11 @@ int launch_depth_post(dslam_engine *e, short *curr_dev, const unsigned short *pr
 int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_render_state *r, const float *M_d,
                     const float *intr, int only_update_visible_list, int *list_out = nullptr, void *count_out = nullptr);
 // push_ring >= 0: also queue the frame's visible list on that ring (fused into the integrate kernel)
+// front: also compute GetImage's front end for (M_d, intr_d, r's image size) into it, in the same launch, if the fusion
+// runs the plain one-camera kernel (front->valid says whether it did; its buffers are sized for r beforehand)
 int launch_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, const dslam_render_state *r,
                      const float *M_d, const float *intr_d, const float *M_rgb, const float *intr_rgb,
-                     bool deintegrate, int push_ring = -1);
+                     bool deintegrate, int push_ring = -1, FrontEndRecord *front = nullptr);
 // the same kernel over a stored list (count header, ids, expected block positions) instead of a render state's
 int launch_integrate_list(dslam_engine *e, dslam_scene *s, const dslam_view *v, const void *count_header, const int *ids,
                           const short4 *expect_pos, const float *M_d, const float *intr_d, const float *M_rgb,

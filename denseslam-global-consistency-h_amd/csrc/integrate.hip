@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "dslam_internal.h"
+#include "frustum_device.h"
 
 #pragma clang fp contract(off)
 
@@ -56,6 +57,32 @@ __device__ __forceinline__ void vox_store(uint4 *a, const uint4 &v) {
 }
 
 
+// GetImage's front end at the fusion pose (FrontEndRecord, dslam_internal.h): the tiles of k_bits_select<SelFrustum<true>>
+// as the first workgroups of the fusion launch.  They read the bitmap of resident entries and the entries' positions --
+// nothing the block workgroups write -- and store into the record's own buffers.
+struct SelFrustumFront : SelFrustum<true> {
+  int n_wg;   // the selection workgroups of the launch (blockIdx 0 .. n_wg - 1): they alone reset the range image
+  __device__ void prologue() const {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += n_wg * blockDim.x) range[i] = make_float2(kFarAway, kVeryClose);
+  }
+};
+// entries per lane whose loads travel together (k_bits_select: 4): the tile shares the fusion kernel's register budget (64
+// VGPRs at 8 waves per SIMD), and with 4 it spills to scratch (3 and 2 do not)
+#ifndef DSLAM_FRONT_BATCH
+#define DSLAM_FRONT_BATCH 3
+#endif
+constexpr int kFrontBatch = DSLAM_FRONT_BATCH;
+struct FrontEndJob {
+  const unsigned *src_bits;
+  SelFrustumFront sel;
+  int *out;
+  int capacity;
+  int *total_out, *tile_sum_out;
+  TileChain ch;
+  SceneCounters *err_cnt;
+  int wgs;   // selection workgroups in front of the block workgroups (0: none)
+};
+
 struct IntegrateParams {
   const int *visible_ids;
   const RenderCounters *rc;
@@ -89,6 +116,7 @@ struct IntegrateParams {
   // [5 + 4h] chunk 1 updated, [6 + 4h] colour pass done, [7 + 4h] stores issued; [12], [13] shader clock at entry and end;
   // [14] voxel-block slot; [15] XCC id << 32 | HW_ID
   unsigned long long *dbg_waves;
+  FrontEndJob fe;  // (FRONT instantiation only)
 };
 
 // a / b for a divisor whose correctly rounded reciprocal y = RN(1/b) is known: q = RN(a*y), r = a - b*q (exact, FMA),
@@ -657,13 +685,17 @@ __device__ __forceinline__ void push_visible_list_job(const IntegrateParams &p, 
   }
 }
 
-template <bool DEINT, bool SAME_CAM, bool PLAIN = false, bool DIAG = false, bool STREAM = false>
+// FRONT: the first p.fe.wgs workgroups are the tiles of GetImage's front end (FrontEndJob), the block workgroups follow them
+template <bool DEINT, bool SAME_CAM, bool PLAIN = false, bool DIAG = false, bool STREAM = false, bool FRONT = false>
 __global__ __launch_bounds__(kWgWaves * 64, 8) void k_integrate(IntegrateParams p) {
   constexpr bool stream = STREAM;   // (cache policy of the voxel chunks: vox_load2)
   static_assert(!PLAIN || (!DEINT && SAME_CAM && DSLAM_PACKED && DSLAM_COLOUR_QUEUE), "PLAIN is the queued one-camera fusion");
   static_assert(!DIAG || PLAIN, "the per-wave timeline exists for the plain fusion kernel");
+  static_assert(!FRONT || (PLAIN && !DIAG && !STREAM), "the front end rides on the plain fusion launch");
+  static_assert(kWgWaves * 64 == kSelThreads, "a block workgroup and a selection tile are the same shape");
+  const int bid = FRONT ? (int)blockIdx.x - p.fe.wgs : (int)blockIdx.x;   // (block workgroups from 0)
   if constexpr (PLAIN) {
-    if ((int)blockIdx.x >= kIntegrateGrid) { push_visible_list_job(p, (int)blockIdx.x - kIntegrateGrid); return; }
+    if (bid >= kIntegrateGrid) { push_visible_list_job(p, bid - kIntegrateGrid); return; }
   }
   __shared__ float inv_tab[kInvTab];
   [[maybe_unused]] unsigned long long diag_entry = 0, diag_cyc = 0;
@@ -684,10 +716,19 @@ __global__ __launch_bounds__(kWgWaves * 64, 8) void k_integrate(IntegrateParams 
     unsigned char list[kColQueue];
   };
   __shared__ ColQueue col_q[kQueueColour ? kWgWaves : 1];
+  if constexpr (FRONT) {
+    if (bid < 0) {   // a selection tile: its LDS lies over the colour queues
+      static_assert(sizeof(col_q) >= sizeof(SelLds), "the selection's LDS does not fit over the colour queues");
+      SelLds *l = reinterpret_cast<SelLds *>(col_q);
+      bits_select_tile<SelFrustumFront, kFrontBatch>(p.fe.src_bits, p.fe.sel, p.fe.out, p.fe.capacity, p.fe.total_out, p.fe.tile_sum_out, p.fe.ch,
+                       p.fe.err_cnt, l->red, &l->ticket, l->list, l->pick, l->pref);
+      return;
+    }
+  }
   for (int i = threadIdx.x; i < kInvTab; i += kWgWaves * 64) inv_tab[i] = recip_table_entry(i);  // = RN(1 / i)
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * (kWgWaves * 64) + threadIdx.x) >> 6));
+  const int wave = __builtin_amdgcn_readfirstlane((int)((bid * (kWgWaves * 64) + (int)threadIdx.x) >> 6));
   constexpr int n_waves = kIntegrateGrid * kWgWaves;  // (the launch below uses exactly this grid)
   if constexpr (DIAG) {
     if (lane == 0) { p.dbg_waves[(size_t)wave * 16] = diag_entry; p.dbg_waves[(size_t)wave * 16 + 12] = diag_cyc; p.dbg_waves[(size_t)wave * 16 + 1] = wall_clock64(); }
@@ -703,7 +744,7 @@ __global__ __launch_bounds__(kWgWaves * 64, 8) void k_integrate(IntegrateParams 
     id_spec = p.visible_ids[wave + zero];
   }
   const int nvis = p.rc->no_visible;
-  if (p.timer_slot && blockIdx.x == 0 && threadIdx.x == 0) *p.timer_slot = nvis;
+  if (p.timer_slot && bid == 0 && threadIdx.x == 0) *p.timer_slot = nvis;
   DSLAM_STAMP(2);
   // entries per wave and round: the largest group that still gives EVERY wave of the grid a group (floor, not ceil: with
   // 11 k visible blocks on 8192 waves, one full round of single blocks plus a partial second one beats 5.5 k waves of two
@@ -950,6 +991,13 @@ static void fill_params(IntegrateParams &ip, dslam_engine *e, dslam_scene *s, co
   ip.dirty = s->dirty_tracking ? s->dirty : nullptr;
   ip.expect_pos = nullptr;
   ip.spec_ids = 0;
+  ip.fe.wgs = 0;
+}
+
+// the fusion runs the plain kernel (k_integrate<..., PLAIN>): none of the optional features is in use
+static bool plain_fusion(const IntegrateParams &ip) {
+  return DSLAM_PACKED && DSLAM_COLOUR_QUEUE && ip.same_cam && !ip.expect_pos && ip.num_shards <= 1 && ip.shard_count < 0 &&
+         !ip.dirty && !ip.stop_max && !ip.depth_weighting;
 }
 
 // stream: the launch is expected to be larger than the Infinity Cache (vox_load2)
@@ -976,8 +1024,16 @@ static int launch_integrate_params(dslam_engine *e, IntegrateParams &ip, bool de
     else if (ip.same_cam) hipExtLaunchKernelGGL((k_integrate<true, true>), grid, block, 0, e->stream, ev0, ev1, 0, ip);
     else hipExtLaunchKernelGGL((k_integrate<true, false>), grid, block, 0, e->stream, ev0, ev1, 0, ip);
   } else {
-    const bool plain = DSLAM_PACKED && DSLAM_COLOUR_QUEUE && ip.same_cam && !ip.expect_pos && ip.num_shards <= 1 &&
-                       ip.shard_count < 0 && !ip.dirty && !ip.stop_max && !ip.depth_weighting;
+    const bool plain = plain_fusion(ip);
+    if constexpr (DSLAM_PACKED && DSLAM_COLOUR_QUEUE) {   // (the builds without the plain kernel never fill ip.fe)
+      if (ip.fe.wgs > 0) {   // (launch_integrate chose this: plain, not streaming)
+        e->front_launches++;
+        const dim3 grid_front(ip.fe.wgs + kIntegrateGrid + kPushWgs);
+        hipExtLaunchKernelGGL((k_integrate<false, true, true, false, false, true>), grid_front, block, 0, e->stream, ev0, ev1, 0, ip);
+        DSLAM_HIP(hipGetLastError());
+        return DSLAM_OK;
+      }
+    }
     // diagnostics: the per-wave timeline of one launch, well into the run (DSLAM_DBG_INTEGRATE=<file>)
     static const char *dbg_file = getenv("DSLAM_DBG_INTEGRATE");
     static int dbg_calls = 0;
@@ -1008,7 +1064,7 @@ static int launch_integrate_params(dslam_engine *e, IntegrateParams &ip, bool de
 
 int launch_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, const dslam_render_state *r,
                      const float *M_d, const float *intr_d, const float *M_rgb, const float *intr_rgb,
-                     bool deintegrate, int push_ring) {
+                     bool deintegrate, int push_ring, FrontEndRecord *front) {
   int rc = ensure_view_depth(e, v);
   if (rc) return rc;
   IntegrateParams ip;
@@ -1022,6 +1078,25 @@ int launch_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, const
   }
   // (the visible count as the host last heard of it: dslam_render_state::vis_hint)
   const bool stream = r->vis_hint && __atomic_load_n(r->vis_hint, __ATOMIC_RELAXED) >= e->push_job_min;
+  // GetImage's front end for this pose rides at the front of the launch.  Only on the plain kernel at the small V of a frame:
+  // a streaming launch is hundreds of microseconds long and the selection's 12 us do not matter there.  (Not with the
+  // per-wave timeline of DSLAM_DBG_INTEGRATE either: that launch is the plain kernel alone.)
+  static const bool dbg_integrate = getenv("DSLAM_DBG_INTEGRATE") != nullptr;
+  if (front) front->valid = false;
+  if (front && !deintegrate && plain_fusion(ip) && !stream && !dbg_integrate && r->n_entries == s->n_entries &&
+      front->n_entries == s->n_entries && front->n_local == r->n_local && front->w == r->w && front->h == r->h) {
+    if ((rc = ensure_scratch(e, s->n_entries, s->p.num_local_blocks))) return rc;
+    int grid;
+    const TileChain ch = next_chain(e, select_tiles(s->n_entries), &grid);
+    SelFrustumFront sel;
+    static_cast<SelFrustum<true> &>(sel) = SelFrustum<true>{s->hash, make_frustum_params(s, r, M_d, intr_d), front->proj_boxes,
+                                                             front->proj_z, front->proj_req, front->range, r->w * r->h};
+    sel.n_wg = grid;
+    ip.fe.src_bits = s->alloc_bits; ip.fe.sel = sel; ip.fe.out = front->visible_ids; ip.fe.capacity = r->n_local;
+    ip.fe.total_out = &front->counters->no_visible; ip.fe.tile_sum_out = front->proj_wg_tiles; ip.fe.ch = ch;
+    ip.fe.err_cnt = s->counters; ip.fe.wgs = grid;
+    front->valid = true;
+  }
   return launch_integrate_params(e, ip, deintegrate, stream);
 }
 

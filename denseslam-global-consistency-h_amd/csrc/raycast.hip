@@ -10,6 +10,7 @@
 // and -- mostly -- the marched blocks are wave-uniform.
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 
 #include "dslam_bits.h"
 #include "raycast_device.h"
@@ -265,6 +266,24 @@ int launch_find_visible_and_depths(dslam_engine *e, const dslam_scene *s, dslam_
   DSLAM_REQUIRE(r->n_entries == N, "render state was created for a different scene size");
   int rc = ensure_scratch(e, N, s->p.num_local_blocks);
   if (rc) return rc;
+  // The last ProcessFrame computed this selection already (FrontEndRecord): same map, pose, intrinsics and image size.  The
+  // render state takes its buffers -- the list, its count, the projections, the per-tile totals, the reset range image --
+  // and gives its own in exchange (the same sizes), all on the engine's one stream.
+  if (FrontEndRecord *f = s->front) {
+    if (f->valid && f->version == s->version && f->w == r->w && f->h == r->h && f->n_local == r->n_local &&
+        f->n_entries == r->n_entries && memcmp(f->M, M, sizeof(f->M)) == 0 && memcmp(f->intr, intr, sizeof(f->intr)) == 0) {
+      std::swap(r->visible_ids, f->visible_ids);
+      std::swap(r->counters, f->counters);
+      std::swap(r->proj_boxes, f->proj_boxes);
+      std::swap(r->proj_z, f->proj_z);
+      std::swap(r->proj_req, f->proj_req);
+      std::swap(r->proj_wg_tiles, f->proj_wg_tiles);
+      std::swap(r->range, f->range);
+      f->valid = false;
+      e->front_adoptions++;
+      return launch_fill_range(e, r, select_tiles(N));
+    }
+  }
   SelFrustum<true> sel{s->hash, make_frustum_params(s, r, M, intr), r->proj_boxes, r->proj_z, r->proj_req, r->range, r->w * r->h};
   launch_bits_select(e, s->alloc_bits, N, sel, r->visible_ids, r->n_local, &r->counters->no_visible, s->counters, r->proj_wg_tiles);
   return launch_fill_range(e, r, select_tiles(N));

@@ -185,6 +185,9 @@ int dslam_debug_set_render_tile_budget(dslam_engine *e, int budget);
 int dslam_debug_set_push_job_min(dslam_engine *e, int min_visible_blocks);
 /* Test hook: how many fusion / de-integration launches of this engine took the streaming (non-temporal) instantiation. */
 int dslam_debug_stream_launches(dslam_engine *e, long long *count_out);
+/* Test hook: how many fusion launches of this engine also computed GetImage's front end for their pose (ProcessFrame,
+ * unless DSLAM_SPECULATIVE_FRONT_END=0), and how many GetImage calls took such a result instead of computing it. */
+int dslam_debug_front_end_counts(dslam_engine *e, long long *computed_out, long long *adopted_out);
 /* Test hook: a one-thread kernel reports the given device-side error bits for the scene (1: allocation ray longer than the
  * order key encodes, 2: a tile count never arrived) exactly as a failing pass would (report_error, csrc/dslam_device.h), so
  * that the way such an error reaches the caller can be tested: returned by this very call on a synchronous engine, by the
