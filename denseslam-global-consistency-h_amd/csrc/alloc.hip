@@ -963,9 +963,9 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   mp.dbg = nullptr;
   static const char *dbg_mark_file = getenv("DSLAM_DBG_MARK");
   static int dbg_mark_calls = 0;
-  unsigned long long *dbg_mark_host = nullptr;
+  PinnedBuffer<unsigned long long> dbg_mark_host;
   if (dbg_mark_file && ++dbg_mark_calls == 60) {
-    DSLAM_HIP(hipHostMalloc((void **)&dbg_mark_host, (size_t)(mp.retest_wgs + pix_blocks) * 32, hipHostMallocDefault));
+    DSLAM_TRY(dbg_mark_host.alloc((size_t)(mp.retest_wgs + pix_blocks) * 4));
     memset(dbg_mark_host, 0, (size_t)(mp.retest_wgs + pix_blocks) * 32);
     mp.dbg = dbg_mark_host;
   }
@@ -974,7 +974,6 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   if (dbg_mark_host) {
     DSLAM_HIP(hipStreamSynchronize(e->stream));
     if (FILE *f = fopen(dbg_mark_file, "wb")) { fwrite(dbg_mark_host, 32, mp.retest_wgs + pix_blocks, f); fclose(f); }
-    (void)hipHostFree(dbg_mark_host);
   }
   v->depth_dirty = false;
 
@@ -987,7 +986,7 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   sp.rc = count_out ? reinterpret_cast<RenderCounters *>(count_out) : r->counters;
   sp.vis_hint = count_out ? nullptr : r->vis_hint;
   sp.hint_min = e->push_job_min;
-  sp.hint_big = r->vis_hint && __atomic_load_n(r->vis_hint, __ATOMIC_RELAXED) >= e->push_job_min;
+  sp.hint_big = r->vis_hint && __atomic_load_n(r->vis_hint.get(), __ATOMIC_RELAXED) >= e->push_job_min;
   sp.visible_ids = list_out ? list_out : r->visible_ids;
   sp.q1 = mp.q1; sp.q2 = mp.q2; sp.mark = mp.mark; sp.retest = e->bits_retest;
   sp.oq1 = e->bits_q1[oth]; sp.oq2 = e->bits_q2[oth]; sp.omark = e->bits_mark[oth];
@@ -1008,9 +1007,9 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   sp.dbg = nullptr;
   static const char *dbg_file = getenv("DSLAM_DBG_SWEEP");
   static int dbg_calls = 0;
-  unsigned long long *dbg_host = nullptr;
+  PinnedBuffer<unsigned long long> dbg_host;
   if (dbg_file && ++dbg_calls == 60) {
-    DSLAM_HIP(hipHostMalloc((void **)&dbg_host, (size_t)n_tiles * 64, hipHostMallocDefault));
+    DSLAM_TRY(dbg_host.alloc((size_t)n_tiles * 8));
     memset(dbg_host, 0, (size_t)n_tiles * 64);
     sp.dbg = dbg_host;
   }
@@ -1020,7 +1019,6 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   if (dbg_host) {
     DSLAM_HIP(hipStreamSynchronize(e->stream));
     if (FILE *f = fopen(dbg_file, "wb")) { fwrite(dbg_host, 64, n_tiles, f); fclose(f); }
-    (void)hipHostFree(dbg_host);
   }
   if (s->p.use_swapping) {
     SelNeedsBlock sel{s->hash, s->alloc_list, s->alloc_bits, s->counters};

@@ -117,79 +117,51 @@ int tickets_resync(dslam_engine *e) {
   return DSLAM_OK;
 }
 
-template <typename T>
-static void free_dev(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
 int ensure_scratch(dslam_engine *e, int entries, int local_blocks) {
   if (entries <= e->scratch_entries && local_blocks <= e->scratch_local_blocks) return DSLAM_OK;
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   const int N = entries > e->scratch_entries ? entries : e->scratch_entries;
   const int L = local_blocks > e->scratch_local_blocks ? local_blocks : e->scratch_local_blocks;
-  free_dev(e->order_keys); free_dev(e->alloc_type); free_dev(e->block_coords); free_dev(e->tile_counts); free_dev(e->tile_offsets);
-  free_dev(e->list_a); free_dev(e->list_b); free_dev(e->list_c); free_dev(e->list_d); free_dev(e->pos_scratch);
-  free_dev(e->agg);
-  for (int k = 0; k < 2; k++) { free_dev(e->bits_q1[k]); free_dev(e->bits_q2[k]); free_dev(e->bits_mark[k]); }
-  free_dev(e->bits_retest);
-  free_dev(e->rem_flags); free_dev(e->freed_flags); free_dev(e->rem_cand); free_dev(e->maint_flags);
+  EngineScratch n;   // built aside: a failure leaves the engine with the complete old set
+  n.scratch_entries = N; n.scratch_local_blocks = L;
   // order keys and allocType: cleared here once, kept clean by the allocation passes (scenes of different sizes share
   // them, so both start at fixed addresses: a pass only ever touches [0, its entry count) of each)
-  DSLAM_HIP(hipMalloc(&e->order_keys, (size_t)N * 4));
-  DSLAM_HIP(hipMemsetAsync(e->order_keys, 0, (size_t)N * 4, e->stream));
-  DSLAM_HIP(hipMalloc(&e->alloc_type, (size_t)N));
-  DSLAM_HIP(hipMemsetAsync(e->alloc_type, 0, (size_t)N, e->stream));
-  DSLAM_HIP(hipMalloc(&e->block_coords, (size_t)N * sizeof(short4)));
+  DSLAM_TRY(n.order_keys.alloc_zeroed(N, e->stream));
+  DSLAM_TRY(n.alloc_type.alloc_zeroed(N, e->stream));
+  DSLAM_TRY(n.block_coords.alloc(N));
   // the bitmaps of the allocation pass (whole tiles; the alternating sets start clean and are kept clean by the passes)
-  e->bits_words = bit_tiles(N) * kBitTileWords;
-  const size_t bits_bytes = (size_t)e->bits_words * sizeof(unsigned);
+  n.bits_words = bit_tiles(N) * kBitTileWords;
   for (int k = 0; k < 2; k++) {
-    DSLAM_HIP(hipMalloc(&e->bits_q1[k], bits_bytes));
-    DSLAM_HIP(hipMalloc(&e->bits_q2[k], bits_bytes));
-    DSLAM_HIP(hipMalloc(&e->bits_mark[k], bits_bytes));
-    DSLAM_HIP(hipMemsetAsync(e->bits_q1[k], 0, bits_bytes, e->stream));
-    DSLAM_HIP(hipMemsetAsync(e->bits_q2[k], 0, bits_bytes, e->stream));
-    DSLAM_HIP(hipMemsetAsync(e->bits_mark[k], 0, bits_bytes, e->stream));
-    e->bits_dirty[k] = 0;
+    DSLAM_TRY(n.bits_q1[k].alloc_zeroed(n.bits_words, e->stream));
+    DSLAM_TRY(n.bits_q2[k].alloc_zeroed(n.bits_words, e->stream));
+    DSLAM_TRY(n.bits_mark[k].alloc_zeroed(n.bits_words, e->stream));
   }
-  DSLAM_HIP(hipMalloc(&e->bits_retest, bits_bytes));
-  DSLAM_HIP(hipMemsetAsync(e->bits_retest, 0, bits_bytes, e->stream));
+  DSLAM_TRY(n.bits_retest.alloc_zeroed(n.bits_words, e->stream));
   int tiles = num_tiles(N > L ? N : L);
   if (tiles < bit_tiles(N) * (kBitTileWords / 32)) tiles = bit_tiles(N) * (kBitTileWords / 32);  // (room for tiles as small as 1024 entries)
-  DSLAM_HIP(hipMalloc(&e->agg, (size_t)tiles * 3 * sizeof(unsigned long long)));
-  DSLAM_HIP(hipMemsetAsync(e->agg, 0, (size_t)tiles * 3 * sizeof(unsigned long long), e->stream));
-  e->agg_tiles = tiles;
-  DSLAM_HIP(hipMalloc(&e->tile_counts, (size_t)tiles * 2 * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&e->tile_offsets, (size_t)tiles * 2 * sizeof(int)));
+  DSLAM_TRY(n.agg.alloc_zeroed((size_t)tiles * 3, e->stream));
+  n.agg_tiles = tiles;
+  DSLAM_TRY(n.tile_counts.alloc((size_t)tiles * 2)); DSLAM_TRY(n.tile_offsets.alloc((size_t)tiles * 2));
   const size_t list_len = (size_t)(N > L ? N : L);
-  DSLAM_HIP(hipMalloc(&e->list_a, list_len * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&e->list_b, list_len * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&e->list_c, list_len * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&e->list_d, list_len * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&e->pos_scratch, (size_t)L * sizeof(short4)));
-  DSLAM_HIP(hipMalloc(&e->rem_flags, (size_t)N));
-  DSLAM_HIP(hipMalloc(&e->freed_flags, (size_t)N));
-  DSLAM_HIP(hipMalloc(&e->rem_cand, (size_t)L + 16));
-  DSLAM_HIP(hipMalloc(&e->maint_flags, 4 * sizeof(int)));
-  DSLAM_HIP(hipMemsetAsync(e->rem_flags, 0, (size_t)N, e->stream));
-  DSLAM_HIP(hipMemsetAsync(e->freed_flags, 0, (size_t)N, e->stream));
-  DSLAM_HIP(hipMemsetAsync(e->rem_cand, 0, (size_t)L + 16, e->stream));
-  DSLAM_HIP(hipMemsetAsync(e->maint_flags, 0, 4 * sizeof(int), e->stream));
+  DSLAM_TRY(n.list_a.alloc(list_len)); DSLAM_TRY(n.list_b.alloc(list_len));
+  DSLAM_TRY(n.list_c.alloc(list_len)); DSLAM_TRY(n.list_d.alloc(list_len));
+  DSLAM_TRY(n.pos_scratch.alloc(L));
+  DSLAM_TRY(n.rem_flags.alloc_zeroed(N, e->stream)); DSLAM_TRY(n.freed_flags.alloc_zeroed(N, e->stream));
+  DSLAM_TRY(n.rem_cand.alloc_zeroed((size_t)L + 16, e->stream));
+  DSLAM_TRY(n.maint_flags.alloc_zeroed(4, e->stream));
   DSLAM_HIP(hipStreamSynchronize(e->stream));
-  e->scratch_entries = N;
-  e->scratch_local_blocks = L;
+  static_cast<EngineScratch &>(*e) = std::move(n);
   return DSLAM_OK;
 }
 
+// regrow: on failure the old pair and its size stay
 static int ensure_staging(dslam_engine *e, size_t bytes) {
   if (bytes <= e->staging_bytes) return DSLAM_OK;
   DSLAM_HIP(hipStreamSynchronize(e->stream));
-  if (e->staging_dev) (void)hipFree(e->staging_dev);
-  if (e->staging_host) (void)hipHostFree(e->staging_host);
-  DSLAM_HIP(hipMalloc(&e->staging_dev, bytes));
-  DSLAM_HIP(hipHostMalloc(&e->staging_host, bytes, hipHostMallocDefault));
-  e->staging_bytes = bytes;
+  DeviceBuffer<char> dev;
+  PinnedBuffer<char> host;
+  DSLAM_TRY(dev.alloc(bytes)); DSLAM_TRY(host.alloc(bytes));
+  e->staging_dev = std::move(dev); e->staging_host = std::move(host); e->staging_bytes = bytes;
   return DSLAM_OK;
 }
 
@@ -206,14 +178,14 @@ static int engine_allocate(dslam_engine *e) {
   DSLAM_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
   DSLAM_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
   e->pinned_bytes = 64 * 1024;
-  DSLAM_HIP(hipHostMalloc(&e->pinned, e->pinned_bytes, hipHostMallocDefault));
+  DSLAM_TRY(e->pinned.alloc(e->pinned_bytes));
   memset(e->pinned, 0, e->pinned_bytes);
-  DSLAM_HIP(hipMalloc(&e->misc_counter, 16 * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&e->ticket, 16 * sizeof(unsigned)));
+  DSLAM_TRY(e->misc_counter.alloc(16));
+  DSLAM_TRY(e->ticket.alloc(16));
   DSLAM_HIP(hipMemset(e->ticket, 0, 16 * sizeof(unsigned)));
   e->ticket_base = 0;
   e->hip_failures_seen = hip_failure_count();
-  DSLAM_HIP(hipHostMalloc((void **)&e->err_host, 64, hipHostMallocDefault));
+  DSLAM_TRY(e->err_host.alloc(16));
   *e->err_host = 0;
   return DSLAM_OK;
 }
@@ -269,23 +241,8 @@ int dslam_engine_destroy(dslam_engine *e) {
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   if (e->copy_stream) { (void)hipStreamSynchronize(e->copy_stream); (void)hipStreamDestroy(e->copy_stream); }
-  free_dev(e->order_keys); free_dev(e->alloc_type); free_dev(e->block_coords); free_dev(e->tile_counts); free_dev(e->tile_offsets);
-  free_dev(e->list_a); free_dev(e->list_b); free_dev(e->list_c); free_dev(e->list_d); free_dev(e->pos_scratch);
-  free_dev(e->agg); free_dev(e->ticket);
-  for (int k = 0; k < 2; k++) { free_dev(e->bits_q1[k]); free_dev(e->bits_q2[k]); free_dev(e->bits_mark[k]); }
-  free_dev(e->bits_retest);
-  free_dev(e->rem_flags); free_dev(e->freed_flags); free_dev(e->rem_cand); free_dev(e->maint_flags);
-  if (e->staging_dev) (void)hipFree(e->staging_dev);
-  if (e->staging_host) (void)hipHostFree(e->staging_host);
-  if (e->pinned) (void)hipHostFree(e->pinned);
-  if (e->err_host) (void)hipHostFree(e->err_host);
-  if (e->timer_counts_dev) (void)hipFree(e->timer_counts_dev);
-  free_dev(e->misc_counter);
-  free_dev(e->mesh_positions); free_dev(e->mesh_colours);
-  if (e->icp_partials_host) (void)hipHostFree(e->icp_partials_host);  // (icp_partials is its device alias)
-  for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
   for (dslam_fence *f : e->fences) {
-    if (f->zombie) { if (f->ev) (void)hipEventDestroy(f->ev); delete f; }
+    if (f->zombie) delete f;
     else f->engine = nullptr;   // the caller still holds it: its destroy call must not look for this engine
   }
   e->fences.clear();
@@ -301,7 +258,7 @@ int dslam_selftest_division(dslam_engine *e, long long samples, long long *misma
   if (rc) return rc;
   DSLAM_HIP(hipMemcpyAsync(e->pinned, dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
   DSLAM_HIP(hipStreamSynchronize(e->stream));
-  *mismatches_out = (long long)*reinterpret_cast<unsigned long long *>(e->pinned);
+  *mismatches_out = (long long)*reinterpret_cast<unsigned long long *>(e->pinned.get());
   return DSLAM_OK;
 }
 
@@ -352,8 +309,7 @@ int dslam_fence_create(dslam_engine *e, dslam_fence **out) {
   *out = nullptr;
   dslam_fence *f = new dslam_fence();
   f->engine = e;
-  const hipError_t err = hipEventCreateWithFlags(&f->ev, hipEventDisableTiming);
-  if (err != hipSuccess) { delete f; return hip_fail(err, "hipEventCreateWithFlags", __FILE__, __LINE__); }
+  if (const int rc = f->ev.create()) { delete f; return rc; }
   e->fences.push_back(f);
   *out = f;
   return DSLAM_OK;
@@ -363,7 +319,6 @@ static void fence_free(dslam_fence *f) {
     auto &v = f->engine->fences;
     v.erase(std::remove(v.begin(), v.end(), f), v.end());
   }
-  if (f->ev) (void)hipEventDestroy(f->ev);
   delete f;
 }
 // a view stops waiting on the fence event it had borrowed for landing buffer b
@@ -405,31 +360,26 @@ int dslam_fence_query(dslam_fence *f, int *done) {
 void *dslam_engine_stream(dslam_engine *e) { return e ? (void *)e->stream : nullptr; }
 
 // ---- scene ---------------------------------------------------------------------------------------------------
-// every device / pinned allocation of a scene; on failure the caller destroys the half-built object (the destroy
-// function frees whatever is there), so no error path leaks
+// Every device / pinned allocation of a handle lives in an owner (dslam_memory.h) that is a member of the handle: deleting the
+// handle frees whatever is there, so no error path leaks, and a half-built object is simply deleted by its create call.
 static int scene_allocate(dslam_engine *e, dslam_scene *s, void *ext_voxels) {
-  const size_t vox_bytes = (size_t)s->p.num_local_blocks * kBlock3 * sizeof(uint2);
-  DSLAM_HIP(hipMalloc(&s->hash, (size_t)s->n_entries * sizeof(HashEntry)));
-  if (ext_voxels) {
-    s->voxels = reinterpret_cast<uint2 *>(ext_voxels);
-    s->voxels_external = true;
-  } else {
-    DSLAM_HIP(hipMalloc(&s->voxels, vox_bytes));
-  }
-  DSLAM_HIP(hipMalloc(&s->alloc_list, (size_t)s->p.num_local_blocks * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&s->excess_list, (size_t)s->p.num_excess * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&s->last_seen, (size_t)s->p.num_local_blocks * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&s->masks, (size_t)s->p.num_local_blocks * 2 * s->history_words * sizeof(unsigned long long)));
-  DSLAM_HIP(hipMalloc(&s->counters, sizeof(SceneCounters)));
-  DSLAM_HIP(hipMalloc(&s->alloc_bits, (size_t)bit_tiles(s->n_entries) * kBitTileWords * sizeof(unsigned)));
+  DSLAM_TRY(s->hash.alloc(s->n_entries));
+  if (!ext_voxels) DSLAM_TRY(s->voxels_own.alloc((size_t)s->p.num_local_blocks * kBlock3));
+  s->voxels = ext_voxels ? reinterpret_cast<uint2 *>(ext_voxels) : s->voxels_own.get();
+  DSLAM_TRY(s->alloc_list.alloc(s->p.num_local_blocks));
+  DSLAM_TRY(s->excess_list.alloc(s->p.num_excess));
+  DSLAM_TRY(s->last_seen.alloc(s->p.num_local_blocks));
+  DSLAM_TRY(s->masks.alloc((size_t)s->p.num_local_blocks * 2 * s->history_words));
+  DSLAM_TRY(s->counters.alloc(1));
+  DSLAM_TRY(s->alloc_bits.alloc((size_t)bit_tiles(s->n_entries) * kBitTileWords));
   if (s->p.use_swapping) {
-    DSLAM_HIP(hipMalloc(&s->swap_state, s->n_entries));
-    DSLAM_HIP(hipMalloc(&s->swap1_bits, (size_t)bit_tiles(s->n_entries) * kBitTileWords * sizeof(unsigned)));
-    DSLAM_HIP(hipMalloc(&s->slot_dev, (size_t)s->n_entries * sizeof(int)));
+    DSLAM_TRY(s->swap_state.alloc(s->n_entries));
+    DSLAM_TRY(s->swap1_bits.alloc((size_t)bit_tiles(s->n_entries) * kBitTileWords));
+    DSLAM_TRY(s->slot_dev.alloc(s->n_entries));
     DSLAM_HIP(hipMemsetAsync(s->slot_dev, 0xff, (size_t)s->n_entries * sizeof(int), e->stream));  // -1 everywhere
-    DSLAM_HIP(hipHostMalloc((void **)&s->next_slot_host, 64, hipHostMallocDefault));
+    DSLAM_TRY(s->next_slot_host.alloc(16));
     *s->next_slot_host = 0;
-    DSLAM_HIP(hipMalloc(&s->slab_ptrs_dev, (size_t)kMaxSlabs * sizeof(uint4 *)));
+    DSLAM_TRY(s->slab_ptrs_dev.alloc(kMaxSlabs));
   }
   int rc = ensure_scratch(e, s->n_entries, s->p.num_local_blocks);
   if (rc) return rc;
@@ -467,66 +417,33 @@ int dslam_scene_create(dslam_engine *e, const dslam_scene_params *p, void *ext_v
   return DSLAM_OK;
 }
 
-static void free_front_end(FrontEndRecord *&f) {
-  if (f) {
-    free_dev(f->visible_ids); free_dev(f->proj_boxes); free_dev(f->proj_z); free_dev(f->proj_req); free_dev(f->proj_wg_tiles);
-    free_dev(f->range); free_dev(f->counters);
-    delete f;
-    f = nullptr;
-  }
-}
-
-static int front_end_allocate(dslam_engine *e, FrontEndRecord *f) {
-  DSLAM_HIP(hipMalloc(&f->visible_ids, (size_t)f->n_local * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&f->proj_boxes, (size_t)f->n_local * sizeof(int4)));
-  DSLAM_HIP(hipMalloc(&f->proj_z, (size_t)f->n_local * sizeof(float2)));
-  DSLAM_HIP(hipMalloc(&f->proj_req, (size_t)f->n_local * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&f->proj_wg_tiles, (size_t)(f->n_entries / 1024 + 1024) * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&f->range, (size_t)f->w * f->h * sizeof(float2)));
-  DSLAM_HIP(hipMalloc(&f->counters, sizeof(RenderCounters)));
-  DSLAM_HIP(hipMemsetAsync(f->counters, 0, sizeof(RenderCounters), e->stream));
-  return DSLAM_OK;
-}
-
 // the scene's FrontEndRecord with buffers the size of r's (GetImage adopts them by exchanging pointers with its render
 // state, so they are sized like a render state's: render_state_allocate)
 static int front_end_for(dslam_engine *e, dslam_scene *s, const dslam_render_state *r, FrontEndRecord **out) {
-  FrontEndRecord *f = s->front;
+  FrontEndRecord *f = s->front.get();
   if (f && f->w == r->w && f->h == r->h && f->n_local == r->n_local && f->n_entries == r->n_entries) {
     *out = f;
     return DSLAM_OK;
   }
   DSLAM_HIP(hipStreamSynchronize(e->stream));   // (the old buffers may still be in use)
-  free_front_end(s->front);
+  s->front.reset();
   // attached to the scene only complete: a failed allocation leaves the scene without a record, never with part of one
-  f = new FrontEndRecord();
-  f->w = r->w; f->h = r->h; f->n_local = r->n_local; f->n_entries = r->n_entries;
-  if (const int rc = front_end_allocate(e, f)) {
-    free_front_end(f);
-    return rc;
-  }
-  *out = s->front = f;
+  std::unique_ptr<FrontEndRecord> n(new FrontEndRecord());
+  n->w = r->w; n->h = r->h; n->n_local = r->n_local; n->n_entries = r->n_entries;
+  DSLAM_TRY(n->visible_ids.alloc(n->n_local));
+  DSLAM_TRY(n->proj_boxes.alloc(n->n_local)); DSLAM_TRY(n->proj_z.alloc(n->n_local)); DSLAM_TRY(n->proj_req.alloc(n->n_local));
+  DSLAM_TRY(n->proj_wg_tiles.alloc((size_t)(n->n_entries / 1024 + 1024)));
+  DSLAM_TRY(n->range.alloc((size_t)n->w * n->h));
+  DSLAM_TRY(n->counters.alloc_zeroed(1, e->stream));
+  s->front = std::move(n);
+  *out = s->front.get();
   return DSLAM_OK;
 }
 
 int dslam_scene_destroy(dslam_scene *s) {
   if (!s) return DSLAM_OK;
+  (void)hipSetDevice(s->engine->device);
   (void)hipStreamSynchronize(s->engine->stream);
-  free_dev(s->hash);
-  if (!s->voxels_external) free_dev(s->voxels);
-  free_dev(s->alloc_list); free_dev(s->excess_list); free_dev(s->last_seen); free_dev(s->masks); free_dev(s->counters);
-  free_dev(s->swap_state); free_dev(s->slab_ptrs_dev); free_dev(s->alloc_bits); free_dev(s->swap1_bits);
-  free_dev(s->dirty); free_dev(s->dirty_list); free_dev(s->dirty_counts);
-  free_dev(s->batch_depth);
-  free_dev(s->batch_born); free_dev(s->batch_opmask); free_dev(s->batch_slot_entry); free_dev(s->batch_marks); free_dev(s->batch_order); free_dev(s->batch_counters);
-  if (s->batch_ops_dev) (void)hipFree(s->batch_ops_dev);
-  if (s->batch_lists_dev) (void)hipFree(s->batch_lists_dev);
-  if (s->batch_staging) (void)hipHostFree(s->batch_staging);
-  if (s->batch_staging_ev) (void)hipEventDestroy(s->batch_staging_ev);
-  for (uint4 *slab : s->slabs) (void)hipHostFree(slab);
-  if (s->next_slot_host) (void)hipHostFree(s->next_slot_host);
-  free_dev(s->slot_dev);
-  free_front_end(s->front);
   delete s;
   return DSLAM_OK;
 }
@@ -575,9 +492,9 @@ int dslam_scene_track_dirty(dslam_engine *e, dslam_scene *s, int enable) {
   if (enable) {
     const size_t n = (size_t)s->p.num_local_blocks;
     if (!s->dirty) {
-      DSLAM_HIP(hipMalloc(&s->dirty, n));
-      DSLAM_HIP(hipMalloc(&s->dirty_list, n * sizeof(int)));
-      DSLAM_HIP(hipMalloc(&s->dirty_counts, 128 * sizeof(int)));
+      SceneDirty d;   // (the scene gets the three together or none)
+      DSLAM_TRY(d.dirty.alloc(n)); DSLAM_TRY(d.dirty_list.alloc(n)); DSLAM_TRY(d.dirty_counts.alloc(128));
+      static_cast<SceneDirty &>(*s) = std::move(d);
     }
     DSLAM_HIP(hipMemsetAsync(s->dirty, 0, n, e->stream));
     s->dirty_shards = 0;
@@ -609,28 +526,16 @@ int dslam_shard_dirty_unpack(dslam_engine *e, dslam_scene *s, int skip_shard, co
 // ---- render state / view --------------------------------------------------------------------------------------
 static int render_state_allocate(dslam_engine *e, dslam_render_state *r) {
   const size_t npix = (size_t)r->w * r->h;
-  DSLAM_HIP(hipMalloc(&r->visible_ids, (size_t)r->n_local * sizeof(int)));
-  DSLAM_HIP(hipHostMalloc((void **)&r->vis_hint, 64, hipHostMallocDefault));
+  DSLAM_TRY(r->visible_ids.alloc(r->n_local));
+  DSLAM_TRY(r->vis_hint.alloc(16));
   *r->vis_hint = 0;
-  DSLAM_HIP(hipMalloc(&r->visible_type, r->n_entries));
-  const size_t vis_bits_bytes = (size_t)bit_tiles(r->n_entries) * kBitTileWords * sizeof(unsigned);
-  DSLAM_HIP(hipMalloc(&r->vis_bits, vis_bits_bytes));
-  DSLAM_HIP(hipMemsetAsync(r->vis_bits, 0, vis_bits_bytes, e->stream));
-  DSLAM_HIP(hipMalloc(&r->range, npix * sizeof(float2)));
-  DSLAM_HIP(hipMalloc(&r->raycast, npix * sizeof(float4)));
-  DSLAM_HIP(hipMalloc(&r->image_rgba, npix * sizeof(uchar4)));
-  DSLAM_HIP(hipMalloc(&r->image_float, npix * sizeof(float)));
-  DSLAM_HIP(hipMalloc(&r->proj_boxes, (size_t)r->n_local * sizeof(int4)));
-  DSLAM_HIP(hipMalloc(&r->proj_z, (size_t)r->n_local * sizeof(float2)));
-  DSLAM_HIP(hipMalloc(&r->proj_req, (size_t)r->n_local * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&r->proj_wg_tiles, (size_t)(r->n_entries / 1024 + 1024) * sizeof(int)));
-  DSLAM_HIP(hipMalloc(&r->counters, sizeof(RenderCounters)));
-  DSLAM_HIP(hipMemsetAsync(r->visible_type, 0, r->n_entries, e->stream));
-  DSLAM_HIP(hipMemsetAsync(r->counters, 0, sizeof(RenderCounters), e->stream));
-  DSLAM_HIP(hipMemsetAsync(r->range, 0, npix * sizeof(float2), e->stream));
-  DSLAM_HIP(hipMemsetAsync(r->raycast, 0, npix * sizeof(float4), e->stream));
-  DSLAM_HIP(hipMemsetAsync(r->image_rgba, 0, npix * sizeof(uchar4), e->stream));
-  DSLAM_HIP(hipMemsetAsync(r->image_float, 0, npix * sizeof(float), e->stream));
+  DSLAM_TRY(r->visible_type.alloc_zeroed(r->n_entries, e->stream));
+  DSLAM_TRY(r->vis_bits.alloc_zeroed((size_t)bit_tiles(r->n_entries) * kBitTileWords, e->stream));
+  DSLAM_TRY(r->range.alloc_zeroed(npix, e->stream)); DSLAM_TRY(r->raycast.alloc_zeroed(npix, e->stream));
+  DSLAM_TRY(r->image_rgba.alloc_zeroed(npix, e->stream)); DSLAM_TRY(r->image_float.alloc_zeroed(npix, e->stream));
+  DSLAM_TRY(r->proj_boxes.alloc(r->n_local)); DSLAM_TRY(r->proj_z.alloc(r->n_local)); DSLAM_TRY(r->proj_req.alloc(r->n_local));
+  DSLAM_TRY(r->proj_wg_tiles.alloc((size_t)(r->n_entries / 1024 + 1024)));
+  DSLAM_TRY(r->counters.alloc_zeroed(1, e->stream));
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   return DSLAM_OK;
 }
@@ -651,13 +556,8 @@ int dslam_render_state_create(dslam_engine *e, const dslam_scene *s, int w, int 
 
 int dslam_render_state_destroy(dslam_render_state *r) {
   if (!r) return DSLAM_OK;
+  (void)hipSetDevice(r->engine->device);
   (void)hipStreamSynchronize(r->engine->stream);
-  free_dev(r->visible_ids); free_dev(r->visible_type); free_dev(r->vis_bits); free_dev(r->range); free_dev(r->raycast);
-  free_dev(r->image_rgba); free_dev(r->image_float); free_dev(r->icp_points); free_dev(r->icp_normals);
-  free_dev(r->raycast_image);
-  free_dev(r->proj_boxes); free_dev(r->proj_z); free_dev(r->proj_req); free_dev(r->proj_wg_tiles); free_dev(r->counters);
-  free_dev(r->multi_mask); free_dev(r->multi_maps); free_dev(r->multi_counts);
-  if (r->vis_hint) (void)hipHostFree(r->vis_hint);
   delete r;
   return DSLAM_OK;
 }
@@ -667,12 +567,12 @@ static int view_allocate(dslam_engine *e, dslam_view *v) {
   // (the RGBA image and the int16 depth image in ONE allocation, the depth image at the next 256-byte boundary: a frame whose two
   // host images sit back to back the same way -- every 640x480 frame out of dslam_host_alloc -- goes up as one copy)
   const size_t c_round = ((size_t)w_rgb * h_rgb * sizeof(uchar4) + 255) & ~(size_t)255;
-  DSLAM_HIP(hipMalloc(&v->rgba, c_round + (size_t)w_d * h_d * sizeof(short)));
-  v->raw_depth = reinterpret_cast<short *>(reinterpret_cast<char *>(v->rgba) + c_round);
-  DSLAM_HIP(hipMalloc(&v->depth, (size_t)w_d * h_d * sizeof(float)));
+  DSLAM_TRY(v->rgba.alloc((c_round + (size_t)w_d * h_d * sizeof(short) + sizeof(uchar4) - 1) / sizeof(uchar4)));
+  v->raw_depth = reinterpret_cast<short *>(reinterpret_cast<char *>(v->rgba.get()) + c_round);
+  DSLAM_TRY(v->depth_own.alloc_zeroed((size_t)w_d * h_d, e->stream));
+  v->depth = v->depth_own;
   v->rgba_src = v->rgba; v->raw_src = v->raw_depth;
   DSLAM_HIP(hipMemsetAsync(v->rgba, 0, (size_t)w_rgb * h_rgb * sizeof(uchar4), e->stream));
-  DSLAM_HIP(hipMemsetAsync(v->depth, 0, (size_t)w_d * h_d * sizeof(float), e->stream));
   DSLAM_HIP(hipMemsetAsync(v->raw_depth, 0, (size_t)w_d * h_d * sizeof(short), e->stream));
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   return DSLAM_OK;
@@ -694,15 +594,10 @@ int dslam_view_create(dslam_engine *e, int w_rgb, int h_rgb, int w_d, int h_d, d
 
 int dslam_view_destroy(dslam_view *v) {
   if (!v) return DSLAM_OK;
+  (void)hipSetDevice(v->engine->device);
   (void)hipStreamSynchronize(v->engine->stream);
   if (v->engine->copy_stream) (void)hipStreamSynchronize(v->engine->copy_stream);
-  free_dev(v->rgba); free_dev(v->depth); free_dev(v->pyramid);   // (raw_depth lives in rgba's allocation)
-  for (int b = 0; b < 2; b++) {
-    release_lender(v, b);
-    free_dev(v->up_rgba[b]);  // (up_raw[b] points into the same allocation)
-    if (v->up_done[b]) (void)hipEventDestroy(v->up_done[b]);
-    if (v->up_consumed[b]) (void)hipEventDestroy(v->up_consumed[b]);
-  }
+  for (int b = 0; b < 2; b++) release_lender(v, b);
   delete v;
   return DSLAM_OK;
 }
@@ -809,14 +704,15 @@ static int upload_view_pipelined(dslam_engine *e, dslam_view *v, const uint8_t *
   static const bool stream_waits = getenv("DSLAM_PIPELINE_STREAM_WAITS") && atoi(getenv("DSLAM_PIPELINE_STREAM_WAITS")) != 0;
   const size_t c_bytes = (size_t)v->w_rgb * v->h_rgb * 4, d_bytes = (size_t)v->w_d * v->h_d * 2;
   if (!v->up_rgba[0]) {
+    ViewLanding n;   // (the view gets both buffers and their events together or nothing)
     for (int b = 0; b < 2; b++) {
       // one allocation per landing buffer (RGBA image, then the depth image): a caller that keeps a frame's two images
       // back to back gets ONE copy per frame
-      DSLAM_HIP(hipMalloc(&v->up_rgba[b], c_bytes + d_bytes));
-      v->up_raw[b] = reinterpret_cast<short *>(reinterpret_cast<char *>(v->up_rgba[b]) + c_bytes);
-      DSLAM_HIP(hipEventCreateWithFlags(&v->up_done[b], hipEventDisableTiming));
-      DSLAM_HIP(hipEventCreateWithFlags(&v->up_consumed[b], hipEventDisableTiming));
+      DSLAM_TRY(n.up_rgba[b].alloc((c_bytes + d_bytes + sizeof(uchar4) - 1) / sizeof(uchar4)));
+      DSLAM_TRY(n.up_done[b].create()); DSLAM_TRY(n.up_consumed[b].create());
     }
+    static_cast<ViewLanding &>(*v) = std::move(n);
+    for (int b = 0; b < 2; b++) v->up_raw[b] = reinterpret_cast<short *>(reinterpret_cast<char *>(v->up_rgba[b].get()) + c_bytes);
   }
   const int b = v->up_next;
   v->up_next ^= 1;
@@ -871,12 +767,12 @@ static int upload_view_host(dslam_engine *e, dslam_view *v, const uint8_t *colou
     // pinned memory; in async mode the previous upload must have drained before the staging buffer is rewritten
     DSLAM_HIP(hipStreamSynchronize(e->stream));
     memcpy(e->staging_host, colour_host, c_bytes);
-    memcpy((char *)e->staging_host + c_bytes, depth_host, d_bytes);
-    colour_src = e->staging_host; depth_src = (char *)e->staging_host + c_bytes;
+    memcpy((char *)e->staging_host.get() + c_bytes, depth_host, d_bytes);
+    colour_src = e->staging_host; depth_src = (char *)e->staging_host.get() + c_bytes;
   }
   void *colour_dst = colour_channels == 4 ? (void *)v->rgba : e->staging_dev;
   if (colour_channels == 4 && static_cast<const char *>(depth_src) == static_cast<const char *>(colour_src) + c_bytes &&
-      reinterpret_cast<char *>(v->raw_depth) == reinterpret_cast<char *>(v->rgba) + c_bytes) {
+      reinterpret_cast<char *>(v->raw_depth) == reinterpret_cast<char *>(v->rgba.get()) + c_bytes) {
     DSLAM_HIP(hipMemcpyAsync(v->rgba, colour_src, c_bytes + d_bytes, hipMemcpyHostToDevice, e->stream));   // (one DMA instead of two: -8 us)
   } else {
     DSLAM_HIP(hipMemcpyAsync(colour_dst, colour_src, c_bytes, hipMemcpyHostToDevice, e->stream));
@@ -955,27 +851,20 @@ int dslam_download_view_rgba(dslam_engine *e, const dslam_view *v, uint8_t *out)
 // ---- keyframe store (fusion-frame database payload resident in HBM) -------------------------------------------
 int dslam_frame_store_create(dslam_engine *e, int w_rgb, int h_rgb, int w_d, int h_d, int capacity, dslam_frame_store **out) {
   DSLAM_REQUIRE(e && out && w_rgb > 0 && h_rgb > 0 && w_d > 0 && h_d > 0 && capacity > 0, "bad argument");
-  dslam_frame_store *fs = new dslam_frame_store();
+  std::unique_ptr<dslam_frame_store> fs(new dslam_frame_store());
   fs->engine = e; fs->w_rgb = w_rgb; fs->h_rgb = h_rgb; fs->w_d = w_d; fs->h_d = h_d; fs->capacity = capacity;
   // slots are padded to 256 bytes so every image starts on an aligned address whatever the image size
   fs->rgba_bytes = ((size_t)w_rgb * h_rgb * 4 + 255) & ~(size_t)255;
   fs->depth_bytes = ((size_t)w_d * h_d * 2 + 255) & ~(size_t)255;
-  hipError_t err = hipMalloc(&fs->rgba, fs->rgba_bytes * capacity);
-  if (err == hipSuccess) err = hipMalloc(&fs->depth, fs->depth_bytes * capacity);
-  if (err != hipSuccess) {
-    free_dev(fs->rgba); free_dev(fs->depth);
-    delete fs;
-    set_last_error("frame store: out of device memory");
-    return DSLAM_ERR_HIP;
-  }
-  *out = fs;
+  DSLAM_TRY(fs->rgba.alloc(fs->rgba_bytes * capacity)); DSLAM_TRY(fs->depth.alloc(fs->depth_bytes * capacity));
+  *out = fs.release();
   return DSLAM_OK;
 }
 
 int dslam_frame_store_destroy(dslam_frame_store *fs) {
   if (!fs) return DSLAM_OK;
+  (void)hipSetDevice(fs->engine->device);
   (void)hipStreamSynchronize(fs->engine->stream);
-  free_dev(fs->rgba); free_dev(fs->depth); free_dev(fs->lists); free_dev(fs->batch_lists);
   delete fs;
   return DSLAM_OK;
 }
@@ -994,10 +883,10 @@ static int store_put_host(dslam_engine *e, dslam_frame_store *fs, int slot, cons
   if ((rc = ensure_staging(e, (size_t)fs->w_rgb * fs->h_rgb * 4 + d_bytes))) return rc;
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   memcpy(e->staging_host, colour, c_bytes);
-  memcpy((char *)e->staging_host + c_bytes, depth, d_bytes);
+  memcpy((char *)e->staging_host.get() + c_bytes, depth, d_bytes);
   unsigned char *rgba_dst = fs->rgba + fs->rgba_bytes * slot;
   DSLAM_HIP(hipMemcpyAsync(channels == 4 ? (void *)rgba_dst : e->staging_dev, e->staging_host, c_bytes, hipMemcpyHostToDevice, e->stream));
-  DSLAM_HIP(hipMemcpyAsync(fs->depth + fs->depth_bytes * slot, (char *)e->staging_host + c_bytes, d_bytes, hipMemcpyHostToDevice, e->stream));
+  DSLAM_HIP(hipMemcpyAsync(fs->depth + fs->depth_bytes * slot, (char *)e->staging_host.get() + c_bytes, d_bytes, hipMemcpyHostToDevice, e->stream));
   if (channels == 3 && (rc = launch_bgr_to_rgba(e, e->staging_dev, (uchar4 *)rgba_dst, fs->w_rgb * fs->h_rgb))) return rc;
   return finish_call(e);
 }
@@ -1052,15 +941,18 @@ int dslam_frame_store_enable_lists(dslam_engine *e, dslam_frame_store *fs, const
   DSLAM_REQUIRE(e && fs && s && fs->engine == e, "bad argument");
   if (fs->lists && fs->list_cap >= s->p.num_local_blocks && fs->list_entries == s->n_entries) return DSLAM_OK;
   DSLAM_HIP(hipStreamSynchronize(e->stream));
-  free_dev(fs->lists);
+  // regrow: on failure the old lists, their sizes and has_list[] / list_ptr[] stay as they were
+  const size_t list_bytes = (kListHeader + (size_t)s->p.num_local_blocks * (sizeof(int) + sizeof(short4)) + 255) & ~(size_t)255;
+  DeviceBuffer<unsigned char> lists;
+  DSLAM_TRY(lists.alloc(list_bytes * fs->capacity));
+  fs->lists = std::move(lists);
   fs->list_cap = s->p.num_local_blocks;
   fs->list_entries = s->n_entries;   // the lists hold entry ids of a table of this size (checked wherever a list is read)
-  fs->list_bytes = (kListHeader + (size_t)fs->list_cap * (sizeof(int) + sizeof(short4)) + 255) & ~(size_t)255;
-  DSLAM_HIP(hipMalloc(&fs->lists, fs->list_bytes * fs->capacity));
+  fs->list_bytes = list_bytes;
   fs->has_list.assign(fs->capacity, 0);
   fs->list_ptr.resize(fs->capacity);
   for (int i = 0; i < fs->capacity; i++) fs->list_ptr[i] = fs->lists + fs->list_bytes * i;
-  free_dev(fs->batch_lists);   // (sized for the old lists)
+  fs->batch_lists.reset();   // (sized for the old lists)
   fs->batch_list_ptr.clear();
   return DSLAM_OK;
 }
@@ -1129,27 +1021,27 @@ static int batch_scratch(dslam_engine *e, dslam_scene *s, dslam_frame_store *fs)
   const size_t npix = (size_t)fs->w_d * fs->h_d;
   if (s->batch_depth_pixels < npix) {   // (1.2 MB per 640x480 keyframe: 39 MB for the 32 of a chunk)
     DSLAM_HIP(hipStreamSynchronize(e->stream));
-    free_dev(s->batch_depth);
+    // regrow: the old images go first (they can be large); on failure the scene has no images and batch_depth_pixels == 0
+    s->batch_depth.reset();
     s->batch_depth_pixels = 0;
-    DSLAM_HIP(hipMalloc(&s->batch_depth, (size_t)kBatchMax * npix * sizeof(float)));
+    DSLAM_TRY(s->batch_depth.alloc((size_t)kBatchMax * npix));
     s->batch_depth_pixels = npix;
   }
   if (!s->batch_born) {
-    DSLAM_HIP(hipMalloc(&s->batch_born, L * sizeof(int)));
-    DSLAM_HIP(hipMalloc(&s->batch_opmask, L * sizeof(unsigned long long)));
-    DSLAM_HIP(hipMalloc(&s->batch_slot_entry, L * sizeof(int)));
-    DSLAM_HIP(hipMalloc(&s->batch_marks, L * 64));
-    DSLAM_HIP(hipMemsetAsync(s->batch_marks, 0, L * 64, e->stream));   // (every batch leaves them zero again)
-    DSLAM_HIP(hipMalloc(&s->batch_order, 8 * L * sizeof(int)));
-    DSLAM_HIP(hipMalloc(&s->batch_counters, 16 * sizeof(int)));   // [0..8): blocks per class, [8]: block-operations
-    DSLAM_HIP(hipMalloc(&s->batch_ops_dev, 2 * kBatchMax * sizeof(HostBatchOp)));
-    DSLAM_HIP(hipMalloc(&s->batch_lists_dev, 3 * kBatchMax * sizeof(HostBatchList)));
-    DSLAM_HIP(hipHostMalloc(&s->batch_staging, 2 * kBatchMax * sizeof(HostBatchOp) + 3 * kBatchMax * sizeof(HostBatchList), hipHostMallocDefault));
-    DSLAM_HIP(hipEventCreateWithFlags(&s->batch_staging_ev, hipEventDisableTiming));
+    SceneBatch n;   // (the scene gets the whole group or nothing: batch_born is the guard for all of it)
+    DSLAM_TRY(n.batch_born.alloc(L)); DSLAM_TRY(n.batch_opmask.alloc(L)); DSLAM_TRY(n.batch_slot_entry.alloc(L));
+    DSLAM_TRY(n.batch_marks.alloc_zeroed(L * 64, e->stream));   // (every batch leaves them zero again)
+    DSLAM_TRY(n.batch_order.alloc(8 * L));
+    DSLAM_TRY(n.batch_counters.alloc(16));   // [0..8): blocks per class, [8]: block-operations
+    DSLAM_TRY(n.batch_ops_dev.alloc(2 * kBatchMax * sizeof(HostBatchOp))); DSLAM_TRY(n.batch_lists_dev.alloc(3 * kBatchMax * sizeof(HostBatchList)));
+    DSLAM_TRY(n.batch_staging.alloc(2 * kBatchMax * sizeof(HostBatchOp) + 3 * kBatchMax * sizeof(HostBatchList)));
+    DSLAM_TRY(n.batch_staging_ev.create());
+    static_cast<SceneBatch &>(*s) = std::move(n);
   }
   if (!fs->batch_lists) {
-    DSLAM_HIP(hipMalloc(&fs->batch_lists, fs->list_bytes * kBatchMax));
-    DSLAM_HIP(hipMemsetAsync(fs->batch_lists, 0, fs->list_bytes * kBatchMax, e->stream));   // (the count headers)
+    DeviceBuffer<unsigned char> lists;
+    DSLAM_TRY(lists.alloc_zeroed(fs->list_bytes * kBatchMax, e->stream));   // (the count headers)
+    fs->batch_lists = std::move(lists);
     fs->batch_list_ptr.resize(kBatchMax);
     for (int i = 0; i < kBatchMax; i++) fs->batch_list_ptr[i] = fs->batch_lists + fs->list_bytes * i;
   }
@@ -1198,7 +1090,7 @@ int dslam_reintegrate_batch(dslam_engine *e, dslam_scene *s, dslam_view *v, dsla
     DSLAM_HIP(hipMemsetAsync(s->batch_counters, 0, 16 * sizeof(int), e->stream));
     // (built in page-locked memory: the copies are queued behind the allocation passes and nothing waits for them here)
     DSLAM_HIP(hipEventSynchronize(s->batch_staging_ev));   // the previous batch's copies have left the buffer
-    HostBatchOp *ops = reinterpret_cast<HostBatchOp *>(s->batch_staging);
+    HostBatchOp *ops = reinterpret_cast<HostBatchOp *>(s->batch_staging.get());
     HostBatchList *lists = reinterpret_cast<HostBatchList *>(ops + 2 * kBatchMax);   // [2K, 3K): the lists whose block positions are filled in at the end
     // phase 1: the allocation passes of the K re-fusions, in keyframe order (they read the table and the keyframes' depth
     // images, not the voxels); every pass' list goes to a scratch buffer, the blocks it allocates are stamped
@@ -1252,7 +1144,7 @@ int dslam_reintegrate_batch(dslam_engine *e, dslam_scene *s, dslam_view *v, dsla
     if ((rc = launch_reintegrate_blocks(e, s, v->w_d, v->h_d, v->w_rgb, v->h_rgb, intr, s->batch_ops_dev,
                                         s->batch_opmask, s->batch_slot_entry, s->batch_order, s->batch_counters, 1, 2 * K)))
       return batch_failed(s, r, fs, slots + first, K, rc);
-    if ((rc = launch_store_list_positions(e, s, reinterpret_cast<const HostBatchList *>(s->batch_lists_dev) + 2 * K, n_pos_jobs)))
+    if ((rc = launch_store_list_positions(e, s, reinterpret_cast<const HostBatchList *>(s->batch_lists_dev.get()) + 2 * K, n_pos_jobs)))
       return batch_failed(s, r, fs, slots + first, K, rc);
     // the lists of the re-fusions become the keyframes' stored lists: the buffers trade places
     for (int k = 0; k < K; k++) std::swap(fs->list_ptr[slots[first + k]], fs->batch_list_ptr[k]);
@@ -1292,7 +1184,7 @@ int dslam_depth_post_processing_device(dslam_engine *e, void *curr_dev, const vo
   if (count_out) {
     DSLAM_HIP(hipMemcpyAsync(e->pinned, count_dev, sizeof(int), hipMemcpyDeviceToHost, e->stream));
     DSLAM_HIP(hipStreamSynchronize(e->stream));
-    *count_out = *(int *)e->pinned;
+    *count_out = *(int *)e->pinned.get();
     return DSLAM_OK;
   }
   return finish_call(e);
@@ -1307,17 +1199,17 @@ int dslam_depth_post_processing(dslam_engine *e, int16_t *curr_host, const int16
   if ((rc = ensure_staging(e, 2 * d_bytes))) return rc;
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   memcpy(e->staging_host, curr_host, d_bytes);
-  memcpy((char *)e->staging_host + d_bytes, prev_host, d_bytes);
+  memcpy((char *)e->staging_host.get() + d_bytes, prev_host, d_bytes);
   DSLAM_HIP(hipMemcpyAsync(e->staging_dev, e->staging_host, 2 * d_bytes, hipMemcpyHostToDevice, e->stream));
   int *count_dev = e->misc_counter;
-  if ((rc = launch_depth_post(e, (short *)e->staging_dev, (const unsigned short *)((char *)e->staging_dev + d_bytes), w, h, Tpc,
+  if ((rc = launch_depth_post(e, (short *)e->staging_dev.get(), (const unsigned short *)((char *)e->staging_dev.get() + d_bytes), w, h, Tpc,
                               intr, threshold, area, count_dev)))
     return rc;
   DSLAM_HIP(hipMemcpyAsync(e->staging_host, e->staging_dev, d_bytes, hipMemcpyDeviceToHost, e->stream));
   DSLAM_HIP(hipMemcpyAsync(e->pinned, count_dev, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   memcpy(curr_host, e->staging_host, d_bytes);
-  if (count_out) *count_out = *(int *)e->pinned;
+  if (count_out) *count_out = *(int *)e->pinned.get();
   return DSLAM_OK;
 }
 
@@ -1529,7 +1421,7 @@ int dslam_render_image(dslam_engine *e, const dslam_scene *s, dslam_render_state
 static int get_image_on_device(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float *M,
                                const float *intr, int type, void *direct_out = nullptr) {
   // a map whose voxel blocks live in caller memory can change behind the engine's back: never memoised
-  const bool hit = r->memo_valid && !s->voxels_external && r->memo_scene == s && r->memo_version == s->version &&
+  const bool hit = r->memo_valid && s->voxels_own && r->memo_scene == s && r->memo_version == s->version &&
                    r->memo_budget == e->render_tile_budget && memcmp(r->memo_M, M, sizeof(r->memo_M)) == 0 &&
                    memcmp(r->memo_intr, intr, sizeof(r->memo_intr)) == 0;
   int rc;
@@ -1601,7 +1493,7 @@ int dslam_get_depth_image_int16(dslam_engine *e, const dslam_scene *s, dslam_ren
   if ((rc = get_image_on_device(e, s, r, M, intr, DSLAM_IMAGE_DEPTH))) return rc;
   // the RGBA image buffer of the render state is idle in this mode: it takes the int16 image (2 of its 4 bytes per pixel)
   const int n = r->w * r->h;
-  short *tmp = reinterpret_cast<short *>(r->image_rgba);
+  short *tmp = reinterpret_cast<short *>(r->image_rgba.get());
   if ((rc = launch_depth_to_int16(e, r->image_float, tmp, n, scale))) return rc;
   DSLAM_HIP(hipMemcpyAsync(out_host, tmp, (size_t)n * 2, hipMemcpyDeviceToHost, e->stream));
   return sync_check(e);
@@ -1661,7 +1553,7 @@ int dslam_mesh_download(dslam_engine *e, float *out_positions, float *out_colour
 // ---- read-back -----------------------------------------------------------------------------------------------
 int dslam_get_stats(dslam_engine *e, const dslam_scene *s, const dslam_render_state *r, dslam_stats *out) {
   DSLAM_REQUIRE(e && s && out, "null argument");
-  char *host = reinterpret_cast<char *>(e->pinned);
+  char *host = reinterpret_cast<char *>(e->pinned.get());
   SceneCounters *sc = reinterpret_cast<SceneCounters *>(host);
   RenderCounters *rc = reinterpret_cast<RenderCounters *>(host + 128);
   DSLAM_HIP(hipMemcpyAsync(sc, s->counters, sizeof(SceneCounters), hipMemcpyDeviceToHost, e->stream));
@@ -1719,7 +1611,7 @@ int dslam_download_excess_list(dslam_engine *e, const dslam_scene *s, int32_t *o
 }
 int dslam_download_visible_ids(dslam_engine *e, const dslam_render_state *r, int32_t *out, int capacity, int *count) {
   DSLAM_REQUIRE(e && r && out, "null argument");
-  RenderCounters *rc = reinterpret_cast<RenderCounters *>(reinterpret_cast<char *>(e->pinned) + 128);
+  RenderCounters *rc = reinterpret_cast<RenderCounters *>(reinterpret_cast<char *>(e->pinned.get()) + 128);
   int st = d2h(e, rc, r->counters, sizeof(RenderCounters));
   if (st) return st;
   int n = rc->no_visible < capacity ? rc->no_visible : capacity;
@@ -1785,7 +1677,7 @@ int dslam_upload_scene_state(dslam_engine *e, dslam_scene *s, const dslam_hash_e
     if (!rc) rc = launch_build_alloc_bits(e, s);
     if (!rc) rc = finish_call(e);
   }
-  SceneCounters *sc = reinterpret_cast<SceneCounters *>(e->pinned);
+  SceneCounters *sc = reinterpret_cast<SceneCounters *>(e->pinned.get());
   if (!rc && (alloc_list || excess_list)) {
     rc = d2h(e, sc, s->counters, sizeof(SceneCounters));
     if (!rc && alloc_list) {
@@ -1811,11 +1703,11 @@ int dslam_upload_visible_ids(dslam_engine *e, dslam_render_state *r, const int32
   r->types_follow_list = false;
   int rc = h2d(e, r->visible_ids, ids, (size_t)count * sizeof(int));
   if (rc) return rc;
-  RenderCounters *rcn = reinterpret_cast<RenderCounters *>(reinterpret_cast<char *>(e->pinned) + 128);
+  RenderCounters *rcn = reinterpret_cast<RenderCounters *>(reinterpret_cast<char *>(e->pinned.get()) + 128);
   rc = d2h(e, rcn, r->counters, sizeof(RenderCounters));
   if (rc) return rc;
   rcn->no_visible = count;
-  __atomic_store_n(r->vis_hint, count, __ATOMIC_RELAXED);
+  __atomic_store_n(r->vis_hint.get(), count, __ATOMIC_RELAXED);
   return h2d(e, r->counters, rcn, sizeof(RenderCounters));
 }
 
@@ -1841,9 +1733,9 @@ int dslam_time_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, c
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   DSLAM_REQUIRE(iterations > 0 && out_ms, "bad argument");
   e->view_reads++;  // (see dslam_engine::last_fence)
-  hipEvent_t a, b;
-  DSLAM_HIP(hipEventCreate(&a));
-  DSLAM_HIP(hipEventCreate(&b));
+  Event a, b;
+  DSLAM_TRY(a.create(hipEventDefault));
+  DSLAM_TRY(b.create(hipEventDefault));
   const bool saved = e->timer_enabled;
   e->timer_enabled = false;
   rc = launch_integrate(e, s, v, r, M_d, intr, nullptr, nullptr, false);  // warm-up
@@ -1854,11 +1746,9 @@ int dslam_time_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, c
   e->timer_enabled = saved;
   float ms = 0;
   DSLAM_HIP(hipEventElapsedTime(&ms, a, b));
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
   *out_ms = ms / iterations;
   if (out_blocks) {
-    RenderCounters *rcn = reinterpret_cast<RenderCounters *>(reinterpret_cast<char *>(e->pinned) + 128);
+    RenderCounters *rcn = reinterpret_cast<RenderCounters *>(reinterpret_cast<char *>(e->pinned.get()) + 128);
     int st = d2h(e, rcn, r->counters, sizeof(RenderCounters));
     if (st) return st;
     *out_blocks = rcn->no_visible;
@@ -1872,9 +1762,12 @@ int dslam_kernel_timer_enable(dslam_engine *e, int enable) {
   if (enable && e->ev_pool.empty()) {
     const size_t n = 2 * 8192;  // up to 8192 timed launches between reads
     DSLAM_REQUIRE(e->pinned_bytes >= 256 + 8192 * sizeof(int), "pinned mirror too small");
-    DSLAM_HIP(hipMalloc(&e->timer_counts_dev, 8192 * sizeof(int)));
-    e->ev_pool.resize(n);
-    for (size_t i = 0; i < n; i++) DSLAM_HIP(hipEventCreate(&e->ev_pool[i]));
+    DeviceBuffer<int> counts;
+    std::vector<Event> pool(n);
+    DSLAM_TRY(counts.alloc(8192));
+    for (size_t i = 0; i < n; i++) DSLAM_TRY(pool[i].create(hipEventDefault));
+    e->timer_counts_dev = std::move(counts);
+    e->ev_pool = std::move(pool);
   }
   e->timer_enabled = enable != 0;
   e->ev_used = 0;
@@ -1885,7 +1778,7 @@ int dslam_kernel_timer_enable(dslam_engine *e, int enable) {
 int dslam_kernel_timer_read(dslam_engine *e, double *out_ms, int64_t *out_launches, int64_t *out_blocks) {
   DSLAM_REQUIRE(e, "null engine");
   DSLAM_HIP(hipStreamSynchronize(e->stream));
-  int *counts = reinterpret_cast<int *>(e->pinned) + 64;
+  int *counts = reinterpret_cast<int *>(e->pinned.get()) + 64;
   if (e->ev_used > 0) {
     DSLAM_HIP(hipMemcpyAsync(counts, e->timer_counts_dev, (e->ev_used / 2) * sizeof(int), hipMemcpyDeviceToHost, e->stream));
     DSLAM_HIP(hipStreamSynchronize(e->stream));

@@ -301,8 +301,8 @@ inline void launch_bits_select(dslam_engine *e, const unsigned *src_bits, int n_
   // diagnostics: per-tile timeline of the 60th selection that has per-tile sums (GetImage's FindVisibleBlocks)
   static const char *dbg_file = getenv("DSLAM_DBG_SELECT");
   static int dbg_calls = 0;
-  unsigned long long *dbg_host = nullptr;
-  if (dbg_file && tile_sum_out && ++dbg_calls == 60 && hipHostMalloc((void **)&dbg_host, (size_t)grid * 64, hipHostMallocDefault) == hipSuccess) {
+  PinnedBuffer<unsigned long long> dbg_host;
+  if (dbg_file && tile_sum_out && ++dbg_calls == 60 && dbg_host.alloc((size_t)grid * 8) == DSLAM_OK) {
     memset(dbg_host, 0, (size_t)grid * 64);
     ch.dbg = dbg_host;
   }
@@ -311,7 +311,6 @@ inline void launch_bits_select(dslam_engine *e, const unsigned *src_bits, int n_
   if (dbg_host) {
     (void)hipStreamSynchronize(e->stream);
     if (FILE *f = fopen(dbg_file, "wb")) { fwrite(dbg_host, 64, grid, f); fclose(f); }
-    (void)hipHostFree(dbg_host);
   }
 }
 

@@ -6,16 +6,17 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/dslam_fusion.h"
 #include "dslam_device.h"
+#include "dslam_memory.h"
 
 namespace dslam {
 
 void set_last_error(const std::string &msg);
-int hip_fail(hipError_t err, const char *what, const char *file, int line);
 
 #define DSLAM_HIP(call)                                                       \
   do {                                                                        \
@@ -34,9 +35,51 @@ int hip_fail(hipError_t err, const char *what, const char *file, int line);
 // host inverse of a column-major 4x4 (ORUtils::Matrix4::inv); used for invM_d = pose_d->GetInvM()
 bool invert_matrix(const float *m, float *dst);
 
+// scratch shared by all scenes of an engine, sized for the largest scene seen (ensure_scratch builds a new set aside and
+// move-assigns it: buffers and sizes change together)
+struct EngineScratch {
+  int scratch_entries = 0;
+  int scratch_local_blocks = 0;
+  DeviceBuffer<unsigned> order_keys;     // [entries] mark-phase order keys; ALL ZERO between allocation passes (the pass that
+                                      // sets a key clears it again, so no pass starts with a 4.7 MB memset)
+  DeviceBuffer<unsigned char> alloc_type;  // [entries] entriesAllocType of the last pass (kept for the parity tests)
+  DeviceBuffer<short4> block_coords;     // [entries] blockCoords
+  // bit-packed summaries of an allocation pass (dslam_device.h): requests on empty bucket heads (q1) / chain ends (q2),
+  // entries a pixel's walk found (mark).  Two sets used alternately: pass k sets bits in set k & 1 and zeroes set
+  // (k + 1) & 1 -- the set of the pass before it -- so no pass starts with a memset; bits_dirty[s] = words of set s that
+  // may be non-zero (scenes of different sizes share the sets).  retest: outcome of the frustum re-test of the entries
+  // that were visible before the pass (every word is written by every pass).
+  DeviceBuffer<unsigned> bits_q1[2], bits_q2[2], bits_mark[2];
+  DeviceBuffer<unsigned> bits_retest;
+  int bits_words = 0;                 // words per bitmap (whole tiles)
+  int bits_dirty[2] = {0, 0};
+  // single-pass ordered compactions: per-tile aggregates published inside one launch ({epoch, counts} in one 8-byte
+  // word per tile; three channels: allocation requests, commit results, visible counts) and the launch counter that
+  // tags them, so the arrays never need clearing
+  DeviceBuffer<unsigned long long> agg;  // [3][agg_tiles]
+  int agg_tiles = 0;
+  DeviceBuffer<int> list_d;              // [max(local_blocks, entries)] general purpose scratch (bucket leaders, live flags)
+  // release pipeline (decay / sliding window): flags that are ALL ZERO between passes (the kernels that consume a flag
+  // clear it), so no pass starts with a memset
+  DeviceBuffer<unsigned char> rem_flags;    // [entries] entry is being released
+  DeviceBuffer<unsigned char> freed_flags;  // [entries] excess slot came free
+  DeviceBuffer<unsigned char> rem_cand;     // [local_blocks] candidate i of the decay pass lost its last measured voxel
+  DeviceBuffer<int> maint_flags;            // device [4]: [0] the pass took something out of a visible list
+  DeviceBuffer<int> tile_counts;         // [2 * tiles] per-tile counts of the ordered compactions
+  DeviceBuffer<int> tile_offsets;        // [2 * tiles]
+  DeviceBuffer<int> list_a;              // [max(local_blocks, entries)] general purpose int lists
+  DeviceBuffer<int> list_b;
+  DeviceBuffer<int> list_c;
+  DeviceBuffer<short4> pos_scratch;      // [local_blocks]
+};
 }  // namespace dslam
 
-struct dslam_engine {
+// (the handles' destructors free memory now: they are not part of the library's exported names)
+#define DSLAM_INTERNAL __attribute__((visibility("hidden")))
+
+using dslam::DeviceBuffer, dslam::Event, dslam::PinnedBuffer;
+
+struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   int device = 0;
   hipStream_t stream = nullptr;
   // A caller's fence recorded behind the last call that read a view is also that view's "consumed" mark: the pipelined
@@ -50,67 +93,33 @@ struct dslam_engine {
   // ProcessFrame computes GetImage's front end for its own pose (FrontEndRecord); DSLAM_SPECULATIVE_FRONT_END=0 turns it off
   bool speculate_front = true;
   dslam_weight_params wp{0, 1, 1.0f};
-  // scratch shared by all scenes of this engine (sized for the largest scene seen)
-  int scratch_entries = 0;
-  int scratch_local_blocks = 0;
-  unsigned *order_keys = nullptr;     // [entries] mark-phase order keys; ALL ZERO between allocation passes (the pass that
-                                      // sets a key clears it again, so no pass starts with a 4.7 MB memset)
-  unsigned char *alloc_type = nullptr;  // [entries] entriesAllocType of the last pass (kept for the parity tests)
-  short4 *block_coords = nullptr;     // [entries] blockCoords
-  // bit-packed summaries of an allocation pass (dslam_device.h): requests on empty bucket heads (q1) / chain ends (q2),
-  // entries a pixel's walk found (mark).  Two sets used alternately: pass k sets bits in set k & 1 and zeroes set
-  // (k + 1) & 1 -- the set of the pass before it -- so no pass starts with a memset; bits_dirty[s] = words of set s that
-  // may be non-zero (scenes of different sizes share the sets).  retest: outcome of the frustum re-test of the entries
-  // that were visible before the pass (every word is written by every pass).
-  unsigned *bits_q1[2] = {nullptr, nullptr}, *bits_q2[2] = {nullptr, nullptr}, *bits_mark[2] = {nullptr, nullptr};
-  unsigned *bits_retest = nullptr;
-  int bits_words = 0;                 // words per bitmap (whole tiles)
-  int bits_dirty[2] = {0, 0};
   unsigned alloc_pass = 0;
   // tickets of the single-pass ordered compactions (dslam_device.h take_ticket): one ever-growing device counter and
   // the value the host knows it has
-  unsigned *ticket = nullptr;         // device [16]: counter k is ticket + k
+  DeviceBuffer<unsigned> ticket;         // device [16]: counter k is ticket + k
   unsigned ticket_base = 0;           // counter 0
   unsigned ticket_base2 = 0;          // counter 1 (a second, independent chain inside the same launch)
   unsigned long long hip_failures_seen = 0;  // ... which is only as good as the launches that were accepted: after any HIP
                                       // failure of the process the bases are read back from the device (tickets_resync)
   // what kernels could not tell anybody (report_error, dslam_device.h): one page-locked word, looked at by every entry
   // point that waits for the stream (sync_check).  Sticky per scene in SceneCounters::error_flags; here: told once.
-  int *err_host = nullptr;
-  // single-pass ordered compactions: per-tile aggregates published inside one launch ({epoch, counts} in one 8-byte
-  // word per tile; three channels: allocation requests, commit results, visible counts) and the launch counter that
-  // tags them, so the arrays never need clearing
-  unsigned long long *agg = nullptr;  // [3][agg_tiles]
-  int agg_tiles = 0;
+  PinnedBuffer<int> err_host;
   unsigned epoch = 0;
   int sweep_grid_cap = 0;             // workgroups of the sweep kernels that are certainly co-resident on this device
-  int *list_d = nullptr;              // [max(local_blocks, entries)] general purpose scratch (bucket leaders, live flags)
-  // release pipeline (decay / sliding window): flags that are ALL ZERO between passes (the kernels that consume a flag
-  // clear it), so no pass starts with a memset
-  unsigned char *rem_flags = nullptr;    // [entries] entry is being released
-  unsigned char *freed_flags = nullptr;  // [entries] excess slot came free
-  unsigned char *rem_cand = nullptr;     // [local_blocks] candidate i of the decay pass lost its last measured voxel
-  int *maint_flags = nullptr;            // device [4]: [0] the pass took something out of a visible list
-  int *tile_counts = nullptr;         // [2 * tiles] per-tile counts of the ordered compactions
-  int *tile_offsets = nullptr;        // [2 * tiles]
-  int *list_a = nullptr;              // [max(local_blocks, entries)] general purpose int lists
-  int *list_b = nullptr;
-  int *list_c = nullptr;
-  short4 *pos_scratch = nullptr;      // [local_blocks]
   // pinned staging
-  void *pinned = nullptr;             // small host mirror for counters / stats
+  PinnedBuffer<void> pinned;             // small host mirror for counters / stats
   size_t pinned_bytes = 0;
-  void *staging_dev = nullptr;        // H2D staging for view uploads (rgba + depth)
+  DeviceBuffer<char> staging_dev;        // H2D staging for view uploads (rgba + depth)
   size_t staging_bytes = 0;
-  void *staging_host = nullptr;
+  PinnedBuffer<char> staging_host;
   // kernel timer (bench roofline): HIP events around the integrate kernel on the engine stream
   bool timer_enabled = false;
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<Event> ev_pool;
   size_t ev_used = 0;
   double timer_ms = 0;
   long long timer_launches = 0;
   long long timer_blocks = 0;
-  int *timer_counts_dev = nullptr;    // visible-block count of each timed launch (written by the kernel)
+  DeviceBuffer<int> timer_counts_dev;    // visible-block count of each timed launch (written by the kernel)
   int sm_count = 256;
   // visible blocks from which on a fusion launch counts as larger than the Infinity Cache (65536 x 4 KiB = 256 MiB): trailing
   // push workgroups (integrate.hip kPushJobMin, decided on the device) and streaming cache policy (decided by the host from
@@ -120,12 +129,11 @@ struct dslam_engine {
   long long front_launches = 0;       // fusion launches that computed GetImage's front end (FrontEndRecord; test hook)
   long long front_adoptions = 0;      // GetImage front ends taken from such a record instead of computed (test hook)
   int render_tile_budget = DSLAM_MAX_RENDERING_BLOCKS;  // MAX_RENDERING_BLOCKS; lowered only by the budget test
-  double *icp_partials_host = nullptr;  // depth tracker: per-workgroup partial sums in mapped pinned host memory
-  double *icp_partials = nullptr;       // ... and the device address of the same buffer
-  int *misc_counter = nullptr;        // device: small result counters of one-off kernels (depthPostProcessing)
+  PinnedBuffer<double> icp_partials;  // depth tracker: per-workgroup partial sums in mapped page-locked memory (kernels: device())
+  DeviceBuffer<int> misc_counter;        // device: small result counters of one-off kernels (depthPostProcessing)
   // the last mesh dslam_mesh_scene produced (ITMMesh: triangles as 3 x Vector3f, metres)
-  float *mesh_positions = nullptr;    // device [mesh_triangles][3][3]
-  float *mesh_colours = nullptr;      // device [mesh_triangles][3][3], only if asked for
+  DeviceBuffer<float> mesh_positions;    // device [mesh_triangles][3][3]
+  DeviceBuffer<float> mesh_colours;      // device [mesh_triangles][3][3], only if asked for
   size_t mesh_bytes = 0;              // capacity of each of the two buffers
   int mesh_triangles = 0;
   bool mesh_has_colour = false;
@@ -141,94 +149,108 @@ struct FrontEndRecord {
   unsigned long long version = 0;     // the scene's version after the ProcessFrame
   float M[16] = {0}, intr[4] = {0};
   int w = 0, h = 0, n_local = 0, n_entries = 0;   // the sizes of the buffers (= those of the render states they may go to)
-  int *visible_ids = nullptr;
-  int4 *proj_boxes = nullptr;
-  float2 *proj_z = nullptr;
-  int *proj_req = nullptr;
-  int *proj_wg_tiles = nullptr;
-  float2 *range = nullptr;
-  dslam::RenderCounters *counters = nullptr;
+  DeviceBuffer<int> visible_ids, proj_req, proj_wg_tiles;
+  DeviceBuffer<int4> proj_boxes;
+  DeviceBuffer<float2> proj_z, range;
+  DeviceBuffer<dslam::RenderCounters> counters;
 };
 
-struct dslam_scene {
-  dslam_engine *engine = nullptr;
-  dslam_scene_params p{};
-  int n_entries = 0;
-  dslam::HashEntry *hash = nullptr;
-  uint2 *voxels = nullptr;
-  bool voxels_external = false;
-  int *alloc_list = nullptr;
-  int *excess_list = nullptr;
-  int *last_seen = nullptr;           // per voxel-block slot
-  dslam::SceneCounters *counters = nullptr;  // device
-  // visible-list history: per voxel-block slot two bit rings (0 fusion, 1 defusion); list k of ring q
-  // owns bit k % (64*history_words) of masks[(slot*2+q)*history_words ...]
-  int history_words = 4;
-  unsigned long long *masks = nullptr;  // device
-  int ring_head[2] = {0, 0}, ring_next[2] = {0, 0}, decay_cursor[2] = {0, 0};
-  int frame_counter = 0;
-  // ITMGlobalCache
-  unsigned char *swap_state = nullptr;  // device [entries]
-  unsigned *alloc_bits = nullptr;       // device [bit tiles]: bit t = entry t holds a resident block (ptr >= 0)
-  unsigned *swap1_bits = nullptr;       // device [bit tiles], swapping only: bit t = swap_state[t] == 1 (host copy to be merged)
-  // host store of swapped-out blocks: page-locked slabs the kernels read and write directly over PCIe (no staging
-  // copy, no host memcpy); an entry's block lives in slot slot_dev[entry]; slots are handed out by an atomic counter
-  std::vector<uint4 *> slabs;           // pinned, kSlabBlocks blocks each, allocated as the store grows
-  uint4 **slab_ptrs_dev = nullptr;      // device [kMaxSlabs]: the same pointers for the kernels
-  int *slot_dev = nullptr;              // device [entries]: slot of the entry's stored block, -1 = none.  The table and
-                                        // the slot counter (SceneCounters::next_slot) live on the device: a swap batch
-                                        // needs no host round trip (round 1: two per ProcessFrame)
-  int *next_slot_host = nullptr;        // pinned: copy of next_slot queued behind every batch that may hand out slots
-  long long slot_bound = 0;             // upper bound of next_slot the host can prove (slabs exist for all of it)
-  int shard = 0, num_shards = 1, chunk_blocks = 256;
-  unsigned long long version = 0;       // bumped by every call that can change the map (GetImage memo key)
-  int shard_first = 0, shard_count = -1;  // contiguous slot range (count < 0: off)
+// The lazily allocated groups of a scene: each exists whole or not at all (built aside, move-assigned when complete).
+struct SceneDirty {
   // sharded re-integration: per voxel-block slot "a (de-)integration pass visited this block since tracking began"
-  unsigned char *dirty = nullptr;       // device [num_local_blocks], allocated by dslam_scene_track_dirty
-  bool dirty_tracking = false;
-  int *dirty_list = nullptr;            // device [num_local_blocks]: the dirty slots in virtual (shard-major) order
-  int *dirty_counts = nullptr;          // device [128]: per shard its number of dirty slots (+ scratch)
+  DeviceBuffer<unsigned char> dirty;       // device [num_local_blocks], allocated by dslam_scene_track_dirty
+  DeviceBuffer<int> dirty_list;            // device [num_local_blocks]: the dirty slots in virtual (shard-major) order
+  DeviceBuffer<int> dirty_counts;          // device [128]: per shard its number of dirty slots (+ scratch)
+};
+struct SceneBatch {
   // block-major re-integration batch (dslam_reintegrate_batch): per voxel-block slot the re-fusion pass of the batch that
   // allocated it (0: it existed before), which operations of the batch touch it, an entry that holds it; the list of
   // touched slots; [0] its length, [1] the work cursor.  alloc_born / alloc_born_stamp: the allocation sweep stamps the
   // blocks it commits while a batch is being planned
-  int *batch_born = nullptr;
-  unsigned long long *batch_opmask = nullptr;
-  int *batch_slot_entry = nullptr, *batch_order = nullptr, *batch_counters = nullptr;   // (batch_order: 8 class lists)
-  unsigned char *batch_marks = nullptr;   // [num_local_blocks][64]: operation k of the batch touches the block (zero between batches)
-  void *batch_ops_dev = nullptr, *batch_lists_dev = nullptr;
-  float *batch_depth = nullptr;           // one float depth image per keyframe of a batch (written by its allocation pass, read by
-  size_t batch_depth_pixels = 0;          // both of its operations in the block launch); pixels per image it was sized for
-  void *batch_staging = nullptr;          // page-locked: the operations and list references of a batch on their way to the device
-  hipEvent_t batch_staging_ev = nullptr;  // ... the copies out of it have been made
-  int *alloc_born = nullptr;
-  int alloc_born_stamp = 0;
-  int dirty_shards = 0, dirty_chunk = 0;  // the layout of the last dslam_shard_dirty_plan
-  FrontEndRecord *front = nullptr;        // allocated by the first ProcessFrame that computes it
+  DeviceBuffer<int> batch_born;
+  DeviceBuffer<unsigned long long> batch_opmask;
+  DeviceBuffer<int> batch_slot_entry, batch_order, batch_counters;   // (batch_order: 8 class lists)
+  DeviceBuffer<unsigned char> batch_marks;   // [num_local_blocks][64]: operation k of the batch touches the block (zero between batches)
+  DeviceBuffer<void> batch_ops_dev, batch_lists_dev;
+  PinnedBuffer<void> batch_staging;          // page-locked: the operations and list references of a batch on their way to the device
+  Event batch_staging_ev;                 // ... the copies out of it have been made
 };
 
-struct dslam_render_state {
+struct DSLAM_INTERNAL dslam_scene : SceneDirty, SceneBatch {
+  dslam_engine *engine = nullptr;
+  dslam_scene_params p{};
+  int n_entries = 0;
+  DeviceBuffer<dslam::HashEntry> hash;
+  uint2 *voxels = nullptr;            // what the kernels use: voxels_own, or the caller's buffer (borrowed, never freed here)
+  DeviceBuffer<uint2> voxels_own;     // empty when the voxels are the caller's
+  DeviceBuffer<int> alloc_list;
+  DeviceBuffer<int> excess_list;
+  DeviceBuffer<int> last_seen;           // per voxel-block slot
+  DeviceBuffer<dslam::SceneCounters> counters;  // device
+  // visible-list history: per voxel-block slot two bit rings (0 fusion, 1 defusion); list k of ring q
+  // owns bit k % (64*history_words) of masks[(slot*2+q)*history_words ...]
+  int history_words = 4;
+  DeviceBuffer<unsigned long long> masks;  // device
+  int ring_head[2] = {0, 0}, ring_next[2] = {0, 0}, decay_cursor[2] = {0, 0};
+  int frame_counter = 0;
+  // ITMGlobalCache
+  DeviceBuffer<unsigned char> swap_state;  // device [entries]
+  DeviceBuffer<unsigned> alloc_bits;       // device [bit tiles]: bit t = entry t holds a resident block (ptr >= 0)
+  DeviceBuffer<unsigned> swap1_bits;       // device [bit tiles], swapping only: bit t = swap_state[t] == 1 (host copy to be merged)
+  // host store of swapped-out blocks: page-locked slabs the kernels read and write directly over PCIe (no staging
+  // copy, no host memcpy); an entry's block lives in slot slot_dev[entry]; slots are handed out by an atomic counter
+  std::vector<PinnedBuffer<uint4>> slabs;          // pinned, kSlabBlocks blocks each, allocated as the store grows
+  DeviceBuffer<uint4 *> slab_ptrs_dev;     // device [kMaxSlabs]: the same pointers for the kernels
+  DeviceBuffer<int> slot_dev;              // device [entries]: slot of the entry's stored block, -1 = none.  The table and
+                                        // the slot counter (SceneCounters::next_slot) live on the device: a swap batch
+                                        // needs no host round trip (round 1: two per ProcessFrame)
+  PinnedBuffer<int> next_slot_host;        // pinned: copy of next_slot queued behind every batch that may hand out slots
+  long long slot_bound = 0;             // upper bound of next_slot the host can prove (slabs exist for all of it)
+  int shard = 0, num_shards = 1, chunk_blocks = 256;
+  unsigned long long version = 0;       // bumped by every call that can change the map (GetImage memo key)
+  int shard_first = 0, shard_count = -1;  // contiguous slot range (count < 0: off)
+  DeviceBuffer<float> batch_depth;           // one float depth image per keyframe of a batch (written by its allocation pass, read by
+  size_t batch_depth_pixels = 0;          // both of its operations in the block launch); pixels per image it was sized for
+  bool dirty_tracking = false;
+  int *alloc_born = nullptr;               // = batch_born while a batch is being planned
+  int alloc_born_stamp = 0;
+  int dirty_shards = 0, dirty_chunk = 0;  // the layout of the last dslam_shard_dirty_plan
+  std::unique_ptr<FrontEndRecord> front;  // allocated by the first ProcessFrame that computes it
+};
+
+// The lazily allocated groups of a render state (whole or not at all, as a scene's).  CreateICPMaps:
+struct RenderIcpMaps {
+  DeviceBuffer<float4> icp_points, icp_normals;
+  DeviceBuffer<uchar4> raycast_image;  // ITMRenderState::raycastImage: the grey tracking raycast CreateICPMaps draws (with the maps)
+};
+struct RenderMulti {
+  // dslam_get_image_multi (multimap.hip), allocated by its first call: per range cell the maps whose blocks project into
+  // it (bit i = map i), the per-map descriptor table, per map its visible-block count
+  DeviceBuffer<unsigned long long> multi_mask;
+  DeviceBuffer<void> multi_maps;
+  DeviceBuffer<int> multi_counts;
+};
+
+struct DSLAM_INTERNAL dslam_render_state : RenderIcpMaps, RenderMulti {
   dslam_engine *engine = nullptr;
   int w = 0, h = 0, n_entries = 0, n_local = 0;
-  int *visible_ids = nullptr;
-  unsigned char *visible_type = nullptr;
-  unsigned *vis_bits = nullptr;   // bit t = visible_type[t] != 0 (kept by every kernel that writes a type)
-  float2 *range = nullptr;      // renderingRangeImage (full image stride)
-  float4 *raycast = nullptr;    // raycastResult
-  uchar4 *image_rgba = nullptr; // RenderImage's outputImage (rgba types)
-  float *image_float = nullptr;
-  float4 *icp_points = nullptr, *icp_normals = nullptr;  // allocated on first use
-  uchar4 *raycast_image = nullptr;  // ITMRenderState::raycastImage: the grey tracking raycast CreateICPMaps draws (with the maps)
-  int4 *proj_boxes = nullptr;   // per visible block: render bbox (ul.x, ul.y, lr.x, lr.y)
-  float2 *proj_z = nullptr;     // per visible block: z range
-  int *proj_req = nullptr;      // per visible block: render tiles required (0 = invalid projection)
-  int *proj_wg_tiles = nullptr; // render tiles requested per workgroup of the projection pass (summed by the next kernel)
-  dslam::RenderCounters *counters = nullptr;  // device
+  DeviceBuffer<int> visible_ids;
+  DeviceBuffer<unsigned char> visible_type;
+  DeviceBuffer<unsigned> vis_bits;   // bit t = visible_type[t] != 0 (kept by every kernel that writes a type)
+  DeviceBuffer<float2> range;      // renderingRangeImage (full image stride)
+  DeviceBuffer<float4> raycast;    // raycastResult
+  DeviceBuffer<uchar4> image_rgba; // RenderImage's outputImage (rgba types)
+  DeviceBuffer<float> image_float;
+  DeviceBuffer<int4> proj_boxes;   // per visible block: render bbox (ul.x, ul.y, lr.x, lr.y)
+  DeviceBuffer<float2> proj_z;     // per visible block: z range
+  DeviceBuffer<int> proj_req;      // per visible block: render tiles required (0 = invalid projection)
+  DeviceBuffer<int> proj_wg_tiles; // render tiles requested per workgroup of the projection pass (summed by the next kernel)
+  DeviceBuffer<dslam::RenderCounters> counters;  // device
   // One page-locked word: the length of the visible list as an allocation pass that RAN left it -- k_alloc_sweep rewrites it
   // whenever the answer to "at least push_job_min blocks?" would change, an uploaded list sets it.  The
   // host looks at it -- without waiting for anything, so on an asynchronous engine it is a frame or two late -- to choose the
   // fusion kernel's cache policy (launch_integrate): a hint, both policies compute the same bytes.
-  int *vis_hint = nullptr;
+  PinnedBuffer<int> vis_hint;
   // entriesVisibleType carries a generation bit (0x80): an allocation pass writes its marks with the pass' bit, so a
   // non-zero byte with the OTHER bit is "visible in the previous pass" (upstream's re-arming of the previous visible
   // list as type 3) without a pass over that list.  The C ABI hands out the plain types (bit masked off).
@@ -244,29 +266,28 @@ struct dslam_render_state {
   unsigned long long memo_version = 0;
   int memo_budget = 0;
   float memo_M[16] = {0}, memo_intr[4] = {0};
-  // dslam_get_image_multi (multimap.hip), allocated by its first call: per range cell the maps whose blocks project into
-  // it (bit i = map i), the per-map descriptor table, per map its visible-block count
-  unsigned long long *multi_mask = nullptr;
-  void *multi_maps = nullptr;
-  int *multi_counts = nullptr;
 };
 
-struct dslam_view {
+struct ViewLanding {
+  // pipelined uploads (async engine + page-locked caller images): two landing buffers, filled on the engine's copy
+  // stream while the compute stream still reads the other one
+  DeviceBuffer<uchar4> up_rgba[2];
+  Event up_done[2];      // copy stream: buffer b has landed
+  Event up_consumed[2];  // compute stream: every kernel that reads buffer b has been passed
+};
+
+struct DSLAM_INTERNAL dslam_view : ViewLanding {
   dslam_engine *engine = nullptr;
   int w_rgb = 0, h_rgb = 0, w_d = 0, h_d = 0;
-  uchar4 *rgba = nullptr;       // own buffers (host uploads land here)
-  float *depth = nullptr;
-  short *raw_depth = nullptr;
-  mutable float *pyramid = nullptr;  // depth tracker: levels 1.. of the depth pyramid (scratch, allocated on first use)
+  DeviceBuffer<uchar4> rgba;       // own buffers (host uploads land here)
+  float *depth = nullptr;       // what the kernels use: depth_own, or (inside a re-integration batch) one of the batch's images
+  DeviceBuffer<float> depth_own;
+  short *raw_depth = nullptr;   // (inside rgba's allocation, behind the RGBA image)
+  mutable DeviceBuffer<float> pyramid;  // depth tracker: levels 1.. of the depth pyramid (scratch, allocated on first use)
   // what the kernels read: own buffers, or the caller's resident frame (dslam_view_update_device: no copy)
   const uchar4 *rgba_src = nullptr;
   const short *raw_src = nullptr;
-  // pipelined uploads (async engine + page-locked caller images): two landing buffers, filled on the engine's copy
-  // stream while the compute stream still reads the other one
-  uchar4 *up_rgba[2] = {nullptr, nullptr};
-  short *up_raw[2] = {nullptr, nullptr};
-  hipEvent_t up_done[2] = {nullptr, nullptr};      // copy stream: buffer b has landed
-  hipEvent_t up_consumed[2] = {nullptr, nullptr};  // compute stream: every kernel that reads buffer b has been passed
+  short *up_raw[2] = {nullptr, nullptr};  // (inside up_rgba[b]'s allocation, behind the RGBA image)
   hipEvent_t up_consumed_by[2] = {nullptr, nullptr};  // the event that says so for the current contents: up_consumed[b] or a caller's fence
   dslam_fence *up_lender[2] = {nullptr, nullptr};     // ... the fence that event belongs to, if it is a caller's
   bool up_used[2] = {false, false};
@@ -277,9 +298,9 @@ struct dslam_view {
 };
 
 // a marker in the engine's stream (dslam_fence_*): lets a pipelining caller learn when a frame's results have landed
-struct dslam_fence {
+struct DSLAM_INTERNAL dslam_fence {
   dslam_engine *engine = nullptr;
-  hipEvent_t ev = nullptr;
+  Event ev;
   bool recorded = false;
   unsigned long long view_reads_at_record = 0;  // engine->view_reads when it was recorded
   int lent_count = 0;   // views that wait on `ev` as their "landing buffer consumed" mark at the moment
@@ -288,15 +309,15 @@ struct dslam_fence {
 
 // mfusionFrameDataBase's image payload (fusionFrameInfo::rgbinfo / depthinfo, DenseSlam.h:431-433) kept in HBM:
 // `capacity` slots of one RGBA image + one int16 depth image each, in two contiguous arrays
-struct dslam_frame_store {
+struct DSLAM_INTERNAL dslam_frame_store {
   dslam_engine *engine = nullptr;
   int w_rgb = 0, h_rgb = 0, w_d = 0, h_d = 0, capacity = 0;
   size_t rgba_bytes = 0, depth_bytes = 0;  // per slot
-  unsigned char *rgba = nullptr;
-  unsigned char *depth = nullptr;
+  DeviceBuffer<unsigned char> rgba;
+  DeviceBuffer<unsigned char> depth;
   // optional: per slot the visible list of the keyframe's fusion (dslam_frame_store_enable_lists):
   // [RenderCounters-sized header: count][int ids[list_cap]][short4 pos[list_cap]]
-  unsigned char *lists = nullptr;
+  DeviceBuffer<unsigned char> lists;
   int list_cap = 0;
   int list_entries = 0;   // hash-table size (entries) of the scene the lists were enabled for: their ids index that table
   size_t list_bytes = 0;  // per slot
@@ -304,7 +325,7 @@ struct dslam_frame_store {
   // where each slot's list lives: a buffer of `lists`, or -- after a re-integration batch, which writes the lists of its
   // re-fusions to scratch buffers and then trades buffers instead of copying -- one of `batch_lists`
   std::vector<unsigned char *> list_ptr;
-  unsigned char *batch_lists = nullptr;          // 32 more list buffers (allocated by the first batch)
+  DeviceBuffer<unsigned char> batch_lists;          // 32 more list buffers (allocated by the first batch)
   std::vector<unsigned char *> batch_list_ptr;
 };
 

@@ -968,10 +968,10 @@ __global__ __launch_bounds__(kWgWaves * 64, 8) void k_integrate(IntegrateParams 
 #undef DSLAM_STAMP
 }
 
-static void fill_params(IntegrateParams &ip, dslam_engine *e, dslam_scene *s, const dslam_view *v,
-                        const dslam_render_state *r, const float *M_d, const float *intr_d, const float *M_rgb,
+static void fill_params(IntegrateParams &ip, dslam_engine *e, dslam_scene *s, const dslam_view *v, const int *visible_ids,
+                        const RenderCounters *counters, const float *M_d, const float *intr_d, const float *M_rgb,
                         const float *intr_rgb) {
-  ip.visible_ids = r->visible_ids; ip.rc = r->counters; ip.hash = s->hash;
+  ip.visible_ids = visible_ids; ip.rc = counters; ip.hash = s->hash;
   ip.voxels16 = reinterpret_cast<uint4 *>(s->voxels);
   ip.depth = v->depth; ip.rgba = v->rgba_src;
   ip.Wd = v->w_d; ip.Hd = v->h_d; ip.Wr = v->w_rgb; ip.Hr = v->h_rgb;
@@ -1039,9 +1039,8 @@ static int launch_integrate_params(dslam_engine *e, IntegrateParams &ip, bool de
     static int dbg_calls = 0;
     if (dbg_file && plain && ++dbg_calls == 60) {
       constexpr size_t kTraceBytes = (size_t)kIntegrateGrid * kWgWaves * 16 * sizeof(unsigned long long);
-      unsigned long long *trace_dev = nullptr;
-      DSLAM_HIP(hipMalloc((void **)&trace_dev, kTraceBytes));
-      DSLAM_HIP(hipMemsetAsync(trace_dev, 0, kTraceBytes, e->stream));
+      DeviceBuffer<unsigned long long> trace_dev;
+      DSLAM_TRY(trace_dev.alloc_zeroed(kTraceBytes / sizeof(unsigned long long), e->stream));
       ip.dbg_waves = trace_dev;
       hipExtLaunchKernelGGL((k_integrate<false, true, DSLAM_PACKED && DSLAM_COLOUR_QUEUE, DSLAM_PACKED && DSLAM_COLOUR_QUEUE>), grid_plain, block, 0, e->stream, ev0, ev1, 0, ip);
       DSLAM_HIP(hipGetLastError());
@@ -1049,7 +1048,6 @@ static int launch_integrate_params(dslam_engine *e, IntegrateParams &ip, bool de
       std::vector<unsigned long long> h(kTraceBytes / sizeof(unsigned long long));
       DSLAM_HIP(hipMemcpy(h.data(), trace_dev, kTraceBytes, hipMemcpyDeviceToHost));
       if (FILE *f = fopen(dbg_file, "wb")) { fwrite(h.data(), 1, kTraceBytes, f); fclose(f); }
-      (void)hipFree(trace_dev);
       return DSLAM_OK;
     }
     if (plain && stream) e->stream_launches++;
@@ -1068,7 +1066,7 @@ int launch_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, const
   int rc = ensure_view_depth(e, v);
   if (rc) return rc;
   IntegrateParams ip;
-  fill_params(ip, e, s, v, r, M_d, intr_d, M_rgb, intr_rgb);
+  fill_params(ip, e, s, v, r->visible_ids, r->counters, M_d, intr_d, M_rgb, intr_rgb);
   ip.masks = s->masks; ip.last_seen = s->last_seen; ip.push_words = 0; ip.push_ring = 0; ip.push_bit = 0; ip.push_frame = 0;
   ip.push_job_min = e->push_job_min;
   ip.spec_ids = r->n_local >= kIntegrateGrid * kWgWaves ? 1 : 0;  // (a visible list has room for every voxel-block slot)
@@ -1077,7 +1075,7 @@ int launch_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, const
     ip.push_words = s->history_words; ip.push_ring = push_ring;
   }
   // (the visible count as the host last heard of it: dslam_render_state::vis_hint)
-  const bool stream = r->vis_hint && __atomic_load_n(r->vis_hint, __ATOMIC_RELAXED) >= e->push_job_min;
+  const bool stream = r->vis_hint && __atomic_load_n(r->vis_hint.get(), __ATOMIC_RELAXED) >= e->push_job_min;
   // GetImage's front end for this pose rides at the front of the launch.  Only on the plain kernel at the small V of a frame:
   // a streaming launch is hundreds of microseconds long and the selection's 12 us do not matter there.  (Not with the
   // per-wave timeline of DSLAM_DBG_INTEGRATE either: that launch is the plain kernel alone.)
@@ -1106,11 +1104,7 @@ int launch_integrate_list(dslam_engine *e, dslam_scene *s, const dslam_view *v, 
   int rc = ensure_view_depth(e, v);
   if (rc) return rc;
   IntegrateParams ip;
-  // (fill_params only takes the list pointer and the counter block from the render state)
-  dslam_render_state list_view;
-  list_view.visible_ids = const_cast<int *>(ids);
-  list_view.counters = reinterpret_cast<RenderCounters *>(const_cast<void *>(count_header));
-  fill_params(ip, e, s, v, &list_view, M_d, intr_d, M_rgb, intr_rgb);
+  fill_params(ip, e, s, v, ids, static_cast<const RenderCounters *>(count_header), M_d, intr_d, M_rgb, intr_rgb);
   ip.expect_pos = expect_pos;
   ip.masks = s->masks; ip.last_seen = s->last_seen; ip.push_words = 0; ip.push_ring = 0; ip.push_bit = 0; ip.push_frame = 0;
   ip.push_job_min = e->push_job_min;

@@ -737,7 +737,7 @@ static int swap_select_to_host(dslam_engine *e, dslam_scene *s, const unsigned c
                                int *out_count) {
   int rc = swap_select<MODE>(e, s, vis_type, m);
   if (rc) return rc;
-  int *host_count = reinterpret_cast<int *>(e->pinned) + 48;
+  int *host_count = reinterpret_cast<int *>(e->pinned.get()) + 48;
   DSLAM_HIP(hipMemcpyAsync(host_count, &s->counters->swap_count, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   *out_count = *host_count;
@@ -747,12 +747,12 @@ static int swap_select_to_host(dslam_engine *e, dslam_scene *s, const unsigned c
 // one more page-locked slab for the host store; its pointer goes to the device table the kernels index
 static int add_slab(dslam_engine *e, dslam_scene *s) {
   if ((int)s->slabs.size() >= kMaxSlabs) { set_last_error("host global cache: slab table full"); return DSLAM_ERR_INVALID; }
-  uint4 *slab = nullptr;
-  DSLAM_HIP(hipHostMalloc((void **)&slab, (size_t)kSlabBlocks * kBlock3 * sizeof(uint2), hipHostMallocDefault));
-  s->slabs.push_back(slab);
-  DSLAM_HIP(hipMemcpyAsync(s->slab_ptrs_dev + (s->slabs.size() - 1), &s->slabs.back(), sizeof(uint4 *), hipMemcpyHostToDevice,
-                           e->stream));
-  DSLAM_HIP(hipStreamSynchronize(e->stream));  // (the source is a vector element)
+  PinnedBuffer<uint4> slab;
+  DSLAM_TRY(slab.alloc((size_t)kSlabBlocks * kBlock3 * sizeof(uint2) / sizeof(uint4)));
+  uint4 *const addr = slab;
+  s->slabs.push_back(std::move(slab));
+  DSLAM_HIP(hipMemcpyAsync(s->slab_ptrs_dev + (s->slabs.size() - 1), &addr, sizeof(uint4 *), hipMemcpyHostToDevice, e->stream));
+  DSLAM_HIP(hipStreamSynchronize(e->stream));  // (the source is a local)
   return DSLAM_OK;
 }
 
@@ -870,7 +870,7 @@ int launch_slide_pop(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int
   SelSlidePop sel{s->hash, s->masks, s->history_words, q, bit, nullptr};
   launch_bits_select(e, s->alloc_bits, N, sel, m.cand_list, s->p.num_local_blocks, &s->counters->swap_count, s->counters);
   DSLAM_HIP(hipGetLastError());
-  int *host_count = reinterpret_cast<int *>(e->pinned) + 48;
+  int *host_count = reinterpret_cast<int *>(e->pinned.get()) + 48;
   DSLAM_HIP(hipMemcpyAsync(host_count, &s->counters->swap_count, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   DSLAM_HIP(hipStreamSynchronize(e->stream));   // (the host store must have slabs for every leaving block)
   const int total = *host_count;

@@ -207,21 +207,21 @@ int launch_mesh_scene(dslam_engine *e, const dslam_scene *s, int max_triangles, 
   hipLaunchKernelGGL(k_mesh_count, dim3(grid), dim3(512), 0, e->stream, p);
   hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(1024), 0, e->stream, e->list_b, e->list_c, live_count, total);
   DSLAM_HIP(hipGetLastError());
-  int *host = reinterpret_cast<int *>(e->pinned);
+  int *host = reinterpret_cast<int *>(e->pinned.get());
   DSLAM_HIP(hipMemcpyAsync(host, total, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   // upstream: `triangles[n] = t; if (n < noMaxTriangles - 1) n++;` -- the list saturates at noMaxTriangles - 1
   const int n = host[0] < max_triangles - 1 ? host[0] : max_triangles - 1;
   const size_t need = (size_t)(n > 0 ? n : 1) * 9 * sizeof(float);
   if (need > e->mesh_bytes || (with_colour && !e->mesh_colours)) {
-    if (e->mesh_positions) (void)hipFree(e->mesh_positions);
-    if (e->mesh_colours) (void)hipFree(e->mesh_colours);
-    e->mesh_positions = e->mesh_colours = nullptr;
+    // regrow: the old mesh goes first (it can be large); on failure the engine has no mesh buffers and mesh_bytes == 0
     const size_t bytes = need > e->mesh_bytes ? need : e->mesh_bytes;
-    e->mesh_bytes = 0;
-    DSLAM_HIP(hipMalloc(&e->mesh_positions, bytes));
-    if (with_colour) DSLAM_HIP(hipMalloc(&e->mesh_colours, bytes));
-    e->mesh_bytes = bytes;
+    e->mesh_positions.reset(); e->mesh_colours.reset();
+    e->mesh_bytes = 0; e->mesh_triangles = 0;
+    DeviceBuffer<float> positions, colours;
+    DSLAM_TRY(positions.alloc(bytes / sizeof(float)));
+    if (with_colour) DSLAM_TRY(colours.alloc(bytes / sizeof(float)));
+    e->mesh_positions = std::move(positions); e->mesh_colours = std::move(colours); e->mesh_bytes = bytes;
   }
   e->mesh_triangles = n;
   e->mesh_has_colour = with_colour != 0;

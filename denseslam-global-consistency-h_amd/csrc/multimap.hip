@@ -425,9 +425,11 @@ static bool is_identity(const float *T) {
 static int ensure_multi_buffers(dslam_render_state *r) {
   if (r->multi_mask) return DSLAM_OK;
   const size_t ncell = (size_t)((r->w + 7) / 8) * ((r->h + 7) / 8);
-  DSLAM_HIP(hipMalloc(&r->multi_mask, ncell * sizeof(unsigned long long)));
-  DSLAM_HIP(hipMalloc(&r->multi_maps, DSLAM_MAX_RENDER_MAPS * sizeof(MultiMap)));
-  DSLAM_HIP(hipMalloc(&r->multi_counts, DSLAM_MAX_RENDER_MAPS * sizeof(int)));
+  RenderMulti n;   // (the render state gets the three together or none)
+  DSLAM_TRY(n.multi_mask.alloc(ncell));
+  DSLAM_TRY(n.multi_maps.alloc(DSLAM_MAX_RENDER_MAPS * sizeof(MultiMap)));
+  DSLAM_TRY(n.multi_counts.alloc(DSLAM_MAX_RENDER_MAPS));
+  static_cast<RenderMulti &>(*r) = std::move(n);
   return DSLAM_OK;
 }
 
@@ -483,7 +485,7 @@ int launch_render_multi(dslam_engine *e, const dslam_scene *const *scenes, const
     DSLAM_HIP(hipGetLastError());
   }
   MultiRenderParams rp;
-  rp.maps = static_cast<const MultiMap *>(r->multi_maps);
+  rp.maps = static_cast<const MultiMap *>(r->multi_maps.get());
   rp.cell_mask = r->multi_mask;
   rp.cw = cw;
   memcpy(rp.M.m, M, 64);

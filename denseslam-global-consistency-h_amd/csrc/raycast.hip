@@ -40,7 +40,7 @@ int launch_count_visible(dslam_engine *e, const dslam_scene *s, const dslam_rend
   DSLAM_HIP(hipMemsetAsync(&r->counters->count_result, 0, sizeof(int), e->stream));
   hipLaunchKernelGGL(k_count_visible, dim3(128), dim3(256), 0, e->stream, r->visible_ids, r->counters, s->hash, min_id,
                      max_id);
-  int *host = reinterpret_cast<int *>(e->pinned);
+  int *host = reinterpret_cast<int *>(e->pinned.get());
   DSLAM_HIP(hipMemcpyAsync(host, &r->counters->count_result, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   *out = *host;
@@ -269,7 +269,7 @@ int launch_find_visible_and_depths(dslam_engine *e, const dslam_scene *s, dslam_
   // The last ProcessFrame computed this selection already (FrontEndRecord): same map, pose, intrinsics and image size.  The
   // render state takes its buffers -- the list, its count, the projections, the per-tile totals, the reset range image --
   // and gives its own in exchange (the same sizes), all on the engine's one stream.
-  if (FrontEndRecord *f = s->front) {
+  if (FrontEndRecord *f = s->front.get()) {
     if (f->valid && f->version == s->version && f->w == r->w && f->h == r->h && f->n_local == r->n_local &&
         f->n_entries == r->n_entries && memcmp(f->M, M, sizeof(f->M)) == 0 && memcmp(f->intr, intr, sizeof(f->intr)) == 0) {
       std::swap(r->visible_ids, f->visible_ids);
@@ -575,9 +575,9 @@ int launch_render(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, 
   static const char *dbg_file = getenv("DSLAM_DBG_WAVETIME");
   static int dbg_calls = 0;
   const int n_waves = ((r->w + 7) / 8) * ((r->h + 7) / 8) * 2;
-  unsigned long long *dbg_host = nullptr;
+  PinnedBuffer<unsigned long long> dbg_host;
   if (dbg_file && ++dbg_calls == 30) {  // one snapshot, well into the run
-    DSLAM_HIP(hipHostMalloc((void **)&dbg_host, (size_t)n_waves * 48, hipHostMallocDefault));
+    DSLAM_TRY(dbg_host.alloc((size_t)n_waves * 6));
     memset(dbg_host, 0, (size_t)n_waves * 48);
     rp.dbg_waves = dbg_host;
   }
@@ -598,7 +598,6 @@ int launch_render(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, 
     DSLAM_HIP(hipStreamSynchronize(e->stream));
     FILE *f = fopen(dbg_file, "wb");
     if (f) { fwrite(dbg_host, 48, n_waves, f); fclose(f); }
-    (void)hipHostFree(dbg_host);
   }
   return DSLAM_OK;
 }
@@ -660,9 +659,10 @@ __global__ __launch_bounds__(256) void k_icp_maps(const float4 *__restrict__ pr,
 
 int launch_icp_maps(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float *M, const float *intr) {
   if (!r->icp_points) {
-    DSLAM_HIP(hipMalloc(&r->icp_points, (size_t)r->w * r->h * sizeof(float4)));
-    DSLAM_HIP(hipMalloc(&r->icp_normals, (size_t)r->w * r->h * sizeof(float4)));
-    DSLAM_HIP(hipMalloc(&r->raycast_image, (size_t)r->w * r->h * sizeof(uchar4)));
+    RenderIcpMaps n;   // (the render state gets the three together or none)
+    DSLAM_TRY(n.icp_points.alloc((size_t)r->w * r->h)); DSLAM_TRY(n.icp_normals.alloc((size_t)r->w * r->h));
+    DSLAM_TRY(n.raycast_image.alloc((size_t)r->w * r->h));
+    static_cast<RenderIcpMaps &>(*r) = std::move(n);
   }
   RenderParams rp;
   int rc = fill_render_params(rp, s, r, M, intr, -1);

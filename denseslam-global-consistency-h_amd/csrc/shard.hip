@@ -87,7 +87,7 @@ int launch_dirty_plan(dslam_engine *e, dslam_scene *s, int num_shards, int chunk
   int rc = ensure_scratch(e, s->n_entries, N);
   if (rc) return rc;
   const ShardLayout L = {N, num_shards, chunk_blocks, N / num_shards};
-  unsigned char *vflags = reinterpret_cast<unsigned char *>(e->list_c);  // >= N bytes
+  unsigned char *vflags = reinterpret_cast<unsigned char *>(e->list_c.get());  // >= N bytes
   const int n_tiles = num_tiles(N);
   hipLaunchKernelGGL(k_dirty_permute, dim3((N + 255) / 256), dim3(256), 0, e->stream, s->dirty, vflags, L);
   hipLaunchKernelGGL(k_dirty_counts, dim3(num_shards), dim3(256), 0, e->stream, vflags, L, s->dirty_counts);
@@ -96,7 +96,7 @@ int launch_dirty_plan(dslam_engine *e, dslam_scene *s, int num_shards, int chunk
   hipLaunchKernelGGL(k_compact_apply_fused, dim3(n_tiles), dim3(256), 0, e->stream, vflags, N, e->tile_counts, s->dirty_list, N,
                      s->dirty_counts + 64);
   DSLAM_HIP(hipGetLastError());
-  int *host = reinterpret_cast<int *>(e->pinned) + 256;
+  int *host = reinterpret_cast<int *>(e->pinned.get()) + 256;
   DSLAM_HIP(hipMemcpyAsync(host, s->dirty_counts, (size_t)num_shards * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   for (int r = 0; r < num_shards; r++) counts_host[r] = host[r];

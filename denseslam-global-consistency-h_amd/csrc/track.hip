@@ -187,12 +187,11 @@ int launch_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state
   int rc = ensure_view_depth(e, v);
   if (rc) return rc;
   // depth pyramid (levels 1.. live in one buffer of the view) and the partial-sum buffers
-  if (!v->pyramid) DSLAM_HIP(hipMalloc(&v->pyramid, (size_t)v->w_d * v->h_d * sizeof(float)));  // sum of levels 1.. < 1/3
-  if (!e->icp_partials_host) {
+  if (!v->pyramid) DSLAM_TRY(v->pyramid.alloc((size_t)v->w_d * v->h_d));  // sum of levels 1.. < 1/3
+  if (!e->icp_partials) {
     // the workgroup partials (240 x 29 doubles) are written straight into mapped pinned host memory: one stream
     // synchronise per iteration instead of a copy launch plus a synchronise
-    DSLAM_HIP(hipHostMalloc((void **)&e->icp_partials_host, (size_t)kIcpGrid * kIcpSums * sizeof(double), hipHostMallocMapped));
-    DSLAM_HIP(hipHostGetDevicePointer((void **)&e->icp_partials, e->icp_partials_host, 0));
+    DSLAM_TRY(e->icp_partials.alloc((size_t)kIcpGrid * kIcpSums, hipHostMallocMapped));
   }
   const float *ldepth[DSLAM_TRACKER_MAX_LEVELS];
   int lw[DSLAM_TRACKER_MAX_LEVELS], lh[DSLAM_TRACKER_MAX_LEVELS];
@@ -241,7 +240,7 @@ int launch_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state
       memcpy(ip.scenePose.m, scenePose, 64);
       ip.points = r->icp_points; ip.normals = r->icp_normals;
       ip.dist_thresh = dist_per_level[level];
-      ip.partials = e->icp_partials;
+      ip.partials = e->icp_partials.device();
       const int grid = std::min(kIcpGrid, (lw[level] * lh[level] + 255) / 256);
       if (type == DSLAM_TRACKER_ITERATION_ROTATION) hipLaunchKernelGGL((k_icp_gh<1>), dim3(grid), dim3(256), 0, e->stream, ip);
       else if (type == DSLAM_TRACKER_ITERATION_TRANSLATION) hipLaunchKernelGGL((k_icp_gh<2>), dim3(grid), dim3(256), 0, e->stream, ip);
@@ -251,7 +250,7 @@ int launch_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state
       double sums[kIcpSums];
       for (int i = 0; i < kIcpSums; i++) sums[i] = 0.0;
       for (int g = 0; g < grid; g++)
-        for (int i = 0; i < kIcpSums; i++) sums[i] += e->icp_partials_host[(size_t)g * kIcpSums + i];
+        for (int i = 0; i < kIcpSums; i++) sums[i] += e->icp_partials[(size_t)g * kIcpSums + i];
       const int valid = (int)sums[28];
       float hessian_new[36] = {0}, nabla_new[6] = {0};
       for (int k = 0, c = 0; k < npara; k++)
