@@ -502,6 +502,13 @@ class CApi:
                    C.byref(res))
         return pose.reshape(4, 4).T.copy(), res
 
+    def debug_icp_sums(self):
+        """The 29 double sums of the tracker's most recent ComputeGandH evaluation: 21 Hessian (lower triangle, row by
+        row), 6 gradient, sum of b^2, valid count."""
+        out = np.empty(29, dtype=np.float64)
+        self._call("debug_icp_sums", self._engine, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
+
     def _image_call(self, name, scene, rs, M, intr, image_type, download=True, out=None):
         """`out`: an existing (H, W) float32 / (H, W, 4) uint8 array to fill instead of a fresh one (e.g. a page-locked
         array from host_alloc, which the copy back DMAs into directly)."""

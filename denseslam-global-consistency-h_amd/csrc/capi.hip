@@ -286,6 +286,12 @@ int dslam_debug_front_end_counts(dslam_engine *e, long long *computed_out, long 
   *adopted_out = e->front_adoptions;
   return DSLAM_OK;
 }
+int dslam_debug_icp_sums(dslam_engine *e, double out[29]) {
+  DSLAM_REQUIRE(e && out, "null argument");
+  DSLAM_REQUIRE(e->icp_have_sums, "no tracker evaluation has run on this engine");
+  memcpy(out, e->icp_last_sums, sizeof e->icp_last_sums);
+  return DSLAM_OK;
+}
 int dslam_debug_inject_device_error(dslam_engine *e, dslam_scene *s, int bits) {
   DSLAM_REQUIRE(e && s && s->engine == e && (bits == 1 || bits == 2 || bits == 3), "bad argument");
   int rc = launch_inject_error(e, s, bits);

@@ -130,6 +130,8 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   long long front_adoptions = 0;      // GetImage front ends taken from such a record instead of computed (test hook)
   int render_tile_budget = DSLAM_MAX_RENDERING_BLOCKS;  // MAX_RENDERING_BLOCKS; lowered only by the budget test
   PinnedBuffer<double> icp_partials;  // depth tracker: per-workgroup partial sums in mapped page-locked memory (kernels: device())
+  double icp_last_sums[29] = {0};     // the totals of the most recent ComputeGandH evaluation (dslam_debug_icp_sums; test hook)
+  bool icp_have_sums = false;
   DeviceBuffer<int> misc_counter;        // device: small result counters of one-off kernels (depthPostProcessing)
   // the last mesh dslam_mesh_scene produced (ITMMesh: triangles as 3 x Vector3f, metres)
   DeviceBuffer<float> mesh_positions;    // device [mesh_triangles][3][3]

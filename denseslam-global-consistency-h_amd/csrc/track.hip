@@ -251,6 +251,8 @@ int launch_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state
       for (int i = 0; i < kIcpSums; i++) sums[i] = 0.0;
       for (int g = 0; g < grid; g++)
         for (int i = 0; i < kIcpSums; i++) sums[i] += e->icp_partials[(size_t)g * kIcpSums + i];
+      memcpy(e->icp_last_sums, sums, sizeof sums);
+      e->icp_have_sums = true;
       const int valid = (int)sums[28];
       float hessian_new[36] = {0}, nabla_new[6] = {0};
       for (int k = 0, c = 0; k < npara; k++)

@@ -498,6 +498,13 @@ typedef struct {
 int dslam_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state *r, const float scene_pose_M[16],
                        float pose_M[16], const float intrinsics_d[4], const dslam_tracker_params *params,
                        dslam_tracker_result *result);
+/* Test hook: the sums of the most recent ComputeGandH evaluation of this engine's tracker, as accumulated in double and
+ * before anything is rounded to float: out[0..20] the Hessian's lower triangle row by row (k, j <= k; the 3-parameter
+ * iteration types fill the first 6), out[21..26] the gradient, out[27] the sum of b^2, out[28] the valid-point count.
+ * A tracked pose mixes all of them through damped solves; a test of the per-pixel function reads them here (one
+ * evaluation is isolated with no_hierarchy_levels = k + 1, no_icp_run_till_level = k and a termination threshold no
+ * step stays below).  Error if no evaluation has run. */
+int dslam_debug_icp_sums(dslam_engine *e, double out[29]);
 
 /* ---- state read-back (stats for the driver; bulk downloads for parity tests and checkpoints) ------ */
 int dslam_get_stats(dslam_engine *e, const dslam_scene *s, const dslam_render_state *r, dslam_stats *out);

@@ -134,6 +134,8 @@ struct oracle_engine {
   int render_tile_budget = DSLAM_MAX_RENDERING_BLOCKS;
   std::vector<float> mesh_pos, mesh_col;  // the last mesh oracle_mesh_scene produced ([n][3][3] each)
   bool mesh_has_colour = false;
+  double icp_last_sums[29] = {0};  // the most recent ComputeGandH evaluation (oracle_debug_icp_sums)
+  bool icp_have_sums = false;
 };
 
 struct oracle_scene {
@@ -1963,7 +1965,7 @@ void coerce_pose(float *M) {
 }
 }  // namespace
 
-extern "C" int oracle_track_camera(oracle_engine *, const oracle_view *v, oracle_render_state *r, const float *scenePose,
+extern "C" int oracle_track_camera(oracle_engine *e, const oracle_view *v, oracle_render_state *r, const float *scenePose,
                         float *pose_M, const float *intr, const dslam_tracker_params *tp, dslam_tracker_result *res) {
   const int levels = tp->no_hierarchy_levels;
   if (levels < 1 || levels > DSLAM_TRACKER_MAX_LEVELS || tp->no_icp_run_till_level < 0) return DSLAM_ERR_INVALID;
@@ -2018,6 +2020,10 @@ extern "C" int oracle_track_camera(oracle_engine *, const oracle_view *v, oracle
             for (int j = 0; j <= k; j++, c++) sumH[c] += (double)(A[k] * A[j]);
           }
         }
+      for (int i = 0; i < 21; i++) e->icp_last_sums[i] = sumH[i];
+      for (int i = 0; i < 6; i++) e->icp_last_sums[21 + i] = sumN[i];
+      e->icp_last_sums[27] = sumF; e->icp_last_sums[28] = (double)valid;
+      e->icp_have_sums = true;
       float hessian_new[36] = {0}, nabla_new[6] = {0};
       for (int k = 0, c = 0; k < npara; k++)
         for (int j = 0; j <= k; j++, c++) hessian_new[k + j * 6] = hessian_new[j + k * 6] = (float)sumH[c];
@@ -2071,6 +2077,12 @@ extern "C" int oracle_track_camera(oracle_engine *, const oracle_view *v, oracle
   }
   memcpy(pose_M, M, 64);
   if (res) { res->iterations = total_iters; res->valid_points_last = last_valid; res->f_last = last_f; res->pad = 0; }
+  return 0;
+}
+
+extern "C" int oracle_debug_icp_sums(oracle_engine *e, double *out) {
+  if (!e || !out || !e->icp_have_sums) return DSLAM_ERR_INVALID;
+  memcpy(out, e->icp_last_sums, sizeof e->icp_last_sums);
   return 0;
 }
 

@@ -42,6 +42,12 @@ class Plane:
     def normal(self, x):
         return np.broadcast_to(self.n, x.shape)
 
+    def ray_depth(self, origin, dirs):
+        """t > 0 with origin + t dirs on the surface, nan where the ray does not reach it (all geometries alike)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = (self.c - origin @ self.n) / (dirs @ self.n)
+        return np.where(t > 0, t, np.nan)
+
 
 class Sphere:
     """Seen from outside (inside=False: d = |x - c| - r) or from inside (d = r - |x - c|)."""
@@ -57,6 +63,15 @@ class Sphere:
         v = x - self.c
         v = v / np.linalg.norm(v, axis=-1, keepdims=True)
         return -v if self.inside else v
+
+    def ray_depth(self, origin, dirs):
+        """Nearer root from outside, farther root from inside."""
+        o = np.asarray(origin, np.float64) - self.c
+        a, hb, c = np.sum(dirs * dirs, -1), dirs @ o, o @ o - self.r ** 2
+        with np.errstate(invalid="ignore"):
+            s = np.sqrt(hb * hb - a * c)
+        t = (-hb + s) / a if self.inside else (-hb - s) / a
+        return np.where(t > 0, t, np.nan)
 
 
 class BoxCorner:
@@ -75,6 +90,12 @@ class BoxCorner:
         out = np.zeros(x.shape)
         np.put_along_axis(out, i[..., None], -1.0, axis=-1)
         return out
+
+    def ray_depth(self, origin, dirs):
+        """The first of the three walls a ray from inside the octant meets."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = np.where(dirs > 0, (self.k - origin) / dirs, np.inf).min(axis=-1)
+        return np.where(np.isfinite(t) & (t > 0), t, np.nan)
 
 
 class Map:
