@@ -1000,14 +1000,6 @@ int dslam_deprocess_frame_stored(dslam_engine *e, dslam_scene *s, const dslam_vi
 // ---- the re-integration batch, block-major (integrate.hip) ---------------------------------------------------------------
 namespace {
 constexpr int kBatchMax = 32;   // keyframes per launch of the block kernel: two operation bits each in a 64-bit mask
-struct HostBatchOp {            // = BatchOp (integrate.hip)
-  float M[16];
-  const void *depth, *rgba;
-  int push_bit, push_frame, pad[2];
-};
-struct HostBatchList {          // = BatchListRef
-  const void *count, *ids, *pos;
-};
 }  // namespace
 
 // A batch that stops after its first mutation (only a HIP failure can do that: every argument was checked before) leaves
@@ -1039,8 +1031,8 @@ static int batch_scratch(dslam_engine *e, dslam_scene *s, dslam_frame_store *fs)
     DSLAM_TRY(n.batch_marks.alloc_zeroed(L * 64, e->stream));   // (every batch leaves them zero again)
     DSLAM_TRY(n.batch_order.alloc(8 * L));
     DSLAM_TRY(n.batch_counters.alloc(16));   // [0..8): blocks per class, [8]: block-operations
-    DSLAM_TRY(n.batch_ops_dev.alloc(2 * kBatchMax * sizeof(HostBatchOp))); DSLAM_TRY(n.batch_lists_dev.alloc(3 * kBatchMax * sizeof(HostBatchList)));
-    DSLAM_TRY(n.batch_staging.alloc(2 * kBatchMax * sizeof(HostBatchOp) + 3 * kBatchMax * sizeof(HostBatchList)));
+    DSLAM_TRY(n.batch_ops_dev.alloc(2 * kBatchMax)); DSLAM_TRY(n.batch_lists_dev.alloc(3 * kBatchMax));
+    DSLAM_TRY(n.batch_staging.alloc(2 * kBatchMax * sizeof(BatchOp) + 3 * kBatchMax * sizeof(BatchListRef)));
     DSLAM_TRY(n.batch_staging_ev.create());
     static_cast<SceneBatch &>(*s) = std::move(n);
   }
@@ -1096,12 +1088,17 @@ int dslam_reintegrate_batch(dslam_engine *e, dslam_scene *s, dslam_view *v, dsla
     DSLAM_HIP(hipMemsetAsync(s->batch_counters, 0, 16 * sizeof(int), e->stream));
     // (built in page-locked memory: the copies are queued behind the allocation passes and nothing waits for them here)
     DSLAM_HIP(hipEventSynchronize(s->batch_staging_ev));   // the previous batch's copies have left the buffer
-    HostBatchOp *ops = reinterpret_cast<HostBatchOp *>(s->batch_staging.get());
-    HostBatchList *lists = reinterpret_cast<HostBatchList *>(ops + 2 * kBatchMax);   // [2K, 3K): the lists whose block positions are filled in at the end
+    BatchOp *ops = reinterpret_cast<BatchOp *>(s->batch_staging.get());
+    BatchListRef *lists = reinterpret_cast<BatchListRef *>(ops + 2 * kBatchMax);   // [2K, 3K): the lists whose block positions are filled in at the end
     // phase 1: the allocation passes of the K re-fusions, in keyframe order (they read the table and the keyframes' depth
     // images, not the voxels); every pass' list goes to a scratch buffer, the blocks it allocates are stamped
     s->alloc_born = s->batch_born;
     int n_pos_jobs = 0;
+    // a list buffer (header, ids, positions) as the kernels take it
+    auto list_ref = [&](const unsigned char *b, bool with_pos) {
+      return BatchListRef{reinterpret_cast<const RenderCounters *>(b), reinterpret_cast<const int *>(b + ids_off),
+                          with_pos ? reinterpret_cast<const short4 *>(b + pos_off) : nullptr};
+    };
     float *const view_depth = v->depth;
     for (int k = 0; k < K; k++) {
       const int slot = slots[first + k];
@@ -1125,24 +1122,24 @@ int dslam_reintegrate_batch(dslam_engine *e, dslam_scene *s, dslam_view *v, dsla
                                             fs->list_cap)))
           break;
       } else {
-        lists[2 * K + n_pos_jobs++] = {nb, nb + ids_off, nb + pos_off};
+        lists[2 * K + n_pos_jobs++] = list_ref(nb, true);
       }
       const unsigned char *ob = list_slot(fs, slot);
-      HostBatchOp &d = ops[2 * k], &f = ops[2 * k + 1];
-      memcpy(d.M, old_M + 16 * (size_t)(first + k), 64);
-      memcpy(f.M, new_M + 16 * (size_t)(first + k), 64);
-      d.depth = f.depth = v->depth; d.rgba = f.rgba = rgba;
+      BatchOp &d = ops[2 * k], &f = ops[2 * k + 1];
+      memcpy(d.M.m, old_M + 16 * (size_t)(first + k), 64);
+      memcpy(f.M.m, new_M + 16 * (size_t)(first + k), 64);
+      d.depth = f.depth = v->depth; d.rgba = f.rgba = static_cast<const uchar4 *>(rgba);
       d.push_bit = d.push_frame = 0; f.push_bit = bit; f.push_frame = frame;
-      lists[2 * k] = {ob, ob + ids_off, ob + pos_off};
-      lists[2 * k + 1] = {nb, nb + ids_off, nullptr};
+      lists[2 * k] = list_ref(ob, true);
+      lists[2 * k + 1] = list_ref(nb, false);
     }
     s->alloc_born = nullptr;
     v->depth = view_depth;
     v->depth_dirty = true;   // (the view's own float image was not written: its next consumer derives it)
     if (rc) return batch_failed(s, r, fs, slots + first, K, rc);
     // phase 2: which operations touch which block, then every touched block once
-    DSLAM_HIP(hipMemcpyAsync(s->batch_ops_dev, ops, 2 * (size_t)K * sizeof(HostBatchOp), hipMemcpyHostToDevice, e->stream));
-    DSLAM_HIP(hipMemcpyAsync(s->batch_lists_dev, lists, 3 * (size_t)K * sizeof(HostBatchList), hipMemcpyHostToDevice, e->stream));
+    DSLAM_HIP(hipMemcpyAsync(s->batch_ops_dev, ops, 2 * (size_t)K * sizeof(BatchOp), hipMemcpyHostToDevice, e->stream));
+    DSLAM_HIP(hipMemcpyAsync(s->batch_lists_dev, lists, 3 * (size_t)K * sizeof(BatchListRef), hipMemcpyHostToDevice, e->stream));
     DSLAM_HIP(hipEventRecord(s->batch_staging_ev, e->stream));
     if ((rc = launch_batch_ops(e, s->batch_lists_dev, 2 * K, s, s->batch_born, s->batch_marks, s->batch_opmask, s->batch_slot_entry,
                                s->batch_order, s->batch_counters)))
@@ -1150,7 +1147,7 @@ int dslam_reintegrate_batch(dslam_engine *e, dslam_scene *s, dslam_view *v, dsla
     if ((rc = launch_reintegrate_blocks(e, s, v->w_d, v->h_d, v->w_rgb, v->h_rgb, intr, s->batch_ops_dev,
                                         s->batch_opmask, s->batch_slot_entry, s->batch_order, s->batch_counters, 1, 2 * K)))
       return batch_failed(s, r, fs, slots + first, K, rc);
-    if ((rc = launch_store_list_positions(e, s, reinterpret_cast<const HostBatchList *>(s->batch_lists_dev.get()) + 2 * K, n_pos_jobs)))
+    if ((rc = launch_store_list_positions(e, s, s->batch_lists_dev + 2 * K, n_pos_jobs)))
       return batch_failed(s, r, fs, slots + first, K, rc);
     // the lists of the re-fusions become the keyframes' stored lists: the buffers trade places
     for (int k = 0; k < K; k++) std::swap(fs->list_ptr[slots[first + k]], fs->batch_list_ptr[k]);

@@ -35,6 +35,23 @@ void set_last_error(const std::string &msg);
 // host inverse of a column-major 4x4 (ORUtils::Matrix4::inv); used for invM_d = pose_d->GetInvM()
 bool invert_matrix(const float *m, float *dst);
 
+// The re-integration batch (integrate.hip) as the host builds it (capi.hip) and the kernels read it: one BatchOp per
+// operation -- [2k] the de-integration of keyframe k at its old pose, [2k + 1] its re-fusion at the new one ...
+struct BatchOp {
+  Mat4 M;                // world -> camera of this operation
+  const float *depth;    // the keyframe's depth image in metres: written by the allocation pass of its re-fusion (k_mark derives
+                         // it from the int16 image exactly as UpdateView does) into the batch's scratch, one image per keyframe
+  const uchar4 *rgba;
+  int push_bit, push_frame;  // re-fusions: the ring bit and frame stamp ProcessFrame(isDefusion) queues the block with
+  int pad[2];
+};
+// ... and one list per operation (k_batch_mark), plus the lists whose block positions k_store_list_positions fills in
+struct BatchListRef {
+  const RenderCounters *count;   // header of the list (no_visible = its length)
+  const int *ids;
+  const short4 *pos;             // stored lists: the block each entry held at fusion time; null: a fresh list
+};
+
 // scratch shared by all scenes of an engine, sized for the largest scene seen (ensure_scratch builds a new set aside and
 // move-assigns it: buffers and sizes change together)
 struct EngineScratch {
@@ -173,7 +190,8 @@ struct SceneBatch {
   DeviceBuffer<unsigned long long> batch_opmask;
   DeviceBuffer<int> batch_slot_entry, batch_order, batch_counters;   // (batch_order: 8 class lists)
   DeviceBuffer<unsigned char> batch_marks;   // [num_local_blocks][64]: operation k of the batch touches the block (zero between batches)
-  DeviceBuffer<void> batch_ops_dev, batch_lists_dev;
+  DeviceBuffer<dslam::BatchOp> batch_ops_dev;
+  DeviceBuffer<dslam::BatchListRef> batch_lists_dev;
   PinnedBuffer<void> batch_staging;          // page-locked: the operations and list references of a batch on their way to the device
   Event batch_staging_ev;                 // ... the copies out of it have been made
 };
@@ -370,11 +388,11 @@ int launch_integrate_list(dslam_engine *e, dslam_scene *s, const dslam_view *v, 
                           const float *intr_rgb, bool deintegrate);
 int launch_store_visible_list(dslam_engine *e, const dslam_scene *s, const dslam_render_state *r, void *header, int *ids,
                               short4 *pos, int capacity);
-int launch_store_list_positions(dslam_engine *e, const dslam_scene *s, const void *jobs_dev, int n_jobs);
-int launch_batch_ops(dslam_engine *e, const void *lists_dev, int n_ops, const dslam_scene *s, const int *born, unsigned char *marks,
+int launch_store_list_positions(dslam_engine *e, const dslam_scene *s, const BatchListRef *jobs_dev, int n_jobs);
+int launch_batch_ops(dslam_engine *e, const BatchListRef *lists_dev, int n_ops, const dslam_scene *s, const int *born, unsigned char *marks,
                      unsigned long long *opmask, int *slot_entry, int *cls_list, int *cls_count);
 int launch_reintegrate_blocks(dslam_engine *e, dslam_scene *s, int w_d, int h_d, int w_rgb, int h_rgb, const float *intr,
-                              const void *ops_dev, const unsigned long long *opmask, const int *slot_entry,
+                              const BatchOp *ops_dev, const unsigned long long *opmask, const int *slot_entry,
                               const int *cls_list, const int *cls_count, int push_ring, int n_ops);
 int alloc_step_cap(const dslam_scene *s, int W, int H, int *cap_out);
 int ensure_view_depth(dslam_engine *e, const dslam_view *v);

@@ -14,6 +14,24 @@
 //   Only 16-byte chunks that changed are written back.
 //   Grid = fixed 512 workgroups of 16 waves (one full residency wave of the 256 CUs), grid-stride over the
 //   visible list whose length is read from device memory (no host round trip after allocation).
+//
+// Instantiations (the host chooses: launch_integrate_params, launch_reintegrate_blocks) and the API path that reaches each:
+//   k_integrate<DEINT, SAME_CAM, PLAIN, DIAG, STREAM, FRONT>
+//     <0,1,1,0,0,0>  ProcessFrame / IntegrateIntoScene in the reference's configuration (plain_fusion)
+//     <0,1,1,0,0,1>  the same with GetImage's front end at the head of the launch (dslam_process_frame with a front record)
+//     <0,1,1,0,1,0>  the same above push_job_min visible blocks: non-temporal voxel traffic
+//     <0,1,1,1,0,0>  the same with the per-wave timeline (env DSLAM_DBG_INTEGRATE)
+//     <0,1,0,0,0,0>  one-camera fusion with an optional feature: stored list, shards, dirty marks, stopIntegratingAtMaxW,
+//                    depth weighting
+//     <0,0,0,0,0,0>  fusion with a colour camera of its own (M_rgb / intr_rgb differ from the depth camera's)
+//     <1,1,0,0,0,0>  DeProcessFrame, dslam_deprocess_frame_stored; <1,1,0,0,1,0> above push_job_min visible blocks
+//     <1,0,0,0,0,0>  de-integration with a colour camera of its own: the one voxel-by-voxel path (deintegrate_voxel_two_cam)
+//   k_reintegrate_blocks<UNIT_W, kHalves>   dslam_reintegrate_batch
+//     <1,2> / <0,2>  unsharded scene, weight 1 / depth weighting;  <1,1> / <0,1>  under dslam_scene_set_shard
+// The colour update (computeUpdatedVoxelColorInfo) is written out in fuse_colour, defuse_colour_word, batch_colour_word and
+// deintegrate_voxel_two_cam; the depth update in fuse_pair, pair_update and deintegrate_voxel_two_cam; the per-wave colour
+// queue in k_integrate and in batch_op_half / batch_colour_fetch.  A change to one goes into the others (DESIGN 4a records
+// what merging them costs the kernels that sit at the 64-register limit).
 #include <hip/hip_ext.h>
 
 #include <cstdio>
@@ -24,38 +42,7 @@
 
 #pragma clang fp contract(off)
 
-// -DDSLAM_PACKED=0 builds the fusion path voxel by voxel (the scalar form the packed one must match bit for bit;
-// used for A/B timing)
-#ifndef DSLAM_PACKED
-#define DSLAM_PACKED 1
-#endif
-// -DDSLAM_COLOUR_QUEUE=0: the colour update inline in every lane's voxel loop (the form the queued one must match; A/B timing)
-#ifndef DSLAM_COLOUR_QUEUE
-#define DSLAM_COLOUR_QUEUE 1
-#endif
 namespace dslam {
-
-// Voxel chunks of a launch that is larger than the Infinity Cache (>= push_job_min = 65536 visible blocks = 256 MiB) are read and
-// written with the non-temporal policy (template parameter STREAM of k_integrate): nothing of such a launch is still cached when
-// somebody comes back for it, and the S-stress launch is 8 % shorter (0.533 -> 0.576 of the peak, three alternations on one box;
-// nt loads alone 0.542, nt stores alone 0.533, write-through `sc1` stores 0.529).  Launches of a real sequence's size keep the
-// default policy -- the ray march that follows reads these lines: nt loads on the bench scene leave the launch at 21.0 us and
-// make the frame 148 us instead of 140.  The policy is part of the instruction, so the HOST chooses the instantiation, by the
-// visible count it last heard of (dslam_render_state::vis_hint: a page-locked word the allocation sweep writes; no wait).  A
-// flag tested inside ONE kernel was tried first: the plain kernel has no register for it (12 bytes of scratch per lane, the
-// bench launch +0.9 us), and the block loop written twice behind one test doubled the scalar spills.
-typedef unsigned vox_v4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void vox_load2(uint4 &v0, uint4 &v1, const uint4 *a0, const uint4 *a1) {
-  const vox_v4 r0 = __builtin_nontemporal_load(reinterpret_cast<const vox_v4 *>(a0));
-  const vox_v4 r1 = __builtin_nontemporal_load(reinterpret_cast<const vox_v4 *>(a1));
-  v0 = make_uint4(r0.x, r0.y, r0.z, r0.w);
-  v1 = make_uint4(r1.x, r1.y, r1.z, r1.w);
-}
-__device__ __forceinline__ void vox_store(uint4 *a, const uint4 &v) {
-  const vox_v4 r = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(r, reinterpret_cast<vox_v4 *>(a));
-}
-
 
 // GetImage's front end at the fusion pose (FrontEndRecord, dslam_internal.h): the tiles of k_bits_select<SelFrustum<true>>
 // as the first workgroups of the fusion launch.  They read the bitmap of resident entries and the entries' positions --
@@ -266,11 +253,11 @@ __device__ __forceinline__ void bilinear_rgb(const uchar4 *__restrict__ rgba, fl
             (float)d.z * dx * dy);
 }
 
-// ComputeUpdatedVoxelInfo<hasColor>::compute on a packed voxel (lo, hi) whose camera-frame position pc = M_d * pm
-// has been assembled by the caller.  Returns true if the voxel changed.
-template <bool DEINT, bool SAME_CAM>
-__device__ __forceinline__ bool update_voxel(unsigned &lo, unsigned &hi, const Vec4 &pc, const Vec4 &pm,
-                                             const IntegrateParams &p, const float *inv_tab) {
+// ComputeUpdatedVoxelInfo<hasColor>::compute of the de-integration on a packed voxel (lo, hi) whose camera-frame position
+// pc = M_d * pm has been assembled by the caller, with a colour camera of its own (M_rgb, intr_rgb): the voxel-by-voxel form,
+// used by the two-camera de-integration k_integrate<true, false> alone.  Returns true if the voxel changed.
+__device__ __forceinline__ bool deintegrate_voxel_two_cam(unsigned &lo, unsigned &hi, const Vec4 &pc, const Vec4 &pm,
+                                                          const IntegrateParams &p, const float *inv_tab) {
   float eta, eta_mu, u, w;
   bool changed = false;
   {  // computeUpdatedVoxelDepthInfo
@@ -285,17 +272,9 @@ __device__ __forceinline__ bool update_voxel(unsigned &lo, unsigned &hi, const V
     const float oldF = div_exact((float)(short)(lo & 0xffffu), 32767.0f, p.inv_32767);
     const int oldW = (int)((lo >> 16) & 0xffu);
     eta_mu = eta / p.mu;  // true IEEE division: the 3-instruction form is NOT exact for arbitrary mu
-    float newF = fminf(1.0f, eta_mu);
-    int newW = new_weight(p, dm);
-    if (!DEINT) {
-      newF = (float)oldW * oldF + (float)newW * newF;
-      newW = oldW + newW;
-      newF = div_exact(newF, (float)newW, inv_tab[newW]);
-      newW = newW < p.max_w ? newW : p.max_w;
-      const unsigned sdf = (unsigned)(unsigned short)float_to_sdf(newF);
-      lo = (lo & 0xff000000u) | ((unsigned)newW << 16) | sdf;
-      changed = true;
-    } else if (oldW >= newW) {
+    const float newF = fminf(1.0f, eta_mu);
+    const int newW = new_weight(p, dm);
+    if (oldW >= newW) {
       const int remW = oldW - newW;
       if (remW == 0) {
         lo = (lo & 0xff000000u) | 0x7fffu;
@@ -310,7 +289,7 @@ __device__ __forceinline__ bool update_voxel(unsigned &lo, unsigned &hi, const V
   }
   if ((eta > p.mu) || (fabsf(eta_mu) > 0.25f)) return changed;
   {  // computeUpdatedVoxelColorInfo
-    if (!SAME_CAM) {
+    {
       const Vec4 pcr = mul(p.M_rgb, pm);
       u = p.fx_r * pcr.x / pcr.z + p.cx_r;
       w = p.fy_r * pcr.y / pcr.z + p.cy_r;
@@ -323,36 +302,22 @@ __device__ __forceinline__ bool update_voxel(unsigned &lo, unsigned &hi, const V
     const float oldW = (float)wc;
     unsigned nc[3];
     unsigned new_wc;
-    if (!DEINT) {
-      float newW = oldW + 1.0f;
-      const float inv_new = inv_tab[wc + 1];
+    if (wc < 1) return changed;
+    const float remW = oldW - 1.0f;
+    if (remW == 0.0f) {
+      nc[0] = nc[1] = nc[2] = 0;
+      new_wc = 0;
+    } else {
+      const float inv_rem = inv_tab[wc - 1];
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         const float oldC = div_exact((float)oc[k], 255.0f, p.inv_255);
         const float c = div_exact(m[k], 255.0f, p.inv_255);
-        const float v = div_exact(oldC * oldW + c * 1.0f, newW, inv_new);
+        float v = div_exact(oldC * oldW - c * 1.0f, remW, inv_rem);
+        v = fmaxf(0.0f, fminf(1.0f, v));
         nc[k] = (unsigned)(unsigned char)(v * 255.0f);
       }
-      newW = fminf(newW, (float)p.max_w);
-      new_wc = (unsigned)(unsigned char)newW;
-    } else {
-      if (wc < 1) return changed;
-      const float remW = oldW - 1.0f;
-      if (remW == 0.0f) {
-        nc[0] = nc[1] = nc[2] = 0;
-        new_wc = 0;
-      } else {
-        const float inv_rem = inv_tab[wc - 1];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          const float oldC = div_exact((float)oc[k], 255.0f, p.inv_255);
-          const float c = div_exact(m[k], 255.0f, p.inv_255);
-          float v = div_exact(oldC * oldW - c * 1.0f, remW, inv_rem);
-          v = fmaxf(0.0f, fminf(1.0f, v));
-          nc[k] = (unsigned)(unsigned char)(v * 255.0f);
-        }
-        new_wc = (unsigned)(unsigned char)remW;
-      }
+      new_wc = (unsigned)(unsigned char)remW;
     }
     lo = (lo & 0x00ffffffu) | (nc[0] << 24);
     hi = (hi & 0xff000000u) | nc[1] | (nc[2] << 8) | (new_wc << 16);
@@ -425,7 +390,7 @@ __device__ __forceinline__ unsigned fuse_colour_word(unsigned pack, float u, flo
   return (lo >> 24) | ((hi & 0xffffffu) << 8);
 }
 
-// computeUpdatedVoxelColorInfo of the de-integration (update_voxel<true, true>'s colour part) on a queued colour word
+// computeUpdatedVoxelColorInfo of the de-integration (deintegrate_voxel_two_cam's colour part) on a queued colour word
 template <bool BUF>
 __device__ __forceinline__ unsigned defuse_colour_word(unsigned pack, float u, float w, const IntegrateParams &p,
                                                        const float *inv_tab) {
@@ -452,13 +417,14 @@ __device__ __forceinline__ unsigned defuse_colour_word(unsigned pack, float u, f
 constexpr int kColQueue = 256;  // one slot per voxel of a half block
 
 // ComputeUpdatedVoxelInfo<hasColor>::compute for the two voxels of one chunk: (vv.x, vv.y) at x, (vv.z, vv.w) at x + 1
-// QUEUE: the colour update is not done here; `cmask` (bit h: voxel h is inside the narrow band) and the projections come
-// back so that the caller can run the colour updates of a half block densely (see k_integrate)
-template <bool SAME_CAM, bool QUEUE = false>
+// SAME_CAM: the colour update is not done here; `cmask` (bit h: voxel h is inside the narrow band) and the projections come
+// back so that the caller can run the colour updates of a half block densely (see k_integrate).  With a colour camera of
+// its own the update runs here, voxel by voxel (fuse_colour<false>), and the three outputs are not written.
+// (From `eta` on these are pair_update<false, false>'s lines; the projection in front of them is pair_project's with early exits.)
+template <bool SAME_CAM>
 __device__ __forceinline__ bool fuse_pair(uint4 &vv, f2 pcx, f2 pcy, f2 pcz, const Vec4 &pm0, const Vec4 &pm1,
-                                          const IntegrateParams &p, const float *inv_tab, unsigned *cmask = nullptr,
-                                          f2 *u_out = nullptr, f2 *w_out = nullptr) {
-  if constexpr (QUEUE) *cmask = 0;
+                                          const IntegrateParams &p, const float *inv_tab, unsigned *cmask, f2 *u_out, f2 *w_out) {
+  if constexpr (SAME_CAM) *cmask = 0;
   bool act0 = pcz.x >= kMinCamZ, act1 = pcz.y >= kMinCamZ;
   if (p.stop_max) {
     act0 = act0 && (int)((vv.x >> 16) & 0xffu) != p.max_w;
@@ -516,7 +482,7 @@ __device__ __forceinline__ bool fuse_pair(uint4 &vv, f2 pcx, f2 pcy, f2 pcz, con
   // colour: only inside the narrow band around the surface
   const bool col0 = act0 && !((eta.x > p.mu) || (fabsf(eta_mu.x) > 0.25f));
   const bool col1 = act1 && !((eta.y > p.mu) || (fabsf(eta_mu.y) > 0.25f));
-  if constexpr (QUEUE) {
+  if constexpr (SAME_CAM) {
     *cmask = (col0 ? 1u : 0u) | (col1 ? 2u : 0u);
     *u_out = u;
     *w_out = w;
@@ -555,7 +521,7 @@ __device__ __forceinline__ void pair_project(PairProj &q, f2 pcx, f2 pcy, f2 pcz
 }
 
 // The depth update of the two voxels (fuse_pair from `eta` on; PLAIN: newW = 1); `cmask` as fuse_pair<., QUEUE> returns
-// it.  DEINT: update_voxel<true, .>'s depth part on both voxels at once -- W' = W - w, F' = clamp((W F - w f) / W'),
+// it.  DEINT: deintegrate_voxel_two_cam's depth part on both voxels at once -- W' = W - w, F' = clamp((W F - w f) / W'),
 // W' = 0 -> the empty voxel, a voxel with W < w is left alone; the narrow-band colour test does not depend on that.
 template <bool DEINT, bool PLAIN>
 __device__ __forceinline__ bool pair_update(uint4 &vv, const PairProj &q, const IntegrateParams &p, const float *inv_tab,
@@ -685,11 +651,20 @@ __device__ __forceinline__ void push_visible_list_job(const IntegrateParams &p, 
   }
 }
 
+// STREAM: voxel chunks of a launch that is larger than the Infinity Cache (>= push_job_min = 65536 visible blocks = 256 MiB) are read and
+// written with the non-temporal policy (load_nt / store_nt, dslam_device.h): nothing of such a launch is still cached when
+// somebody comes back for it, and the S-stress launch is 8 % shorter (0.533 -> 0.576 of the peak, three alternations on one box;
+// nt loads alone 0.542, nt stores alone 0.533, write-through `sc1` stores 0.529).  Launches of a real sequence's size keep the
+// default policy -- the ray march that follows reads these lines: nt loads on the bench scene leave the launch at 21.0 us and
+// make the frame 148 us instead of 140.  The policy is part of the instruction, so the HOST chooses the instantiation, by the
+// visible count it last heard of (dslam_render_state::vis_hint: a page-locked word the allocation sweep writes; no wait).  A
+// flag tested inside ONE kernel was tried first: the plain kernel has no register for it (12 bytes of scratch per lane, the
+// bench launch +0.9 us), and the block loop written twice behind one test doubled the scalar spills.
 // FRONT: the first p.fe.wgs workgroups are the tiles of GetImage's front end (FrontEndJob), the block workgroups follow them
 template <bool DEINT, bool SAME_CAM, bool PLAIN = false, bool DIAG = false, bool STREAM = false, bool FRONT = false>
 __global__ __launch_bounds__(kWgWaves * 64, 8) void k_integrate(IntegrateParams p) {
-  constexpr bool stream = STREAM;   // (cache policy of the voxel chunks: vox_load2)
-  static_assert(!PLAIN || (!DEINT && SAME_CAM && DSLAM_PACKED && DSLAM_COLOUR_QUEUE), "PLAIN is the queued one-camera fusion");
+  constexpr bool stream = STREAM;   // (cache policy of the voxel chunks: load_nt / store_nt)
+  static_assert(!PLAIN || (!DEINT && SAME_CAM), "PLAIN is the queued one-camera fusion");
   static_assert(!DIAG || PLAIN, "the per-wave timeline exists for the plain fusion kernel");
   static_assert(!FRONT || (PLAIN && !DIAG && !STREAM), "the front end rides on the plain fusion launch");
   static_assert(kWgWaves * 64 == kSelThreads, "a block workgroup and a selection tile are the same shape");
@@ -702,8 +677,8 @@ __global__ __launch_bounds__(kWgWaves * 64, 8) void k_integrate(IntegrateParams 
   [[maybe_unused]] bool diag_first = true;  // a wave records its first block
   if constexpr (DIAG) { diag_entry = wall_clock64(); diag_cyc = clock64(); }
 #define DSLAM_STAMP(k) do { if constexpr (DIAG) { if (lane == 0 && diag_first) p.dbg_waves[(size_t)wave * 16 + (k)] = wall_clock64(); } } while (0)
-  // the one-camera fusion variant runs its colour updates densely from a per-wave LDS queue (fuse_colour_word)
-  constexpr bool kQueueColour = SAME_CAM && DSLAM_PACKED && DSLAM_COLOUR_QUEUE;
+  // the one-camera variants run their colour updates densely from a per-wave LDS queue (fuse_colour_word, defuse_colour_word)
+  constexpr bool kQueueColour = SAME_CAM;
   // the split update (pair_project / pair_update): plain fusion, and the one-camera de-integration (41.6 -> 34.2 us per
   // launch against the voxel-by-voxel form it replaces; the general fusion variant has no registers for it)
   constexpr bool kPairPath = PLAIN || (DEINT && kQueueColour);
@@ -886,20 +861,16 @@ __global__ __launch_bounds__(kWgWaves * 64, 8) void k_integrate(IntegrateParams 
         const float fz = (float)(gz + j * 2 + vz0) * p.voxel_size;
         const float az0 = p.M_d.m[8] * fz, az1 = p.M_d.m[9] * fz, az2 = p.M_d.m[10] * fz;
         bool ch = false;
-        if constexpr (!DEINT && DSLAM_PACKED) {
+        if constexpr (!DEINT) {
           // both voxels of the chunk at once (packed FP32): pc = ((pxy + az) + m12..14), as in the scalar form
           const f2 a0 = {az0, az0}, a1 = {az1, az1}, a2 = {az2, az2};
           const f2 t0 = {p.M_d.m[12], p.M_d.m[12]}, t1 = {p.M_d.m[13], p.M_d.m[13]}, t2 = {p.M_d.m[14], p.M_d.m[14]};
           const f2 px = {pxy[0][0], pxy[1][0]}, py = {pxy[0][1], pxy[1][1]}, pz = {pxy[0][2], pxy[1][2]};
           const Vec4 pm0 = {fxv[0], fy, fz, 1.0f}, pm1 = {fxv[1], fy, fz, 1.0f};
-          if constexpr (kQueueColour) {
-            unsigned cm;
-            f2 uo, wo;
-            ch = fuse_pair<SAME_CAM, true>(v[jj], (px + a0) + t0, (py + a1) + t1, (pz + a2) + t2, pm0, pm1, p, inv_tab, &cm, &uo, &wo);
-            queue_colour(jj, cm, uo, wo);
-          } else {
-            ch = fuse_pair<SAME_CAM>(v[jj], (px + a0) + t0, (py + a1) + t1, (pz + a2) + t2, pm0, pm1, p, inv_tab);
-          }
+          unsigned cm;
+          f2 uo, wo;
+          ch = fuse_pair<SAME_CAM>(v[jj], (px + a0) + t0, (py + a1) + t1, (pz + a2) + t2, pm0, pm1, p, inv_tab, &cm, &uo, &wo);
+          if constexpr (kQueueColour) queue_colour(jj, cm, uo, wo);
         } else {
 #pragma unroll
           for (int h = 0; h < 2; h++) {
@@ -911,7 +882,8 @@ __global__ __launch_bounds__(kWgWaves * 64, 8) void k_integrate(IntegrateParams 
             pc.z = (pxy[h][2] + az2) + p.M_d.m[14];
             pc.w = 1.0f;
             pm.x = fxv[h]; pm.y = fy; pm.z = fz; pm.w = 1.0f;
-            ch |= update_voxel<DEINT, SAME_CAM>(lo, hi, pc, pm, p, inv_tab);
+            static_assert(DEINT && !SAME_CAM, "the voxel-by-voxel form is the two-camera de-integration");
+            ch |= deintegrate_voxel_two_cam(lo, hi, pc, pm, p, inv_tab);
           }
         }
         chs[jj] = ch;
@@ -968,11 +940,26 @@ __global__ __launch_bounds__(kWgWaves * 64, 8) void k_integrate(IntegrateParams 
 #undef DSLAM_STAMP
 }
 
+// what the scene and the engine decide, the same for the per-frame launches and the re-integration batch (ring push off)
+static void fill_scene_params(IntegrateParams &ip, const dslam_engine *e, const dslam_scene *s) {
+  ip.hash = s->hash;
+  ip.voxels16 = reinterpret_cast<uint4 *>(s->voxels);
+  ip.voxel_size = s->p.voxel_size; ip.mu = s->p.mu; ip.max_w = s->p.max_w;
+  ip.inv_32767 = 1.0f / 32767.0f; ip.inv_255 = 1.0f / 255.0f;
+  ip.stop_max = s->p.stop_integrating_at_max_w;
+  ip.depth_weighting = e->wp.depth_weighting; ip.max_new_w = e->wp.max_new_w; ip.max_distance = e->wp.max_distance;
+  ip.shard = s->shard; ip.num_shards = s->num_shards; ip.chunk_blocks = s->chunk_blocks;
+  ip.shard_first = s->shard_first; ip.shard_count = s->shard_count;
+  ip.dirty = s->dirty_tracking ? s->dirty : nullptr;
+  ip.masks = s->masks; ip.last_seen = s->last_seen; ip.push_words = 0; ip.push_ring = 0; ip.push_bit = 0; ip.push_frame = 0;
+  ip.push_job_min = e->push_job_min;
+}
+
 static void fill_params(IntegrateParams &ip, dslam_engine *e, dslam_scene *s, const dslam_view *v, const int *visible_ids,
                         const RenderCounters *counters, const float *M_d, const float *intr_d, const float *M_rgb,
                         const float *intr_rgb) {
-  ip.visible_ids = visible_ids; ip.rc = counters; ip.hash = s->hash;
-  ip.voxels16 = reinterpret_cast<uint4 *>(s->voxels);
+  fill_scene_params(ip, e, s);
+  ip.visible_ids = visible_ids; ip.rc = counters;
   ip.depth = v->depth; ip.rgba = v->rgba_src;
   ip.Wd = v->w_d; ip.Hd = v->h_d; ip.Wr = v->w_rgb; ip.Hr = v->h_rgb;
   memcpy(ip.M_d.m, M_d, 64);
@@ -980,15 +967,8 @@ static void fill_params(IntegrateParams &ip, dslam_engine *e, dslam_scene *s, co
   const float *kr = intr_rgb ? intr_rgb : intr_d;
   ip.fx_d = intr_d[0]; ip.fy_d = intr_d[1]; ip.cx_d = intr_d[2]; ip.cy_d = intr_d[3];
   ip.fx_r = kr[0]; ip.fy_r = kr[1]; ip.cx_r = kr[2]; ip.cy_r = kr[3];
-  ip.voxel_size = s->p.voxel_size; ip.mu = s->p.mu; ip.max_w = s->p.max_w;
-  ip.inv_32767 = 1.0f / 32767.0f; ip.inv_255 = 1.0f / 255.0f;
   ip.same_cam = (memcmp(ip.M_d.m, ip.M_rgb.m, 64) == 0 && kr[0] == intr_d[0] && kr[1] == intr_d[1] && kr[2] == intr_d[2] &&
                  kr[3] == intr_d[3] && v->w_rgb == v->w_d && v->h_rgb == v->h_d) ? 1 : 0;
-  ip.stop_max = s->p.stop_integrating_at_max_w;
-  ip.depth_weighting = e->wp.depth_weighting; ip.max_new_w = e->wp.max_new_w; ip.max_distance = e->wp.max_distance;
-  ip.shard = s->shard; ip.num_shards = s->num_shards; ip.chunk_blocks = s->chunk_blocks;
-  ip.shard_first = s->shard_first; ip.shard_count = s->shard_count;
-  ip.dirty = s->dirty_tracking ? s->dirty : nullptr;
   ip.expect_pos = nullptr;
   ip.spec_ids = 0;
   ip.fe.wgs = 0;
@@ -996,11 +976,11 @@ static void fill_params(IntegrateParams &ip, dslam_engine *e, dslam_scene *s, co
 
 // the fusion runs the plain kernel (k_integrate<..., PLAIN>): none of the optional features is in use
 static bool plain_fusion(const IntegrateParams &ip) {
-  return DSLAM_PACKED && DSLAM_COLOUR_QUEUE && ip.same_cam && !ip.expect_pos && ip.num_shards <= 1 && ip.shard_count < 0 &&
+  return ip.same_cam && !ip.expect_pos && ip.num_shards <= 1 && ip.shard_count < 0 &&
          !ip.dirty && !ip.stop_max && !ip.depth_weighting;
 }
 
-// stream: the launch is expected to be larger than the Infinity Cache (vox_load2)
+// stream: the launch is expected to be larger than the Infinity Cache (k_integrate's STREAM: load_nt / store_nt)
 static int launch_integrate_params(dslam_engine *e, IntegrateParams &ip, bool deintegrate, bool stream) {
   ip.timer_slot = nullptr;
   ip.dbg_waves = nullptr;
@@ -1025,14 +1005,12 @@ static int launch_integrate_params(dslam_engine *e, IntegrateParams &ip, bool de
     else hipExtLaunchKernelGGL((k_integrate<true, false>), grid, block, 0, e->stream, ev0, ev1, 0, ip);
   } else {
     const bool plain = plain_fusion(ip);
-    if constexpr (DSLAM_PACKED && DSLAM_COLOUR_QUEUE) {   // (the builds without the plain kernel never fill ip.fe)
-      if (ip.fe.wgs > 0) {   // (launch_integrate chose this: plain, not streaming)
-        e->front_launches++;
-        const dim3 grid_front(ip.fe.wgs + kIntegrateGrid + kPushWgs);
-        hipExtLaunchKernelGGL((k_integrate<false, true, true, false, false, true>), grid_front, block, 0, e->stream, ev0, ev1, 0, ip);
-        DSLAM_HIP(hipGetLastError());
-        return DSLAM_OK;
-      }
+    if (ip.fe.wgs > 0) {   // (launch_integrate chose this: plain, not streaming)
+      e->front_launches++;
+      const dim3 grid_front(ip.fe.wgs + kIntegrateGrid + kPushWgs);
+      hipExtLaunchKernelGGL((k_integrate<false, true, true, false, false, true>), grid_front, block, 0, e->stream, ev0, ev1, 0, ip);
+      DSLAM_HIP(hipGetLastError());
+      return DSLAM_OK;
     }
     // diagnostics: the per-wave timeline of one launch, well into the run (DSLAM_DBG_INTEGRATE=<file>)
     static const char *dbg_file = getenv("DSLAM_DBG_INTEGRATE");
@@ -1042,7 +1020,7 @@ static int launch_integrate_params(dslam_engine *e, IntegrateParams &ip, bool de
       DeviceBuffer<unsigned long long> trace_dev;
       DSLAM_TRY(trace_dev.alloc_zeroed(kTraceBytes / sizeof(unsigned long long), e->stream));
       ip.dbg_waves = trace_dev;
-      hipExtLaunchKernelGGL((k_integrate<false, true, DSLAM_PACKED && DSLAM_COLOUR_QUEUE, DSLAM_PACKED && DSLAM_COLOUR_QUEUE>), grid_plain, block, 0, e->stream, ev0, ev1, 0, ip);
+      hipExtLaunchKernelGGL((k_integrate<false, true, true, true>), grid_plain, block, 0, e->stream, ev0, ev1, 0, ip);
       DSLAM_HIP(hipGetLastError());
       DSLAM_HIP(hipStreamSynchronize(e->stream));
       std::vector<unsigned long long> h(kTraceBytes / sizeof(unsigned long long));
@@ -1051,8 +1029,8 @@ static int launch_integrate_params(dslam_engine *e, IntegrateParams &ip, bool de
       return DSLAM_OK;
     }
     if (plain && stream) e->stream_launches++;
-    if (plain && stream) hipExtLaunchKernelGGL((k_integrate<false, true, DSLAM_PACKED && DSLAM_COLOUR_QUEUE, false, true>), grid_plain, block, 0, e->stream, ev0, ev1, 0, ip);
-    else if (plain) hipExtLaunchKernelGGL((k_integrate<false, true, DSLAM_PACKED && DSLAM_COLOUR_QUEUE>), grid_plain, block, 0, e->stream, ev0, ev1, 0, ip);
+    if (plain && stream) hipExtLaunchKernelGGL((k_integrate<false, true, true, false, true>), grid_plain, block, 0, e->stream, ev0, ev1, 0, ip);
+    else if (plain) hipExtLaunchKernelGGL((k_integrate<false, true, true>), grid_plain, block, 0, e->stream, ev0, ev1, 0, ip);
     else if (ip.same_cam) hipExtLaunchKernelGGL((k_integrate<false, true>), grid, block, 0, e->stream, ev0, ev1, 0, ip);
     else hipExtLaunchKernelGGL((k_integrate<false, false>), grid, block, 0, e->stream, ev0, ev1, 0, ip);
   }
@@ -1067,8 +1045,6 @@ int launch_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, const
   if (rc) return rc;
   IntegrateParams ip;
   fill_params(ip, e, s, v, r->visible_ids, r->counters, M_d, intr_d, M_rgb, intr_rgb);
-  ip.masks = s->masks; ip.last_seen = s->last_seen; ip.push_words = 0; ip.push_ring = 0; ip.push_bit = 0; ip.push_frame = 0;
-  ip.push_job_min = e->push_job_min;
   ip.spec_ids = r->n_local >= kIntegrateGrid * kWgWaves ? 1 : 0;  // (a visible list has room for every voxel-block slot)
   if (push_ring >= 0) {
     if ((rc = prepare_push_visible_list(e, s, push_ring, &ip.push_bit, &ip.push_frame))) return rc;
@@ -1106,8 +1082,6 @@ int launch_integrate_list(dslam_engine *e, dslam_scene *s, const dslam_view *v, 
   IntegrateParams ip;
   fill_params(ip, e, s, v, ids, static_cast<const RenderCounters *>(count_header), M_d, intr_d, M_rgb, intr_rgb);
   ip.expect_pos = expect_pos;
-  ip.masks = s->masks; ip.last_seen = s->last_seen; ip.push_words = 0; ip.push_ring = 0; ip.push_bit = 0; ip.push_frame = 0;
-  ip.push_job_min = e->push_job_min;
   return launch_integrate_params(e, ip, deintegrate, false);
 }
 
@@ -1126,15 +1100,7 @@ int launch_integrate_list(dslam_engine *e, dslam_scene *s, const dslam_view *v, 
 //                  bit 2k + 1: the re-fusion of keyframe k lists it
 //   ops[2k], ops[2k + 1]   pose and images of the two operations
 // Blocks differ in how many operations they take: they are ordered longest first and dealt round-robin over the waves.
-struct BatchOp {
-  Mat4 M;                // world -> camera of this operation (old pose: de-integration, new pose: re-fusion)
-  const float *depth;    // the keyframe's depth image in metres: written by the allocation pass of its re-fusion (k_mark derives
-                         // it from the int16 image exactly as UpdateView does) into the batch's scratch, one image per keyframe
-  const uchar4 *rgba;
-  int push_bit, push_frame;  // re-fusions: the ring bit and frame stamp ProcessFrame(isDefusion) queues the block with
-  int pad[2];
-};
-
+// (BatchOp: dslam_internal.h -- the host builds the table)
 struct BatchParams {
   IntegrateParams ip;    // what does not change over the batch (intrinsics, mu, sizes, weights, shard, rings ...)
   const BatchOp *ops;
@@ -1315,17 +1281,9 @@ __device__ __forceinline__ void batch_op(uint4 (&v)[kHalves][2], bool (&chs)[kHa
   }
 }
 
-// (-DDSLAM_BATCH_WAVES / -DDSLAM_BATCH_MIN_WAVES / -DDSLAM_BATCH_UNSHARDED_HALVES: occupancy experiments of round 4)
-#ifndef DSLAM_BATCH_WAVES
-#define DSLAM_BATCH_WAVES 8
-#endif
-#ifndef DSLAM_BATCH_MIN_WAVES
-#define DSLAM_BATCH_MIN_WAVES 1
-#endif
-#ifndef DSLAM_BATCH_UNSHARDED_HALVES
-#define DSLAM_BATCH_UNSHARDED_HALVES 2
-#endif
-constexpr int kBatchWgWaves = DSLAM_BATCH_WAVES;
+constexpr int kBatchWgWaves = 8;          // waves per workgroup ("More waves do not help the block launch either")
+constexpr int kBatchMinWaves = 1;         // minimum waves per SIMD asked of the compiler: none (the same measurement)
+constexpr int kBatchUnshardedHalves = 2;  // unit of an unsharded launch: a whole block (1.19 against 1.25 ms)
 // 4096 waves = what is resident at once (4 per SIMD at this register count).  Units are dealt round-robin over the list
 // ordered longest first -- NOT fetched from a device counter: ~77 k fetches from one address serialise at ~12 ns each,
 // which was 0.9 ms of a 1.2 ms launch and the whole launch of a rank that owns an eighth of the blocks.
@@ -1336,7 +1294,7 @@ constexpr int kBatchGrid = 512;
 // then ends with the longest chain of operations on one unit, and a half block's is half as long (rank 0 of 8: 0.46
 // against 0.52 ms in round 3).
 template <bool UNIT_W, int kHalves>
-__global__ __launch_bounds__(kBatchWgWaves * 64, DSLAM_BATCH_MIN_WAVES) void k_reintegrate_blocks(BatchParams bp) {
+__global__ __launch_bounds__(kBatchWgWaves * 64, kBatchMinWaves) void k_reintegrate_blocks(BatchParams bp) {
   __shared__ float inv_tab[kInvTab];
   __shared__ BatchColQueue<kHalves> col_q[kBatchWgWaves];
   __shared__ BatchOp s_ops[64];   // the batch's operations: read per operation from LDS, not with a ~1 us scalar load each
@@ -1347,6 +1305,7 @@ __global__ __launch_bounds__(kBatchWgWaves * 64, DSLAM_BATCH_MIN_WAVES) void k_r
     s_cum[8] = run;
   }
   for (int i = threadIdx.x; i < kInvTab; i += kBatchWgWaves * 64) inv_tab[i] = recip_table_entry(i);
+  static_assert(sizeof(BatchOp) % 4 == 0, "the table goes to LDS word by word");
   for (int i = threadIdx.x; i < bp.n_ops * (int)(sizeof(BatchOp) / 4); i += kBatchWgWaves * 64)
     reinterpret_cast<unsigned *>(s_ops)[i] = reinterpret_cast<const unsigned *>(bp.ops)[i];
   __syncthreads();
@@ -1433,11 +1392,7 @@ __global__ __launch_bounds__(kBatchWgWaves * 64, DSLAM_BATCH_MIN_WAVES) void k_r
 // operation's list: the keyframe's stored fusion-time list (de-integration; entries that no longer hold that block, or
 // whose block the batch itself allocated at or after re-fusion k, are skipped -- what dslam_deprocess_frame_stored would
 // have found at that point of the sequence) or the list the re-fusion's allocation pass left (kept in the batch's scratch).
-struct BatchListRef {
-  const RenderCounters *count;   // header of the list (no_visible = its length)
-  const int *ids;
-  const short4 *pos;             // stored lists: the block each entry held at fusion time; null: a fresh list
-};
+// (the lists: BatchListRef, dslam_internal.h)
 __global__ __launch_bounds__(256) void k_batch_mark(const BatchListRef *__restrict__ lists, const HashEntry *__restrict__ hash,
                                                     const int *__restrict__ born, unsigned char *marks, int *slot_entry) {
   const int op = blockIdx.y, k = op >> 1;
@@ -1526,10 +1481,10 @@ __global__ __launch_bounds__(256) void k_batch_assemble(uint4 *marks16, int n_sl
     if (cls[it] >= 0) cls_list[(size_t)cls[it] * n_slots + s_base[cls[it]] + pos[it]] = ((blockIdx.x * kAsmIter + it) * 256 + threadIdx.x) >> 2;
 }
 
-int launch_batch_ops(dslam_engine *e, const void *lists_dev, int n_ops, const dslam_scene *s, const int *born, unsigned char *marks,
+int launch_batch_ops(dslam_engine *e, const BatchListRef *lists_dev, int n_ops, const dslam_scene *s, const int *born, unsigned char *marks,
                      unsigned long long *opmask, int *slot_entry, int *cls_list, int *cls_count) {
   const int L = s->p.num_local_blocks;
-  hipLaunchKernelGGL(k_batch_mark, dim3(32, n_ops), dim3(256), 0, e->stream, reinterpret_cast<const BatchListRef *>(lists_dev), s->hash,
+  hipLaunchKernelGGL(k_batch_mark, dim3(32, n_ops), dim3(256), 0, e->stream, lists_dev, s->hash,
                      born, marks, slot_entry);
   hipLaunchKernelGGL(k_batch_assemble, dim3((L * 4 + 256 * kAsmIter - 1) / (256 * kAsmIter)), dim3(256), 0, e->stream, reinterpret_cast<uint4 *>(marks), L, opmask,
                      cls_list, cls_count);
@@ -1538,40 +1493,30 @@ int launch_batch_ops(dslam_engine *e, const void *lists_dev, int n_ops, const ds
 }
 
 int launch_reintegrate_blocks(dslam_engine *e, dslam_scene *s, int w_d, int h_d, int w_rgb, int h_rgb, const float *intr,
-                              const void *ops_dev, const unsigned long long *opmask, const int *slot_entry,
+                              const BatchOp *ops_dev, const unsigned long long *opmask, const int *slot_entry,
                               const int *cls_list, const int *cls_count, int push_ring, int n_ops) {
   BatchParams bp;
   IntegrateParams &ip = bp.ip;
-  memset(&ip, 0, sizeof(ip));
-  ip.hash = s->hash;
-  ip.voxels16 = reinterpret_cast<uint4 *>(s->voxels);
+  memset(&ip, 0, sizeof(ip));   // (no list, no images, no matrices: the operations bring their own)
+  fill_scene_params(ip, e, s);
   ip.Wd = w_d; ip.Hd = h_d; ip.Wr = w_rgb; ip.Hr = h_rgb;
   ip.fx_d = intr[0]; ip.fy_d = intr[1]; ip.cx_d = intr[2]; ip.cy_d = intr[3];
   ip.fx_r = intr[0]; ip.fy_r = intr[1]; ip.cx_r = intr[2]; ip.cy_r = intr[3];
-  ip.voxel_size = s->p.voxel_size; ip.mu = s->p.mu; ip.max_w = s->p.max_w;
-  ip.inv_32767 = 1.0f / 32767.0f; ip.inv_255 = 1.0f / 255.0f;
   ip.same_cam = 1;
-  ip.stop_max = 0;
-  ip.depth_weighting = e->wp.depth_weighting; ip.max_new_w = e->wp.max_new_w; ip.max_distance = e->wp.max_distance;
-  ip.shard = s->shard; ip.num_shards = s->num_shards; ip.chunk_blocks = s->chunk_blocks;
-  ip.shard_first = s->shard_first; ip.shard_count = s->shard_count;
-  ip.dirty = s->dirty_tracking ? s->dirty : nullptr;
-  ip.masks = s->masks; ip.last_seen = s->last_seen;
-  ip.push_words = push_ring >= 0 ? s->history_words : 0;
-  ip.push_ring = push_ring >= 0 ? push_ring : 0;
-  bp.ops = reinterpret_cast<const BatchOp *>(ops_dev);
+  ip.stop_max = 0;   // (dslam_reintegrate_batch refuses scenes with stopIntegratingAtMaxW)
+  if (push_ring >= 0) { ip.push_words = s->history_words; ip.push_ring = push_ring; }
+  bp.ops = ops_dev;
   bp.opmask = opmask; bp.slot_entry = slot_entry; bp.cls_list = cls_list; bp.cls_count = cls_count; bp.n_local = s->p.num_local_blocks;
   bp.n_ops = n_ops;
   const bool sharded = ip.num_shards > 1 || ip.shard_count >= 0;
-  static const int grid_wgs = getenv("DSLAM_BATCH_GRID") ? atoi(getenv("DSLAM_BATCH_GRID")) : kBatchGrid;   // (experiments: occupancy of the block launch)
-  bp.grid_waves = grid_wgs * kBatchWgWaves;
-  const dim3 grid(grid_wgs), block(kBatchWgWaves * 64);
+  bp.grid_waves = kBatchGrid * kBatchWgWaves;
+  const dim3 grid(kBatchGrid), block(kBatchWgWaves * 64);
   if (ip.depth_weighting) {
     if (sharded) hipLaunchKernelGGL((k_reintegrate_blocks<false, 1>), grid, block, 0, e->stream, bp);
-    else hipLaunchKernelGGL((k_reintegrate_blocks<false, DSLAM_BATCH_UNSHARDED_HALVES>), grid, block, 0, e->stream, bp);
+    else hipLaunchKernelGGL((k_reintegrate_blocks<false, kBatchUnshardedHalves>), grid, block, 0, e->stream, bp);
   } else {
     if (sharded) hipLaunchKernelGGL((k_reintegrate_blocks<true, 1>), grid, block, 0, e->stream, bp);
-    else hipLaunchKernelGGL((k_reintegrate_blocks<true, DSLAM_BATCH_UNSHARDED_HALVES>), grid, block, 0, e->stream, bp);
+    else hipLaunchKernelGGL((k_reintegrate_blocks<true, kBatchUnshardedHalves>), grid, block, 0, e->stream, bp);
   }
   DSLAM_HIP(hipGetLastError());
   return DSLAM_OK;
@@ -1603,9 +1548,9 @@ __global__ __launch_bounds__(256) void k_store_list_positions(const BatchListRef
     out[i] = make_short4(e.pos[0], e.pos[1], e.pos[2], 0);
   }
 }
-int launch_store_list_positions(dslam_engine *e, const dslam_scene *s, const void *jobs_dev, int n_jobs) {
+int launch_store_list_positions(dslam_engine *e, const dslam_scene *s, const BatchListRef *jobs_dev, int n_jobs) {
   if (n_jobs <= 0) return DSLAM_OK;
-  hipLaunchKernelGGL(k_store_list_positions, dim3(32, n_jobs), dim3(256), 0, e->stream, reinterpret_cast<const BatchListRef *>(jobs_dev), s->hash);
+  hipLaunchKernelGGL(k_store_list_positions, dim3(32, n_jobs), dim3(256), 0, e->stream, jobs_dev, s->hash);
   DSLAM_HIP(hipGetLastError());
   return DSLAM_OK;
 }

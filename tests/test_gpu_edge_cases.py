@@ -33,6 +33,32 @@ def test_separate_rgb_camera_variant(pkg, synth, gpu, oracle):
     assert (snaps["gpu"]["voxels"]["w_color"] > 0).sum() > 1000
 
 
+def test_separate_rgb_camera_deintegration(pkg, synth, gpu, oracle):
+    """The two-camera de-integration (k_integrate<true, false>, the one voxel-by-voxel path): four frames fused with a
+    colour camera of its own, two of them taken out again with the same M_rgb / intr_rgb.  Some colour weights go down and
+    some stay above 0, so neither the early return (w_color < 1) nor the remW == 0 branch is the only one taken."""
+    wl = synth.s_tiny()
+    p = util.small_params(pkg, wl)
+    T = synth.pose_matrix(synth.look_rotation(0.01, 0.005), [0.02, -0.01, 0.0]).astype(np.float32)
+    M_rgb_of = lambda M: (T @ M).astype(np.float32)
+    intr_rgb = np.asarray(wl.intr, np.float32) * np.float32(1.02)
+    snaps, fused = {}, {}
+    for name, api in (("gpu", gpu), ("oracle", oracle)):
+        s, rs, v = _fuse(api, pkg, wl, p, 4, M_rgb_of=M_rgb_of, intr_rgb=intr_rgb)
+        fused[name] = util.snapshot(api, s, rs)
+        for i in (1, 2):
+            rgba, mm, M = wl.frame(i)
+            api.view_update(v, rgba, mm, timestamp=float(i))
+            api.deprocess_frame(s, v, rs, M, wl.intr, M_rgb=M_rgb_of(M), intr_rgb=intr_rgb)
+        snaps[name] = util.snapshot(api, s, rs)
+    util.assert_same_state(fused["gpu"], fused["oracle"], "separate RGB camera, fused")
+    util.assert_same_state(snaps["gpu"], snaps["oracle"], "separate RGB camera, two frames de-integrated")
+    before, after = fused["gpu"]["voxels"]["w_color"], snaps["gpu"]["voxels"]["w_color"]
+    assert (after < before).sum() > 1000, "no colour weight went down"
+    assert (after > 0).sum() > 1000, "no colour weight stayed above 0"
+    assert ((after == 0) & (before > 0)).sum() > 0, "no colour was taken out completely"
+
+
 def test_stop_integrating_at_max_w(pkg, synth, gpu, oracle):
     wl = synth.s_tiny()
     p = util.small_params(pkg, wl, max_w=2, stop_integrating_at_max_w=1)

@@ -95,7 +95,7 @@ def test_ring_push_by_trailing_workgroups(pkg, synth, gpu, oracle):
 def test_streaming_instantiations_of_fusion_and_deintegration(pkg, synth, gpu, oracle):
     """Launches over at least push_job_min visible blocks run the STREAM instantiations of k_integrate (non-temporal loads and
     stores of the voxel blocks, chosen by the host from the visible count the allocation sweep reported;
-    integrate.hip vox_load2).  With the threshold at 0 every fusion AND de-integration of an online-correction sequence takes
+    integrate.hip STREAM: load_nt / store_nt).  With the threshold at 0 every fusion AND de-integration of an online-correction sequence takes
     them: same map as the oracle after every frame."""
     wl = synth.s_tiny()
     p = util.small_params(pkg, wl)

@@ -27,6 +27,40 @@ def test_batch_equals_loop_and_oracle(pkg, synth, gpu, oracle, maintenance):
     assert not np.array_equal(g_batch["first"]["voxels"].view(np.uint64), g_batch["second"]["voxels"].view(np.uint64))
 
 
+@pytest.mark.parametrize("sharded", [False, True])
+def test_batch_with_depth_weighting_equals_loop_and_oracle(pkg, synth, gpu, oracle, sharded):
+    """The depth-weighted forms of the block kernel: k_reintegrate_blocks<false, 2>, and <false, 1> under set_shard (rank 0
+    of 2 on both engines, for the fusions that build the map too: half-block units, the other rank's blocks left alone)."""
+    wl = synth.s_tiny()
+    p = util.small_params(pkg, wl, history_words=1)
+
+    class Sharded:   # the engine with every new scene put under set_shard(0, 2)
+        def __init__(self, api):
+            self._api = api
+
+        def __getattr__(self, name):
+            return getattr(self._api, name)
+
+        def create_scene(self, params):
+            scene = self._api.create_scene(params)
+            self._api.set_shard(scene, 0, 2, 8)
+            return scene
+
+    out = {}
+    try:
+        for name, api, call in (("g_batch", gpu, "batch"), ("g_loop", gpu, "loop"), ("o_batch", oracle, "batch")):
+            api.set_fusion_weight_params(True, 5, 2.5)
+            out[name] = scenarios.batch_scenario(Sharded(api) if sharded else api, pkg, synth, wl, p, False, call)
+    finally:
+        for api in (gpu, oracle):
+            api.set_fusion_weight_params(False, 1, 1.0)
+    for key in ("first", "second"):
+        scenarios.assert_same_full_state(out["g_batch"][key], out["g_loop"][key], f"{key}: HIP batch vs HIP per-keyframe loop")
+        scenarios.assert_same_full_state(out["g_batch"][key], out["o_batch"][key], f"{key}: HIP batch vs oracle")
+    assert out["g_batch"]["second"]["voxels"]["w_depth"].max() > 3, "the depth weights were not in use"
+    assert not np.array_equal(out["g_batch"]["first"]["voxels"].view(np.uint64), out["g_batch"]["second"]["voxels"].view(np.uint64))
+
+
 def test_batch_longer_than_one_mask(pkg, synth, gpu, oracle):
     """More keyframes than one 64-bit operation mask holds (32): the batch is cut, the result is not."""
     wl = synth.s_tiny()
