@@ -960,21 +960,11 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   mp.fx = intr[0]; mp.fy = intr[1]; mp.voxel_size = s->p.voxel_size;
   mp.swapping = s->p.use_swapping ? 1 : 0;
   const int pix_blocks = (W * H + 255) / 256;
-  mp.dbg = nullptr;
-  static const char *dbg_mark_file = getenv("DSLAM_DBG_MARK");
-  static int dbg_mark_calls = 0;
-  PinnedBuffer<unsigned long long> dbg_mark_host;
-  if (dbg_mark_file && ++dbg_mark_calls == 60) {
-    DSLAM_TRY(dbg_mark_host.alloc((size_t)(mp.retest_wgs + pix_blocks) * 4));
-    memset(dbg_mark_host, 0, (size_t)(mp.retest_wgs + pix_blocks) * 32);
-    mp.dbg = dbg_mark_host;
-  }
+  static DiagDump mark_dump("DSLAM_DBG_MARK", 60);
+  mp.dbg = mark_dump.arm(mp.retest_wgs + pix_blocks, 32);
   hipLaunchKernelGGL(k_mark, dim3(mp.retest_wgs + pix_blocks), dim3(256), 0, e->stream, mp);
   dbg_sync(e, "k_mark");
-  if (dbg_mark_host) {
-    DSLAM_HIP(hipStreamSynchronize(e->stream));
-    if (FILE *f = fopen(dbg_mark_file, "wb")) { fwrite(dbg_mark_host, 32, mp.retest_wgs + pix_blocks, f); fclose(f); }
-  }
+  DSLAM_TRY(mark_dump.write(e));
   v->depth_dirty = false;
 
   SweepParams sp;
@@ -1004,22 +994,12 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   sp.depth = v->depth; sp.W = W; sp.H = H;
   sp.invM = mp.invM; sp.inv_fx = mp.inv_fx; sp.inv_fy = mp.inv_fy; sp.cx = mp.cx; sp.cy = mp.cy;
   sp.mu = mp.mu; sp.one_over_block = mp.one_over_block; sp.cap_shift = cap_shift;
-  sp.dbg = nullptr;
-  static const char *dbg_file = getenv("DSLAM_DBG_SWEEP");
-  static int dbg_calls = 0;
-  PinnedBuffer<unsigned long long> dbg_host;
-  if (dbg_file && ++dbg_calls == 60) {
-    DSLAM_TRY(dbg_host.alloc((size_t)n_tiles * 8));
-    memset(dbg_host, 0, (size_t)n_tiles * 64);
-    sp.dbg = dbg_host;
-  }
+  static DiagDump sweep_dump("DSLAM_DBG_SWEEP", 60);
+  sp.dbg = sweep_dump.arm(n_tiles, 64);
   if (s->p.use_swapping) hipLaunchKernelGGL((k_alloc_sweep<true, kSweepWpt>), dim3(grid), dim3(256), 0, e->stream, sp);
   else hipLaunchKernelGGL((k_alloc_sweep<false, kSweepWpt>), dim3(grid), dim3(256), 0, e->stream, sp);
   dbg_sync(e, "k_alloc_sweep");
-  if (dbg_host) {
-    DSLAM_HIP(hipStreamSynchronize(e->stream));
-    if (FILE *f = fopen(dbg_file, "wb")) { fwrite(dbg_host, 64, n_tiles, f); fclose(f); }
-  }
+  DSLAM_TRY(sweep_dump.write(e));
   if (s->p.use_swapping) {
     SelNeedsBlock sel{s->hash, s->alloc_list, s->alloc_bits, s->counters};
     launch_bits_select(e, r->vis_bits, N, sel, (int *)nullptr, N, (int *)nullptr, s->counters);

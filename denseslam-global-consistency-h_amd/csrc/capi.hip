@@ -1370,10 +1370,13 @@ int dslam_save_to_global_memory(dslam_engine *e, dslam_scene *s) {
 }
 
 // ---- visualisation -------------------------------------------------------------------------------------------
+// raycastResult / the lists behind it are about to be rewritten: the GetImage memo (dslam_render_state::memo_*) is stale
+static void drop_memo(dslam_render_state *r) { r->memo_valid = false; }
+
 int dslam_find_visible_blocks(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
                               const float intr[4]) {
   DSLAM_REQUIRE(e && s && r && M && intr, "null argument");
-  r->memo_valid = false;  // raycastResult / the lists behind it are about to be rewritten
+  drop_memo(r);
   r->types_follow_list = false;
   int rc = launch_find_visible(e, s, r, M, intr);
   if (rc) return rc;
@@ -1387,7 +1390,7 @@ int dslam_count_visible_blocks(dslam_engine *e, const dslam_scene *s, const dsla
 int dslam_create_expected_depths(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
                                  const float intr[4]) {
   DSLAM_REQUIRE(e && s && r && M && intr, "null argument");
-  r->memo_valid = false;  // raycastResult / the lists behind it are about to be rewritten
+  drop_memo(r);
   int rc = launch_expected_depths(e, s, r, M, intr);
   if (rc) return rc;
   return finish_call(e);
@@ -1412,7 +1415,7 @@ static int image_out(dslam_engine *e, dslam_render_state *r, int type, uint8_t *
 int dslam_render_image(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
                        const float intr[4], int type, uint8_t *out_rgba, float *out_float) {
   DSLAM_REQUIRE(e && s && r && M && intr, "null argument");
-  r->memo_valid = false;  // raycastResult / the lists behind it are about to be rewritten
+  drop_memo(r);
   DSLAM_REQUIRE(type >= 0 && type <= DSLAM_IMAGE_DEPTH, "unknown image type");
   int rc = launch_render(e, s, r, M, intr, type);
   if (rc) return rc;
@@ -1429,7 +1432,7 @@ static int get_image_on_device(dslam_engine *e, const dslam_scene *s, dslam_rend
                    memcmp(r->memo_intr, intr, sizeof(r->memo_intr)) == 0;
   int rc;
   if (hit) return launch_render(e, s, r, M, intr, type, true, direct_out);
-  r->memo_valid = false;
+  drop_memo(r);
   r->types_follow_list = false;  // FindVisibleBlocks replaces this render state's list
   if ((rc = launch_find_visible_and_depths(e, s, r, M, intr))) return rc;
   if ((rc = launch_render(e, s, r, M, intr, type, false, direct_out))) return rc;
@@ -1439,23 +1442,29 @@ static int get_image_on_device(dslam_engine *e, const dslam_scene *s, dslam_rend
   return DSLAM_OK;
 }
 
+// Where the kernels of a GetImage call store the image: a page-locked output image (dslam_host_alloc) is written by the
+// render kernel itself (no copy behind the kernel); null: into the render state's image
+static void *direct_image(const dslam_render_state *r, int type, uint8_t *out_rgba, float *out_float) {
+  void *out = type == DSLAM_IMAGE_DEPTH ? (void *)out_float : (void *)out_rgba;
+  const size_t bytes = (size_t)r->w * r->h * 4;
+  return out && !(out_rgba && out_float) && in_pinned_range(out, bytes) ? out : nullptr;
+}
+// ... and the rest of its way to the caller once they are enqueued
+static int deliver_image(dslam_engine *e, dslam_render_state *r, int type, uint8_t *out_rgba, float *out_float,
+                         const void *direct) {
+  // synchronous engine: the image is there on return (what the reference's callers assume); async engine: the
+  // caller pipelines and learns from a fence (dslam_fence_*) when the kernel has stored the last pixel
+  if (direct) return finish_call(e);
+  return image_out(e, r, type, out_rgba, out_float);
+}
+
 int dslam_get_image(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
                     const float intr[4], int type, uint8_t *out_rgba, float *out_float) {
   DSLAM_REQUIRE(e && s && r && M && intr, "null argument");
   DSLAM_REQUIRE(type >= 0 && type <= DSLAM_IMAGE_DEPTH, "unknown image type");
-  // a page-locked output image (dslam_host_alloc) is written by the render kernel itself: no copy behind the kernel
-  void *out = type == DSLAM_IMAGE_DEPTH ? (void *)out_float : (void *)out_rgba;
-  const size_t bytes = (size_t)r->w * r->h * 4;
-  if (out && !(out_rgba && out_float) && in_pinned_range(out, bytes)) {
-    int rc = get_image_on_device(e, s, r, M, intr, type, out);
-    if (rc) return rc;
-    // synchronous engine: the image is there on return (what the reference's callers assume); async engine: the
-    // caller pipelines and learns from a fence (dslam_fence_*) when the kernel has stored the last pixel
-    return finish_call(e);
-  }
-  int rc = get_image_on_device(e, s, r, M, intr, type);
-  if (rc) return rc;
-  return image_out(e, r, type, out_rgba, out_float);
+  void *direct = direct_image(r, type, out_rgba, out_float);
+  DSLAM_TRY(get_image_on_device(e, s, r, M, intr, type, direct));
+  return deliver_image(e, r, type, out_rgba, out_float, direct);
 }
 
 int dslam_get_image_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
@@ -1476,17 +1485,10 @@ int dslam_get_image_multi(dslam_engine *e, const dslam_scene *const *scenes, con
     DSLAM_REQUIRE(s->p.num_local_blocks <= r->n_local, "the render state's visible-list capacity is below a scene's num_local_blocks");
     DSLAM_REQUIRE(invert_matrix(T_map_from_world + 16 * i, inv), "a map transform is singular");
   }
-  r->memo_valid = false;  // raycastResult / range image are about to be rewritten (and never memoised for several maps)
-  void *out = type == DSLAM_IMAGE_DEPTH ? (void *)out_float : (void *)out_rgba;
-  const size_t bytes = (size_t)r->w * r->h * 4;
-  if (out && !(out_rgba && out_float) && in_pinned_range(out, bytes)) {
-    int rc = launch_render_multi(e, scenes, T_map_from_world, num_maps, r, M, intr, type, out);
-    if (rc) return rc;
-    return finish_call(e);
-  }
-  int rc = launch_render_multi(e, scenes, T_map_from_world, num_maps, r, M, intr, type);
-  if (rc) return rc;
-  return image_out(e, r, type, out_rgba, out_float);
+  drop_memo(r);   // (and nothing is memoised for several maps)
+  void *direct = direct_image(r, type, out_rgba, out_float);
+  DSLAM_TRY(launch_render_multi(e, scenes, T_map_from_world, num_maps, r, M, intr, type, direct));
+  return deliver_image(e, r, type, out_rgba, out_float, direct);
 }
 
 int dslam_get_depth_image_int16(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
@@ -1505,7 +1507,7 @@ int dslam_get_depth_image_int16(dslam_engine *e, const dslam_scene *s, dslam_ren
 int dslam_create_icp_maps(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
                           const float intr[4], float *out_points, float *out_normals) {
   DSLAM_REQUIRE(e && s && r && M && intr, "null argument");
-  r->memo_valid = false;  // raycastResult / the lists behind it are about to be rewritten
+  drop_memo(r);
   int rc;
   if ((rc = launch_expected_depths(e, s, r, M, intr))) return rc;
   if ((rc = launch_icp_maps(e, s, r, M, intr))) return rc;
@@ -1702,7 +1704,7 @@ int dslam_upload_voxel_blocks(dslam_engine *e, dslam_scene *s, int first, int n,
 }
 int dslam_upload_visible_ids(dslam_engine *e, dslam_render_state *r, const int32_t *ids, int count) {
   DSLAM_REQUIRE(e && r && ids && count >= 0 && count <= r->n_local, "bad visible list");
-  r->memo_valid = false;  // raycastResult / the lists behind it are about to be rewritten
+  drop_memo(r);
   r->types_follow_list = false;
   int rc = h2d(e, r->visible_ids, ids, (size_t)count * sizeof(int));
   if (rc) return rc;

@@ -292,26 +292,19 @@ __global__ __launch_bounds__(kSelThreads) void k_bits_select(const unsigned *__r
 
 // out[0 .. min(total, capacity)) = the selected entries, ascending; *total_out = min(total, capacity).
 // err_cnt: error bit 1 is reported there if a tile count never arrived (bounded spin; report_error, dslam_device.h)
+// Returns non-zero only from the diagnostic dump (DSLAM_DBG_SELECT), which only selections with per-tile sums arm.
 template <class Sel>
-inline void launch_bits_select(dslam_engine *e, const unsigned *src_bits, int n_entries, const Sel &sel, int *out, int capacity,
+inline int launch_bits_select(dslam_engine *e, const unsigned *src_bits, int n_entries, const Sel &sel, int *out, int capacity,
                                int *total_out, SceneCounters *err_cnt, int *tile_sum_out = nullptr) {
   const int n_words = bit_tiles(n_entries) * kBitTileWords;
   int grid;
   TileChain ch = next_chain(e, n_words / kSelTileWords, &grid);
   // diagnostics: per-tile timeline of the 60th selection that has per-tile sums (GetImage's FindVisibleBlocks)
-  static const char *dbg_file = getenv("DSLAM_DBG_SELECT");
-  static int dbg_calls = 0;
-  PinnedBuffer<unsigned long long> dbg_host;
-  if (dbg_file && tile_sum_out && ++dbg_calls == 60 && dbg_host.alloc((size_t)grid * 8) == DSLAM_OK) {
-    memset(dbg_host, 0, (size_t)grid * 64);
-    ch.dbg = dbg_host;
-  }
+  static DiagDump dump("DSLAM_DBG_SELECT", 60);
+  if (tile_sum_out) ch.dbg = dump.arm(grid, 64);
   hipLaunchKernelGGL(k_bits_select<Sel>, dim3(grid), dim3(kSelThreads), 0, e->stream, src_bits, sel, out, capacity, total_out,
                      tile_sum_out, ch, err_cnt);
-  if (dbg_host) {
-    (void)hipStreamSynchronize(e->stream);
-    if (FILE *f = fopen(dbg_file, "wb")) { fwrite(dbg_host, 64, grid, f); fclose(f); }
-  }
+  return dump.write(e);
 }
 
 }  // namespace dslam

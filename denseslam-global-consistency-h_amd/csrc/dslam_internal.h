@@ -361,6 +361,39 @@ inline void dbg_sync(dslam_engine *e, const char *what) {
   fprintf(stderr, " %s\n", err == hipSuccess ? "ok" : hipGetErrorString(err));
   fflush(stderr);
 }
+// diagnostics (<env>=<file>): the per-wave / per-tile records ONE launch of a site leaves -- its `ordinal`-th, well into the
+// run -- in a zeroed page-locked buffer, written to the file as they are.  One static object per site:
+//   static DiagDump dump("DSLAM_DBG_X", 60);
+//   params.dbg = dump.arm(records, bytes_per_record);   // null on every launch but that one
+//   <launch>
+//   DSLAM_TRY(dump.write(e));                           // nothing unless armed
+class DiagDump {
+ public:
+  DiagDump(const char *env, int ordinal) : file_(getenv(env)), ordinal_(ordinal) {}
+  // the pointer the kernel stores its records through, or null: not this launch (or the allocation failed: write says so)
+  unsigned long long *arm(size_t records, size_t bytes_per_record) {
+    if (!file_ || ++calls_ != ordinal_) return nullptr;
+    bytes_ = records * bytes_per_record;
+    if ((rc_ = buf_.alloc(bytes_)) != DSLAM_OK) return nullptr;
+    memset(buf_, 0, bytes_);
+    return static_cast<unsigned long long *>(buf_.get());
+  }
+  // after the launch: wait for it and write the file; the code of a failed arm or of the wait otherwise
+  int write(dslam_engine *e) {
+    if (const int rc = rc_) { rc_ = DSLAM_OK; return rc; }
+    if (!buf_) return DSLAM_OK;
+    PinnedBuffer<void> buf = std::move(buf_);   // (armed once: the buffer goes with this call)
+    DSLAM_HIP(hipStreamSynchronize(e->stream));
+    if (FILE *f = fopen(file_, "wb")) { fwrite(buf, 1, bytes_, f); fclose(f); }
+    return DSLAM_OK;
+  }
+
+ private:
+  const char *file_;
+  int ordinal_, calls_ = 0, rc_ = DSLAM_OK;
+  size_t bytes_ = 0;
+  PinnedBuffer<void> buf_;
+};
 // kernels' host launchers (one translation unit per subsystem)
 int launch_scene_reset(dslam_engine *e, dslam_scene *s);
 int launch_inject_error(dslam_engine *e, dslam_scene *s, int bits);

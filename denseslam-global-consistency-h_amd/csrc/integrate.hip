@@ -1013,21 +1013,14 @@ static int launch_integrate_params(dslam_engine *e, IntegrateParams &ip, bool de
       return DSLAM_OK;
     }
     // diagnostics: the per-wave timeline of one launch, well into the run (DSLAM_DBG_INTEGRATE=<file>)
-    static const char *dbg_file = getenv("DSLAM_DBG_INTEGRATE");
-    static int dbg_calls = 0;
-    if (dbg_file && plain && ++dbg_calls == 60) {
-      constexpr size_t kTraceBytes = (size_t)kIntegrateGrid * kWgWaves * 16 * sizeof(unsigned long long);
-      DeviceBuffer<unsigned long long> trace_dev;
-      DSLAM_TRY(trace_dev.alloc_zeroed(kTraceBytes / sizeof(unsigned long long), e->stream));
-      ip.dbg_waves = trace_dev;
+    static DiagDump dump("DSLAM_DBG_INTEGRATE", 60);
+    if (plain) ip.dbg_waves = dump.arm((size_t)kIntegrateGrid * kWgWaves, 16 * sizeof(unsigned long long));
+    if (ip.dbg_waves) {
       hipExtLaunchKernelGGL((k_integrate<false, true, true, true>), grid_plain, block, 0, e->stream, ev0, ev1, 0, ip);
       DSLAM_HIP(hipGetLastError());
-      DSLAM_HIP(hipStreamSynchronize(e->stream));
-      std::vector<unsigned long long> h(kTraceBytes / sizeof(unsigned long long));
-      DSLAM_HIP(hipMemcpy(h.data(), trace_dev, kTraceBytes, hipMemcpyDeviceToHost));
-      if (FILE *f = fopen(dbg_file, "wb")) { fwrite(h.data(), 1, kTraceBytes, f); fclose(f); }
-      return DSLAM_OK;
+      return dump.write(e);
     }
+    DSLAM_TRY(dump.write(e));   // (an arm that failed)
     if (plain && stream) e->stream_launches++;
     if (plain && stream) hipExtLaunchKernelGGL((k_integrate<false, true, true, false, true>), grid_plain, block, 0, e->stream, ev0, ev1, 0, ip);
     else if (plain) hipExtLaunchKernelGGL((k_integrate<false, true, true>), grid_plain, block, 0, e->stream, ev0, ev1, 0, ip);

@@ -90,15 +90,7 @@ struct MultiRenderParams {
   const MultiMap *maps;
   const unsigned long long *cell_mask;
   int cw;
-  Mat4 M, invM;
-  float inv_fx, inv_fy, cx, cy;
-  float one_over_vs, voxel_size, mu, inv_32767;
-  int W, H;
-  const float2 *range;
-  float4 *raycast;
-  uchar4 *out_rgba;
-  float *out_float;
-  int type;
+  RayCamera cam;
 };
 
 // lowest set bit of a wave-uniform mask, as a scalar
@@ -132,17 +124,8 @@ __device__ __forceinline__ Vec3 to_world_dir(const MultiMap &m, const Vec3 &g) {
   return r;
 }
 
-// trilinear blend of 8 tap values in trilinear_sdf's order (x, then y, then z)
-__device__ __forceinline__ float lerp8(const float s[8], float cx, float cy, float cz) {
-  float res1 = (1.0f - cx) * s[0] + cx * s[1];
-  res1 = (1.0f - cy) * res1 + cy * ((1.0f - cx) * s[2] + cx * s[3]);
-  float res2 = (1.0f - cx) * s[4] + cx * s[5];
-  res2 = (1.0f - cy) * res2 + cy * ((1.0f - cx) * s[6] + cx * s[7]);
-  return (1.0f - cz) * res1 + cz * res2;
-}
-
-// the 8 taps (both voxel words) of the trilinear cell at (x0, y0, z0), as gather_taps_batched; returns whether any tap
-// lies in an allocated block
+// the 8 taps (both voxel words) of the trilinear cell at (x0, y0, z0), as gather_taps_batched (which loads the low words only); returns whether
+// any tap lies in an allocated block
 __device__ __forceinline__ bool gather_cell(const VolumeRef &vol, int x0, int y0, int z0, uint2 t[8]) {
   const int bxa[2] = {x0 >> 3, (x0 + 1) >> 3}, bya[2] = {y0 >> 3, (y0 + 1) >> 3}, bza[2] = {z0 >> 3, (z0 + 1) >> 3};
   int base[8];
@@ -205,32 +188,14 @@ __device__ float multi_trilinear(const MultiRenderParams &p, unsigned long long 
 // castRay (cast_ray<false> in raycast.hip) with every read combined over the maps of the cell's mask
 __device__ __forceinline__ bool cast_ray_multi(Vec4 &out, int x, int y, const MultiRenderParams &p, const float2 minmax,
                                                const unsigned long long cell_mk) {
-  Vec4 pc;
-  Vec3 ps, pe, dir, res;
+  const RayCamera &c = p.cam;
   float sdf = 1.0f;
-  float total, step, total_max;
-  const float step_scale = p.mu * p.one_over_vs;
-
-  pc.z = minmax.x;
-  pc.x = pc.z * (((float)x - p.cx) * p.inv_fx);
-  pc.y = pc.z * (((float)y - p.cy) * p.inv_fy);
-  pc.w = 1.0f;
-  total = sqrtf(pc.x * pc.x + pc.y * pc.y + pc.z * pc.z) * p.one_over_vs;
-  Vec4 q = mul(p.invM, pc);
-  ps.x = q.x * p.one_over_vs; ps.y = q.y * p.one_over_vs; ps.z = q.z * p.one_over_vs;
-
-  pc.z = minmax.y;
-  pc.x = pc.z * (((float)x - p.cx) * p.inv_fx);
-  pc.y = pc.z * (((float)y - p.cy) * p.inv_fy);
-  pc.w = 1.0f;
-  total_max = sqrtf(pc.x * pc.x + pc.y * pc.y + pc.z * pc.z) * p.one_over_vs;
-  q = mul(p.invM, pc);
-  pe.x = q.x * p.one_over_vs; pe.y = q.y * p.one_over_vs; pe.z = q.z * p.one_over_vs;
-
-  dir.x = pe.x - ps.x; dir.y = pe.y - ps.y; dir.z = pe.z - ps.z;
-  const float dn = 1.0f / sqrtf(dir.x * dir.x + dir.y * dir.y + dir.z * dir.z);
-  dir.x *= dn; dir.y *= dn; dir.z *= dn;
-  res = ps;
+  const float step_scale = c.mu * c.one_over_vs;
+  const RaySegment seg = ray_segment(c, x, y, minmax);
+  const Vec3 dir = seg.dir;
+  Vec3 res = seg.start;
+  float total = seg.total, step;
+  const float total_max = seg.total_max;
   // per-lane block cache: one entry, tagged with its map
   IndexCache cache = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1};
   int cache_map = -1;
@@ -248,7 +213,7 @@ __device__ __forceinline__ bool cast_ray_multi(Vec4 &out, int x, int y, const Mu
       const int base = lookup_block(volume_of(m), vx >> 3, vy >> 3, vz >> 3, cache);
       if (base >= 0) {
         const unsigned raw = m.voxels[(size_t)base + (unsigned)((vx & 7) | ((vy & 7) << 3) | ((vz & 7) << 6))].x;
-        b.add(div_exact((float)(short)(raw & 0xffffu), 32767.0f, p.inv_32767), (float)((raw >> 16) & 0xffu));
+        b.add(div_exact((float)(short)(raw & 0xffffu), 32767.0f, c.inv_32767), (float)((raw >> 16) & 0xffu));
       }
     }
     if (b.n == 0) {
@@ -263,36 +228,7 @@ __device__ __forceinline__ bool cast_ray_multi(Vec4 &out, int x, int y, const Mu
     res.x += step * dir.x; res.y += step * dir.y; res.z += step * dir.z;
     total += step;
   }
-  bool pt_found;
-  if (sdf <= 0.0f) {
-    step = sdf * step_scale;
-    res.x += step * dir.x; res.y += step * dir.y; res.z += step * dir.z;
-    sdf = multi_trilinear(p, cell_mk, res);
-    step = sdf * step_scale;
-    res.x += step * dir.x; res.y += step * dir.y; res.z += step * dir.z;
-    pt_found = true;
-  } else {
-    pt_found = false;
-  }
-  out.x = res.x; out.y = res.y; out.z = res.z; out.w = pt_found ? 1.0f : 0.0f;
-  return pt_found;
-}
-
-// read_colour_interp's arithmetic on gathered taps
-__device__ __forceinline__ Vec4 colour_from_taps(const uint2 t[8], float cx, float cy, float cz) {
-  float rx = 0.0f, ry = 0.0f, rz = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const int ox = k & 1, oy = (k >> 1) & 1, oz = (k >> 2) & 1;
-    const uint2 v = t[k];
-    const float wx = ox ? cx : (1.0f - cx), wy = oy ? cy : (1.0f - cy), wz = oz ? cz : (1.0f - cz);
-    const float w = wx * wy * wz;
-    rx += w * (float)(v.x >> 24);
-    ry += w * (float)(v.y & 0xffu);
-    rz += w * (float)((v.y >> 8) & 0xffu);
-  }
-  Vec4 r = {rx / 255.0f, ry / 255.0f, rz / 255.0f, 255.0f / 255.0f};
-  return r;
+  return refine_hit(out, res, dir, sdf, step_scale, [&](const Vec3 &pt) { return multi_trilinear(p, cell_mk, pt); });
 }
 
 // one running sum per component (the same law, component by component)
@@ -313,39 +249,25 @@ struct Blend3 {
   }
 };
 
-// k_render<1, SHADE> over several maps: march, depth, and the three shaded types
+// k_render<SHADE> over several maps: march, depth, and the three shaded types
 template <bool SHADE>
-__global__ __launch_bounds__(64) void k_render_multi(MultiRenderParams p) {
+__global__ __launch_bounds__(64) void k_render_multi(MultiRenderParams mp) {
+  const RayCamera &p = mp.cam;
   const int lane = threadIdx.x & 63;
   const int x = blockIdx.x * 8 + (lane & 7), y = blockIdx.y * 8 + (lane >> 3);
-  const unsigned long long m0 = p.cell_mask[blockIdx.x + blockIdx.y * p.cw];
+  const unsigned long long m0 = mp.cell_mask[blockIdx.x + blockIdx.y * mp.cw];
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)m0), hi = __builtin_amdgcn_readfirstlane((unsigned)(m0 >> 32));
   const unsigned long long cell_mk = ((unsigned long long)hi << 32) | lo;
   if (x >= p.W || y >= p.H) return;
   const int loc = x + y * p.W;
   const int loc2 = (int)floorf((float)x / 8.0f) + (int)floorf((float)y / 8.0f) * p.W;
   Vec4 pr;
-  cast_ray_multi(pr, x, y, p, p.range[loc2], cell_mk);
+  cast_ray_multi(pr, x, y, mp, p.range[loc2], cell_mk);
   p.raycast[loc] = make_float4(pr.x, pr.y, pr.z, pr.w);
   if (p.type < 0) return;
 
-  const Vec3 pt = {pr.x, pr.y, pr.z};
-  bool found = pr.w > 0;
-  if (p.type == DSLAM_IMAGE_DEPTH) {
-    float d = 0.0f;
-    if (found) {
-      Vec4 pw = {pt.x * p.voxel_size, pt.y * p.voxel_size, pt.z * p.voxel_size, 1.0f};
-      d = mul(p.M, pw).z;
-    }
-    p.out_float[loc] = d;
-    return;
-  }
-  if (!SHADE) return;
-  Vec3 n = {0, 0, 0};
-  float angle = 0.0f;
-  if (found) {
-    const Vec3 light = {-p.invM.m[8], -p.invM.m[9], -p.invM.m[10]};
-    // combined 6-tap normal: each map's gradient in the world frame, confidence = trilinear w_depth at the point
+  // combined 6-tap normal: each map's gradient in the world frame, confidence = trilinear w_depth at the point
+  auto normal = [&](const Vec3 &pt) {
     Blend3 b = {0, 0.0f, 0.0f, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f}};
     Vec3 first_any = {0.0f, 0.0f, 0.0f};
     bool have_any = false;
@@ -353,7 +275,7 @@ __global__ __launch_bounds__(64) void k_render_multi(MultiRenderParams p) {
     while (mk) {
       const int i = first_map(mk);
       mk &= mk - 1;
-      const MultiMap &m = p.maps[i];
+      const MultiMap &m = mp.maps[i];
       const VolumeRef vol = volume_of(m);
       const Vec3 q = to_map(m, pt);
       IndexCache c = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1};
@@ -368,52 +290,36 @@ __global__ __launch_bounds__(64) void k_render_multi(MultiRenderParams p) {
         b.add(g, lerp8(wt, q.x - fx, q.y - fy, q.z - fz));
       }
     }
-    n = b.n == 0 ? first_any : b.value();
-    const float ns = 1.0f / sqrtf(n.x * n.x + n.y * n.y + n.z * n.z);
-    n.x *= ns; n.y *= ns; n.z *= ns;
-    angle = n.x * light.x + n.y * light.y + n.z * light.z;
-    if (!(angle > 0.0f)) found = false;
-  }
-  uchar4 o = make_uchar4(0, 0, 0, 0);
-  if (found) {
-    if (p.type == DSLAM_IMAGE_COLOUR_FROM_VOLUME) {
-      // combined colour: confidence = trilinear w_color
-      Blend3 b = {0, 0.0f, 0.0f, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f}};
-      Vec3 first_any = {0.0f, 0.0f, 0.0f};
-      bool have_any = false;
-      unsigned long long mk = cell_mk;
-      while (mk) {
-        const int i = first_map(mk);
-        mk &= mk - 1;
-        const MultiMap &m = p.maps[i];
-        const Vec3 q = to_map(m, pt);
-        const float fx = floorf(q.x), fy = floorf(q.y), fz = floorf(q.z);
-        uint2 t[8];
-        const bool hit = gather_cell(volume_of(m), (int)fx, (int)fy, (int)fz, t);
-        const float cx = q.x - fx, cy = q.y - fy, cz = q.z - fz;
-        const Vec4 c4 = colour_from_taps(t, cx, cy, cz);
-        const Vec3 c3 = {c4.x, c4.y, c4.z};
-        if (!have_any) { first_any = c3; have_any = true; }
-        if (hit) {
-          float wt[8];
+    return b.n == 0 ? first_any : b.value();
+  };
+  // combined colour: confidence = trilinear w_color
+  auto colour = [&](const Vec3 &pt) {
+    Blend3 b = {0, 0.0f, 0.0f, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f}};
+    Vec3 first_any = {0.0f, 0.0f, 0.0f};
+    bool have_any = false;
+    unsigned long long mk = cell_mk;
+    while (mk) {
+      const int i = first_map(mk);
+      mk &= mk - 1;
+      const MultiMap &m = mp.maps[i];
+      const Vec3 q = to_map(m, pt);
+      const float fx = floorf(q.x), fy = floorf(q.y), fz = floorf(q.z);
+      uint2 t[8];
+      const bool hit = gather_cell(volume_of(m), (int)fx, (int)fy, (int)fz, t);
+      const float cx = q.x - fx, cy = q.y - fy, cz = q.z - fz;
+      const Vec4 c4 = colour_from_taps(t, cx, cy, cz);
+      const Vec3 c3 = {c4.x, c4.y, c4.z};
+      if (!have_any) { first_any = c3; have_any = true; }
+      if (hit) {
+        float wt[8];
 #pragma unroll
-          for (int k = 0; k < 8; k++) wt[k] = (float)((t[k].y >> 16) & 0xffu);
-          b.add(c3, lerp8(wt, cx, cy, cz));
-        }
+        for (int k = 0; k < 8; k++) wt[k] = (float)((t[k].y >> 16) & 0xffu);
+        b.add(c3, lerp8(wt, cx, cy, cz));
       }
-      const Vec3 clr = b.n == 0 ? first_any : b.value();
-      o = make_uchar4((unsigned char)(clr.x * 255.0f), (unsigned char)(clr.y * 255.0f), (unsigned char)(clr.z * 255.0f),
-                      255);
-    } else if (p.type == DSLAM_IMAGE_COLOUR_FROM_NORMAL) {
-      o = make_uchar4((unsigned char)((0.3f + (-n.x + 1.0f) * 0.35f) * 255.0f),
-                      (unsigned char)((0.3f + (-n.y + 1.0f) * 0.35f) * 255.0f),
-                      (unsigned char)((0.3f + (-n.z + 1.0f) * 0.35f) * 255.0f), 255);
-    } else {
-      const unsigned char g = (unsigned char)((0.8f * angle + 0.2f) * 255.0f);
-      o = make_uchar4(g, g, g, g);
     }
-  }
-  p.out_rgba[loc] = o;
+    return b.n == 0 ? first_any : b.value();
+  };
+  store_pixel<SHADE>(p, loc, pr, normal, colour);
 }
 
 static bool is_identity(const float *T) {
@@ -488,18 +394,7 @@ int launch_render_multi(dslam_engine *e, const dslam_scene *const *scenes, const
   rp.maps = static_cast<const MultiMap *>(r->multi_maps.get());
   rp.cell_mask = r->multi_mask;
   rp.cw = cw;
-  memcpy(rp.M.m, M, 64);
-  if (!invert_matrix(M, rp.invM.m)) { set_last_error("pose matrix is singular"); return DSLAM_ERR_INVALID; }
-  rp.inv_fx = 1.0f / intr[0]; rp.inv_fy = 1.0f / intr[1]; rp.cx = intr[2]; rp.cy = intr[3];
-  rp.voxel_size = vs; rp.one_over_vs = 1.0f / vs; rp.mu = scenes[0]->p.mu;
-  rp.inv_32767 = 1.0f / 32767.0f;
-  rp.W = r->w; rp.H = r->h;
-  rp.range = r->range; rp.raycast = r->raycast; rp.out_rgba = r->image_rgba; rp.out_float = r->image_float;
-  rp.type = type;
-  if (image_out_override) {
-    if (type == DSLAM_IMAGE_DEPTH) rp.out_float = static_cast<float *>(image_out_override);
-    else rp.out_rgba = static_cast<uchar4 *>(image_out_override);
-  }
+  DSLAM_TRY(fill_ray_camera(rp.cam, scenes[0], r, M, intr, type, image_out_override));
   if (type == DSLAM_IMAGE_DEPTH || type < 0)
     hipLaunchKernelGGL(k_render_multi<false>, dim3(cw, ch), dim3(64), 0, e->stream, rp);
   else

@@ -8,6 +8,13 @@
 // Mapping: the ray march is latency/gather bound (random 16-B hash probes + 8-B voxel reads).  One wavefront (= one
 // workgroup) renders an 8x8 pixel tile, i.e. exactly one cell of the 1/8-resolution range image, so (zmin, zmax)
 // and -- mostly -- the marched blocks are wave-uniform.
+//
+// The instantiations of k_render<SHADE, DIAG, REUSE> and the calls that reach them (launch_render unless said otherwise):
+//   <false>               march, and the depth image if asked for: type < 0 or DSLAM_IMAGE_DEPTH; launch_icp_maps
+//   <true>                march + one of the three shaded types
+//   <false, false, true>  GetImage memo hit (reuse_raycast): depth image from the stored raycast result
+//   <true, false, true>   GetImage memo hit: a shaded type from the stored raycast result
+//   <false, true>         diagnostics: the one launch that DSLAM_DBG_WAVETIME dumps (march with per-wave cycle counts)
 #include <cstdio>
 #include <cstdlib>
 #include <utility>
@@ -96,11 +103,8 @@ __global__ __launch_bounds__(256) void k_project_blocks(const int *__restrict__ 
 // slice of the visible list.  Overlapping blocks are accumulated with LDS atomics (ds_min/ds_max), then every touched cell
 // is flushed with ONE global atomic pair -- instead of one contended global atomic pair per (block, cell).
 constexpr int kRangeTile = 16;
-constexpr int kRangeSlices = 32;
-#ifndef DSLAM_RANGE_BIG
-#define DSLAM_RANGE_BIG 32
-#endif
-constexpr int kRangeBigBox = DSLAM_RANGE_BIG;   // cells of a tile above which a box is taken by the whole workgroup  // workgroups per tile; each strides over the visible list
+constexpr int kRangeSlices = 32;   // workgroups per tile; each strides over the visible list
+constexpr int kRangeBigBox = 32;   // cells of a tile above which a box is taken by the whole workgroup
 
 __global__ __launch_bounds__(256) void k_fill_range_tiles(const RenderCounters *rc, const int4 *__restrict__ boxes,
                                                           const float2 *__restrict__ zr, const int *__restrict__ req,
@@ -285,7 +289,7 @@ int launch_find_visible_and_depths(dslam_engine *e, const dslam_scene *s, dslam_
     }
   }
   SelFrustum<true> sel{s->hash, make_frustum_params(s, r, M, intr), r->proj_boxes, r->proj_z, r->proj_req, r->range, r->w * r->h};
-  launch_bits_select(e, s->alloc_bits, N, sel, r->visible_ids, r->n_local, &r->counters->no_visible, s->counters, r->proj_wg_tiles);
+  DSLAM_TRY(launch_bits_select(e, s->alloc_bits, N, sel, r->visible_ids, r->n_local, &r->counters->no_visible, s->counters, r->proj_wg_tiles));
   return launch_fill_range(e, r, select_tiles(N));
 }
 
@@ -295,17 +299,8 @@ int launch_find_visible_and_depths(dslam_engine *e, const dslam_scene *s, dslam_
 // ---------------------------------------------------------------------------------------------------------
 struct RenderParams {
   VolumeRef vol;
-  Mat4 M, invM;
-  float inv_fx, inv_fy, cx, cy;
-  float one_over_vs, voxel_size, mu, inv_32767;
-  int W, H;
-  const float2 *range;
-  float4 *raycast;
-  uchar4 *out_rgba;
-  float *out_float;
-  int type;  // dslam_image_type, or -1: raycast only
+  RayCamera cam;
   unsigned long long *dbg_waves;  // diagnostics only (env DSLAM_DBG_WAVETIME=<file>): per wave {cycles, max iterations, straddling iterations, their cycles, setup cycles, refinement cycles}
-  int dbg_flags;  // diagnostics only (env DSLAM_DBG_FLAGS: 8 = 16x16 workgroups)
   float split_len;  // > 0: tiles with a longer depth range (voxels) are marched by two wavefronts; the grid is (W/8, 2 H/8)
 };
 
@@ -319,40 +314,24 @@ template <bool DIAG>
 __device__ __forceinline__ bool cast_ray(Vec4 &out, int x, int y, const RenderParams &p, const float2 minmax,
                                          MarchDiag &diag) {
   const unsigned long long t_enter = DIAG ? __builtin_amdgcn_s_memtime() : 0ull;
-  Vec4 pc;
-  Vec3 ps, pe, dir, res;
+  const RayCamera &c = p.cam;
   float sdf = 1.0f;
-  float total, step, total_max;
-  const float step_scale = p.mu * p.one_over_vs;
-
-  pc.z = minmax.x;
-  pc.x = pc.z * (((float)x - p.cx) * p.inv_fx);
-  pc.y = pc.z * (((float)y - p.cy) * p.inv_fy);
-  pc.w = 1.0f;
-  total = sqrtf(pc.x * pc.x + pc.y * pc.y + pc.z * pc.z) * p.one_over_vs;
-  Vec4 q = mul(p.invM, pc);
-  ps.x = q.x * p.one_over_vs; ps.y = q.y * p.one_over_vs; ps.z = q.z * p.one_over_vs;
-
-  pc.z = minmax.y;
-  pc.x = pc.z * (((float)x - p.cx) * p.inv_fx);
-  pc.y = pc.z * (((float)y - p.cy) * p.inv_fy);
-  pc.w = 1.0f;
-  total_max = sqrtf(pc.x * pc.x + pc.y * pc.y + pc.z * pc.z) * p.one_over_vs;
-  q = mul(p.invM, pc);
-  pe.x = q.x * p.one_over_vs; pe.y = q.y * p.one_over_vs; pe.z = q.z * p.one_over_vs;
-
-  dir.x = pe.x - ps.x; dir.y = pe.y - ps.y; dir.z = pe.z - ps.z;
-  const float dn = 1.0f / sqrtf(dir.x * dir.x + dir.y * dir.y + dir.z * dir.z);
-  dir.x *= dn; dir.y *= dn; dir.z *= dn;
-  res = ps;
+  const float step_scale = c.mu * c.one_over_vs;
+  const RaySegment seg = ray_segment(c, x, y, minmax);
+  const Vec3 dir = seg.dir;
+  Vec3 res = seg.start;
+  float total = seg.total, step;
+  const float total_max = seg.total_max;
   IndexCache cache = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1};
   int iter = 0;
-  __shared__ int s_slow_flag;
   unsigned long long t_iter = 0;
-  if (DIAG) {
+  int *slow_flag = nullptr;  // DIAG: some lane of the wave took the straddling-cell path in this iteration
+  if constexpr (DIAG) {
+    __shared__ int s_slow_flag;
+    slow_flag = &s_slow_flag;
     diag.slow_iters = 0; diag.wave_iters = 0; diag.slow_cycles = 0;
     diag.setup_cycles = __builtin_amdgcn_s_memtime() - t_enter;
-    s_slow_flag = 0;
+    *slow_flag = 0;
     t_iter = __builtin_amdgcn_s_memtime();
   }
   while (total < total_max) {
@@ -361,9 +340,9 @@ __device__ __forceinline__ bool cast_ray(Vec4 &out, int x, int y, const RenderPa
       const unsigned long long now = __builtin_amdgcn_s_memtime();
       if (iter > 1) {
         diag.wave_iters++;
-        if (s_slow_flag) { diag.slow_iters++; diag.slow_cycles += now - t_iter; }
+        if (*slow_flag) { diag.slow_iters++; diag.slow_cycles += now - t_iter; }
       }
-      s_slow_flag = 0;
+      *slow_flag = 0;
       t_iter = now;
     }
     // Measured on MI355X (DSLAM_DBG_WAVETIME dump): the launch keeps only ~1.1 waves per SIMD resident on average
@@ -404,12 +383,12 @@ __device__ __forceinline__ bool cast_ray(Vec4 &out, int x, int y, const RenderPa
       const unsigned r01 = nx ? raw[1] : raw[0], r23 = nx ? raw[3] : raw[2];
       const unsigned r45 = nx ? raw[5] : raw[4], r67 = nx ? raw[7] : raw[6];
       const unsigned rn = nz ? (ny ? r67 : r45) : (ny ? r23 : r01);
-      sdf = div_exact((float)(short)(rn & 0xffffu), 32767.0f, p.inv_32767);
+      sdf = div_exact((float)(short)(rn & 0xffffu), 32767.0f, c.inv_32767);
       if ((sdf <= 0.1f) && (sdf >= -0.5f)) {
         const bool all_in = (x0 >> 3) == bx && ((x0 + 1) >> 3) == bx && (y0 >> 3) == by && ((y0 + 1) >> 3) == by &&
                             (z0 >> 3) == bz && ((z0 + 1) >> 3) == bz;
         if (!all_in) {  // the cell straddles blocks: fetch it properly
-          if (DIAG) s_slow_flag = 1;
+          if (DIAG) *slow_flag = 1;
           gather_taps_batched(p.vol, x0, y0, z0, raw);
         }
         sdf = trilinear_raw(raw, res.x - f0x, res.y - f0y, res.z - f0z);
@@ -422,18 +401,8 @@ __device__ __forceinline__ bool cast_ray(Vec4 &out, int x, int y, const RenderPa
   }
   diag.iters = iter;
   const unsigned long long t_tail = DIAG ? __builtin_amdgcn_s_memtime() : 0ull;
-  bool pt_found;
-  if (sdf <= 0.0f) {
-    step = sdf * step_scale;
-    res.x += step * dir.x; res.y += step * dir.y; res.z += step * dir.z;
-    sdf = read_sdf_interp_batched(p.vol, res);
-    step = sdf * step_scale;
-    res.x += step * dir.x; res.y += step * dir.y; res.z += step * dir.z;
-    pt_found = true;
-  } else {
-    pt_found = false;
-  }
-  out.x = res.x; out.y = res.y; out.z = res.z; out.w = pt_found ? 1.0f : 0.0f;
+  const bool pt_found = refine_hit(out, res, dir, sdf, step_scale,
+                                   [&](const Vec3 &pt) { return read_sdf_interp_batched(p.vol, pt); });
   if (DIAG) diag.tail_cycles = __builtin_amdgcn_s_memtime() - t_tail;
   return pt_found;
 }
@@ -442,17 +411,18 @@ __device__ __forceinline__ bool cast_ray(Vec4 &out, int x, int y, const RenderPa
 // shading code, which keeps it at <= 64 VGPRs = 8 waves per SIMD (the march is latency-bound, occupancy is what
 // hides its load round trips).  SHADE = true adds the normal / colour modes.
 // REUSE = true: raycastResult already holds this very view's march (GetImage memo) -- shade only.
-template <int WAVES, bool SHADE, bool DIAG = false, bool REUSE = false>
-__global__ __launch_bounds__(WAVES * 64, 5) void k_render(RenderParams p) {
+template <bool SHADE, bool DIAG = false, bool REUSE = false>
+__global__ __launch_bounds__(64, 5) void k_render(RenderParams rp) {
+  const RayCamera &p = rp.cam;
   // one wavefront = one workgroup = an 8x8 pixel tile = exactly one cell of the 1/8-resolution range image.
   // Single-wave workgroups let the dispatcher backfill a SIMD the moment a short tile finishes (ray lengths vary
   // by 10x between tiles), instead of holding 4 waves until the slowest of a 16x16 tile is done.
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   // (measured: dealing each XCD a contiguous band of tiles for L2 locality is slower, 104 vs 100 us -- the long
   // rays of one image region then pile up on one XCD; the march is bound by its longest dependent-load chain)
-  const int x = (WAVES == 4) ? blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7) : blockIdx.x * 8 + (lane & 7);
-  int y = (WAVES == 4) ? blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3) : blockIdx.y * 8 + (lane >> 3);
-  if (WAVES == 1 && p.split_len > 0.0f) {
+  const int x = blockIdx.x * 8 + (lane & 7);
+  int y = blockIdx.y * 8 + (lane >> 3);
+  if (rp.split_len > 0.0f) {
     // The launch ends when its longest wavefront ends, and a step of a wavefront costs the union of what its rays do
     // (measured: the first 32 steps of the longest tile, all 64 rays alive, take twice as long as its last 36).  So a
     // tile whose rays have far to go -- depth range of its cell of the range image, in voxels -- is marched by TWO
@@ -461,7 +431,7 @@ __global__ __launch_bounds__(WAVES * 64, 5) void k_render(RenderParams p) {
     // one of an unsplit tile leaves at once.  Rays are independent: the images do not change.
     const int ty = blockIdx.y >> 1, sub = blockIdx.y & 1;
     const float2 mm = p.range[(int)blockIdx.x + ty * p.W];
-    const bool split = (mm.y - mm.x) * p.one_over_vs > p.split_len;
+    const bool split = (mm.y - mm.x) * p.one_over_vs > rp.split_len;
     if (split ? (lane >= 32) : (sub != 0)) return;
     y = ty * 8 + (split ? sub * 4 : 0) + (lane >> 3);
     // (the launch ends with these wavefronts: while short tiles share their SIMDs they issue first -- 138.2 -> 137.5 us per frame,
@@ -478,7 +448,7 @@ __global__ __launch_bounds__(WAVES * 64, 5) void k_render(RenderParams p) {
     const float4 q = p.raycast[loc];
     pr.x = q.x; pr.y = q.y; pr.z = q.z; pr.w = q.w;
   } else {
-    cast_ray<DIAG>(pr, x, y, p, p.range[loc2], diag);
+    cast_ray<DIAG>(pr, x, y, rp, p.range[loc2], diag);
   }
   if (DIAG) {  // diagnostic instantiation (DSLAM_DBG_WAVETIME): per-wave cycles and march length
     const unsigned long long dt = __builtin_amdgcn_s_memtime() - t_start;
@@ -486,120 +456,73 @@ __global__ __launch_bounds__(WAVES * 64, 5) void k_render(RenderParams p) {
     int mx = diag.iters;
     for (int d = 32; d > 0; d >>= 1) { const int o = __shfl_xor(mx, d, 64); mx = mx > o ? mx : o; }
     if (diag.iters == mx) {  // (several lanes may tie; they write the same values)
-      const int wid = (blockIdx.y * gridDim.x + blockIdx.x) * WAVES + wave;
-      p.dbg_waves[6 * wid] = dt;
-      p.dbg_waves[6 * wid + 1] = (unsigned long long)mx;
-      p.dbg_waves[6 * wid + 2] = (unsigned long long)diag.slow_iters;
-      p.dbg_waves[6 * wid + 3] = diag.slow_cycles;
-      p.dbg_waves[6 * wid + 4] = diag.setup_cycles;
-      p.dbg_waves[6 * wid + 5] = diag.tail_cycles;
+      const int wid = blockIdx.y * gridDim.x + blockIdx.x;
+      rp.dbg_waves[6 * wid] = dt;
+      rp.dbg_waves[6 * wid + 1] = (unsigned long long)mx;
+      rp.dbg_waves[6 * wid + 2] = (unsigned long long)diag.slow_iters;
+      rp.dbg_waves[6 * wid + 3] = diag.slow_cycles;
+      rp.dbg_waves[6 * wid + 4] = diag.setup_cycles;
+      rp.dbg_waves[6 * wid + 5] = diag.tail_cycles;
     }
   }
   if (!REUSE) p.raycast[loc] = make_float4(pr.x, pr.y, pr.z, pr.w);
   if (p.type < 0) return;
 
-  const Vec3 pt = {pr.x, pr.y, pr.z};
-  bool found = pr.w > 0;
-  if (p.type == DSLAM_IMAGE_DEPTH) {
-    float d = 0.0f;
-    if (found) {
-      Vec4 pw = {pt.x * p.voxel_size, pt.y * p.voxel_size, pt.z * p.voxel_size, 1.0f};
-      d = mul(p.M, pw).z;
-    }
-    p.out_float[loc] = d;
-    return;
+  IndexCache c = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1};  // (the colour read starts from the normal's last block)
+  store_pixel<SHADE>(p, loc, pr, [&](const Vec3 &pt) { return normal_from_sdf(rp.vol, pt, c); },
+                     [&](const Vec3 &pt) { return read_colour_interp(rp.vol, pt, c); });
+}
+
+int fill_ray_camera(RayCamera &c, const dslam_scene *s, const dslam_render_state *r, const float *M, const float *intr,
+                    int type, void *image_out_override) {
+  memcpy(c.M.m, M, 64);
+  if (!invert_matrix(M, c.invM.m)) { set_last_error("pose matrix is singular"); return DSLAM_ERR_INVALID; }
+  c.inv_fx = 1.0f / intr[0]; c.inv_fy = 1.0f / intr[1]; c.cx = intr[2]; c.cy = intr[3];
+  c.voxel_size = s->p.voxel_size; c.one_over_vs = 1.0f / s->p.voxel_size; c.mu = s->p.mu;
+  c.inv_32767 = 1.0f / 32767.0f;
+  c.W = r->w; c.H = r->h;
+  c.range = r->range; c.raycast = r->raycast; c.out_rgba = r->image_rgba; c.out_float = r->image_float;
+  c.type = type;
+  if (image_out_override) {
+    if (type == DSLAM_IMAGE_DEPTH) c.out_float = static_cast<float *>(image_out_override);
+    else c.out_rgba = static_cast<uchar4 *>(image_out_override);
   }
-  if (!SHADE) return;
-  IndexCache c = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1};
-  Vec3 n = {0, 0, 0};
-  float angle = 0.0f;
-  if (found) {
-    const Vec3 light = {-p.invM.m[8], -p.invM.m[9], -p.invM.m[10]};
-    n = normal_from_sdf(p.vol, pt, c);
-    const float ns = 1.0f / sqrtf(n.x * n.x + n.y * n.y + n.z * n.z);
-    n.x *= ns; n.y *= ns; n.z *= ns;
-    angle = n.x * light.x + n.y * light.y + n.z * light.z;
-    if (!(angle > 0.0f)) found = false;
-  }
-  uchar4 o = make_uchar4(0, 0, 0, 0);
-  if (found) {
-    if (p.type == DSLAM_IMAGE_COLOUR_FROM_VOLUME) {
-      const Vec4 clr = read_colour_interp(p.vol, pt, c);
-      o = make_uchar4((unsigned char)(clr.x * 255.0f), (unsigned char)(clr.y * 255.0f), (unsigned char)(clr.z * 255.0f),
-                      255);
-    } else if (p.type == DSLAM_IMAGE_COLOUR_FROM_NORMAL) {
-      o = make_uchar4((unsigned char)((0.3f + (-n.x + 1.0f) * 0.35f) * 255.0f),
-                      (unsigned char)((0.3f + (-n.y + 1.0f) * 0.35f) * 255.0f),
-                      (unsigned char)((0.3f + (-n.z + 1.0f) * 0.35f) * 255.0f), 255);
-    } else {
-      const unsigned char g = (unsigned char)((0.8f * angle + 0.2f) * 255.0f);
-      o = make_uchar4(g, g, g, g);
-    }
-  }
-  p.out_rgba[loc] = o;
+  return DSLAM_OK;
 }
 
 static int fill_render_params(RenderParams &rp, const dslam_scene *s, dslam_render_state *r, const float *M,
-                              const float *intr, int type) {
+                              const float *intr, int type, void *image_out_override = nullptr) {
   rp.vol.hash = s->hash; rp.vol.voxels = s->voxels; rp.vol.mask = (unsigned)(s->p.num_buckets - 1);
   rp.vol.num_buckets = s->p.num_buckets;
-  memcpy(rp.M.m, M, 64);
-  if (!invert_matrix(M, rp.invM.m)) { set_last_error("pose matrix is singular"); return DSLAM_ERR_INVALID; }
-  rp.inv_fx = 1.0f / intr[0]; rp.inv_fy = 1.0f / intr[1]; rp.cx = intr[2]; rp.cy = intr[3];
-  rp.voxel_size = s->p.voxel_size; rp.one_over_vs = 1.0f / s->p.voxel_size; rp.mu = s->p.mu;
-  rp.inv_32767 = 1.0f / 32767.0f;
-  rp.W = r->w; rp.H = r->h;
-  rp.range = r->range; rp.raycast = r->raycast; rp.out_rgba = r->image_rgba; rp.out_float = r->image_float;
-  rp.type = type;
-  static const int dbg_flags = getenv("DSLAM_DBG_FLAGS") ? atoi(getenv("DSLAM_DBG_FLAGS")) : 0;
-  rp.dbg_flags = dbg_flags; rp.dbg_waves = nullptr; rp.split_len = 0.0f;
+  DSLAM_TRY(fill_ray_camera(rp.cam, s, r, M, intr, type, image_out_override));
+  rp.dbg_waves = nullptr; rp.split_len = 0.0f;
   return DSLAM_OK;
 }
 
 // grid of the single-wave march kernels; `split`: long tiles get two wavefronts (see k_render)
 static dim3 march_grid(RenderParams &rp, const dslam_render_state *r, bool split) {
-  static const float split_len = getenv("DSLAM_RENDER_SPLIT") ? (float)atof(getenv("DSLAM_RENDER_SPLIT")) : kSplitLen;
-  rp.split_len = split ? split_len : 0.0f;
-  return dim3((r->w + 7) / 8, ((r->h + 7) / 8) * (rp.split_len > 0.0f ? 2 : 1));
+  rp.split_len = split ? kSplitLen : 0.0f;
+  return dim3((r->w + 7) / 8, ((r->h + 7) / 8) * (split ? 2 : 1));
 }
 
 int launch_render(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float *M, const float *intr,
                   int type, bool reuse_raycast, void *image_out_override) {
   RenderParams rp;
-  int rc = fill_render_params(rp, s, r, M, intr, type);
-  if (rc) return rc;
-  if (image_out_override) {  // a page-locked caller image: the kernel stores the pixels there itself (over PCIe)
-    if (type == DSLAM_IMAGE_DEPTH) rp.out_float = static_cast<float *>(image_out_override);
-    else rp.out_rgba = static_cast<uchar4 *>(image_out_override);
-  }
-  static const char *dbg_file = getenv("DSLAM_DBG_WAVETIME");
-  static int dbg_calls = 0;
-  const int n_waves = ((r->w + 7) / 8) * ((r->h + 7) / 8) * 2;
-  PinnedBuffer<unsigned long long> dbg_host;
-  if (dbg_file && ++dbg_calls == 30) {  // one snapshot, well into the run
-    DSLAM_TRY(dbg_host.alloc((size_t)n_waves * 6));
-    memset(dbg_host, 0, (size_t)n_waves * 48);
-    rp.dbg_waves = dbg_host;
-  }
+  DSLAM_TRY(fill_render_params(rp, s, r, M, intr, type, image_out_override));
+  static DiagDump dump("DSLAM_DBG_WAVETIME", 30);
+  rp.dbg_waves = dump.arm((size_t)((r->w + 7) / 8) * ((r->h + 7) / 8) * 2, 48);   // (6 words per wavefront of the split grid)
   const dim3 grid1 = march_grid(rp, r, !reuse_raycast);
   if (reuse_raycast) {
-    if (type == DSLAM_IMAGE_DEPTH || type < 0) hipLaunchKernelGGL((k_render<1, false, false, true>), grid1, dim3(64), 0, e->stream, rp);
-    else hipLaunchKernelGGL((k_render<1, true, false, true>), grid1, dim3(64), 0, e->stream, rp);
-  } else if (rp.dbg_flags & 8)
-    hipLaunchKernelGGL((k_render<4, true>), dim3((r->w + 15) / 16, (r->h + 15) / 16), dim3(256), 0, e->stream, rp);
-  else if (rp.dbg_waves)
-    hipLaunchKernelGGL((k_render<1, false, true>), grid1, dim3(64), 0, e->stream, rp);
+    if (type == DSLAM_IMAGE_DEPTH || type < 0) hipLaunchKernelGGL((k_render<false, false, true>), grid1, dim3(64), 0, e->stream, rp);
+    else hipLaunchKernelGGL((k_render<true, false, true>), grid1, dim3(64), 0, e->stream, rp);
+  } else if (rp.dbg_waves)
+    hipLaunchKernelGGL((k_render<false, true>), grid1, dim3(64), 0, e->stream, rp);
   else if (type == DSLAM_IMAGE_DEPTH || type < 0)
-    hipLaunchKernelGGL((k_render<1, false>), grid1, dim3(64), 0, e->stream, rp);
+    hipLaunchKernelGGL((k_render<false>), grid1, dim3(64), 0, e->stream, rp);
   else
-    hipLaunchKernelGGL((k_render<1, true>), grid1, dim3(64), 0, e->stream, rp);
+    hipLaunchKernelGGL((k_render<true>), grid1, dim3(64), 0, e->stream, rp);
   DSLAM_HIP(hipGetLastError());
-  if (dbg_host) {
-    DSLAM_HIP(hipStreamSynchronize(e->stream));
-    FILE *f = fopen(dbg_file, "wb");
-    if (f) { fwrite(dbg_host, 48, n_waves, f); fclose(f); }
-  }
-  return DSLAM_OK;
+  return dump.write(e);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -665,12 +588,11 @@ int launch_icp_maps(dslam_engine *e, const dslam_scene *s, dslam_render_state *r
     static_cast<RenderIcpMaps &>(*r) = std::move(n);
   }
   RenderParams rp;
-  int rc = fill_render_params(rp, s, r, M, intr, -1);
-  if (rc) return rc;
+  DSLAM_TRY(fill_render_params(rp, s, r, M, intr, -1));
   const dim3 grid((r->w + 15) / 16, (r->h + 15) / 16);
-  hipLaunchKernelGGL((k_render<1, false>), march_grid(rp, r, true), dim3(64), 0, e->stream, rp);
-  hipLaunchKernelGGL(k_icp_maps, grid, dim3(256), 0, e->stream, r->raycast, r->w, r->h, s->p.voxel_size, -rp.invM.m[8],
-                     -rp.invM.m[9], -rp.invM.m[10], r->icp_points, r->icp_normals, r->raycast_image);
+  hipLaunchKernelGGL((k_render<false>), march_grid(rp, r, true), dim3(64), 0, e->stream, rp);
+  hipLaunchKernelGGL(k_icp_maps, grid, dim3(256), 0, e->stream, r->raycast, r->w, r->h, s->p.voxel_size, -rp.cam.invM.m[8],
+                     -rp.cam.invM.m[9], -rp.cam.invM.m[10], r->icp_points, r->icp_normals, r->raycast_image);
   DSLAM_HIP(hipGetLastError());
   return DSLAM_OK;
 }

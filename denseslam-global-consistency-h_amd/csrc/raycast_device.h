@@ -1,6 +1,7 @@
 // raycast_device.h -- the device side of the ray march shared by raycast.hip (one map) and multimap.hip (several
-// maps): the voxel reads of castRay and the shading pass (the frustum test and projection are in frustum_device.h).
-// Moved here unchanged from raycast.hip.
+// maps): the camera of a render launch, the ray segment of a pixel, the voxel reads of castRay, the refinement behind the
+// march and the pixel epilogue (the frustum test and projection are in frustum_device.h).  The march loops themselves are
+// the renderers' own.
 #pragma once
 #include <cstring>
 
@@ -57,10 +58,6 @@ __device__ __forceinline__ float rd_sdf(const VolumeRef &vol, int x, int y, int 
 // (int)(x < 0 ? x - 0.5f : x + 0.5f); copysign folds the compare + select into one bit-field insert (-0.0 gives 0
 // either way)
 __device__ __forceinline__ int iround(float x) { return (int)(x + __builtin_copysignf(0.5f, x)); }
-
-__device__ __forceinline__ float read_sdf_uninterp(const VolumeRef &vol, const Vec3 &pt, bool &found, IndexCache &c) {
-  return rd_sdf(vol, iround(pt.x), iround(pt.y), iround(pt.z), found, c) / 32767.0f;
-}
 
 // block base pointer (voxel index of the block's first voxel) or -1; refreshes the per-lane cache on a hit
 __device__ __forceinline__ int lookup_block(const VolumeRef &vol, int bx, int by, int bz, IndexCache &c) {
@@ -169,19 +166,25 @@ __device__ __forceinline__ float div_exact(float a, float b, float y) {
   return __fmaf_rn(r, y, q);
 }
 
-__device__ __forceinline__ float trilinear_sdf(const uint2 t[8], float cx, float cy, float cz) {
-  float s[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) s[k] = (float)(short)(t[k].x & 0xffffu);
+// trilinear blend of 8 tap values: x, then y, then z
+__device__ __forceinline__ float lerp8(const float s[8], float cx, float cy, float cz) {
   float res1 = (1.0f - cx) * s[0] + cx * s[1];
   res1 = (1.0f - cy) * res1 + cy * ((1.0f - cx) * s[2] + cx * s[3]);
   float res2 = (1.0f - cx) * s[4] + cx * s[5];
   res2 = (1.0f - cy) * res2 + cy * ((1.0f - cx) * s[6] + cx * s[7]);
-  return div_exact((1.0f - cz) * res1 + cz * res2, 32767.0f, 1.0f / 32767.0f);
+  return (1.0f - cz) * res1 + cz * res2;
+}
+
+__device__ __forceinline__ float trilinear_sdf(const uint2 t[8], float cx, float cy, float cz) {
+  float s[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) s[k] = (float)(short)(t[k].x & 0xffffu);
+  return div_exact(lerp8(s, cx, cy, cz), 32767.0f, 1.0f / 32767.0f);
 }
 
 // The 8 taps (low voxel words) of the trilinear cell at (x0, y0, z0) in two load round trips: every block of the
 // cell resolved together, then the 8 taps together; a tap whose block is not allocated reads the empty voxel.
+// (multimap.hip's gather_cell is the same with 8-byte tap loads: merged, k_render's march would load both words too.)
 __device__ __forceinline__ void gather_taps_batched(const VolumeRef &vol, int x0, int y0, int z0, unsigned raw[8]) {
   const int bxa[2] = {x0 >> 3, (x0 + 1) >> 3}, bya[2] = {y0 >> 3, (y0 + 1) >> 3}, bza[2] = {z0 >> 3, (z0 + 1) >> 3};
   int base[8];
@@ -207,7 +210,7 @@ __device__ __forceinline__ float trilinear_raw(const unsigned raw[8], float cx, 
   return trilinear_sdf(t, cx, cy, cz);
 }
 
-// readFromSDF_float_interpolated; same values as read_sdf_interp, two round trips instead of up to nine
+// readFromSDF_float_interpolated in two round trips instead of up to nine
 __device__ __forceinline__ float read_sdf_interp_batched(const VolumeRef &vol, const Vec3 &pt) {
   const float fx = floorf(pt.x), fy = floorf(pt.y), fz = floorf(pt.z);
   unsigned raw[8];
@@ -215,23 +218,9 @@ __device__ __forceinline__ float read_sdf_interp_batched(const VolumeRef &vol, c
   return trilinear_raw(raw, pt.x - fx, pt.y - fy, pt.z - fz);
 }
 
-__device__ __forceinline__ float read_sdf_interp(const VolumeRef &vol, const Vec3 &pt, bool &found, IndexCache &c) {
-  const float fx = floorf(pt.x), fy = floorf(pt.y), fz = floorf(pt.z);
-  const int x = (int)fx, y = (int)fy, z = (int)fz;
-  const float cx = pt.x - fx, cy = pt.y - fy, cz = pt.z - fz;
-  uint2 t[8];
-  gather_taps(vol, x, y, z, c, t);
-  found = true;
-  return trilinear_sdf(t, cx, cy, cz);
-}
-
-__device__ __forceinline__ Vec4 read_colour_interp(const VolumeRef &vol, const Vec3 &pt, IndexCache &c) {
-  const float fx = floorf(pt.x), fy = floorf(pt.y), fz = floorf(pt.z);
-  const int x = (int)fx, y = (int)fy, z = (int)fz;
-  const float cx = pt.x - fx, cy = pt.y - fy, cz = pt.z - fz;
+// trilinear colour of 8 gathered taps (readFromSDF_color4u_interpolated's arithmetic)
+__device__ __forceinline__ Vec4 colour_from_taps(const uint2 t[8], float cx, float cy, float cz) {
   float rx = 0.0f, ry = 0.0f, rz = 0.0f;
-  uint2 t[8];
-  gather_taps(vol, x, y, z, c, t);
 #pragma unroll
   for (int k = 0; k < 8; k++) {
     const int ox = k & 1, oy = (k >> 1) & 1, oz = (k >> 2) & 1;
@@ -244,6 +233,13 @@ __device__ __forceinline__ Vec4 read_colour_interp(const VolumeRef &vol, const V
   }
   Vec4 r = {rx / 255.0f, ry / 255.0f, rz / 255.0f, 255.0f / 255.0f};
   return r;
+}
+
+__device__ __forceinline__ Vec4 read_colour_interp(const VolumeRef &vol, const Vec3 &pt, IndexCache &c) {
+  const float fx = floorf(pt.x), fy = floorf(pt.y), fz = floorf(pt.z);
+  uint2 t[8];
+  gather_taps(vol, (int)fx, (int)fy, (int)fz, c, t);
+  return colour_from_taps(t, pt.x - fx, pt.y - fy, pt.z - fz);
 }
 
 // computeSingleNormalFromSDF (un-normalised gradient)
@@ -294,6 +290,121 @@ __device__ __forceinline__ Vec3 normal_from_sdf(const VolumeRef &vol, const Vec3
   p2 = tmp.x * nx * ny + tmp.y * cx * ny + tmp.z * nx * cy + tmp.w * cx * cy;
   ret.z = (p1 * nz + p2 * cz - v1) / 32767.0f;
   return ret;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// what the one-map and the several-map renderer share around their march loops
+// ---------------------------------------------------------------------------------------------------------
+// the camera and the images of one render launch (filled by fill_ray_camera, raycast.hip)
+struct RayCamera {
+  Mat4 M, invM;
+  float inv_fx, inv_fy, cx, cy;
+  float one_over_vs, voxel_size, mu, inv_32767;
+  int W, H;
+  const float2 *range;
+  float4 *raycast;
+  uchar4 *out_rgba;
+  float *out_float;
+  int type;  // dslam_image_type, or -1: raycast only
+};
+
+// s: the scene (of several: the first, they agree) whose voxel_size and mu the march uses.  image_out_override: a page-locked
+// caller image the kernel stores the pixels of `type` into itself (over PCIe) instead of the render state's image.
+int fill_ray_camera(RayCamera &c, const dslam_scene *s, const dslam_render_state *r, const float *M, const float *intr,
+                    int type, void *image_out_override = nullptr);
+
+// castRay's set-up: the ray of pixel (x, y) between the depths (zmin, zmax) of its range cell, in voxel units
+struct RaySegment {
+  Vec3 start, dir;         // dir: unit length
+  float total, total_max;  // distance from the camera at the start / at the end
+};
+
+__device__ __forceinline__ RaySegment ray_segment(const RayCamera &p, int x, int y, const float2 minmax) {
+  RaySegment s;
+  Vec4 pc;
+  Vec3 pe;
+  pc.z = minmax.x;
+  pc.x = pc.z * (((float)x - p.cx) * p.inv_fx);
+  pc.y = pc.z * (((float)y - p.cy) * p.inv_fy);
+  pc.w = 1.0f;
+  s.total = sqrtf(pc.x * pc.x + pc.y * pc.y + pc.z * pc.z) * p.one_over_vs;
+  Vec4 q = mul(p.invM, pc);
+  s.start.x = q.x * p.one_over_vs; s.start.y = q.y * p.one_over_vs; s.start.z = q.z * p.one_over_vs;
+
+  pc.z = minmax.y;
+  pc.x = pc.z * (((float)x - p.cx) * p.inv_fx);
+  pc.y = pc.z * (((float)y - p.cy) * p.inv_fy);
+  pc.w = 1.0f;
+  s.total_max = sqrtf(pc.x * pc.x + pc.y * pc.y + pc.z * pc.z) * p.one_over_vs;
+  q = mul(p.invM, pc);
+  pe.x = q.x * p.one_over_vs; pe.y = q.y * p.one_over_vs; pe.z = q.z * p.one_over_vs;
+
+  s.dir.x = pe.x - s.start.x; s.dir.y = pe.y - s.start.y; s.dir.z = pe.z - s.start.z;
+  const float dn = 1.0f / sqrtf(s.dir.x * s.dir.x + s.dir.y * s.dir.y + s.dir.z * s.dir.z);
+  s.dir.x *= dn; s.dir.y *= dn; s.dir.z *= dn;
+  return s;
+}
+
+// castRay behind its loop: a march that ended at sdf <= 0 is refined by two steps of sdf * step_scale, the second with
+// the trilinear read at the point the first one reached (trilinear(pt): that read); out = (point, found ? 1 : 0)
+template <class Trilinear>
+__device__ __forceinline__ bool refine_hit(Vec4 &out, Vec3 res, const Vec3 &dir, float sdf, float step_scale,
+                                           Trilinear trilinear) {
+  const bool pt_found = sdf <= 0.0f;
+  if (pt_found) {
+    float step = sdf * step_scale;
+    res.x += step * dir.x; res.y += step * dir.y; res.z += step * dir.z;
+    sdf = trilinear(res);
+    step = sdf * step_scale;
+    res.x += step * dir.x; res.y += step * dir.y; res.z += step * dir.z;
+  }
+  out.x = res.x; out.y = res.y; out.z = res.z; out.w = pt_found ? 1.0f : 0.0f;
+  return pt_found;
+}
+
+// The pixel `loc` of an image of p.type (>= 0) from its raycast result pr: the depth image, or -- SHADE instantiations --
+// the three shaded types (SHADE = false compiles the shading, and with it both callables, away).  normal(pt): the
+// un-normalised gradient at the point, colour(pt): the volume's colour there (.x .y .z in 0 .. 1).
+template <bool SHADE, class Normal, class Colour>
+__device__ __forceinline__ void store_pixel(const RayCamera &p, int loc, const Vec4 &pr, Normal normal, Colour colour) {
+  const Vec3 pt = {pr.x, pr.y, pr.z};
+  bool found = pr.w > 0;
+  if (p.type == DSLAM_IMAGE_DEPTH) {
+    float d = 0.0f;
+    if (found) {
+      Vec4 pw = {pt.x * p.voxel_size, pt.y * p.voxel_size, pt.z * p.voxel_size, 1.0f};
+      d = mul(p.M, pw).z;
+    }
+    p.out_float[loc] = d;
+    return;
+  }
+  if (!SHADE) return;
+  Vec3 n = {0, 0, 0};
+  float angle = 0.0f;
+  if (found) {
+    const Vec3 light = {-p.invM.m[8], -p.invM.m[9], -p.invM.m[10]};
+    n = normal(pt);
+    const float ns = 1.0f / sqrtf(n.x * n.x + n.y * n.y + n.z * n.z);
+    n.x *= ns; n.y *= ns; n.z *= ns;
+    angle = n.x * light.x + n.y * light.y + n.z * light.z;
+    if (!(angle > 0.0f)) found = false;
+  }
+  uchar4 o = make_uchar4(0, 0, 0, 0);
+  if (found) {
+    if (p.type == DSLAM_IMAGE_COLOUR_FROM_VOLUME) {
+      const auto clr = colour(pt);
+      o = make_uchar4((unsigned char)(clr.x * 255.0f), (unsigned char)(clr.y * 255.0f), (unsigned char)(clr.z * 255.0f),
+                      255);
+    } else if (p.type == DSLAM_IMAGE_COLOUR_FROM_NORMAL) {
+      o = make_uchar4((unsigned char)((0.3f + (-n.x + 1.0f) * 0.35f) * 255.0f),
+                      (unsigned char)((0.3f + (-n.y + 1.0f) * 0.35f) * 255.0f),
+                      (unsigned char)((0.3f + (-n.z + 1.0f) * 0.35f) * 255.0f), 255);
+    } else {
+      const unsigned char g = (unsigned char)((0.8f * angle + 0.2f) * 255.0f);
+      o = make_uchar4(g, g, g, g);
+    }
+  }
+  p.out_rgba[loc] = o;
 }
 
 }  // namespace dslam

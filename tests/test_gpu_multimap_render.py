@@ -291,6 +291,43 @@ def test_memo_determinism_and_async(pkg, gpu):
         gpu.host_free(out)
 
 
+def test_page_locked_output_equals_pageable(pkg, gpu, synth):
+    """The composite render stored by the kernel itself into a page-locked caller image (host_alloc) against the same call
+    into a pageable array (rendered into the render state's image, copied behind the kernel): the same bytes for all four
+    image types, on the synchronous engine and on the async engine behind a fence.  Two fused maps of the 70 x 45 room (a
+    width that is no multiple of the 8-pixel tile), the second under a rigid pose."""
+    wl = synth.s_room(70, 45)
+    W, H = wl.W, wl.H
+    A, _, _ = util.run_sequence(gpu, pkg, wl, util.small_params(pkg, wl), 3)
+    B, _, _ = util.run_sequence(gpu, pkg, wl, util.small_params(pkg, wl), 2)
+    scenes, poses = [A, B], [I4, pose(yaw=0.04, t=(0.03, 0.0, -0.02))]
+    M, intr = wl.frame(2)[2], wl.intr
+    rs = roomiest(gpu, scenes, W, H)
+    want = {name: gpu.get_image_multi(scenes, poses, rs, M, intr, getattr(pkg, name)).copy() for name in TYPES}
+    assert (want["IMAGE_DEPTH"] > 0).sum() > 0.1 * W * H and (want["IMAGE_SHADED"][..., 3] > 0).sum() > 0.1 * W * H
+    pinned = {name: gpu.host_alloc((H, W) if name == "IMAGE_DEPTH" else (H, W, 4),
+                                   np.float32 if name == "IMAGE_DEPTH" else np.uint8) for name in TYPES}
+    fence = gpu.fence_create()
+    try:
+        for is_async in (False, True):
+            gpu.set_async(is_async)
+            for name in TYPES:
+                out = pinned[name]
+                out[...] = 0
+                gpu.get_image_multi(scenes, poses, rs, M, intr, getattr(pkg, name), out=out)
+                if is_async:
+                    gpu.fence_record(fence)
+                    gpu.fence_wait(fence)
+                got = np.asarray(out)
+                assert np.array_equal(got.view(np.uint8), want[name].view(np.uint8)), \
+                    f"{name}, async={is_async}: {np.sum(got != want[name])} values differ"
+    finally:
+        gpu.set_async(False)
+        gpu.synchronize()
+        for out in pinned.values():
+            gpu.host_free(out)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 7. the ITMLib mirror
 # ---------------------------------------------------------------------------------------------------------------------
