@@ -593,6 +593,28 @@ class CApi:
         self._call("mesh_download", self._engine, _fptr(pos), _fptr(col) if colour else None, C.c_int(n.value))
         return pos[:n.value], (col[:n.value] if colour else None)
 
+    def mesh_scene_multi(self, scenes, map_poses, max_triangles=0, colour=False):
+        """dslam_mesh_scene_multi: one mesh of several local maps in the world frame.  `scenes` / `map_poses` as
+        get_image_multi.  Returns (positions [n, 3, 3] float32 in metres, colours [n, 3, 3] float32 in [0, 1] or None,
+        per_map_counts [len(scenes)] int32): the triangles of map 0, then map 1, ..."""
+        scenes = list(scenes)
+        T = np.asarray(map_poses, dtype=np.float32)
+        if T.ndim != 3 or T.shape[1:] != (4, 4):
+            raise ValueError("map_poses must be N 4x4 matrices")
+        if len(T) != len(scenes):
+            raise ValueError(f"{len(scenes)} scenes but {len(T)} map poses")
+        k = len(scenes)
+        ptrs = (C.c_void_p * max(k, 1))(*[None if s is None else s.ptr for s in scenes])
+        t_abi = np.ascontiguousarray(np.transpose(T, (0, 2, 1))).reshape(-1) if k else np.zeros(16, np.float32)
+        n = C.c_int(0)
+        counts = np.zeros(max(k, 1), dtype=np.int32)
+        self._call("mesh_scene_multi", self._engine, ptrs, _fptr(t_abi), C.c_int(k), C.c_int(int(max_triangles)),
+                   C.c_int(int(colour)), C.byref(n), counts.ctypes.data_as(C.POINTER(C.c_int32)))
+        pos = np.empty((max(n.value, 1), 3, 3), dtype=np.float32)
+        col = np.empty((max(n.value, 1), 3, 3), dtype=np.float32) if colour else None
+        self._call("mesh_download", self._engine, _fptr(pos), _fptr(col) if colour else None, C.c_int(n.value))
+        return pos[:n.value], (col[:n.value] if colour else None), counts[:k]
+
     # -- page-locked host images -----------------------------------------------------------------------
     def host_alloc(self, shape, dtype):
         """A zero-filled numpy array over page-locked memory (dslam_host_alloc): view_update* in synchronous mode

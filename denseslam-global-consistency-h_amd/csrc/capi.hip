@@ -2,6 +2,7 @@
 // composition of kernels into the ITMLib engine calls (ITMDenseMapper::ProcessFrame, ITMMainEngine::GetImage ...).
 // No arithmetic of the hot path lives here; there is no CPU fallback: without a HIP device the engine cannot be
 // created and every entry point fails.
+#include <climits>
 #include <cctype>
 #include <atomic>
 #include <cstdio>
@@ -1540,6 +1541,27 @@ int dslam_mesh_scene(dslam_engine *e, const dslam_scene *s, int max_triangles, i
   if (max_triangles <= 0) max_triangles = s->p.num_local_blocks * 32;  // ITMMesh::noMaxTriangles
   int rc = launch_mesh_scene(e, s, max_triangles, with_colour, out_num_triangles);
   if (rc) return rc;
+  return finish_call(e);
+}
+
+int dslam_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                           int max_triangles, int with_colour, int *out_num_triangles, int32_t *out_map_triangles) {
+  DSLAM_REQUIRE(e && scenes && T_map_from_world && out_num_triangles, "null argument");
+  DSLAM_REQUIRE(num_maps >= 1 && num_maps <= DSLAM_MAX_RENDER_MAPS, "num_maps must be 1 .. DSLAM_MAX_RENDER_MAPS");
+  long long blocks = 0;
+  for (int i = 0; i < num_maps; i++) {
+    const dslam_scene *s = scenes[i];
+    float inv[16];
+    DSLAM_REQUIRE(s, "a scene in the list is NULL");
+    DSLAM_REQUIRE(s->engine == e, "a scene in the list belongs to another engine");
+    DSLAM_REQUIRE(s->p.voxel_size == scenes[0]->p.voxel_size && s->p.mu == scenes[0]->p.mu,
+                  "all scenes of a composite mesh need the same voxel_size and mu");
+    DSLAM_REQUIRE(invert_matrix(T_map_from_world + 16 * i, inv), "a map transform is singular");
+    blocks += s->p.num_local_blocks;
+  }
+  if (max_triangles <= 0) max_triangles = (int)std::min<long long>(blocks * 32, INT_MAX);  // the maps' noMaxTriangles together
+  DSLAM_TRY(launch_mesh_scene_multi(e, scenes, T_map_from_world, num_maps, max_triangles, with_colour, out_num_triangles,
+                                    out_map_triangles));
   return finish_call(e);
 }
 

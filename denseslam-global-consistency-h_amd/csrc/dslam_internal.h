@@ -157,6 +157,9 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   int mesh_triangles = 0;
   bool mesh_has_colour = false;
   bool mesh_table_ready = false;      // the case table sits in this device's constant memory
+  // dslam_mesh_scene_multi (multimesh.hip): its copy of the case table, and the per-map descriptor table of one map pass
+  bool multimesh_table_ready = false;
+  DeviceBuffer<void> multimesh_maps;
 };
 
 // GetImage's front end for the pose of the last ProcessFrame: FindVisibleBlocks with the projections of its blocks and a reset
@@ -448,6 +451,9 @@ int launch_render_multi(dslam_engine *e, const dslam_scene *const *scenes, const
                         const float *M, const float *intr, int type, void *image_out_override = nullptr);
 int launch_icp_maps(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float *M, const float *intr);
 int launch_mesh_scene(dslam_engine *e, const dslam_scene *s, int max_triangles, int with_colour, int *out_num);
+// scenes / T (N x 16, world -> map) already checked by dslam_mesh_scene_multi; out_map: [n] triangles per map, or null
+int launch_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T, int n, int max_triangles,
+                            int with_colour, int *out_num, int32_t *out_map);
 int launch_decay(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int max_weight, int min_age, int force_all,
                  int which);
 int launch_slide_pop(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int which);

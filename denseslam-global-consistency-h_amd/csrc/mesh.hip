@@ -17,6 +17,7 @@
 
 #include "dslam_bits.h"
 #include "mc_tables.h"
+#include "mesh_device.h"
 
 #pragma clang fp contract(off)
 
@@ -39,27 +40,6 @@ struct MeshParams {
   float factor;            // voxel size: vertices leave in metres
   int limit;               // triangles with rank >= limit are dropped (upstream: noMaxTriangles - 1)
 };
-
-// the live list: every entry with a resident block, ascending -- the scene's alloc_bits as a list (dslam_bits.h)
-struct SelLive {
-  DSLAM_SEL_NO_LOAD
-  const HashEntry *hash;
-  __device__ bool test(int t, const NoPayload &) const { return hash[t].ptr >= 0; }
-  __device__ void prologue() const {}
-  __device__ int emit(int, int, bool, const NoPayload &) const { return 0; }
-  __device__ void finish(int) const {}
-};
-
-// findVoxel's block search: walk the bucket's chain for a resident block at (bx, by, bz); -1 when there is none
-__device__ __forceinline__ int find_block_ptr(const HashEntry *hash, int num_buckets, unsigned mask, int bx, int by, int bz) {
-  int idx = hash_index(bx, by, bz, mask);
-  while (true) {
-    const HashEntry he = load_entry(hash, idx);
-    if (he.pos[0] == bx && he.pos[1] == by && he.pos[2] == bz && he.ptr >= 0) return he.ptr;
-    if (he.offset < 1) return -1;
-    idx = num_buckets + he.offset - 1;
-  }
-}
 
 // buildVertList's first half: the 8 corner samples and the case index; -1 = skip this cube.  With STORE the samples
 // go to LDS ([corner][thread], conflict-free), where the emit pass indexes them by a run-time corner number.
@@ -126,22 +106,6 @@ __global__ __launch_bounds__(1024) void k_mesh_scan(const int *block_counts, int
   int totals[1];
   scan_tiles<1>(block_counts, block_offsets, *live_count, totals);
   if (threadIdx.x == 0) *total_out = totals[0];
-}
-
-// sdfInterp: the zero crossing between two corners (positions in voxel units); t is shared with the colour
-struct Crossing { float t; int take; };  // take: 1 = first corner, 2 = second corner, 0 = interpolate with t
-__device__ __forceinline__ Crossing crossing(float v1, float v2) {
-  Crossing r{0.0f, 0};
-  if (fabsf(0.0f - v1) < 0.00001f) r.take = 1;
-  else if (fabsf(0.0f - v2) < 0.00001f) r.take = 2;
-  else if (fabsf(v1 - v2) < 0.00001f) r.take = 1;
-  else r.t = (0.0f - v1) / (v2 - v1);
-  return r;
-}
-__device__ __forceinline__ float lerp_value(const Crossing &k, float a, float b) {
-  if (k.take == 1) return a;
-  if (k.take == 2) return b;
-  return a + k.t * (b - a);
 }
 
 template <bool COLOUR>

@@ -438,6 +438,44 @@ class ITMMainEngine {
     if (settings->meshWithColour) mesh->colours.resize((size_t)n);
   }
 
+  /// (extension) The whole reconstruction as one mesh in the global frame: every local map of mapManager under its
+  /// estimatedGlobalPose.GetM(), one surface where maps overlap -- the reference writes one mesh per local map, each in its
+  /// own coordinates (SystemEntry.cpp:364-370).  dslam_mesh_scene_multi, law in DESIGN.md section 12.  Does nothing
+  /// before the first local map; honours settings->meshWithColour.
+  void MeshAllLocalMaps(ITMMesh *mesh) {
+    const int n = mapManager->numLocalMaps();
+    if (n == 0) return;
+    if (n > DSLAM_MAX_RENDER_MAPS)
+      throw std::runtime_error("MeshAllLocalMaps: " + std::to_string(n) + " local maps, at most " +
+                               std::to_string(DSLAM_MAX_RENDER_MAPS) + " can be meshed in one call");
+    std::vector<const dslam_scene *> scenes(n);
+    std::vector<float> T((size_t)n * 16);
+    for (int i = 0; i < n; i++) {
+      const ITMLocalMap *m = mapManager->getLocalMap(i);
+      scenes[i] = m->scene->handle;
+      memcpy(&T[(size_t)i * 16], m->estimatedGlobalPose.GetM().m, 16 * sizeof(float));
+    }
+    int total = 0;
+    dslam_check(dslam_mesh_scene_multi(engine_, scenes.data(), T.data(), n, (int)mesh->noMaxTriangles, settings->meshWithColour,
+                                       &total, nullptr), "dslam_mesh_scene_multi");
+    mesh->noTotalTriangles = (unsigned)total;
+    mesh->triangles.resize((size_t)total + 1);  // never a null data()
+    mesh->colours.resize(settings->meshWithColour ? (size_t)total + 1 : 0);
+    dslam_check(dslam_mesh_download(engine_, &mesh->triangles[0].p0.x, settings->meshWithColour ? &mesh->colours[0].p0.x : nullptr, total),
+                "dslam_mesh_download");
+    mesh->triangles.resize((size_t)total);
+    if (settings->meshWithColour) mesh->colours.resize((size_t)total);
+  }
+  /// (extension) MeshAllLocalMaps into one OBJ file: replaces the export loop over the local maps.
+  void SaveAllLocalMapsToMesh(const char *objFileName) {
+    const int n = mapManager->numLocalMaps();
+    if (n == 0) return;
+    const unsigned long long cap = (unsigned long long)settings->numLocalBlocks * 32ull * (unsigned long long)n;
+    ITMMesh mesh((unsigned)(cap > 0x7fffffffull ? 0x7fffffffull : cap));
+    MeshAllLocalMaps(&mesh);
+    mesh.WriteOBJ(objFileName);
+  }
+
   dslam_engine *GetDslamEngine() const { return engine_; }
 
  protected:

@@ -469,6 +469,46 @@ int dslam_mesh_scene(dslam_engine *e, const dslam_scene *s, int max_triangles, i
 int dslam_mesh_download(dslam_engine *e, float *out_positions_host, float *out_colours_host,
                         int capacity_triangles);
 
+/* One mesh of the whole reconstruction: every local map of the map graph, each under its estimatedGlobalPose, in one
+ * triangle list in the world frame (metres).  The reference writes one mesh-<n>-frames.obj per local map, each in its
+ * own coordinates (SystemEntry.cpp:364-370, DenseSlam.cpp:638-643); loaded together they lie on top of each other at the
+ * origin, and posed by hand they show two or three surfaces wherever maps overlap.  scenes / T_map_from_world are exactly as
+ * in dslam_get_image_multi (column-major, metres, world -> map).  The law is this project's own.
+ * With T~_i = T_i with its translation in voxel units, A_ij = T~_j T~_i^-1 (voxels of map i -> voxels of map j) and
+ * B_i = T~_i^-1, both computed on the host in double from the float inputs and rounded to float32 (A_ij is exactly the
+ * identity when T_i and T_j are bit-identical): for every allocated block of map i and every cube of it with corner 0 at
+ * the integer voxel g of map i
+ *   1. own gate: the cube is skipped when one of its 8 corner voxels of map i is missing or has sdf == 1 (as
+ *      dslam_mesh_scene);
+ *   2. coverage gate: ... or when an earlier map j < i holds a valid voxel (resident block, w_depth > 0, raw sdf != 32767)
+ *      at iround(A_ij (g + 1/2)): earlier maps own overlapped space, later maps fill only what is left;
+ *   3. corner values, one per lattice point of map i (every cube sharing the point sees the same value, so the mesh of one
+ *      map stays watertight): the contributors are combined in list order, map i at its own position.  Own map: the
+ *      voxel's sdf with weight w_depth (colour: the voxel's colour with weight w_color).  Every other map j: the
+ *      trilinear read at A_ij (g + corner) exactly as dslam_get_image_multi's (found = any of the 8 taps in a resident
+ *      block, weight = trilinear w_depth; colour: the trilinear colour on the 0 .. 255 scale with the trilinear w_color).
+ *      Only the own map found -> its value unchanged, bit for bit; several -> sum(w v) / sum(w), accumulated in float32
+ *      in list order; sum(w) == 0 -> the own map's value;
+ *   4. triangles: case index from the combined values (< 0), zero crossings and case table as dslam_mesh_scene in map-i
+ *      voxel coordinates; each vertex v leaves as (B_i v) * voxel_size, rows evaluated as ((a x + b y) + c z) + d (a T_i
+ *      that is exactly the identity skips the transform).
+ * So a list of one identity map is dslam_mesh_scene bit for bit, maps that do not reach each other give the concatenation
+ * of their posed meshes, and where maps overlap there is one surface at the weighted consensus.  Seams between maps are
+ * NOT stitched: along the edge of a later map's contribution a crack of up to about one voxel is accepted, and within a
+ * voxel of a map's block edge, where another map's read finds only part of its taps (the missing ones read as sdf 1),
+ * the surface is drawn up to 0.21 mu behind its place.
+ * Triangle order: the triangles of map 0, then map 1, ...; inside a map dslam_mesh_scene's order.  out_map_triangles
+ * ([num_maps] or NULL): the triangles map i contributed after saturation; they sum to *out_num_triangles.
+ * max_triangles <= 0 selects the sum of num_local_blocks * 32 over the list (clamped to INT_MAX); the list saturates at
+ * max_triangles - 1.  The mesh stays on the device until dslam_mesh_download; a later dslam_mesh_scene replaces it.  The
+ * maps are only read.  Waits for the stream as dslam_mesh_scene does, on synchronous and asynchronous engines.
+ * DSLAM_ERR_INVALID (the engine's previous mesh stays as it was): num_maps outside 1 .. DSLAM_MAX_RENDER_MAPS, a NULL
+ * scene, a scene of another engine or with another voxel_size / mu than scenes[0], a singular T_i, NULL
+ * out_num_triangles. */
+int dslam_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world,
+                           int num_maps, int max_triangles, int with_colour, int *out_num_triangles,
+                           int32_t *out_map_triangles);
+
 /* ---- depth tracker (ICP) ---------------------------------------------------------------------- */
 /* trackingController->Track(trackingState, view) (InfiniTamDriver.h:151-163, reached through
  * DenseSlam.cpp:200-206 when the reference runs without ORB-SLAM2 odometry): upstream InfiniTAM v2's
