@@ -215,6 +215,92 @@ def integrate(vox, block_pos, depth, rgba, M_d, intr, vs, mu, max_w, M_rgb=None,
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# A.8 the merge of a host copy into a resident block (upstream CombineVoxelInformation), in exact integer arithmetic
+# ---------------------------------------------------------------------------------------------------------------------
+# The merged value is trunc(q), q = (w_h v_h + w_d v_d) / (w_h + w_d): a rational with denominator w_h + w_d, computed
+# here from integers.  A float32 engine evaluates ((w_h (v_h / s) + w_d (v_d / s)) / (w_h + w_d)) s with s = 32767 (sdf)
+# or 255 (colour): every operand and intermediate has magnitude <= 1 before the weights scale it, and a term passes
+# five roundings of relative size u = 2^-24 on its way (v / s, the product with its weight, the sum, the quotient, the
+# product with s; the weights and their sum are exact), so the float32 result lies within 5 u s of q: 0.0098 for the sdf,
+# 7.6e-5 for a colour channel.  The bands below cover that (1 / 100 and 1 / 1000); only where an integer lies within the
+# band of q can a correct float32 merge land on the other side of the truncation: a *tie*.  Everywhere else the value is
+# exact.  The denominators are at most 510, so a colour q within 1e-3 of an integer IS that integer (1 / 510 > 1e-3).
+SDF_BAND_INV, CLR_BAND_INV = 100, 1000
+
+
+def _trunc_div(n, d):
+    """n / d truncated toward zero, integers, d > 0."""
+    return np.sign(n) * (np.abs(n) // d)
+
+
+def _merge_half(vh, wh, vd, wd, band_inv):
+    """One half of one merge on int64 arrays (values, their weights).  Returns (lo, hi, q, tie): the permitted results
+    are trunc(q - band) and trunc(q + band) (equal unless an integer lies inside the band), q as float64, and whether q
+    lies within the band of an integer."""
+    num, den = wh * vh + wd * vd, np.maximum(wh + wd, 1)
+    lo = _trunc_div(num * band_inv - den, den * band_inv)
+    hi = _trunc_div(num * band_inv + den, den * band_inv)
+    r = np.abs(num) % den  # |q|'s distance below / above the neighbouring integers, in units of 1 / den
+    tie = np.minimum(r, den - r) * band_inv <= den
+    return lo, hi, num / den, tie
+
+
+def combine_stored(host_block, device_block, max_w):
+    """SURVEY A.8's merge of a stored block into the resident one, voxel by voxel; the depth half (sdf, w_depth) and the
+    colour half (clr, w_color) independently.  A half whose host weight is 0 is left byte-identical; otherwise its
+    weight becomes min(w_host + w_device, max_w) and its value the weighted mean truncated toward zero.
+    Returns (lo, hi, info): two voxel arrays that agree in every weight (and the pad byte, which is the device's) and
+    hold, value by value, the two results a float32 evaluation may reach (lo == hi except at a tie).  info: the exact
+    quotients (`q_sdf`, `q_clr`), which halves merged (`merged_depth`, `merged_colour`) and the tie masks."""
+    h, d = np.asarray(host_block), np.asarray(device_block)
+    lo, hi = d.copy(), d.copy()
+    i64 = lambda a: a.astype(np.int64)
+    md, mc = h["w_depth"] != 0, h["w_color"] != 0
+    a, b, q_s, tie_s = _merge_half(i64(h["sdf"]), i64(h["w_depth"]), i64(d["sdf"]), i64(d["w_depth"]), SDF_BAND_INV)
+    w = np.minimum(i64(h["w_depth"]) + i64(d["w_depth"]), max_w)
+    for out, v in ((lo, np.minimum(a, b)), (hi, np.maximum(a, b))):
+        out["sdf"] = np.where(md, v, d["sdf"])
+        out["w_depth"] = np.where(md, w, d["w_depth"])
+    wh, wd = i64(h["w_color"])[..., None], i64(d["w_color"])[..., None]
+    a, b, q_c, tie_c = _merge_half(i64(h["clr"]), wh, i64(d["clr"]), wd, CLR_BAND_INV)
+    w = np.minimum(wh[..., 0] + wd[..., 0], max_w)
+    for out, v in ((lo, np.minimum(a, b)), (hi, np.maximum(a, b))):
+        out["clr"] = np.where(mc[..., None], v, d["clr"])
+        out["w_color"] = np.where(mc, w, d["w_color"])
+    info = dict(q_sdf=np.where(md, q_s, d["sdf"]), q_clr=np.where(mc[..., None], q_c, d["clr"]), merged_depth=md,
+                merged_colour=mc, tie_sdf=md & tie_s, tie_clr=mc[..., None] & tie_c)
+    return lo, hi, info
+
+
+def merge_tie_share(info):
+    """Ties among the merged values (one sdf and three colour channels per voxel, each counted where its half merged)."""
+    n = int(info["merged_depth"].sum()) + 3 * int(info["merged_colour"].sum())
+    return (int(info["tie_sdf"].sum()) + int(info["tie_clr"].sum())) / max(n, 1)
+
+
+def check_combined(got, lo, hi, info, what=""):
+    """`got` against combine_stored's answer: weights and pad exact, every value one of its permitted results (so a
+    non-tie value equals trunc(q) exactly and |got - q| <= 1 everywhere).  Returns the figures DESIGN 4c records."""
+    got = np.asarray(got)
+    for f in ("w_depth", "w_color", "_pad"):
+        bad = got[f] != lo[f]
+        assert not bad.any(), f"{what}: {f} differs in {int(bad.sum())} voxels, first got {got[f][bad][:4]}, want {lo[f][bad][:4]}"
+    out = {}
+    for f, q, tie in (("sdf", info["q_sdf"], info["tie_sdf"]), ("clr", info["q_clr"], info["tie_clr"])):
+        g = got[f].astype(np.int64)
+        bad = (g != lo[f]) & (g != hi[f])
+        assert not bad.any(), (f"{what}: {int(bad.sum())} {f} values are none of the permitted results; first got "
+                               f"{g[bad][:4]}, permitted {lo[f][bad][:4]} / {hi[f][bad][:4]}, q {q[bad][:4]}")
+        err = np.abs(g - q)
+        assert err.max(initial=0.0) <= 1.0, f"{what}: |got - q| = {err.max()} for {f}"
+        other = g != np.trunc(q).astype(np.int64)  # (a float64 quotient of integers truncates as the rational does)
+        dist = np.abs(q - np.round(q))
+        out[f] = dict(ties=int(tie.sum()), worst_err=float(err.max(initial=0.0)), off_truncation=int(other.sum()),
+                      worst_distance_off_truncation=float(dist[other].max(initial=0.0)))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # A.2 / A.7 reads, castRay, the shading normal
 # ---------------------------------------------------------------------------------------------------------------------
 def read_trilinear(m, p):

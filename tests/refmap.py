@@ -15,9 +15,12 @@ scratch (types, coordinates), a render state's type bytes and visible list, swap
 last_seen per voxel-block slot, the integer depth weights per voxel (Decay's predicate reads them; the caller feeds
 them from ref64.integrate), and the counters of dslam_get_stats these calls move.
 Of A.8 the integer part is in: which entries hold a host copy, its depth weights, the states, and which blocks
-swap-in merges (w = min(w_host + w_device, maxW)) and swap-out parks; that is what ProcessFrame and SlideWindow of a
-swapping scene need.  Out of the model: voxel values (sdf, colour) and so the merged sdf / colour, the transfer buffers,
-SaveToGlobalMemory, the defusion-ring calls, the batched re-integration, sharding, FindVisibleBlocks.
+swap-in merges (w = min(w_host + w_device, maxW)) and swap-out parks, in ProcessFrame, SlideWindow, the direct
+swap-in / swap-out calls and SaveToGlobalMemory (`save_to_global`).  Every merge and every park is also written to
+`events`, in order, so that a caller who carries voxel values (refmap_checks.Rig, with ref64.combine_stored) can move them
+the same way.  Both list rings are driven: q = 1 is the defusion ring of ProcessFrame(isDefusion), SlideWindowDefusionPart
+and DecayDefusionPart.  Out of the model: voxel values (sdf, colour), the transfer buffers, the batched re-integration,
+sharding, FindVisibleBlocks.
 """
 import numpy as np
 
@@ -230,6 +233,7 @@ class MapModel:
         self.has_stored = np.zeros(self.n_entries, bool)  # host store (swapping scenes): which entries hold a block,
         self.stored_w = np.zeros((self.n_entries, 512), np.uint8) if self.swapping else None  # and its depth weights
         self.last_swapped_in = self.last_swapped_out = 0
+        self.events = []  # ("merge" | "park", entry, slot) in the order they happen; the caller empties it
         self._reindex()
 
     def load(self, hash_table, alloc_list, last_free, excess_list, last_free_ex, weights=None):
@@ -401,12 +405,14 @@ class MapModel:
 
     def _merge_stored(self, t, slot):
         """CombineVoxelInformation's weights: where the host copy has a measurement, w = min(w_host + w_device, maxW)."""
+        self.events.append(("merge", t, slot))
         src, dst = self.stored_w[t].astype(np.int64), self.w[slot].astype(np.int64)
         self.w[slot] = np.where(src != 0, np.minimum(src + dst, self.max_w), dst).astype(np.uint8)
 
     def _park(self, t):
         """The block of entry t goes to the host store; the entry stays, its slot returns to the pool."""
         slot = int(self.hash["ptr"][t])
+        self.events.append(("park", t, slot))
         self.stored_w[t] = self.w[slot]
         self.has_stored[t] = True
         self.last_free += 1
@@ -429,6 +435,27 @@ class MapModel:
             self.swap_state[t] = 0
             self._park(int(t))
         self.last_swapped_out = len(out)
+
+    def save_to_global(self):
+        """SaveToGlobalMemory(scene), A.8's last line: nothing resident stays behind.  Every pending entry (state 1) is
+        merged, whatever the transfer size; the resident entries that never were visible since they got their block
+        (state 0) count as merged too, after taking in a host copy if they have one; then every resident entry is
+        parked, visible or not.  The call has no render state: type bytes and the visible list stay as they were."""
+        while (self.swap_state == 1).any():
+            self.swap_in()
+        fresh = np.nonzero((self.swap_state == 0) & (self.hash["ptr"] >= 0))[0]
+        with_copy = int(self.has_stored[fresh].sum())
+        for t in fresh:
+            if self.has_stored[t]:
+                self._merge_stored(int(t), int(self.hash["ptr"][t]))
+        self.swap_state[fresh] = 2
+        out = np.nonzero((self.swap_state == 2) & (self.hash["ptr"] >= 0))[0]
+        for t in out:
+            self.swap_state[t] = 0
+            self._park(int(t))
+        self.last_swapped_in, self.last_swapped_out = 0, len(out)
+        return dict(promoted=len(fresh), promoted_with_copy=with_copy, parked=len(out),
+                    parked_visible=int((self.visible_type[out] > 0).sum()))
 
     # -- DESIGN 5: batch release -----------------------------------------------------------------------------------------
     def release(self, batch):

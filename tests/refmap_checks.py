@@ -6,7 +6,14 @@ and the inputs, never from an engine.
 What is compared (exactly): the table bytes of every entry with ptr >= -1, ptr / offset of all entries, both free
 stacks up to their tops, visible ids, type bytes (as dslam_download_visible_types hands them out: without the pass'
 generation bit), swap states, last_seen, the allocation scratch (types; coordinates where a type is set), the depth
-weight of every voxel, and the counters of dslam_get_stats the modelled calls move."""
+weight of every voxel, and the counters of dslam_get_stats the modelled calls move.
+
+In a scene with host swapping the Rig also carries every voxel's sdf and colour, on the device and in the host store, as
+an interval [lo, hi] of permitted values: an integration leaves ref64.integrate's value give or take 1 LSB (the rule of
+ref64_checks), a merge takes the interval of ref64.combine_stored (exact unless a tie), a park moves a block to the host
+store byte for byte, and everything else leaves a voxel as it was.  After every call the engine's voxels and stored blocks
+must lie inside, and the Rig then takes the engine's bytes as the next call's inputs: a block no call touches is compared
+byte for byte, and a merge's inputs are what the engine held before the call."""
 import os
 
 import numpy as np
@@ -42,6 +49,13 @@ class Rig:
         self.m = refmap.MapModel(params, W, H)
         self.vox = np.repeat(EMPTY, self.m.nl * 512).reshape(self.m.nl, 512)
         self.max_w = params.max_w
+        if self.m.swapping:  # the upper ends of the value intervals (vox is the lower end), and the host store likewise
+            self.vox_hi = self.vox.copy()
+            self.stored = np.repeat(EMPTY, self.m.n_entries * 512).reshape(self.m.n_entries, 512)
+            self.stored_hi = self.stored.copy()
+        self.merges = dict(blocks=0, values=0, ties=0, exact_blocks=0, worst_err=dict(sdf=0.0, clr=0.0),
+                           off_truncation=dict(sdf=0, clr=0), worst_distance_off_truncation=dict(sdf=0.0, clr=0.0))
+        self._exact_merges = []
         self.samples = self.block_ties = self.step_tie_samples = self.vis_ties = self.gate_ties = 0
         half = params.mu / (2.0 * params.voxel_size)  # 2 |dir|: the step count is its ceil
         self.shipped_mu = abs(half - round(half)) < 0.1  # on the rounding edge: step ties are counted apart
@@ -66,8 +80,83 @@ class Rig:
             self.vox[s]["w_depth"] = w
             self.vox[s]["sdf"] = 0
             self.m.w[s] = w
+            if self.m.swapping:
+                self.vox_hi[s] = self.vox[s]
             if self.api is not None:
                 self.api.upload_voxel_blocks(self.scene, int(s), self.vox[s:s + 1])
+
+    def set_blocks(self, slots, blocks):
+        """upload_voxel_blocks: the given slots get the given voxels, every byte."""
+        for s, b in zip(slots, blocks):
+            self.vox[s] = b
+            self.m.w[s] = b["w_depth"]
+            if self.m.swapping:
+                self.vox_hi[s] = b
+            if self.api is not None:
+                self.api.upload_voxel_blocks(self.scene, int(s), self.vox[s:s + 1])
+
+    # -- voxel values in a swapping scene --------------------------------------------------------------------------------
+    def _sync(self, what):
+        """Before a call: the engine's voxels become the call's inputs (they were checked after the previous call)."""
+        if self.api is not None:
+            got = self.api.download_voxel_blocks(self.scene)
+            assert np.array_equal(got["w_depth"], self.m.w), f"{what}: depth weights before the call"
+            self.vox = got
+            if self.m.swapping:
+                self.vox_hi = got.copy()
+
+    def _integrated(self, slots, ref):
+        """ref64.integrate's result for the given slots: weights exact, sdf and colour to 1 LSB."""
+        self.vox[slots] = ref
+        self.m.w[slots] = ref["w_depth"]
+        if self.m.swapping:
+            lo, hi = ref.copy(), ref.copy()
+            lo["sdf"], hi["sdf"] = np.maximum(ref["sdf"].astype(np.int64) - 1, -32767), np.minimum(ref["sdf"].astype(np.int64) + 1, 32767)
+            lo["clr"], hi["clr"] = np.maximum(ref["clr"].astype(np.int64) - 1, 0), np.minimum(ref["clr"].astype(np.int64) + 1, 255)
+            self.vox[slots], self.vox_hi[slots] = lo, hi
+
+    def _move_values(self):
+        """Carry the values through the merges and parks the model logged, in their order."""
+        ev, self.m.events = self.m.events, []
+        if not self.m.swapping:
+            return
+        i = 0
+        while i < len(ev):
+            j = i
+            while j < len(ev) and ev[j][0] == ev[i][0]:
+                j += 1
+            t, s = np.array([e[1] for e in ev[i:j]]), np.array([e[2] for e in ev[i:j]])
+            if ev[i][0] == "merge":
+                exact = np.array_equal(self.stored[t], self.stored_hi[t]) and np.array_equal(self.vox[s], self.vox_hi[s])
+                lo, hi, info = ref64.combine_stored(self.stored[t], self.vox[s], self.max_w)
+                if not exact:
+                    hi = ref64.combine_stored(self.stored_hi[t], self.vox_hi[s], self.max_w)[1]
+                self.vox[s], self.vox_hi[s] = lo, hi
+                self.merges["blocks"] += len(s)
+                self.merges["values"] += int(info["merged_depth"].sum()) + 3 * int(info["merged_colour"].sum())
+                self.merges["ties"] += int(info["tie_sdf"].sum()) + int(info["tie_clr"].sum())
+                if exact:
+                    self._exact_merges.append((s, lo, hi, info))
+            else:
+                self.stored[t], self.stored_hi[t] = self.vox[s], self.vox_hi[s]
+                self.vox[s] = self.vox_hi[s] = EMPTY[0]
+                kept = []  # a block merged and parked by one call is checked in the host store, by its interval
+                for ms, lo, hi, info in self._exact_merges:
+                    k = ~np.isin(ms, s)
+                    if k.any():
+                        kept.append((ms[k], lo[k], hi[k], {n: v[k] for n, v in info.items()}))
+                self._exact_merges = kept
+            i = j
+
+    @staticmethod
+    def _inside(got, lo, hi, what):
+        for f in ("w_depth", "w_color", "_pad"):
+            assert np.array_equal(got[f], lo[f]), f"{what}: {f} differs in {int((got[f] != lo[f]).sum())} voxels"
+        for f in ("sdf", "clr"):
+            g = got[f].astype(np.int64)
+            bad = (g < lo[f]) | (g > hi[f])
+            assert not bad.any(), (f"{what}: {int(bad.sum())} {f} values outside the permitted interval; first got "
+                                   f"{g[bad][:4]}, permitted {lo[f][bad][:4]} .. {hi[f][bad][:4]}")
 
     # -- calls ---------------------------------------------------------------------------------------------------------
     def _count(self, info):
@@ -88,18 +177,14 @@ class Rig:
         self.compare(f"{what} allocate", scratch=True)
         return info
 
-    def process_frame(self, M, intr, what=""):
-        if self.api is not None:  # sdf / colour may be 1 LSB from ref64: re-read; the weights are the model's own
-            got = self.api.download_voxel_blocks(self.scene)
-            assert np.array_equal(got["w_depth"], self.m.w), f"{what}: depth weights before fusion"
-            self.vox = got
+    def process_frame(self, M, intr, what="", is_defusion=False):
+        self._sync(what)  # sdf / colour may be 1 LSB from ref64: re-read; the weights are the model's own
         info = self.m.allocate(self.depth, M, intr, False)
         self._count(info)
         ids, slots, pos = self.m.resident_visible()
         ref, _ = ref64.integrate(self.vox[slots], pos, self.depth, self.rgba, M, intr, self.m.vs, self.m.mu, self.max_w)
-        self.vox[slots] = ref
-        self.m.w[slots] = ref["w_depth"]
-        info["wrapped"] = self.m.push_visible_list(0)
+        self._integrated(slots, ref)
+        info["wrapped"] = self.m.push_visible_list(1 if is_defusion else 0)  # A.11: the flag only routes the list
         info["fused_blocks"] = len(slots)
         if self.m.swapping:  # ProcessFrame ends with swap-in and swap-out (A.8)
             self.m.swap_in()
@@ -107,21 +192,43 @@ class Rig:
             info.update(swapped_in=self.m.last_swapped_in, swapped_out=self.m.last_swapped_out)
             self._after_upkeep()
         if self.api is not None:
-            self.api.process_frame(self.scene, self.view, self.rs, M, intr)
-        self.compare(f"{what} process_frame", scratch=True)
+            self.api.process_frame(self.scene, self.view, self.rs, M, intr, is_defusion=is_defusion)
+        self.compare(f"{what} process_frame" + (" (defusion ring)" if is_defusion else ""), scratch=True)
+        return info
+
+    def deprocess_frame(self, M, intr, what=""):
+        """A.11 DeProcessFrame: a visible-list-only pass at the pose, then the inverse update; no list is queued, and a
+        swapping scene neither merges nor parks."""
+        self._sync(what)
+        info = self.m.allocate(self.depth, M, intr, True)
+        self._count(info)
+        ids, slots, pos = self.m.resident_visible()
+        ref, _ = ref64.integrate(self.vox[slots], pos, self.depth, self.rgba, M, intr, self.m.vs, self.m.mu, self.max_w,
+                                 deintegrate=True)
+        info["emptied_voxels"] = int(((ref["w_depth"] == 0) & (self.m.w[slots] > 0)).sum())
+        info["defused_blocks"] = int((ref["w_depth"] != self.m.w[slots]).any(axis=1).sum())
+        self._integrated(slots, ref)
+        if self.api is not None:
+            self.api.deprocess_frame(self.scene, self.view, self.rs, M, intr)
+        self.compare(f"{what} deprocess_frame", scratch=True)
         return info
 
     def _after_upkeep(self):
-        gone = (self.m.w == 0) & (self.vox["w_depth"] > 0)
-        self.vox[gone] = EMPTY[0]
-        self.vox["w_depth"] = self.m.w  # merged weights (the merged sdf / colour are re-read from an engine, or unused)
+        """Voxels the model reset (Decay) or moved away, and the values of the blocks it merged or parked."""
+        self._move_values()
+        for vox in (self.vox, self.vox_hi) if self.m.swapping else (self.vox,):
+            gone = (self.m.w == 0) & (vox["w_depth"] > 0)
+            vox[gone] = EMPTY[0]
+            if self.m.swapping:
+                assert np.array_equal(vox["w_depth"], self.m.w), "combine_stored's depth weights and the model's differ"
+            vox["w_depth"] = self.m.w
 
-    def decay(self, max_weight, min_age, force_all, what=""):
-        info = self.m.decay(max_weight, min_age, force_all)
+    def decay(self, max_weight, min_age, force_all, what="", defusion_part=False):
+        info = self.m.decay(max_weight, min_age, force_all, q=1 if defusion_part else 0)
         self._after_upkeep()
         if self.api is not None:
-            self.api.decay(self.scene, self.rs, max_weight, min_age, force_all)
-        self.compare(f"{what} decay({max_weight}, {min_age}, {force_all})")
+            self.api.decay(self.scene, self.rs, max_weight, min_age, force_all, defusion_part=defusion_part)
+        self.compare(f"{what} decay({max_weight}, {min_age}, {force_all}, defusion_part={defusion_part})")
         return info
 
     def slide_window(self, max_age, what=""):
@@ -132,9 +239,46 @@ class Rig:
         self.compare(f"{what} slide_window({max_age})")
         return info
 
+    def slide_window_defusion_part(self, max_age, max_size, what=""):
+        """SlideWindow's rule on the defusion ring until max_size lists remain; max_age is not used."""
+        info = self.m.slide_window(max_size, q=1)
+        self._after_upkeep()
+        if self.api is not None:
+            self.api.slide_window_defusion_part(self.scene, self.rs, max_age, max_size)
+        self.compare(f"{what} slide_window_defusion_part({max_age}, {max_size})")
+        return info
+
+    def swap_in(self, what=""):
+        self.m.swap_in()
+        self._after_upkeep()
+        if self.api is not None:
+            self.api.swap_in(self.scene, self.rs)
+        self.compare(f"{what} swap_in")
+        return dict(swapped_in=self.m.last_swapped_in)
+
+    def swap_out(self, what=""):
+        self.m.swap_out()
+        self._after_upkeep()
+        if self.api is not None:
+            self.api.swap_out(self.scene, self.rs)
+        self.compare(f"{what} swap_out")
+        return dict(swapped_out=self.m.last_swapped_out)
+
+    def flush(self, what=""):
+        info = self.m.save_to_global()
+        self._after_upkeep()
+        if self.api is not None:
+            self.api.save_to_global_memory(self.scene)
+        self.compare(f"{what} save_to_global_memory")
+        return info
+
     def reset(self):
         self.m.reset()
         self.vox[:] = EMPTY[0]
+        if self.m.swapping:
+            self.vox_hi[:] = EMPTY[0]
+            self.stored[:] = EMPTY[0]
+            self.stored_hi[:] = EMPTY[0]
         if self.api is not None:
             self.api.reset_scene(self.scene)
         self.compare("reset")  # the render state is not the scene's: its type bytes and list stay
@@ -143,6 +287,7 @@ class Rig:
     def compare(self, what, scratch=False, weights=True):
         self.calls += 1
         if self.api is None:
+            self._exact_merges = []
             return
         api, m = self.api, self.m
         what = f"call {self.calls} ({what})"
@@ -162,11 +307,17 @@ class Rig:
         assert np.array_equal(ty, m.visible_type), f"{what}: type bytes differ at {np.nonzero(ty != m.visible_type)[0][:8]}"
         if m.swapping:
             assert np.array_equal(api.download_swap_states(self.scene), m.swap_state), f"{what}: swap states differ"
-            for t in range(m.n_entries):  # the host store: which entries hold a copy, and its depth weights
+            held = []
+            for t in range(m.n_entries):  # the host store: which entries hold a copy, its depth weights, its bytes
                 has, blk = api.download_stored_block(self.scene, t)
                 assert has == bool(m.has_stored[t]), f"{what}: host copy of entry {t}: {has}, model {bool(m.has_stored[t])}"
                 if has:
                     assert np.array_equal(blk["w_depth"], m.stored_w[t]), f"{what}: stored weights of entry {t} differ"
+                    held.append(blk)
+            if held:
+                t, held = np.nonzero(m.has_stored)[0], np.stack(held)
+                self._inside(held, self.stored[t], self.stored_hi[t], f"{what}: stored blocks")
+                self.stored[t], self.stored_hi[t] = held, held
         assert np.array_equal(api.download_last_seen(self.scene), m.last_seen), f"{what}: last_seen differs"
         if scratch:
             ty, co = api.download_alloc_scratch(self.scene)
@@ -174,8 +325,21 @@ class Rig:
             sel = m.alloc_type > 0
             assert np.array_equal(co[sel], m.coords[sel]), f"{what}: block coordinates of the requests differ"
         if weights:
-            w = api.download_voxel_blocks(self.scene)["w_depth"]
+            got = api.download_voxel_blocks(self.scene)
+            w = got["w_depth"]
             assert np.array_equal(w, m.w), f"{what}: depth weights differ in {(w != m.w).any(axis=1).sum()} blocks"
+            if m.swapping:
+                self._inside(got, self.vox, self.vox_hi, f"{what}: voxel blocks")
+                for s, lo, hi, info in self._exact_merges:  # inputs known to the byte: the merge's own figures
+                    fig = ref64.check_combined(got[s], lo, hi, info, f"{what}: merged blocks")
+                    self.merges["exact_blocks"] += len(s)
+                    for f in ("sdf", "clr"):
+                        self.merges["worst_err"][f] = max(self.merges["worst_err"][f], fig[f]["worst_err"])
+                        self.merges["off_truncation"][f] += fig[f]["off_truncation"]
+                        self.merges["worst_distance_off_truncation"][f] = max(
+                            self.merges["worst_distance_off_truncation"][f], fig[f]["worst_distance_off_truncation"])
+                self.vox, self.vox_hi = got, got.copy()
+        self._exact_merges = []
 
     def finish(self):
         """The tie caps of the case, from the model's counts alone.  Returns the figures."""
@@ -572,9 +736,293 @@ def case_swapping_window(api, pkg, synth):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# A.8's merge on chosen voxels, the flush, the defusion ring
+# ---------------------------------------------------------------------------------------------------------------------
+def _const_block(sdf, wd, clr, wc, pad=0):
+    b = np.zeros(512, am.VOXEL_DTYPE)
+    b["sdf"], b["w_depth"], b["clr"], b["w_color"], b["_pad"] = sdf, wd, clr, wc, pad
+    return b
+
+
+def crafted_blocks(seed, k, max_w):
+    """(host, device): k voxel blocks for each side of a merge.  The first half is seeded-random over the full ranges
+    (sdf -32767 .. 32767, colour 0 .. 255, depth and colour weights drawn independently, host weights 1 .. max_w, device
+    weights 0 .. max_w, a random pad byte); the second half cycles through the edge rows, each filling a whole block so
+    that every lane and every 16-byte chunk of a lane sees it."""
+    rng = np.random.default_rng(seed)
+    n = k // 2
+    host, dev = np.zeros((k, 512), am.VOXEL_DTYPE), np.zeros((k, 512), am.VOXEL_DTYPE)
+    for b, lo in ((host, 1), (dev, 0)):
+        b["sdf"][:n] = rng.integers(-32767, 32768, (n, 512))
+        b["clr"][:n] = rng.integers(0, 256, (n, 512, 3))
+        b["w_depth"][:n] = rng.integers(lo, max_w + 1, (n, 512))
+        b["w_color"][:n] = rng.integers(lo, max_w + 1, (n, 512))
+        b["_pad"][:n] = rng.integers(0, 256, (n, 512))
+    c = lambda w: min(w, max_w)
+    half = max_w // 2
+    rows = [  # (host: sdf, w_depth, colour, w_color), (device: the same)
+        ((1234, 0, (9, 8, 7), 0), (-555, c(3), (1, 2, 3), c(2))),                    # host weight 0: nothing changes
+        ((-12345, c(5), (200, 100, 50), c(7)), (-20000, 0, (31, 32, 33), 0)),         # device weight 0
+        ((1000, max_w, (10, 250, 128), max_w), (-3001, max_w, (251, 11, 127), max_w)),  # both at max_w
+        ((20001, half, (3, 60, 255), half), (-7, max_w - half, (254, 61, 0), max_w - half)),          # sum == max_w
+        ((20001, half + 1, (3, 60, 255), half + 1), (-7, max_w - half, (254, 61, 0), max_w - half)),  # sum == max_w + 1
+        ((777, c(3), (77, 77, 77), c(2)), (777, c(2), (77, 77, 77), c(3))),           # equal values: q is an integer
+        ((32767, c(3), (255, 255, 255), c(3)), (32767, c(2), (255, 255, 255), c(1))),  # +1 on both sides; 255 on 255
+        ((-32767, c(2), (0, 0, 0), c(3)), (-32767, c(3), (255, 255, 255), c(2))),      # -1 on both sides; 0 on 255
+        ((32767, c(2), (255, 0, 255), c(1)), (-32767, c(3), (0, 255, 0), c(3))),       # +1 against -1
+        ((4321, 0, (90, 80, 70), c(3)), (-99, c(2), (10, 20, 31), c(2))),             # depth half idle, colour half merges
+        ((4321, c(3), (90, 80, 70), 0), (-99, c(2), (10, 20, 31), c(2))),             # the reverse
+        ((1234, 0, (9, 8, 7), 0), (-4321, 0, (50, 60, 70), 0)),                       # no weight anywhere, values kept
+    ]
+    for i in range(n, k):
+        h, d = rows[(i - n) % len(rows)]
+        host[i], dev[i] = _const_block(*h, pad=(17 * i) & 255), _const_block(*d, pad=(29 * i + 5) & 255)
+        if h[1] == 0 and d[1] > 0:  # an idle depth half must hand back EVERY device value: one per voxel, both signs
+            dev[i]["sdf"] = (np.arange(512) * 127 + 61 * i) % 65535 - 32767
+        if h[3] == 0 and d[3] > 0:
+            dev[i]["clr"] = ((np.arange(512)[:, None] * np.array([1, 3, 7]) + 11 * i) % 256)
+    return host, dev
+
+
+def crafted_reach(host, dev, max_w):
+    """How many voxels of the crafted pair reach each edge row (from the data, not from how it was built)."""
+    h, d = host.reshape(-1), dev.reshape(-1)
+    hw, dw, hc, dc = (a.astype(np.int64) for a in (h["w_depth"], d["w_depth"], h["w_color"], d["w_color"]))
+    both = (hw > 0) & (dw > 0)
+    allc = lambda a, v: (a["clr"] == v).all(axis=1)
+    return dict(host_weight_0=int(((hw == 0) & (hc == 0) & (dw > 0) & (dc > 0) & (h["sdf"] != 32767) & (h["sdf"] != d["sdf"])).sum()),
+                no_weight_anywhere=int(((hw == 0) & (hc == 0) & (dw == 0) & (dc == 0) & (d["sdf"] != 32767) & (d["clr"] != 0).all(axis=1)).sum()),
+                device_weight_0=int(((dw == 0) & (hw > 0)).sum()), device_colour_weight_0=int(((dc == 0) & (hc > 0)).sum()),
+                both_at_max=int(((hw == max_w) & (dw == max_w) & (hc == max_w) & (dc == max_w)).sum()),
+                sum_is_max=int((both & (hw + dw == max_w)).sum()), sum_is_max_plus_1=int((both & (hw + dw == max_w + 1)).sum()),
+                colour_sum_is_max=int(((hc > 0) & (dc > 0) & (hc + dc == max_w)).sum()),
+                colour_sum_is_max_plus_1=int(((hc > 0) & (dc > 0) & (hc + dc == max_w + 1)).sum()),
+                clamped=int((both & (hw + dw > max_w)).sum()),
+                equal_sdf=int((both & (h["sdf"] == d["sdf"]) & (np.abs(h["sdf"]) < 32767)).sum()),
+                plus_on_plus=int((both & (h["sdf"] == 32767) & (d["sdf"] == 32767)).sum()),
+                minus_on_minus=int((both & (h["sdf"] == -32767) & (d["sdf"] == -32767)).sum()),
+                plus_on_minus=int((both & (h["sdf"] == 32767) & (d["sdf"] == -32767)).sum()),
+                colour_255_on_255=int(((hc > 0) & (dc > 0) & allc(h, 255) & allc(d, 255)).sum()),
+                colour_0_on_255=int(((hc > 0) & (dc > 0) & allc(h, 0) & allc(d, 255)).sum()),
+                depth_idle_colour_merges=int(((hw == 0) & (hc > 0)).sum()), colour_idle_depth_merges=int(((hw > 0) & (hc == 0)).sum()),
+                unequal_weights=int(((hw != hc) & (hw > 0) & (hc > 0)).sum()))
+
+
+def case_crafted_merge(api, pkg, synth, max_w, K=64):
+    """A.8's merge with both sides chosen by the test: K blocks are overwritten with the host-side voxels and parked by
+    ProcessFrame's swap-out, come back through an allocation pass, are overwritten with the device-side voxels and merged
+    by a direct swap-in, and are parked again by a direct swap-out; every voxel against ref64.combine_stored."""
+    host, dev = crafted_blocks(400 + max_w, K, max_w)
+    reach = crafted_reach(host, dev, max_w)
+    assert all(v >= 512 for v in reach.values()), reach
+    lo, hi, info = ref64.combine_stored(host, dev, max_w)
+    rnd = {k: v[:K // 2] for k, v in info.items()}
+    share = ref64.merge_tie_share(rnd)
+    if max_w == 100:  # the cap for weights up to 100, from the reference alone
+        assert share <= 0.08, share
+    out = dict(reach=reach, tie_share_random_half=share, tie_share_all=ref64.merge_tie_share(info))
+    # the reference against itself where the answer is known without it
+    assert np.array_equal(lo[host["w_depth"] == 0]["sdf"], dev[host["w_depth"] == 0]["sdf"])
+    z = (dev["w_depth"] == 0) & (host["w_depth"] > 0)
+    toward_zero = host[z]["sdf"] - np.sign(host[z]["sdf"])  # q is the host's value, an integer: a tie on its inner side
+    assert np.array_equal(np.where(host[z]["sdf"] > 0, hi[z]["sdf"], lo[z]["sdf"]), host[z]["sdf"])
+    assert np.array_equal(np.where(host[z]["sdf"] > 0, lo[z]["sdf"], hi[z]["sdf"]), toward_zero)
+    assert np.array_equal(lo[z]["w_depth"], host[z]["w_depth"])
+
+    rig, wl = _fused_rig(api, pkg, synth, [0], use_swapping=1, num_buckets=0x80, max_w=max_w)
+    _, _, M0 = wl.frame(0)
+    rgba1, mm1, M1 = wl.frame(120)
+    # (1) K visible entries that the second pose does not keep
+    ids, slots, pos = rig.m.resident_visible()
+    _, enl = refmap.block_visibility(pos, M1, wl.intr, rig.m.vs, wl.W, wl.H)
+    pick = np.nonzero(~enl)[0]
+    assert len(pick) >= K, len(pick)
+    pick = pick[np.linspace(0, len(pick) - 1, K).astype(np.int64)]
+    ents, first_slots = ids[pick], slots[pick]
+    rig.set_blocks(first_slots, host)
+    untouched = rig.vox.copy()
+    # (2) the camera turns away: ProcessFrame's swap-out parks them, byte for byte, and resets their slots
+    rig.frame(rgba1, mm1)
+    rig.process_frame(M1, wl.intr, "crafted: turned away")
+    assert (rig.m.hash["ptr"][ents] == -1).all() and rig.m.has_stored[ents].all() and (rig.m.swap_state[ents] == 0).all()
+    assert rig.stored[ents].tobytes() == host.tobytes() and rig.stored_hi[ents].tobytes() == host.tobytes()
+    assert (rig.vox[first_slots] == EMPTY[0]).all()
+    if api is not None:
+        for t, b in zip(ents, host):
+            has, blk = api.download_stored_block(rig.scene, int(t))
+            assert has and blk.tobytes() == b.tobytes(), f"stored block of entry {t} is not the block that was parked"
+        assert (api.download_voxel_blocks(rig.scene)[first_slots] == EMPTY[0]).all(), "a vacated slot is not empty"
+    # (3) back at the first pose with an allocation pass alone: re-allocated, pending
+    rgba0, mm0, _ = wl.frame(0)
+    rig.frame(rgba0, mm0)
+    a = rig.allocate(M0, wl.intr, what="crafted: back")
+    new_slots = rig.m.hash["ptr"][ents].astype(np.int64)
+    assert (new_slots >= 0).all() and (rig.m.swap_state[ents] == 1).all() and a["reallocated"] >= K, a
+    rig.set_blocks(new_slots, dev)
+    before = rig.vox.copy()
+    stored_before = rig.stored.copy()
+    rig.swap_in("crafted")
+    assert (rig.m.swap_state[ents] == 2).all() and rig.m.last_swapped_in >= K
+    assert np.array_equal(rig.stored, stored_before)
+    others = np.setdiff1d(np.arange(rig.m.nl), rig.m.hash["ptr"][(rig.m.hash["ptr"] >= 0) & rig.m.has_stored])
+    assert np.array_equal(rig.vox[others], before[others]) and len(others) >= 64
+    if api is not None:
+        got = api.download_voxel_blocks(rig.scene)
+        out["figures"] = ref64.check_combined(got[new_slots], lo, hi, info, f"crafted merge, max_w {max_w}")
+        out["figures_random_half"] = ref64.check_combined(got[new_slots[:K // 2]], lo[:K // 2], hi[:K // 2], rnd)
+        assert got[others].tobytes() == before[others].tobytes(), "a block outside the merge changed"
+        for t, b in zip(ents, host):
+            assert api.download_stored_block(rig.scene, int(t))[1].tobytes() == b.tobytes(), "swap-in changed a stored copy"
+        merged = got[new_slots]
+    else:
+        merged = None
+    # (4) away again, an allocation pass and a direct swap-out: the stored copy is the merged block now
+    rig.frame(rgba1, mm1)
+    rig.allocate(M1, wl.intr, what="crafted: away again")
+    rig.swap_out("crafted")
+    assert (rig.m.hash["ptr"][ents] == -1).all() and rig.m.last_swapped_out >= K
+    if api is not None:
+        for t, b in zip(ents, merged):
+            assert api.download_stored_block(rig.scene, int(t))[1].tobytes() == b.tobytes(), \
+                f"entry {t}: the second park did not refresh the stored copy"
+    out.update(merges=rig.merges, ties=rig.finish())
+    return out
+
+
+def case_flush(api, pkg, synth):
+    """SaveToGlobalMemory on a scene with visible blocks, pending entries, and resident entries in state 0 with and
+    without a host copy; then frames that re-allocate and merge what was flushed, a second flush (the stored copies are
+    refreshed), Decay and SlideWindow."""
+    rig, wl = _fused_rig(api, pkg, synth, [0], use_swapping=1, num_buckets=0x80)
+    m = rig.m
+    # resident entries in state 0 without a host copy: the table of a map, loaded into a scene that was reset
+    table = (m.hash.copy(), m.alloc_list.copy(), m.last_free, m.excess_list.copy(), m.last_free_ex)
+    rig.reset()
+    rig.load(*table)
+    slots = m.hash["ptr"][m.hash["ptr"] >= 0]
+    rig.set_weights(slots[0::2], 3)
+    f0 = rig.flush("never visible")
+    assert f0["promoted"] == len(slots) >= 100 and f0["promoted_with_copy"] == 0 and f0["parked"] == len(slots), f0
+    for i in (0, 40, 80):  # every block comes back and takes its copy in
+        rgba, mm, M = wl.frame(i)
+        rig.frame(rgba, mm)
+        rig.process_frame(M, wl.intr, f"flush case, frame {i}")
+    # resident entries in state 0 with a host copy: parked entries handed a block behind the engine's back
+    h, al, lf = m.hash.copy(), m.alloc_list.copy(), m.last_free
+    parked = np.nonzero((h["ptr"] == -1) & m.has_stored & (m.swap_state == 0))[0][::2]
+    for t in parked:
+        h["ptr"][t] = al[lf]
+        lf -= 1
+    rig.load(h, al, lf, m.excess_list, m.last_free_ex)
+    give = m.hash["ptr"][parked]
+    rig.set_weights(give[0::2], 3)
+    rig.set_weights(give[1::2], m.max_w)
+    # pending entries: an allocation pass at an earlier pose re-allocates parked blocks and leaves them in state 1
+    rgba, mm, M = wl.frame(40)
+    rig.frame(rgba, mm)
+    a = rig.allocate(M, wl.intr, what="flush: pending")
+    pending = int(((m.swap_state == 1) & m.has_stored & (m.hash["ptr"] >= 0)).sum())
+    resident = int((m.hash["ptr"] >= 0).sum())
+    f = rig.flush("first")
+    assert pending >= 30 and f["promoted_with_copy"] >= 20, (pending, f, a)
+    assert f["parked"] == resident and f["parked_visible"] >= 30 and not (m.hash["ptr"] >= 0).any(), f
+    assert m.last_free == m.nl - 1 and not (m.swap_state != 0).any()
+    listed_without_block = int((m.hash["ptr"][m.visible_ids] == -1).sum())
+    assert listed_without_block >= 30  # the render state was not touched: the next pass finds these entries listed
+    reach = dict(never_visible=f0, pending=pending, first=f, listed_without_block=listed_without_block)
+    back = rig.process_frame(M, wl.intr, "after the flush")
+    assert back["reallocated"] >= 30 and back["swapped_in"] >= 30 and back["retested"] >= 10, back
+    rgba, mm, M = wl.frame(80)
+    rig.frame(rgba, mm)
+    rig.process_frame(M, wl.intr, "after the flush, turned")
+    f2 = rig.flush("second")
+    assert f2["parked"] >= 30 and f2["promoted"] == 0, f2
+    rgba, mm, M = wl.frame(60)
+    rig.frame(rgba, mm)
+    again = rig.process_frame(M, wl.intr, "after the second flush")
+    d = rig.decay(1, 0, True, "flush case")
+    s = rig.slide_window(1, "flush case")
+    s0 = rig.slide_window(0, "flush case")
+    assert again["reallocated"] >= 30 and d["candidates"] >= 30 and s["parked"] + s0["parked"] >= 30, (again, d, s, s0)
+    rig.flush("nothing resident")
+    assert m.last_swapped_out == 0
+    reach.update(second=f2, reallocated=back["reallocated"] + again["reallocated"], merges=rig.merges)
+    assert rig.merges["blocks"] >= 100, rig.merges
+    return dict(reach=reach, ties=rig.finish())
+
+
+def case_defusion_ring(api, pkg, synth, swapping, first_ring):
+    """The defusion ring (A.11): keyframes are fused, some are de-integrated and fused again at perturbed
+    poses with isDefusion, so that their lists go to ring 1; then one ring is emptied (`first_ring`), the other one is
+    decayed and trimmed, list by list, and emptied as well.  A block both rings hold must outlive either."""
+    rig, wl = _fused_rig(api, pkg, synth, [], use_swapping=int(swapping), num_buckets=0x80)
+    m = rig.m
+    keyframes = [0, 10, 20, 30, 40, 50]
+    for i in keyframes:
+        rgba, mm, M = wl.frame(i)
+        rig.frame(rgba, mm)
+        rig.process_frame(M, wl.intr, f"keyframe {i}")
+    defused = 0
+    for k, i in enumerate((10, 30, 50, 20)):
+        rgba, mm, M = wl.frame(i)
+        rig.frame(rgba, mm)
+        defused += rig.deprocess_frame(M, wl.intr, f"keyframe {i}")["defused_blocks"]
+        rig.process_frame(turned(synth, wl, i, 0.05 * (k + 1), -0.04 * (k + 1)), wl.intr, f"keyframe {i} again", is_defusion=True)
+    ring = [set().union(*m.lists[q].values()) for q in (0, 1)]
+    reach = dict(only_fusion=len(ring[0] - ring[1]), only_defusion=len(ring[1] - ring[0]), both=len(ring[0] & ring[1]),
+                 defused_blocks=defused)
+    assert reach["only_defusion"] >= 30 and reach["both"] >= 30 and defused >= 100, reach
+    # (a swapping scene has parked what left the view: every block still resident was listed by a re-fusion as well)
+    assert reach["only_fusion"] >= (0 if swapping else 30), reach
+    assert m.stats()["fusion_fifo_len"] == 6 and m.stats()["defusion_fifo_len"] == 4
+    held = lambda: {int(s) for s in m.hash["ptr"][m.hash["ptr"] >= 0]}
+    both = ring[0] & ring[1] & held()
+    a = rig.decay(1, 1, False, "defusion ring, aged lists", defusion_part=True)
+    assert a["candidates"] >= 30, a
+    if first_ring == 0:
+        w = rig.slide_window(2, "fusion ring to 2")
+        w0 = rig.slide_window(0, "fusion ring to 0")
+        gone = w["only_in_popped"] + w0["only_in_popped"]
+        assert gone >= (0 if swapping else 30) and m.stats()["fusion_fifo_len"] == 0 and m.stats()["defusion_fifo_len"] == 4
+        survivors = {s for s in both if m.referenced(s)} & held()
+        assert len(survivors) >= 30 and all(any(s in l for l in m.lists[1].values()) for s in survivors), len(survivors)
+        b = rig.decay(1, 0, True, "defusion ring, sweep", defusion_part=True)
+        t = rig.slide_window_defusion_part(6, 3, "to 3")
+        t1 = rig.slide_window_defusion_part(0, 1, "to 1")
+        assert t["pops"] == 1 and t1["pops"] == 2 and m.stats()["defusion_fifo_len"] == 1
+        t0 = rig.slide_window_defusion_part(6, 0, "to 0")
+    else:
+        t = rig.slide_window_defusion_part(6, 3, "to 3")
+        t1 = rig.slide_window_defusion_part(0, 1, "to 1")
+        assert t["pops"] == 1 and t1["pops"] == 2 and m.stats()["defusion_fifo_len"] == 1 and m.stats()["fusion_fifo_len"] == 6
+        t0 = rig.slide_window_defusion_part(6, 0, "to 0")
+        gone = t["only_in_popped"] + t1["only_in_popped"] + t0["only_in_popped"]
+        assert gone >= 30 and m.stats()["defusion_fifo_len"] == 0
+        survivors = {s for s in both if m.referenced(s)} & held()
+        assert len(survivors) >= 30 and all(any(s in l for l in m.lists[0].values()) for s in survivors), len(survivors)
+        b = rig.decay(1, 0, True, "fusion ring left, sweep", defusion_part=True)
+        rig.slide_window(2, "fusion ring to 2")
+        rig.slide_window(0, "fusion ring to 0")
+    assert m.stats()["fusion_fifo_len"] == 0 and m.stats()["defusion_fifo_len"] == 0
+    if swapping:
+        assert not (m.hash["ptr"] >= 0).any() and m.has_stored.sum() >= 100  # every block parked, every entry kept
+    else:
+        assert not (m.hash["ptr"] >= -1).any() and m.last_free == m.nl - 1  # every block released
+    reach.update(survivors=len(survivors), left_with_first_ring=gone, slid=m.slid, merges=rig.merges["blocks"])
+    # a frame afterwards: the stacks, the table and (swapping) the host store are used as the calls left them
+    rgba, mm, M = wl.frame(20)
+    rig.frame(rgba, mm)
+    rig.process_frame(M, wl.intr, "afterwards")
+    return dict(reach=reach, ties=rig.finish())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # seeded sequences
 # ---------------------------------------------------------------------------------------------------------------------
-def seeds(default_count=12):
+FIRST_NEW_SEED = 12  # seeds below it run exactly the sequences they always ran
+
+
+def seeds(default_count=18):
     spec = os.environ.get("DSLAM_MAPMODEL_SEEDS")
     if spec:
         first, count = (int(v) for v in spec.split(":"))
@@ -582,34 +1030,92 @@ def seeds(default_count=12):
     return list(range(default_count))
 
 
-def run_sequence(api, pkg, synth, seed, n_calls=30, mu_vox=MU_OFF):
+def run_sequence(api, pkg, synth, seed, n_calls=30, mu_vox=MU_OFF, script=None, swapping=None):
+    """Seeds from FIRST_NEW_SEED on (and scripted sequences) also draw the defusion-ring calls, and every third of them
+    runs on a scene with host swapping, where the direct swap calls and the flush join the mix.  What is new is drawn
+    from a stream of its own (`xr`), so the calls and arguments of the older seeds are what they were."""
     rng = np.random.default_rng(1000 + seed)
+    xr = np.random.default_rng(77000 + seed)
+    new = seed >= FIRST_NEW_SEED or script is not None
+    if swapping is None:
+        swapping = new and seed % 3 == 0
     W, H = 96, 72
     wl = synth.s_tiny(W, H)
+    kw = dict(use_swapping=1) if swapping else {}
     rig = Rig(api, pkg, scene_params(pkg, mu_vox=mu_vox, num_buckets=int(rng.choice([0x80, 0x100, 0x400])),
                                      num_local_blocks=int(rng.choice([0x300, 0x600, 0x1000])),
-                                     num_excess=int(rng.choice([0x80, 0x400, 0x1000])), history_words=1), W, H)
-    log = []
+                                     num_excess=int(rng.choice([0x80, 0x400, 0x1000])), history_words=1, **kw), W, H)
+    extra = ["refuse"] * 3 + ["slide_defusion", "decay_defusion"] + (["swap_in", "swap_out", "flush"] * 2 if swapping else [])
+    log, infos, fused = [], [], []
     frame = int(rng.integers(0, 180))
-    for _ in range(n_calls):
+    for k in range(len(script) if script is not None else n_calls):
         op = rng.choice(["frame"] * 6 + ["allocate"] * 2 + ["decay_sweep"] * 2 + ["decay_aged"] * 2 + ["slide"] * 2 + ["reset"])
+        if script is not None:
+            op = script[k]
+        elif new and xr.random() < 0.45:
+            op = xr.choice(extra)
+        info = None
         if op in ("frame", "allocate"):
             frame += int(rng.integers(1, 12))
             rgba, mm, _ = wl.frame(frame)
             rig.frame(rgba, mm)
             M = turned(synth, wl, frame, float(rng.uniform(-0.2, 0.2)), float(rng.uniform(-0.15, 0.15)))
             if op == "frame":
-                rig.process_frame(M, wl.intr, f"seed {seed}")
+                info = rig.process_frame(M, wl.intr, f"seed {seed}")
+                fused.append((frame, M))
             else:
-                rig.allocate(M, wl.intr, only=bool(rng.integers(0, 2)), what=f"seed {seed}")
+                info = rig.allocate(M, wl.intr, only=bool(rng.integers(0, 2)), what=f"seed {seed}")
         elif op == "reset":
             rig.reset()
+            fused = []
         elif op == "slide":
-            rig.slide_window(int(rng.integers(0, 5)), f"seed {seed}")
+            info = rig.slide_window(int(rng.integers(0, 5)), f"seed {seed}")
+        elif op in ("decay_sweep", "decay_aged"):
+            info = rig.decay(int(rng.choice([1, 2, 255])), int(rng.integers(0, 4)), op == "decay_sweep", f"seed {seed}")
+        elif op == "refuse":  # online correction's step: a fused keyframe leaves the map and comes back at a corrected pose
+            if fused:
+                j = int(xr.integers(0, len(fused)))
+                f, M = fused[j]
+                rgba, mm, _ = wl.frame(f)
+                rig.frame(rgba, mm)
+                rig.deprocess_frame(M, wl.intr, f"seed {seed}")
+                M = turned(synth, wl, f, float(xr.uniform(-0.2, 0.2)), float(xr.uniform(-0.15, 0.15)))
+                info = rig.process_frame(M, wl.intr, f"seed {seed}", is_defusion=True)
+                fused[j] = (f, M)
+        elif op == "slide_defusion":
+            info = rig.slide_window_defusion_part(int(xr.integers(0, 5)), int(xr.integers(0, 4)), f"seed {seed}")
+        elif op == "decay_defusion":
+            info = rig.decay(int(xr.choice([1, 2, 255])), int(xr.integers(0, 3)), bool(xr.integers(0, 2)), f"seed {seed}",
+                             defusion_part=True)
+        elif op == "swap_in":
+            info = rig.swap_in(f"seed {seed}")
+        elif op == "swap_out":
+            info = rig.swap_out(f"seed {seed}")
+        elif op == "flush":
+            info = rig.flush(f"seed {seed}")
         else:
-            rig.decay(int(rng.choice([1, 2, 255])), int(rng.integers(0, 4)), op == "decay_sweep", f"seed {seed}")
-        log.append(op)
-    return dict(ops=log, decayed=rig.m.decayed, slid=rig.m.slid, ties=rig.finish())
+            raise ValueError(op)
+        log.append(str(op))
+        infos.append(info)
+    return dict(ops=log, infos=infos, swapping=bool(swapping), decayed=rig.m.decayed, slid=rig.m.slid, merges=rig.merges,
+                ties=rig.finish())
+
+
+FLUSH_SCRIPT = ["frame", "frame", "frame", "flush", "frame", "frame", "decay_sweep", "slide", "frame", "allocate", "swap_in",
+                "flush", "frame", "refuse", "swap_out", "slide_defusion", "frame"]
+
+
+def case_flush_sequence(api, pkg, synth):
+    """A scripted sequence at the sequences' size: a flush followed by frames that re-allocate and merge the flushed
+    blocks, a Decay and a SlideWindow, then a second flush behind a direct swap-in."""
+    out = run_sequence(api, pkg, synth, 2, script=FLUSH_SCRIPT, swapping=True)
+    i = FLUSH_SCRIPT.index("flush")
+    assert out["infos"][i]["parked"] >= 100 and out["infos"][i]["parked_visible"] >= 50, out["infos"][i]
+    after = out["infos"][i + 1]
+    assert after["reallocated"] >= 50 and after["swapped_in"] >= 50, after
+    assert out["infos"][i + 3]["candidates"] >= 30 and out["infos"][i + 4]["parked"] >= 30, out["infos"][i + 3:i + 5]
+    assert out["merges"]["blocks"] >= 200, out["merges"]
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------

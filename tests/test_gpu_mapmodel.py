@@ -63,6 +63,26 @@ def test_swapping_scene_window_and_decay(pkg, gpu, synth):
     print(mc.case_swapping_window(gpu, pkg, synth)["reach"])
 
 
+@pytest.mark.parametrize("max_w", [100, 4, 255])
+def test_crafted_merge(pkg, gpu, synth, max_w):
+    out = mc.case_crafted_merge(gpu, pkg, synth, max_w)
+    print(out["tie_share_random_half"], out["tie_share_all"], out["figures"], out["figures_random_half"])
+
+
+def test_flush_to_the_host_store(pkg, gpu, synth):
+    print(mc.case_flush(gpu, pkg, synth)["reach"])
+
+
+@pytest.mark.parametrize("first_ring", [0, 1])
+@pytest.mark.parametrize("swapping", [False, True])
+def test_defusion_ring(pkg, gpu, synth, swapping, first_ring):
+    print(mc.case_defusion_ring(gpu, pkg, synth, swapping, first_ring)["reach"])
+
+
+def test_sequence_flush_then_merge(pkg, gpu, synth):
+    print(mc.case_flush_sequence(gpu, pkg, synth)["merges"])
+
+
 @pytest.mark.parametrize("seed", mc.seeds())
 def test_sequence(pkg, gpu, synth, seed):
     print(mc.run_sequence(gpu, pkg, synth, seed)["ties"])

@@ -1,4 +1,4 @@
-"""The map model of refmap.py (SURVEY.md A.1, A.4, A.6, A.9, A.10; DESIGN.md section 5) against the CPU oracle: check
+"""The map model of refmap.py (SURVEY.md A.1, A.4, A.6, A.8 - A.11; DESIGN.md section 5) against the CPU oracle: check
 bodies in refmap_checks.py, shared with test_gpu_mapmodel.py.  Plus what needs no engine: the reach counts and tie caps
 of every case from the model alone, and the model's own building blocks against hand-derived answers."""
 import ctypes
@@ -66,6 +66,26 @@ def test_swapping_scene_window_and_decay(pkg, oracle, synth):
     print(mc.case_swapping_window(oracle, pkg, synth)["reach"])
 
 
+@pytest.mark.parametrize("max_w", [100, 4, 255])
+def test_crafted_merge(pkg, oracle, synth, max_w):
+    out = mc.case_crafted_merge(oracle, pkg, synth, max_w)
+    print(out["tie_share_random_half"], out["tie_share_all"], out["figures"], out["figures_random_half"])
+
+
+def test_flush_to_the_host_store(pkg, oracle, synth):
+    print(mc.case_flush(oracle, pkg, synth)["reach"])
+
+
+@pytest.mark.parametrize("first_ring", [0, 1])
+@pytest.mark.parametrize("swapping", [False, True])
+def test_defusion_ring(pkg, oracle, synth, swapping, first_ring):
+    print(mc.case_defusion_ring(oracle, pkg, synth, swapping, first_ring)["reach"])
+
+
+def test_sequence_flush_then_merge(pkg, oracle, synth):
+    print(mc.case_flush_sequence(oracle, pkg, synth)["merges"])
+
+
 @pytest.mark.parametrize("seed", mc.seeds())
 def test_sequence(pkg, oracle, synth, seed):
     print(mc.run_sequence(oracle, pkg, synth, seed)["ties"])
@@ -102,9 +122,68 @@ def test_reach_and_tie_caps_from_the_model_alone(pkg, synth):
         mc.case_release(None, pkg, synth, seed)
     mc.case_slide_window(None, pkg, synth)
     mc.case_swapping_window(None, pkg, synth)
-    for seed in mc.seeds():
+    for seed in [s for s in mc.seeds() if s < mc.FIRST_NEW_SEED]:  # (the later seeds: in the test below)
         mc.run_sequence(None, pkg, synth, seed)
     mc.run_sequence(None, pkg, synth, 3, mu_vox=mc.MU_SHIPPED)
+
+
+def test_reach_of_the_swapping_and_defusion_cases_from_the_model_alone(pkg, synth):
+    """The crafted merge's edge rows (each in >= 512 voxels) and tie cap, the flush's and the defusion ring's reach
+    floors, and what the new seeds draw: no engine in the loop."""
+    for max_w in (100, 4, 255):
+        out = mc.case_crafted_merge(None, pkg, synth, max_w)
+        assert min(out["reach"].values()) >= 512
+    mc.case_flush(None, pkg, synth)
+    for swapping in (False, True):
+        for first_ring in (0, 1):
+            mc.case_defusion_ring(None, pkg, synth, swapping, first_ring)
+    mc.case_flush_sequence(None, pkg, synth)
+    ops, merged = {}, 0
+    for seed in [s for s in mc.seeds() if s >= mc.FIRST_NEW_SEED]:
+        out = mc.run_sequence(None, pkg, synth, seed)
+        assert out["swapping"] == (seed % 3 == 0)
+        merged += out["merges"]["blocks"]
+        for op in out["ops"]:
+            ops[op] = ops.get(op, 0) + 1
+    if mc.seeds() == list(range(18)):
+        assert all(ops.get(op, 0) >= 3 for op in ("refuse", "slide_defusion", "decay_defusion", "swap_in", "swap_out", "flush")), ops
+        assert merged >= 300, merged
+
+
+def test_combine_stored_by_hand():
+    """SURVEY A.8's merge on voxels worked out by hand."""
+    import analytic_maps as am
+    import ref64
+    h, d = np.zeros(6, am.VOXEL_DTYPE), np.zeros(6, am.VOXEL_DTYPE)
+    #            sdf   w  colour        w
+    rows = [((100, 1, (10, 20, 30), 1), (-101, 1, (11, 20, 33), 3)),    # -1/2 -> 0;   (10+33)/4 = 10.75, 20, (30+99)/4 = 32.25
+            ((-7, 3, (0, 0, 255), 2), (-8, 1, (255, 0, 0), 2)),         # -29/4 = -7.25 -> -7;  127.5 -> 127, 0, 127
+            ((5, 0, (1, 2, 3), 0), (9, 2, (4, 5, 6), 1)),               # no host measurement: nothing changes
+            ((32767, 200, (255, 255, 255), 200), (32767, 100, (255, 255, 255), 90)),  # weights clamp at 255
+            ((300, 2, (9, 9, 9), 0), (0, 0, (7, 7, 7), 5)),             # depth: the host's value and weight; colour idle
+            ((3, 1, (1, 1, 1), 1), (4, 2, (1, 1, 2), 2))]               # 11/3 -> 3; colour 1, 1, 5/3 -> 1
+    for i, (a, b) in enumerate(rows):
+        h[i], d[i] = mc._const_block(*a)[0], mc._const_block(*b)[0]
+    lo, hi, info = ref64.combine_stored(h, d, 255)
+    # a quotient that is an integer n > 0 is a tie (float32 may end just below it): n - 1 and n are permitted; every
+    # other quotient here is far from an integer and has one permitted result
+    for f, tie in (("sdf", info["tie_sdf"]), ("clr", info["tie_clr"])):
+        assert np.array_equal(hi[f].astype(int) - lo[f], tie & (hi[f] > 0)), f
+    assert info["tie_sdf"].tolist() == [False, False, False, True, True, False]
+    assert info["tie_clr"].tolist() == [[False, True, False], [False, True, False], [False] * 3, [True] * 3, [False] * 3, [True, True, False]]
+    lo = hi
+    want = [(0, 2, (10, 20, 32), 4), (-7, 4, (127, 0, 127), 4), (9, 2, (4, 5, 6), 1), (32767, 255, (255, 255, 255), 255),
+            (300, 2, (7, 7, 7), 5), (3, 3, (1, 1, 1), 3)]
+    for i, wnt in enumerate(want):
+        got = (int(lo[i]["sdf"]), int(lo[i]["w_depth"]), tuple(int(c) for c in lo[i]["clr"]), int(lo[i]["w_color"]))
+        assert got == wnt, (i, got, wnt)
+    # a tie: 199 x 1 + 1 x 2 over 200 = 1.005, within 1/100 of 1 but on its far side; 99 x 1 + 1 x 0 over 100 = 0.99
+    h, d = np.zeros(2, am.VOXEL_DTYPE), np.zeros(2, am.VOXEL_DTYPE)
+    h[0], d[0] = mc._const_block(1, 199, 0, 0)[0], mc._const_block(2, 1, 0, 0)[0]
+    h[1], d[1] = mc._const_block(1, 99, 0, 0)[0], mc._const_block(0, 1, 0, 0)[0]
+    lo, hi, info = ref64.combine_stored(h, d, 255)
+    assert list(lo["sdf"]) == [0, 0] and list(hi["sdf"]) == [1, 1] and info["tie_sdf"].all()
+    assert list(lo["w_depth"]) == [200, 100]
 
 
 def test_step_count_is_a_rounding_matter_at_the_shipped_mu(synth):
