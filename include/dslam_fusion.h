@@ -220,7 +220,9 @@ int dslam_view_destroy(dslam_view *v);
  * depth_mm: int16 millimetres (:106-110); depth_m = d<=0 ? -1 : d*affine_a + affine_b with
  * (a,b) = (1/1000, 0) from CreateItmCalib (:58,79).
  * use_bilateral_filter: ITMViewBuilder's five passes of the 5x5 bilateral depth filter (upstream InfiniTAM v2
- * filterDepth); the filtered image keeps upstream's 2-pixel border of 0 (= no measurement). */
+ * filterDepth); the filtered image keeps upstream's 2-pixel border of 0 (= no measurement).  A depth image below
+ * 5 x 5 has no pixel the filter could write: with the filter on, every update entry point refuses such a view
+ * with an error (the next update without the filter is served as usual). */
 int dslam_view_update(dslam_engine *e, dslam_view *v, const uint8_t *rgba_host, const int16_t *depth_mm_host,
                       float affine_a, float affine_b, double timestamp, int use_bilateral_filter);
 /* same, inputs already resident in HBM (frame database kept on device). */
