@@ -215,6 +215,216 @@ def integrate(vox, block_pos, depth, rgba, M_d, intr, vs, mu, max_w, M_rgb=None,
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# A.5 / A.11 once more, value by value: what a float32 evaluation in the spec's operation order may store
+# ---------------------------------------------------------------------------------------------------------------------
+U32 = 2.0 ** -24  # the relative size of one float32 rounding
+
+
+def _bilinear_f64(rgba, ix, iy, dx, dy):
+    W = rgba.shape[1]
+    flat = rgba.reshape(-1, 4)[:, :3].astype(np.float64)
+    a, b = flat[ix + iy * W], flat[ix + 1 + iy * W]
+    c, d = flat[ix + (iy + 1) * W], flat[ix + 1 + (iy + 1) * W]
+    return (a * ((1 - dx) * (1 - dy))[:, None] + b * (dx * (1 - dy))[:, None] + c * ((1 - dx) * dy)[:, None]
+            + d * (dx * dy)[:, None])
+
+
+def _permitted(q, band, lo_clip, hi_clip):
+    """trunc(q - band), trunc(q + band) (C's conversion: toward zero), each clamped as the spec clamps the quotient."""
+    a = np.clip(np.trunc(np.clip(q - band, lo_clip, hi_clip)), lo_clip, hi_clip).astype(np.int64)
+    b = np.clip(np.trunc(np.clip(q + band, lo_clip, hi_clip)), lo_clip, hi_clip).astype(np.int64)
+    return a, b
+
+
+def update_exact(vox, block_pos, depth, rgba, M_d, intr, vs, mu, max_w, M_rgb=None, intr_rgb=None, stop_at_max=False,
+                 wp=None, deintegrate=False):
+    """`integrate` above with every stored value pinned instead of allowed 1 LSB.  Same arguments.  Returns (lo, hi, info)
+    in the style of combine_stored: two voxel arrays that agree in every weight and pad byte and hold, value by value, the
+    two results trunc(q - band) and trunc(q + band) a float32 evaluation in the spec's order may store; q is the exact
+    value (float64 of integer and dyadic operands: its own error, 1e-12 LSB, is nothing beside the bands) and a value is
+    a *tie* where the two differ.  S = 32767 for the sdf and 255 for a colour channel, u = 2^-24, W / w the stored and the
+    new weight, F = sdf / S, f = min(1, eta / mu); every operand has magnitude <= 1 before a weight scales it.
+
+    Bands (absolute, in LSB of the stored value; derived from the roundings alone, before any engine ran):
+      fusion, sdf.  RN(sdf / S): u.  RN(W F): u W more, 2 u W in the numerator.  RN(eta / mu): u (none when mu is a power
+        of two; eta itself is exact for dyadic inputs, and |eta32 - eta64| w / mu is added where it is not).  RN(w f): 2 u w
+        in the numerator.  The sum: u (W + w).  Numerator: 3 u (W + w), i.e. 3 u after the exact division; the quotient's
+        rounding u, the product with S u: 5 u S = 0.0098.  One more u for the second-order terms: band = 6 u S = 0.0117.
+      fusion, colour.  The bilinear sample at the float32 position (dx, 1 - dx, dy, 1 - dy are exact in float32): two
+        roundings per term, three sums, 5 u m.  RN(m / 255): 6 u in c.  RN(C / 255), RN(C' Wc): 2 u Wc.  The sum:
+        u (Wc + 1).  Numerator (3 Wc + 7) u over Wc + 1, quotient u, product u, one u more:
+        band = 255 u ((3 Wc + 7) / (Wc + 1) + 3), between 6 u 255 = 9.1e-5 and 10 u 255 = 1.5e-4; plus the distance
+        between the value at the float32 position and at the float64 one (a kernel may round the projection otherwise).
+      de-integration, sdf.  Numerator W F - w f: 2 u W + 2 u w + u |N|, divided by r = W - w; quotient Q = N / r rounds by
+        u |Q|, the clamped product by u S: band = u S ((2 W + 2 w) / r + 2 |Q| + 2) (the last u as above): it grows with
+        W / (W - w).  A quotient beyond +-1 by more than the band is exactly +-S.
+      de-integration, colour.  Likewise with w = 1, 6 u in c: band = 255 u ((2 Wc + 6) / r + 2 |Q| + 2), r = Wc - 1,
+        clamped to [0, 255], plus the position term.
+    Weights are exact: min(W + w, max_w); W - w where W >= w (0: the empty voxel, sdf 32767), else the depth half is left
+    alone while the colour half still updates (it needs Wc >= 1; Wc - 1 = 0 gives colour 0); stopIntegratingAtMaxW is a
+    fusion rule and a de-integration ignores it.
+    Predicates (depth > 0, eta < -mu, image bounds, the pixel picked, the 0.25 gate; W >= w is an integer test) are taken
+    in float32 with float64 beside them, as `integrate` does; a voxel where they disagree is in info['pred_tie'] and its
+    values are not pinned.
+    info: q_sdf, q_clr, tie_sdf, tie_clr, band_sdf, band_clr, pred_tie; the masks projected (into the depth image), seen (a
+    depth > 0 there: eta is defined), taken (eta >= -mu), upd_depth, colour_seen (inside the gate and the colour image),
+    upd_colour; eta, f, w_new and the colour sample."""
+    M_rgb = M_d if M_rgb is None else M_rgb
+    intr_rgb = intr if intr_rgb is None else intr_rgb
+    lo = vox.copy()
+    Hd, Wd = depth.shape
+    Hr, Wr = rgba.shape[:2]
+    vi = (np.asarray(block_pos, np.int64)[:, None, :] * 8 + LOCAL[None]).reshape(-1, 3)
+    v = lo.reshape(-1)
+    pm32, pm64 = vi.astype(F) * F(vs), vi * float(F(vs))
+    mu32, mu64 = F(mu), float(F(mu))
+    # -- the measurement ---------------------------------------------------------------------------------------------
+    pc32, pc64 = mat_vec_f32(M_d, pm32), mat_vec_f64(M_d, pm64)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        u32, w32 = project_f32(intr, pc32)
+        u64, w64 = project_f64(intr, pc64)
+    ok = (pc32[:, 2] > 0) & (u32 >= 1) & (u32 <= F(Wd - 2)) & (w32 >= 1) & (w32 <= F(Hd - 2))
+    ok64 = (pc64[:, 2] > 0) & (u64 >= 1) & (u64 <= Wd - 2) & (w64 >= 1) & (w64 <= Hd - 2)
+    ties = ok != ok64
+    projected = ok.copy()
+    ui, wi = np.zeros(len(vi), np.int64), np.zeros(len(vi), np.int64)
+    ui[ok] = (u32[ok] + F(0.5)).astype(np.int64)
+    wi[ok] = (w32[ok] + F(0.5)).astype(np.int64)
+    both = ok & ok64
+    with np.errstate(invalid="ignore"):
+        ties |= both & (((u64 + 0.5).astype(np.int64) != ui) | ((w64 + 0.5).astype(np.int64) != wi))
+    dm32 = np.where(ok, depth.reshape(-1)[ui + wi * Wd], F(-1))
+    ok &= dm32 > 0
+    eta32 = dm32 - pc32[:, 2]
+    eta64 = dm32.astype(np.float64) - pc64[:, 2]
+    ties |= ok & ((eta32 < -mu32) != (eta64 < -mu64))
+    seen = ok.copy()  # a depth measurement exists; eta is defined
+    ok &= eta32 >= -mu32
+    taken = ok.copy()
+    if stop_at_max and not deintegrate:
+        ok &= v["w_depth"] != max_w
+    S = 32767.0
+    s = v["sdf"].astype(np.float64)
+    W = v["w_depth"].astype(np.int64)
+    em = eta64 / mu64
+    f = np.minimum(1.0, em)
+    w = new_weight(dm32, wp)
+    d_eta = np.abs(eta32.astype(np.float64) - eta64) / mu64 * S
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if not deintegrate:
+            upd_d = ok
+            q = (W * s + w * f * S) / (W + w)
+            band = np.full(len(vi), 6 * U32 * S) + d_eta * w / (W + w)
+            a, b = _permitted(q, band, -S, S)
+            new_w = np.minimum(W + w, max_w)
+        else:
+            r = W - w
+            upd_d = ok & (r >= 0)
+            q = (W * s - w * f * S) / r
+            band = U32 * S * ((2 * W + 2 * w) / r + 2 * np.abs(q) / S + 2) + d_eta * w / r
+            a, b = _permitted(q, band, -S, S)
+            a, b, q = (np.where(r == 0, 32767, x) for x in (a, b, q))
+            band = np.where(r == 0, 0.0, band)
+            new_w = r
+    hi = lo.copy()
+    vh = hi.reshape(-1)
+    for out, val in ((v, np.minimum(a, b)), (vh, np.maximum(a, b))):
+        out["sdf"] = np.where(upd_d, val, out["sdf"]).astype(np.int16)
+        out["w_depth"] = np.where(upd_d, new_w, W).astype(np.uint8)
+    q_sdf, band_sdf = np.where(upd_d, q, s), np.where(upd_d, band, 0.0)
+    tie_sdf = upd_d & (a != b)
+    # -- colour: only where the depth measurement was taken, and only close to the surface --------------------------
+    with np.errstate(divide="ignore", invalid="ignore"):
+        gate32 = (eta32 > mu32) | (np.abs(eta32 / mu32) > F(0.25))
+        gate64 = (eta64 > mu64) | (np.abs(em) > 0.25)
+    ties |= ok & (gate32 != gate64)
+    c_ok = ok & ~gate32
+    pr32, pr64 = mat_vec_f32(M_rgb, pm32), mat_vec_f64(M_rgb, pm64)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        ru32, rw32 = project_f32(intr_rgb, pr32)
+        ru64, rw64 = project_f64(intr_rgb, pr64)
+    inb32 = (ru32 >= 1) & (ru32 <= F(Wr - 2)) & (rw32 >= 1) & (rw32 <= F(Hr - 2))
+    inb64 = (ru64 >= 1) & (ru64 <= Wr - 2) & (rw64 >= 1) & (rw64 <= Hr - 2)
+    ties |= c_ok & (inb32 != inb64)
+    c_ok &= inb32
+    Wc = v["w_color"].astype(np.int64)
+    colour_seen = c_ok.copy()
+    if deintegrate:
+        c_ok &= Wc >= 1
+    q_clr = v["clr"].astype(np.float64)
+    sample = np.full((len(vi), 3), np.nan)
+    band_clr = np.zeros((len(vi), 3))
+    tie_clr = np.zeros((len(vi), 3), bool)
+    idx = np.nonzero(c_ok)[0]
+    if len(idx):
+        ix, iy = np.floor(ru32[idx]).astype(np.int64), np.floor(rw32[idx]).astype(np.int64)
+        m = _bilinear_f64(rgba, ix, iy, ru32[idx].astype(np.float64) - ix, rw32[idx].astype(np.float64) - iy)
+        m_at64 = _bilinear_f64(rgba, ix, iy, ru64[idx] - ix, rw64[idx] - iy)
+        C, wc = q_clr[idx], Wc[idx].astype(np.float64)[:, None]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if not deintegrate:
+                q = (C * wc + m) / (wc + 1)
+                band = 255 * U32 * ((3 * wc + 7) / (wc + 1) + 3) + np.abs(m - m_at64) / (wc + 1)
+                new_wc = np.minimum(wc[:, 0] + 1, max_w)
+            else:
+                r = wc - 1
+                q = (C * wc - m) / r
+                band = 255 * U32 * ((2 * wc + 6) / r + 2 * np.abs(q) / 255 + 2) + np.abs(m - m_at64) / r
+                new_wc = r[:, 0]
+            a, b = _permitted(q, band, 0.0, 255.0)
+            if deintegrate:
+                a, b, q = (np.where(r == 0, 0, x) for x in (a, b, q))
+                band = np.where(r == 0, 0.0, band)
+        for out, val in ((v, np.minimum(a, b)), (vh, np.maximum(a, b))):
+            out["clr"][idx] = val.astype(np.uint8)
+            out["w_color"][idx] = new_wc.astype(np.uint8)
+        q_clr[idx], band_clr[idx], tie_clr[idx], sample[idx] = q, band, a != b, m
+    shp = vox.shape
+    info = dict(q_sdf=q_sdf.reshape(shp), q_clr=q_clr.reshape(shp + (3,)), tie_sdf=tie_sdf.reshape(shp),
+                tie_clr=tie_clr.reshape(shp + (3,)), pred_tie=ties.reshape(shp), projected=projected.reshape(shp),
+                upd_depth=upd_d.reshape(shp), upd_colour=c_ok.reshape(shp), seen=seen.reshape(shp),
+                taken=taken.reshape(shp), colour_seen=colour_seen.reshape(shp), sample=sample.reshape(shp + (3,)),
+                eta=np.where(seen, eta64, np.nan).reshape(shp), f=f.reshape(shp), w_new=w.reshape(shp), band_sdf=band_sdf.reshape(shp),
+                band_clr=band_clr.reshape(shp + (3,)))
+    return lo, hi, info
+
+
+def update_tie_share(info, sel=None):
+    """Ties among the updated values (one sdf per updated depth half, three channels per updated colour half) of the
+    blocks `sel` (all by default)."""
+    pick = (lambda a: a) if sel is None else (lambda a: a[sel])
+    n = int(pick(info["upd_depth"]).sum()) + 3 * int(pick(info["upd_colour"]).sum())
+    return (int(pick(info["tie_sdf"]).sum()) + int(pick(info["tie_clr"]).sum())) / max(n, 1)
+
+
+def check_updated(got, lo, hi, info, what=""):
+    """`got` against update_exact's answer: weights and pad exact, every value one of its permitted results (so a non-tie
+    value equals trunc(q) exactly), |got - q| <= 1 on every voxel that is no tie and <= 1 + band at a tie (with q just
+    above an integer k the lower permitted result is k - 1: the distance can pass 1 by the band, never by more); voxels
+    with a predicate tie are left out.  Returns the figures DESIGN 4c records."""
+    got = np.asarray(got)
+    keep = ~info["pred_tie"]
+    for f in ("w_depth", "w_color", "_pad"):
+        bad = (got[f] != lo[f]) & keep
+        assert not bad.any(), f"{what}: {f} differs in {int(bad.sum())} voxels, first got {got[f][bad][:4]}, want {lo[f][bad][:4]}"
+    out = {}
+    for f, q, tie, band in (("sdf", info["q_sdf"], info["tie_sdf"], info["band_sdf"]),
+                            ("clr", info["q_clr"], info["tie_clr"], info["band_clr"])):
+        k = keep if f == "sdf" else keep[..., None]
+        g = got[f].astype(np.int64)
+        bad = (g != lo[f]) & (g != hi[f]) & k
+        assert not bad.any(), (f"{what}: {int(bad.sum())} {f} values are none of the permitted results; first got "
+                               f"{g[bad][:4]}, permitted {lo[f][bad][:4]} / {hi[f][bad][:4]}, q {q[bad][:4]}")
+        ends = (-32767.0, 32767.0) if f == "sdf" else (0.0, 255.0)
+        err = np.where(k, np.abs(g - np.clip(q, *ends)), 0.0)
+        over = err - 1.0 - np.where(tie, band, 0.0)
+        assert over.max(initial=-1.0) <= 0.0, f"{what}: |got - q| = {err[over > 0][:4]} for {f}, bands {band[over > 0][:4]}"
+        out[f] = dict(ties=int(tie.sum()), worst_err=float(err.max(initial=0.0)),
+                      at_upper_result=int((tie & (g == hi[f]) & k).sum()))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # A.8 the merge of a host copy into a resident block (upstream CombineVoxelInformation), in exact integer arithmetic
 # ---------------------------------------------------------------------------------------------------------------------
 # The merged value is trunc(q), q = (w_h v_h + w_d v_d) / (w_h + w_d): a rational with denominator w_h + w_d, computed
