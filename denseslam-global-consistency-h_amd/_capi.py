@@ -54,6 +54,29 @@ class TrackerResult(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("valid_points_last", C.c_int32), ("f_last", C.c_float), ("pad", C.c_int32)]
 
 
+class RegisterParams(C.Structure):
+    """dslam_register_params; a field left at 0 selects its default."""
+    _fields_ = [("band", C.c_float), ("residual_gate", C.c_float), ("max_evaluations", C.c_int32),
+                ("min_valid", C.c_int32), ("term_rotation", C.c_float), ("term_translation_voxels", C.c_float)]
+
+    def __init__(self, band=0.0, residual_gate=0.0, max_evaluations=0, min_valid=0, term_rotation=0.0,
+                 term_translation_voxels=0.0):
+        super().__init__(band, residual_gate, max_evaluations, min_valid, term_rotation, term_translation_voxels)
+
+
+class RegisterResult(C.Structure):
+    """dslam_register_result."""
+    _fields_ = [("evaluations", C.c_int32), ("stop_reason", C.c_int32), ("candidates", C.c_int32),
+                ("valid_last", C.c_int32), ("cost_first", C.c_float), ("cost_last", C.c_float),
+                ("conditioning", C.c_float), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+assert C.sizeof(RegisterParams) == 24 and C.sizeof(RegisterResult) == 32  # the header's layouts
+
+
 class WeightParams(C.Structure):
     _fields_ = [("depth_weighting", C.c_int32), ("max_new_w", C.c_int32), ("max_distance", C.c_float)]
 
@@ -614,6 +637,23 @@ class CApi:
         col = np.empty((max(n.value, 1), 3, 3), dtype=np.float32) if colour else None
         self._call("mesh_download", self._engine, _fptr(pos), _fptr(col) if colour else None, C.c_int(n.value))
         return pos[:n.value], (col[:n.value] if colour else None), counts[:k]
+
+    # -- map registration ------------------------------------------------------------------------------
+    def register_maps(self, src, dst, X0, params=None):
+        """dslam_register_maps: the rigid transform from `src`'s frame to `dst`'s (4x4, metres), estimated from the two
+        maps' voxels starting at X0.  Returns (X as a 4x4 float32 array, RegisterResult)."""
+        X = mat_to_abi(X0).copy()
+        res = RegisterResult()
+        self._call("register_maps", self._engine, src.ptr, dst.ptr, _fptr(X), C.byref(params) if params is not None else None,
+                   C.byref(res))
+        return X.reshape(4, 4).T.copy(), res
+
+    def debug_register_sums(self):
+        """The 33 double sums of the most recent registration evaluation (pivot at the origin): 21 Hessian (lower
+        triangle, row by row), 6 gradient, sum of b^2, valid count, 3 sum of q, candidate count."""
+        out = np.empty(33, dtype=np.float64)
+        self._call("debug_register_sums", self._engine, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
 
     # -- page-locked host images -----------------------------------------------------------------------
     def host_alloc(self, shape, dtype):

@@ -4,6 +4,7 @@
 // created and every entry point fails.
 #include <climits>
 #include <cctype>
+#include <cmath>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -1563,6 +1564,37 @@ int dslam_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, co
   DSLAM_TRY(launch_mesh_scene_multi(e, scenes, T_map_from_world, num_maps, max_triangles, with_colour, out_num_triangles,
                                     out_map_triangles));
   return finish_call(e);
+}
+
+// ---- map registration ------------------------------------------------------------------------------------------
+int dslam_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_scene *dst, float X_dst_from_src[16],
+                        const dslam_register_params *params, dslam_register_result *result) {
+  DSLAM_REQUIRE(e && src && dst && X_dst_from_src && result, "null argument");
+  DSLAM_REQUIRE(src->engine == e && dst->engine == e, "a scene belongs to another engine");
+  DSLAM_REQUIRE(src->p.voxel_size == dst->p.voxel_size && src->p.mu == dst->p.mu,
+                "the two maps of a registration need the same voxel_size and mu");
+  for (int i = 0; i < 16; i++) DSLAM_REQUIRE(std::isfinite(X_dst_from_src[i]), "the start transform is not finite");
+  float inv[16];
+  DSLAM_REQUIRE(invert_matrix(X_dst_from_src, inv), "the start transform is singular");
+  dslam_register_params rp = {0.0f, 0.0f, 0, 0, 0.0f, 0.0f};
+  if (params) rp = *params;
+  DSLAM_REQUIRE(rp.band >= 0.0f && rp.residual_gate >= 0.0f && rp.max_evaluations >= 0 && rp.min_valid >= 0 &&
+                    rp.term_rotation >= 0.0f && rp.term_translation_voxels >= 0.0f,
+                "a registration parameter is negative (or not a number)");
+  if (rp.band == 0.0f) rp.band = 0.5f;
+  if (rp.residual_gate == 0.0f) rp.residual_gate = 0.75f;
+  if (rp.max_evaluations == 0) rp.max_evaluations = 30;
+  if (rp.min_valid == 0) rp.min_valid = 500;
+  if (rp.term_rotation == 0.0f) rp.term_rotation = 1e-5f;
+  if (rp.term_translation_voxels == 0.0f) rp.term_translation_voxels = 1e-3f;
+  return launch_register_maps(e, src, dst, X_dst_from_src, &rp, result);
+}
+
+int dslam_debug_register_sums(dslam_engine *e, double out[33]) {
+  DSLAM_REQUIRE(e && out, "null argument");
+  DSLAM_REQUIRE(e->reg_have_sums, "no registration evaluation has run on this engine");
+  memcpy(out, e->reg_last_sums, sizeof e->reg_last_sums);
+  return DSLAM_OK;
 }
 
 int dslam_mesh_download(dslam_engine *e, float *out_positions, float *out_colours, int capacity_triangles) {

@@ -160,6 +160,10 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   // dslam_mesh_scene_multi (multimesh.hip): its copy of the case table, and the per-map descriptor table of one map pass
   bool multimesh_table_ready = false;
   DeviceBuffer<void> multimesh_maps;
+  // dslam_register_maps (register.hip): per-workgroup partial sums in mapped page-locked memory, as the tracker's
+  PinnedBuffer<double> reg_partials;
+  double reg_last_sums[33] = {0};     // the totals of the most recent evaluation (dslam_debug_register_sums; test hook)
+  bool reg_have_sums = false;
 };
 
 // GetImage's front end for the pose of the last ProcessFrame: FindVisibleBlocks with the projections of its blocks and a reset
@@ -454,6 +458,9 @@ int launch_mesh_scene(dslam_engine *e, const dslam_scene *s, int max_triangles, 
 // scenes / T (N x 16, world -> map) already checked by dslam_mesh_scene_multi; out_map: [n] triangles per map, or null
 int launch_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T, int n, int max_triangles,
                             int with_colour, int *out_num, int32_t *out_map);
+// src / dst / X / params already checked (and defaulted) by dslam_register_maps; X: in the start, out the estimate
+int launch_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_scene *dst, float *X,
+                         const dslam_register_params *params, dslam_register_result *result);
 int launch_decay(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int max_weight, int min_age, int force_all,
                  int which);
 int launch_slide_pop(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int which);

@@ -425,6 +425,49 @@ class ITMMainEngine {
     MeshScene(&mesh, scene);
     mesh.WriteOBJ(objFileName);
   }
+
+  /// (extension) Align local map `src` to local map `dst` from their voxels alone (dslam_register_maps, law in DESIGN.md
+  /// section 13): the start is X = T_dst T_src^-1 from the two estimatedGlobalPoses; when the registration converges
+  /// (stop reason 0) the source's estimatedGlobalPose becomes X^-1 T_dst and the call returns true, otherwise the pose is
+  /// left alone.  Both compositions are made in double by RigidInverse / RigidProduct below, so a caller of the C ABI can
+  /// reproduce them bit for bit.  Call it before GetImageAllLocalMaps / SaveAllLocalMapsToMesh, whose blend needs the
+  /// maps' relative poses right to a fraction of a voxel.
+  bool AlignLocalMap(int src, int dst, dslam_register_result *out = nullptr) {
+    ITMLocalMap *ms = mapManager->getLocalMap(src);
+    const ITMLocalMap *md = mapManager->getLocalMap(dst);
+    double Ts[16], Td[16], inv[16], X[16];
+    for (int i = 0; i < 16; i++) { Ts[i] = (double)ms->estimatedGlobalPose.GetM().m[i]; Td[i] = (double)md->estimatedGlobalPose.GetM().m[i]; }
+    RigidInverse(Ts, inv);
+    RigidProduct(Td, inv, X);
+    float Xf[16];
+    for (int i = 0; i < 16; i++) Xf[i] = (float)X[i];
+    dslam_register_result res;
+    dslam_check(dslam_register_maps(engine_, ms->scene->handle, md->scene->handle, Xf, nullptr, &res), "dslam_register_maps");
+    if (out) *out = res;
+    if (res.stop_reason != 0) return false;
+    for (int i = 0; i < 16; i++) X[i] = (double)Xf[i];
+    RigidInverse(X, inv);
+    RigidProduct(inv, Td, X);
+    Matrix4f M;
+    for (int i = 0; i < 16; i++) M.m[i] = (float)X[i];
+    ms->estimatedGlobalPose.SetM(M);
+    return true;
+  }
+  /// inverse of a rigid transform (column-major): [R^T | -(R^T t)], each sum evaluated left to right
+  static void RigidInverse(const double M[16], double out[16]) {
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) out[c * 4 + r] = M[r * 4 + c];
+      out[12 + r] = -((M[r * 4 + 0] * M[12] + M[r * 4 + 1] * M[13]) + M[r * 4 + 2] * M[14]);
+      out[r * 4 + 3] = 0.0;
+    }
+    out[15] = 1.0;
+  }
+  /// C = A B (column-major), each entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3
+  static void RigidProduct(const double A[16], const double B[16], double C[16]) {
+    for (int c = 0; c < 4; c++)
+      for (int r = 0; r < 4; r++)
+        C[c * 4 + r] = ((A[0 * 4 + r] * B[c * 4 + 0] + A[1 * 4 + r] * B[c * 4 + 1]) + A[2 * 4 + r] * B[c * 4 + 2]) + A[3 * 4 + r] * B[c * 4 + 3];
+  }
   /// ITMMeshingEngine::MeshScene(mesh, scene)
   void MeshScene(ITMMesh *mesh, const ITMScene<ITMVoxel, ITMVoxelIndex> *scene) {
     int n = 0;

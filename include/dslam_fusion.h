@@ -511,6 +511,67 @@ int dslam_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, co
                            int num_maps, int max_triangles, int with_colour, int *out_num_triangles,
                            int32_t *out_map_triangles);
 
+/* ---- map registration ------------------------------------------------------------------------- */
+/* SDF-to-SDF alignment of two overlapping local maps (no counterpart in the reference, whose map-to-map constraints come
+ * from frames tracked in two maps at once; the law is this project's own).  X is the rigid transform
+ * from the source map's frame to the destination map's (metres, column-major; for maps with world -> map transforms T_src,
+ * T_dst it is T_dst T_src^-1); X~ is X with its translation in voxel units, kept in double on the host and rounded to
+ * float32 (first three rows) for each evaluation.  One evaluation at X~: every voxel of every resident block of the
+ * source, at integer voxel position p with fields (sdf_s, w_s),
+ *   1. candidate gate: w_s > 0 and |sdf_s| < (int)(band * 32767); candidates are counted in N;
+ *   2. q = X~ p, rows evaluated as ((a x + b y) + c z) + d in float32 (an X that is exactly the identity reads at p
+ *      itself); cell floor(q), fractions c = q - floor(q);
+ *   3. destination gate: all 8 taps of the cell lie in resident blocks of the destination, each with w_depth > 0 and a
+ *      raw sdf other than +-32767; otherwise the voxel is a miss;
+ *   4. value and gradient from those 8 taps, float32, s[k] = raw[k] / 32767 with tap k = (k & 1, (k >> 1) & 1, k >> 2),
+ *      u = 1 - c per axis:
+ *        x00 = ux s0 + cx s1, x10 = ux s2 + cx s3, x01 = ux s4 + cx s5, x11 = ux s6 + cx s7,
+ *        y0 = uy x00 + cy x10, y1 = uy x01 + cy x11, d = uz y0 + cz y1,
+ *        gx = uz (uy (s1 - s0) + cy (s3 - s2)) + cz (uy (s5 - s4) + cy (s7 - s6)),
+ *        gy = uz (x10 - x00) + cz (x11 - x01), gz = y1 - y0;
+ *   5. b = sdf_s / 32767 - d; |b| > residual_gate is a miss too; otherwise the voxel is valid with the row
+ *      A = [q x g, g] (rotation about the destination's origin, then translation);
+ *   6. 33 sums, accumulated in double from float32 products: [0..20] the lower triangle of sum A^T A row by row,
+ *      [21..26] sum b A, [27] sum b^2, [28] the valid count, [29..31] sum q over the valid voxels, [32] N.
+ * cost = (sum b^2 + (N - valid) residual_gate^2) / N: every miss pays the gate, so the cost cannot fall by shedding
+ * overlap.  Iteration (host, double): the sums are re-pivoted to the centroid c = sum q / valid (H_c = P H P^T, g_c = P g,
+ * P = [[I, -[c]x], [0, I]]); the step solves (H_c + lambda diag H_c) y = g_c and is applied on the left of X~ as
+ * q' = c + R(y0..2)(q - c) + y3..5; it is accepted when the new evaluation has valid >= min_valid and a lower cost.
+ * lambda starts at 1, is divided by 10 (not below 1e-6) on acceptance and multiplied by 10 on rejection.
+ * stop_reason: 0 an accepted step taken with lambda <= 1 had |rotation| < term_rotation and |translation| <
+ * term_translation_voxels; 1 max_evaluations reached (max_evaluations = 1: the start pose is evaluated once and returned);
+ * 2 lambda > 1e6; 3 fewer than min_valid valid voxels at the start pose.  On every stop reason X returns the last
+ * accepted pose (untouched if no step was accepted).  conditioning: the smallest eigenvalue of D^-1/2 H_c D^-1/2,
+ * D = diag H_c, at the last accepted evaluation (0 if a diagonal entry is 0 or stop_reason is 3): small when the geometry
+ * does not fix all six freedoms; the call never refuses on it.
+ * Both maps are only read (blocks that are swapped out are simply not resident); no render state is involved.  Waits for
+ * the stream on synchronous and asynchronous engines, as dslam_track_camera does.  DSLAM_ERR_INVALID with X untouched: a
+ * NULL argument other than params, a scene of another engine, different voxel_size / mu, a non-finite or singular X, a
+ * negative parameter. */
+typedef struct {
+  float band;                      /* 0 -> 0.5 */
+  float residual_gate;             /* 0 -> 0.75 */
+  int32_t max_evaluations;         /* 0 -> 30 */
+  int32_t min_valid;               /* 0 -> 500 */
+  float term_rotation;             /* radians; 0 -> 1e-5 */
+  float term_translation_voxels;   /* 0 -> 1e-3 */
+} dslam_register_params;
+typedef struct {
+  int32_t evaluations;
+  int32_t stop_reason;
+  int32_t candidates;              /* N */
+  int32_t valid_last;              /* valid voxels at the returned pose */
+  float cost_first;                /* cost at the start pose */
+  float cost_last;                 /* cost at the returned pose */
+  float conditioning;
+  int32_t pad;
+} dslam_register_result;
+int dslam_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_scene *dst,
+                        float X_dst_from_src[16] /* in: start, out: estimate */,
+                        const dslam_register_params *params /* NULL: defaults */, dslam_register_result *result);
+/* Test hook: the 33 raw sums (pivot at the origin) of the engine's most recent evaluation.  Error if none has run. */
+int dslam_debug_register_sums(dslam_engine *e, double out[33]);
+
 /* ---- depth tracker (ICP) ---------------------------------------------------------------------- */
 /* trackingController->Track(trackingState, view) (InfiniTamDriver.h:151-163, reached through
  * DenseSlam.cpp:200-206 when the reference runs without ORB-SLAM2 odometry): upstream InfiniTAM v2's
