@@ -77,6 +77,27 @@ class RegisterResult(C.Structure):
 assert C.sizeof(RegisterParams) == 24 and C.sizeof(RegisterResult) == 32  # the header's layouts
 
 
+class MergeParams(C.Structure):
+    """dslam_merge_params; max_passes = 0 selects its default."""
+    _fields_ = [("max_passes", C.c_int32), ("with_colour", C.c_int32)]
+
+    def __init__(self, max_passes=0, with_colour=1):
+        super().__init__(max_passes, with_colour)
+
+
+class MergeResult(C.Structure):
+    """dslam_merge_result."""
+    _fields_ = [("passes", C.c_int32), ("exhausted", C.c_int32), ("src_blocks", C.c_int32),
+                ("blocks_allocated", C.c_int32), ("blocks_touched", C.c_int32), ("requests_unserved", C.c_int32),
+                ("src_candidates", C.c_int64), ("out_of_range", C.c_int64), ("voxels_changed", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+assert C.sizeof(MergeParams) == 8 and C.sizeof(MergeResult) == 48  # the header's layouts
+
+
 class WeightParams(C.Structure):
     _fields_ = [("depth_weighting", C.c_int32), ("max_new_w", C.c_int32), ("max_distance", C.c_float)]
 
@@ -653,6 +674,21 @@ class CApi:
         triangle, row by row), 6 gradient, sum of b^2, valid count, 3 sum of q, candidate count."""
         out = np.empty(33, dtype=np.float64)
         self._call("debug_register_sums", self._engine, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
+
+    # -- map merge -------------------------------------------------------------------------------------
+    def merge_maps(self, src, dst, X, params=None):
+        """dslam_merge_maps: fuse `src` into `dst` under X (source frame -> destination frame, 4x4, metres), on the
+        device; `src` is only read.  Returns the MergeResult."""
+        res = MergeResult()
+        self._call("merge_maps", self._engine, src.ptr, dst.ptr, _fptr(mat_to_abi(X)),
+                   C.byref(params) if params is not None else None, C.byref(res))
+        return res
+
+    def debug_merge_phases(self, enable):
+        """The phase times (ms) of the last merge measured with the hook on; then turns the hook on or off."""
+        out = np.zeros(5, dtype=np.float64)
+        self._call("debug_merge_phases", self._engine, C.c_int(int(enable)), out.ctypes.data_as(C.POINTER(C.c_double)))
         return out
 
     # -- page-locked host images -----------------------------------------------------------------------

@@ -1597,6 +1597,41 @@ int dslam_debug_register_sums(dslam_engine *e, double out[33]) {
   return DSLAM_OK;
 }
 
+// ---- map merge --------------------------------------------------------------------------------------------------
+int dslam_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_dst_from_src[16],
+                     const dslam_merge_params *params, dslam_merge_result *result) {
+  DSLAM_REQUIRE(e && src && dst && X_dst_from_src && result, "null argument");
+  DSLAM_REQUIRE(src->engine == e && dst->engine == e, "a scene belongs to another engine");
+  DSLAM_REQUIRE(src != dst, "a map cannot be merged into itself");
+  DSLAM_REQUIRE(memcmp(&src->p.voxel_size, &dst->p.voxel_size, sizeof(float)) == 0 && memcmp(&src->p.mu, &dst->p.mu, sizeof(float)) == 0,
+                "the two maps of a merge need the same voxel_size and mu");
+  DSLAM_REQUIRE(!src->p.use_swapping && !dst->p.use_swapping, "maps that use swapping cannot be merged");
+  DSLAM_REQUIRE(src->num_shards == 1 && dst->num_shards == 1 && src->shard_count < 0 && dst->shard_count < 0,
+                "sharded maps cannot be merged");
+  for (int i = 0; i < 16; i++) DSLAM_REQUIRE(std::isfinite(X_dst_from_src[i]), "the transform is not finite");
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double dot = 0.0;
+      for (int k = 0; k < 3; k++) dot += (double)X_dst_from_src[i * 4 + k] * (double)X_dst_from_src[j * 4 + k];
+      DSLAM_REQUIRE(fabs(dot - (i == j ? 1.0 : 0.0)) <= 1e-4, "the transform's rotation block is not orthonormal");
+    }
+  DSLAM_REQUIRE((double)src->p.num_local_blocks * 512.0 < 4294967295.0, "the source has more blocks than the 32-bit order key can name");
+  dslam_merge_params mp = {0, 1};
+  if (params) mp = *params;
+  DSLAM_REQUIRE(mp.max_passes >= 0, "max_passes is negative");
+  if (mp.max_passes == 0) mp.max_passes = 16;
+  dst->version = next_map_version();  // the map changes: GetImage memos of this scene are stale
+  if (dst->front) dst->front->valid = false;
+  return launch_merge_maps(e, src, dst, X_dst_from_src, &mp, result);
+}
+
+int dslam_debug_merge_phases(dslam_engine *e, int enable, double out_ms[5]) {
+  DSLAM_REQUIRE(e, "null argument");
+  if (out_ms) memcpy(out_ms, e->merge_phase_ms, sizeof e->merge_phase_ms);
+  e->merge_phases_on = enable != 0;
+  return DSLAM_OK;
+}
+
 int dslam_mesh_download(dslam_engine *e, float *out_positions, float *out_colours, int capacity_triangles) {
   DSLAM_REQUIRE(e && out_positions && capacity_triangles >= 0, "bad argument");
   DSLAM_REQUIRE(capacity_triangles >= e->mesh_triangles, "dslam_mesh_download: buffer smaller than the mesh");

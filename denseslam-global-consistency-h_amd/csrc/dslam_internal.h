@@ -89,6 +89,28 @@ struct EngineScratch {
   DeviceBuffer<int> list_c;
   DeviceBuffer<short4> pos_scratch;      // [local_blocks]
 };
+
+// dslam_merge_maps (merge.hip): what its kernels count for the host, and its own scratch -- allocated by the first call,
+// grown as a whole (built aside, move-assigned), so the alternating bitmap sets of the allocation pass are left alone
+struct MergeCounters {
+  int live;                 // resident entries of the source
+  int requests;             // slots asked for in the current pass
+  int served1, served2;     // ... of them served (empty bucket heads / chain ends)
+  int touched;              // destination entries to fuse into
+  int pad[3];
+  unsigned long long candidates, out_of_range;
+};
+struct MergeScratch {
+  int src_entries = 0, dst_entries = 0, words = 0;
+  DeviceBuffer<unsigned> keys;           // [dst_entries] order keys; ALL ZERO between calls (the serve step clears what it reads)
+  DeviceBuffer<unsigned> bits;           // [4][words]: requests on empty heads, on chain ends, either; touched entries
+  DeviceBuffer<int> ranks;               // [dst_entries] rank of a request among those of its type
+  DeviceBuffer<int> touched_list;        // [dst_entries]
+  DeviceBuffer<int> live_list;           // [src_entries]
+  DeviceBuffer<MergeCounters> counters;
+  PinnedBuffer<MergeCounters> counters_host;
+  PinnedBuffer<unsigned long long> changed;   // mapped: voxels changed, one count per workgroup of the block kernel
+};
 }  // namespace dslam
 
 // (the handles' destructors free memory now: they are not part of the library's exported names)
@@ -164,6 +186,12 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   PinnedBuffer<double> reg_partials;
   double reg_last_sums[33] = {0};     // the totals of the most recent evaluation (dslam_debug_register_sums; test hook)
   bool reg_have_sums = false;
+  dslam::MergeScratch merge;          // dslam_merge_maps (merge.hip)
+  // dslam_debug_merge_phases (bench hook): wall clock of the last merge's phases, each closed by a wait for the stream --
+  // [0] the source's live list, [1] mark kernels, [2] ordered selections (ranks, serve, touched list), [3] block kernel,
+  // [4] read-backs
+  bool merge_phases_on = false;
+  double merge_phase_ms[5] = {0, 0, 0, 0, 0};
 };
 
 // GetImage's front end for the pose of the last ProcessFrame: FindVisibleBlocks with the projections of its blocks and a reset
@@ -461,6 +489,9 @@ int launch_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, c
 // src / dst / X / params already checked (and defaulted) by dslam_register_maps; X: in the start, out the estimate
 int launch_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_scene *dst, float *X,
                          const dslam_register_params *params, dslam_register_result *result);
+// src / dst / X / params already checked (and defaulted) by dslam_merge_maps
+int launch_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float *X,
+                      const dslam_merge_params *params, dslam_merge_result *result);
 int launch_decay(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int max_weight, int min_age, int force_all,
                  int which);
 int launch_slide_pop(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int which);

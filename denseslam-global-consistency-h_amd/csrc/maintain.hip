@@ -23,6 +23,7 @@
 // Every flag array of this pipeline is all zero between passes: the kernel that consumes a flag clears it, so no pass
 // starts with a memset.  Round 1 spent 16 (decay) + 13 (window pop) launches per keyframe on this path; now 8 + 6, all of
 // which return at once when their device-side count is zero.
+#include "combine_device.h"
 #include "dslam_bits.h"
 
 #pragma clang fp contract(off)
@@ -576,43 +577,6 @@ struct SelSwapOut {
   __device__ int emit(int, int, bool, const NoPayload &) const { return 0; }
   __device__ void finish(int) const {}
 };
-
-// CombineVoxelInformation: merge the host copy (src) into the resident voxel (dst)
-__device__ __forceinline__ void combine_voxel(unsigned slo, unsigned shi, unsigned &dlo, unsigned &dhi, int maxW) {
-  {
-    int newW = (int)((dlo >> 16) & 0xffu);
-    const int oldW = (int)((slo >> 16) & 0xffu);
-    if (oldW != 0) {
-      float newF = sdf_to_float((short)(dlo & 0xffffu));
-      const float oldF = sdf_to_float((short)(slo & 0xffffu));
-      newF = (float)oldW * oldF + (float)newW * newF;
-      newW = oldW + newW;
-      newF /= (float)newW;
-      newW = newW < maxW ? newW : maxW;
-      dlo = (dlo & 0xff000000u) | ((unsigned)newW << 16) | (unsigned)(unsigned short)float_to_sdf(newF);
-    }
-  }
-  {
-    const int newW = (int)((dhi >> 16) & 0xffu), oldW = (int)((shi >> 16) & 0xffu);
-    if (oldW != 0) {
-      const int sumW = oldW + newW;
-      const unsigned dc[3] = {dlo >> 24, dhi & 0xffu, (dhi >> 8) & 0xffu};
-      const unsigned sc[3] = {slo >> 24, shi & 0xffu, (shi >> 8) & 0xffu};
-      unsigned nc[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        float v = (float)dc[k] / 255.0f;
-        const float oc = (float)sc[k] / 255.0f;
-        v = oc * (float)oldW + v * (float)newW;
-        v /= (float)sumW;
-        nc[k] = (unsigned)(unsigned char)(v * 255.0f);
-      }
-      const unsigned w = (unsigned)(sumW < maxW ? sumW : maxW);
-      dlo = (dlo & 0x00ffffffu) | (nc[0] << 24);
-      dhi = (dhi & 0xff000000u) | nc[1] | (nc[2] << 8) | (w << 16);
-    }
-  }
-}
 
 // address of a stored block in the page-locked host slabs
 __device__ __forceinline__ uint4 *stored_block(uint4 *const *slabs, int slot) {

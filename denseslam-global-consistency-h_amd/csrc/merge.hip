@@ -1,0 +1,437 @@
+// merge.hip -- fuse one local map into another on the device (dslam_merge_maps; ITMMainEngine::MergeLocalMap in the mirror).
+//
+// Reference: none.  The reference keeps its local maps apart for good; the law below is this project's own definition
+// (include/dslam_fusion.h states it in full).  The source is only read.
+//
+//   X~ : source voxels -> destination voxels, Y~ its inverse; the first three rows, row-major, float32 (host: double).
+//   1. push    every source voxel with w_depth > 0, in the order (rank r of its entry among the resident entries, linear
+//              index l), key r * 512 + l + 1, names the destination block B = floor(X~ p + 0.5) >> 3 it falls into;
+//   2. passes  k_merge_mark looks every B up in the destination: a hit sets the entry's bit in `touched`, a miss does
+//              atomicMax(keys[slot], key) on the slot AllocateSceneFromDepth would use and sets the slot's request bits.
+//              Three ordered selections (dslam_bits.h) then serve the requests in hash-index order: over q1 and over q2
+//              to give every request its rank among those of its own type, over q1 | q2 to give it its rank among all --
+//              with both the closed form of DESIGN.md section 3 says whether the pools still hold a block for it and
+//              which.  The winner's B is recomputed from its key.  One small read-back per pass tells the host whether
+//              another pass is needed (different blocks that asked for the same slot).
+//   3. pull    k_merge_blocks: one workgroup per touched destination block at a time (fixed grid, grid-stride over the
+//              ordered list of touched entries), lane t the voxels 2t and 2t + 1 -- the block moves as 16-byte accesses.
+//              Each voxel reads the source trilinearly at Y~ p' (to_map / gather_cell / lerp8 of multimap_device.h), packs
+//              the result as a voxel and merges it with combine_voxel (combine_device.h), as a swap-in does.
+// No kernel here waits for another workgroup; the pass loop is bounded by max_passes on the host.
+#include <chrono>
+#include <cmath>
+#include <cstring>
+
+#include "combine_device.h"
+#include "dslam_bits.h"
+#include "mesh_device.h"
+#include "multimap_device.h"
+
+#pragma clang fp contract(off)
+
+namespace dslam {
+
+constexpr int kMergeGrid = 512;      // workgroups of the mark and block kernels: two per CU of an MI355X
+constexpr int kMergeThreads = 256;
+
+// its own type: the selection kernel of this translation unit is not mesh.hip's
+struct SelLiveMerge : SelLive {};
+
+// the destination block a source voxel falls into; false: outside the table's short range
+__device__ __forceinline__ bool merge_target(const MultiMap &fwd, const HashEntry &he, int l, int B[3]) {
+  const Vec3 p = {(float)(he.pos[0] * kBlock + (l & 7)), (float)(he.pos[1] * kBlock + ((l >> 3) & 7)), (float)(he.pos[2] * kBlock + (l >> 6))};
+  const Vec3 q = to_map(fwd, p);
+  const float tx = floorf(q.x + 0.5f), ty = floorf(q.y + 0.5f), tz = floorf(q.z + 0.5f);
+  const bool ok = tx >= -262144.0f && tx < 262144.0f && ty >= -262144.0f && ty < 262144.0f && tz >= -262144.0f && tz < 262144.0f;
+  B[0] = ok ? (int)tx >> 3 : 0;
+  B[1] = ok ? (int)ty >> 3 : 0;
+  B[2] = ok ? (int)tz >> 3 : 0;
+  return ok;
+}
+
+__global__ void k_merge_begin(SceneCounters *cnt, MergeCounters *mc) {
+  cnt->base_free = cnt->last_free;
+  cnt->base_free_ex = cnt->last_free_ex;
+  mc->requests = 0; mc->served1 = 0; mc->served2 = 0;
+  mc->candidates = 0; mc->out_of_range = 0;
+}
+
+__global__ void k_merge_end(SceneCounters *cnt, const MergeCounters *mc) {
+  const int succ = mc->served1 + mc->served2;   // every success takes exactly one voxel-block slot
+  cnt->last_free = cnt->base_free - succ;
+  cnt->base_free = cnt->base_free - succ;
+  cnt->last_free_ex = cnt->base_free_ex - mc->served2;
+}
+
+struct MergeMarkParams {
+  const HashEntry *src_hash;
+  const uint2 *src_voxels;
+  const int *live_list;
+  MultiMap fwd;              // T = X~ (its map pointers are not used)
+  const HashEntry *dst_hash;
+  unsigned mask;
+  int num_buckets;
+  unsigned *keys, *q1, *q2, *req, *touched;
+  MergeCounters *mc;
+};
+
+__global__ __launch_bounds__(kMergeThreads) void k_merge_mark(MergeMarkParams p) {
+  const int live = p.mc->live;
+  const int lane = threadIdx.x & 63;
+  int n_cand = 0, n_oor = 0;
+  for (int job = blockIdx.x * 2; job < live * 2; job += (job & 1) ? gridDim.x * 2 - 1 : 1) {
+    const int r = job >> 1, l = (int)threadIdx.x + kMergeThreads * (job & 1);
+    const HashEntry he = load_entry(p.src_hash, p.live_list[r]);
+    bool cand = false;
+    int B[3] = {0, 0, 0};
+    if (he.ptr >= 0) {  // (uniform; a live entry holds a block)
+      const unsigned own = p.src_voxels[(size_t)he.ptr * kBlock3 + l].x;
+      if (((own >> 16) & 0xffu) != 0u) {
+        n_cand++;
+        cand = merge_target(p.fwd, he, l, B);
+        n_oor += cand ? 0 : 1;
+      }
+    }
+    // Neighbouring lanes are neighbouring voxels of a row and mostly fall into the same block: a lane whose right
+    // neighbour asks for the same block leaves the probe to it (keys grow with the lane, so the prober's is the largest)
+    const int rc = __shfl_down((int)cand, 1, 64), rx = __shfl_down(B[0], 1, 64), ry = __shfl_down(B[1], 1, 64), rz = __shfl_down(B[2], 1, 64);
+    if (!cand || (lane < 63 && rc && rx == B[0] && ry == B[1] && rz == B[2])) continue;
+    int h = hash_index(B[0], B[1], B[2], p.mask);
+    HashEntry e = load_entry(p.dst_hash, h);   // one 16-byte load per chain step
+    bool found = e.pos[0] == B[0] && e.pos[1] == B[1] && e.pos[2] == B[2] && e.ptr >= -1;
+    if (!found && e.ptr >= -1) {
+      while (e.offset >= 1) {
+        h = p.num_buckets + e.offset - 1;
+        e = load_entry(p.dst_hash, h);
+        if (e.pos[0] == B[0] && e.pos[1] == B[1] && e.pos[2] == B[2] && e.ptr >= -1) { found = true; break; }
+      }
+    }
+    const unsigned bit = 1u << (h & 31);
+    if (found) {
+      if (!(p.touched[h >> 5] & bit)) atomicOr(&p.touched[h >> 5], bit);
+    } else {
+      atomicMax(&p.keys[h], (unsigned)r * (unsigned)kBlock3 + (unsigned)l + 1u);
+      atomicOr(&(e.ptr >= -1 ? p.q2 : p.q1)[h >> 5], bit);
+      atomicOr(&p.req[h >> 5], bit);
+    }
+  }
+  // integer counts: the order of the additions does not matter
+  for (int d = 32; d > 0; d >>= 1) { n_cand += __shfl_xor(n_cand, d, 64); n_oor += __shfl_xor(n_oor, d, 64); }
+  if (lane == 0 && n_cand) {
+    atomicAdd(&p.mc->candidates, (unsigned long long)n_cand);
+    if (n_oor) atomicAdd(&p.mc->out_of_range, (unsigned long long)n_oor);
+  }
+}
+
+// rank of a request among the requests of its own type
+struct SelMergeRank {
+  DSLAM_SEL_NO_LOAD
+  int *ranks;
+  __device__ bool test(int, const NoPayload &) const { return true; }
+  __device__ void prologue() const {}
+  __device__ int emit(int t, int rank, bool, const NoPayload &) const { ranks[t] = rank; return 0; }
+  __device__ void finish(int) const {}
+};
+
+// the serve step: rank = requests of either type in front of this one, in hash-index order
+struct SelMergeServe {
+  DSLAM_SEL_NO_LOAD
+  HashEntry *hash;           // the destination
+  int num_buckets;
+  const int *alloc_list, *excess_list;
+  unsigned *alloc_bits, *touched;
+  const unsigned *q2;
+  unsigned *keys;
+  const int *ranks;
+  SceneCounters *cnt;
+  MergeCounters *mc;
+  const HashEntry *src_hash;
+  const int *live_list;
+  MultiMap fwd;
+  int *born;
+  int born_stamp;
+  __device__ bool test(int, const NoPayload &) const { return true; }
+  __device__ void prologue() const {}
+  __device__ int emit(int t, int rank, bool, const NoPayload &) const {
+    const bool is2 = (q2[t >> 5] >> (t & 31)) & 1u;
+    const int own = ranks[t];
+    const int k1 = is2 ? rank - own : own, k2 = is2 ? own : rank - own;
+    // the winner: the block the largest key asked for (and the keys clean for the next pass)
+    const unsigned kz = keys[t] - 1u;
+    keys[t] = 0;
+    int B[3];
+    merge_target(fwd, load_entry(src_hash, live_list[kz >> 9]), (int)(kz & 511u), B);
+    // voxel-block slots taken by all earlier requests in hash-index order (closed form)
+    const int base_free = cnt->base_free, base_free_ex = cnt->base_free_ex;
+    const int avail_vba = base_free + 1, avail_ex = base_free_ex + 1;
+    const int vr = k1 + (k2 < avail_ex ? k2 : avail_ex);
+    if (vr >= avail_vba || (is2 && k2 >= avail_ex)) return 0;
+    const int slot = alloc_list[base_free - vr];
+    int entry = t;
+    if (is2) {
+      const int ex_off = excess_list[base_free_ex - k2];
+      hash[t].offset = ex_off + 1;
+      entry = num_buckets + ex_off;
+    }
+    store_entry(hash, entry, B[0], B[1], B[2], 0, slot);
+    bit_set(alloc_bits, entry);
+    bit_set(touched, entry);
+    if (born) born[slot] = born_stamp;
+    atomicAdd(is2 ? &mc->served2 : &mc->served1, 1);
+    return 0;
+  }
+  __device__ void finish(int) const {}
+};
+
+struct SelMergeTouched {
+  DSLAM_SEL_NO_LOAD
+  __device__ bool test(int, const NoPayload &) const { return true; }
+  __device__ void prologue() const {}
+  __device__ int emit(int, int, bool, const NoPayload &) const { return 0; }
+  __device__ void finish(int) const {}
+};
+
+struct MergeBlockParams {
+  const HashEntry *dst_hash;
+  uint4 *dst_voxels;         // two voxels per element
+  const int *touched_list;
+  const MergeCounters *mc;
+  MultiMap src;              // the source read from the destination's voxel frame: T = Y~
+  int max_w, with_colour;
+  unsigned long long *changed;   // [gridDim.x]
+};
+
+// the source resampled at the destination voxel (px, py, pz), packed as a voxel; the empty voxel where the source has
+// nothing to give
+__device__ __forceinline__ uint2 merge_resample(const MergeBlockParams &p, const VolumeRef &vol, int px, int py, int pz) {
+  const uint2 empty = make_uint2(kEmptyVoxelLo, kEmptyVoxelHi);
+  if (p.src.identity) {
+    const int ptr = find_block_ptr(vol.hash, vol.num_buckets, vol.mask, px >> 3, py >> 3, pz >> 3);
+    if (ptr < 0) return empty;
+    uint2 v = vol.voxels[(size_t)ptr * kBlock3 + ((px & 7) | ((py & 7) << 3) | ((pz & 7) << 6))];
+    if (!p.with_colour) v.y &= 0xff00ffffu;
+    return v;
+  }
+  const Vec3 pt = {(float)px, (float)py, (float)pz};
+  const Vec3 q = to_map(p.src, pt);
+  // a block coordinate outside the short range is never resident (and this keeps the casts below defined)
+  if (!(fabsf(q.x) < 262144.0f && fabsf(q.y) < 262144.0f && fabsf(q.z) < 262144.0f)) return empty;
+  const float fx = floorf(q.x), fy = floorf(q.y), fz = floorf(q.z);
+  uint2 t[8];
+  if (!gather_cell(vol, (int)fx, (int)fy, (int)fz, t)) return empty;
+  unsigned wd = 255u, wc = 255u;
+  float s[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const unsigned a = (t[k].x >> 16) & 0xffu, c = (t[k].y >> 16) & 0xffu;
+    wd = a < wd ? a : wd;
+    wc = c < wc ? c : wc;
+    s[k] = sdf_to_float((short)(t[k].x & 0xffffu));
+  }
+  if (wd == 0u) return empty;
+  const float cx = q.x - fx, cy = q.y - fy, cz = q.z - fz;
+  uint2 out;
+  out.x = (unsigned)(unsigned short)float_to_sdf(lerp8(s, cx, cy, cz)) | (wd << 16);
+  out.y = 0u;
+  if (p.with_colour && wc != 0u) {
+    float c0[8], c1[8], c2[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) { c0[k] = (float)(t[k].x >> 24); c1[k] = (float)(t[k].y & 0xffu); c2[k] = (float)((t[k].y >> 8) & 0xffu); }
+    out.x |= (unsigned)(unsigned char)(lerp8(c0, cx, cy, cz) + 0.5f) << 24;
+    out.y = (unsigned)(unsigned char)(lerp8(c1, cx, cy, cz) + 0.5f) | ((unsigned)(unsigned char)(lerp8(c2, cx, cy, cz) + 0.5f) << 8) | (wc << 16);
+  }
+  return out;
+}
+
+__global__ __launch_bounds__(kMergeThreads) void k_merge_blocks(MergeBlockParams p) {
+  const int n = p.mc->touched;
+  const VolumeRef vol = volume_of(p.src);
+  const int tid = threadIdx.x;
+  const int x = (tid & 3) * 2, y = (tid >> 2) & 7, z = tid >> 5;
+  int changed = 0;
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    const HashEntry he = load_entry(p.dst_hash, p.touched_list[i]);
+    if (he.ptr < 0) continue;  // (uniform; a touched entry holds a block)
+    uint4 *blk = p.dst_voxels + (size_t)he.ptr * (kBlock3 / 2);
+    const uint4 was = blk[tid];
+    uint4 d = was;
+    const int px = he.pos[0] * kBlock + x, py = he.pos[1] * kBlock + y, pz = he.pos[2] * kBlock + z;
+    const uint2 s0 = merge_resample(p, vol, px, py, pz);
+    const uint2 s1 = merge_resample(p, vol, px + 1, py, pz);
+    combine_voxel(s0.x, s0.y, d.x, d.y, p.max_w);
+    combine_voxel(s1.x, s1.y, d.z, d.w, p.max_w);
+    const int c = (int)(d.x != was.x || d.y != was.y) + (int)(d.z != was.z || d.w != was.w);
+    if (c) blk[tid] = d;
+    changed += c;
+  }
+  // one count per workgroup, summed by the host (a workgroup without a block writes its zero)
+  __shared__ int red[kMergeThreads / 64];
+  for (int dlt = 32; dlt > 0; dlt >>= 1) changed += __shfl_xor(changed, dlt, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = changed;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long v = 0;
+    for (int w = 0; w < kMergeThreads / 64; w++) v += (unsigned long long)red[w];
+    p.changed[blockIdx.x] = v;
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------
+namespace {
+
+int ensure_merge_scratch(dslam_engine *e, int src_entries, int dst_entries) {
+  MergeScratch &have = e->merge;
+  if (have.keys && have.src_entries >= src_entries && have.dst_entries >= dst_entries) return DSLAM_OK;
+  DSLAM_HIP(hipStreamSynchronize(e->stream));   // (nothing in flight may still use the old set)
+  MergeScratch m;
+  m.src_entries = std::max(src_entries, have.src_entries);
+  m.dst_entries = std::max(dst_entries, have.dst_entries);
+  m.words = bit_tiles(m.dst_entries) * kBitTileWords;
+  DSLAM_TRY(m.keys.alloc_zeroed((size_t)m.dst_entries, e->stream));
+  DSLAM_TRY(m.bits.alloc((size_t)m.words * 4));
+  DSLAM_TRY(m.ranks.alloc((size_t)m.dst_entries));
+  DSLAM_TRY(m.touched_list.alloc((size_t)m.dst_entries));
+  DSLAM_TRY(m.live_list.alloc((size_t)m.src_entries));
+  DSLAM_TRY(m.counters.alloc_zeroed(1, e->stream));
+  DSLAM_TRY(m.counters_host.alloc(1));
+  DSLAM_TRY(m.changed.alloc((size_t)kMergeGrid, hipHostMallocMapped));
+  have = std::move(m);
+  return DSLAM_OK;
+}
+
+// dslam_debug_merge_phases: wall clock per phase, each closed by a wait for the stream (only when the hook is on)
+struct PhaseClock {
+  dslam_engine *e;
+  std::chrono::steady_clock::time_point t0;
+  explicit PhaseClock(dslam_engine *e_) : e(e_), t0(std::chrono::steady_clock::now()) {}
+  int lap(int phase) {
+    if (!e->merge_phases_on) return DSLAM_OK;
+    DSLAM_HIP(hipStreamSynchronize(e->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    e->merge_phase_ms[phase] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+    return DSLAM_OK;
+  }
+};
+
+}  // namespace
+
+// src / dst / X / params already checked and defaulted by dslam_merge_maps
+int launch_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float *X_in,
+                      const dslam_merge_params *mp, dslam_merge_result *res) {
+  DSLAM_TRY(ensure_scratch(e, std::max(src->n_entries, dst->n_entries), std::max(src->p.num_local_blocks, dst->p.num_local_blocks)));
+  DSLAM_TRY(ensure_merge_scratch(e, src->n_entries, dst->n_entries));
+  MergeScratch &m = e->merge;
+  const int N = dst->n_entries;
+  unsigned *q1 = m.bits, *q2 = m.bits + m.words, *req = m.bits + 2 * (size_t)m.words, *touched = m.bits + 3 * (size_t)m.words;
+  MergeCounters *mc = m.counters;
+
+  // X~ and Y~ = (R^T, -R^T t~): double, rounded to float32
+  MultiMap fwd, inv;
+  memset(&fwd, 0, sizeof fwd);
+  memset(&inv, 0, sizeof inv);
+  {
+    const double vs = (double)src->p.voxel_size;
+    double R[3][3], t[3];
+    bool identity = true;
+    for (int i = 0; i < 16; i++) identity = identity && X_in[i] == ((i % 5) == 0 ? 1.0f : 0.0f);
+    for (int row = 0; row < 3; row++) {
+      for (int col = 0; col < 3; col++) R[row][col] = (double)X_in[col * 4 + row];
+      t[row] = (double)X_in[12 + row] / vs;
+    }
+    for (int row = 0; row < 3; row++) {
+      for (int col = 0; col < 3; col++) {
+        fwd.T[row * 4 + col] = (float)R[row][col];
+        inv.T[row * 4 + col] = (float)R[col][row];
+      }
+      fwd.T[row * 4 + 3] = (float)t[row];
+      inv.T[row * 4 + 3] = (float)-((R[0][row] * t[0] + R[1][row] * t[1]) + R[2][row] * t[2]);
+    }
+    fwd.identity = inv.identity = identity ? 1 : 0;
+  }
+  inv.hash = src->hash; inv.voxels = src->voxels;
+  inv.mask = (unsigned)(src->p.num_buckets - 1); inv.num_buckets = src->p.num_buckets;
+
+  for (double &ms : e->merge_phase_ms) ms = 0.0;
+  PhaseClock clock(e);
+  DSLAM_HIP(hipMemsetAsync(m.bits, 0, (size_t)m.words * 4 * sizeof(unsigned), e->stream));
+  SelLiveMerge live;
+  live.hash = src->hash;
+  DSLAM_TRY(launch_bits_select(e, src->alloc_bits, src->n_entries, live, m.live_list, src->n_entries, &mc->live, src->counters));
+  DSLAM_HIP(hipGetLastError());
+  DSLAM_TRY(clock.lap(0));
+
+  MergeMarkParams kp;
+  memset(&kp, 0, sizeof kp);
+  kp.src_hash = src->hash; kp.src_voxels = src->voxels; kp.live_list = m.live_list;
+  kp.fwd = fwd;
+  kp.dst_hash = dst->hash; kp.mask = (unsigned)(dst->p.num_buckets - 1); kp.num_buckets = dst->p.num_buckets;
+  kp.keys = m.keys; kp.q1 = q1; kp.q2 = q2; kp.req = req; kp.touched = touched; kp.mc = mc;
+
+  SelMergeRank rank;
+  rank.ranks = m.ranks;
+  SelMergeServe serve;
+  serve.hash = dst->hash; serve.num_buckets = dst->p.num_buckets;
+  serve.alloc_list = dst->alloc_list; serve.excess_list = dst->excess_list;
+  serve.alloc_bits = dst->alloc_bits; serve.touched = touched; serve.q2 = q2; serve.keys = m.keys; serve.ranks = m.ranks;
+  serve.cnt = dst->counters; serve.mc = mc;
+  serve.src_hash = src->hash; serve.live_list = m.live_list; serve.fwd = fwd;
+  serve.born = dst->alloc_born; serve.born_stamp = dst->alloc_born_stamp;
+
+  memset(res, 0, sizeof *res);
+  MergeCounters *host = m.counters_host;
+  for (int pass = 0;; pass++) {
+    if (pass > 0) DSLAM_HIP(hipMemsetAsync(m.bits, 0, (size_t)m.words * 3 * sizeof(unsigned), e->stream));
+    hipLaunchKernelGGL(k_merge_begin, dim3(1), dim3(1), 0, e->stream, dst->counters.get(), mc);
+    hipLaunchKernelGGL(k_merge_mark, dim3(kMergeGrid), dim3(kMergeThreads), 0, e->stream, kp);
+    dbg_sync(e, "k_merge_mark");
+    DSLAM_TRY(clock.lap(1));
+    DSLAM_TRY(launch_bits_select(e, q1, N, rank, (int *)nullptr, N, (int *)nullptr, dst->counters));
+    DSLAM_TRY(launch_bits_select(e, q2, N, rank, (int *)nullptr, N, (int *)nullptr, dst->counters));
+    DSLAM_TRY(launch_bits_select(e, req, N, serve, (int *)nullptr, N, &mc->requests, dst->counters));
+    hipLaunchKernelGGL(k_merge_end, dim3(1), dim3(1), 0, e->stream, dst->counters.get(), (const MergeCounters *)mc);
+    DSLAM_HIP(hipGetLastError());
+    DSLAM_TRY(clock.lap(2));
+    DSLAM_HIP(hipMemcpyAsync(host, mc, sizeof(MergeCounters), hipMemcpyDeviceToHost, e->stream));
+    DSLAM_HIP(hipStreamSynchronize(e->stream));
+    DSLAM_TRY(clock.lap(4));
+    const int served = host->served1 + host->served2;
+    res->passes = pass + 1;
+    res->blocks_allocated += served;
+    if (pass == 0) {
+      res->src_blocks = host->live;
+      res->src_candidates = (int64_t)host->candidates;
+      res->out_of_range = (int64_t)host->out_of_range;
+    }
+    if (host->requests == 0) break;
+    if (served == 0 || res->passes >= mp->max_passes) {
+      res->exhausted = 1;
+      res->requests_unserved = host->requests - served;
+      break;
+    }
+  }
+  SelMergeTouched sel_touched;
+  DSLAM_TRY(launch_bits_select(e, touched, N, sel_touched, m.touched_list, N, &mc->touched, dst->counters));
+  MergeBlockParams bp;
+  memset(&bp, 0, sizeof bp);
+  bp.dst_hash = dst->hash; bp.dst_voxels = reinterpret_cast<uint4 *>(dst->voxels);
+  bp.touched_list = m.touched_list; bp.mc = mc;
+  bp.src = inv;
+  bp.max_w = dst->p.max_w; bp.with_colour = mp->with_colour;
+  bp.changed = m.changed.device();
+  DSLAM_TRY(clock.lap(2));   // (the ordered list of touched entries counts as selection work)
+  hipLaunchKernelGGL(k_merge_blocks, dim3(kMergeGrid), dim3(kMergeThreads), 0, e->stream, bp);
+  dbg_sync(e, "k_merge_blocks");
+  DSLAM_HIP(hipGetLastError());
+  DSLAM_TRY(clock.lap(3));
+  DSLAM_HIP(hipMemcpyAsync(host, mc, sizeof(MergeCounters), hipMemcpyDeviceToHost, e->stream));
+  DSLAM_HIP(hipStreamSynchronize(e->stream));
+  res->blocks_touched = host->touched;
+  unsigned long long changed = 0;
+  for (int g = 0; g < kMergeGrid; g++) changed += m.changed[g];
+  res->voxels_changed = (int64_t)changed;
+  DSLAM_TRY(clock.lap(4));
+  return device_errors(e);
+}
+
+}  // namespace dslam

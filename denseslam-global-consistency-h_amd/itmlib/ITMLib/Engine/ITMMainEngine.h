@@ -453,6 +453,24 @@ class ITMMainEngine {
     ms->estimatedGlobalPose.SetM(M);
     return true;
   }
+  /// (extension) Fuse local map `src` into local map `dst` on the device (dslam_merge_maps, law in DESIGN.md section 14)
+  /// under X = T_dst T_src^-1 from the two estimatedGlobalPoses, composed as AlignLocalMap composes it -- call that first.
+  /// `src` is only read and stays in the graph: dropping it is the caller's decision.  Returns false when the pools of
+  /// `dst` ran dry (what could be allocated is fused all the same).
+  bool MergeLocalMap(int src, int dst, dslam_merge_result *out = nullptr) {
+    const ITMLocalMap *ms = mapManager->getLocalMap(src);
+    ITMLocalMap *md = mapManager->getLocalMap(dst);
+    double Ts[16], Td[16], inv[16], X[16];
+    for (int i = 0; i < 16; i++) { Ts[i] = (double)ms->estimatedGlobalPose.GetM().m[i]; Td[i] = (double)md->estimatedGlobalPose.GetM().m[i]; }
+    RigidInverse(Ts, inv);
+    RigidProduct(Td, inv, X);
+    float Xf[16];
+    for (int i = 0; i < 16; i++) Xf[i] = (float)X[i];
+    dslam_merge_result res;
+    dslam_check(dslam_merge_maps(engine_, ms->scene->handle, md->scene->handle, Xf, nullptr, &res), "dslam_merge_maps");
+    if (out) *out = res;
+    return res.exhausted == 0;
+  }
   /// inverse of a rigid transform (column-major): [R^T | -(R^T t)], each sum evaluated left to right
   static void RigidInverse(const double M[16], double out[16]) {
     for (int r = 0; r < 3; r++) {

@@ -572,6 +572,54 @@ int dslam_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_sce
 /* Test hook: the 33 raw sums (pivot at the origin) of the engine's most recent evaluation.  Error if none has run. */
 int dslam_debug_register_sums(dslam_engine *e, double out[33]);
 
+/* Fuse one local map into another on the device (no counterpart in the reference; the law is this project's own,
+ * DESIGN.md section 14).  X is what dslam_register_maps takes and returns: source frame -> destination frame, metres,
+ * column-major.  X~ is X with its translation in voxel units, Y~ its inverse (R^T, -R^T t); both are formed on the host
+ * in double and rounded to float32 (12 entries each); an X that is exactly the identity reads at p itself both ways.
+ *   1. targets (push): source voxels in order -- resident entries ascending by hash index (rank r), then the voxel's
+ *      linear index l (x fastest) -- with key r * 512 + l + 1; a candidate has w_depth > 0 (no band gate: observed free
+ *      space merges too); q = X~ p, rows evaluated as ((a x + b y) + c z) + d in float32; target voxel floor(q + 0.5f)
+ *      per axis, target block B = t >> 3; a B outside int16 is skipped and counted in out_of_range;
+ *   2. allocation passes: every candidate's B is looked up in dst; a hit marks the entry touched, a miss requests the
+ *      slot the allocation pass would use for that bucket (empty bucket head: type 1, otherwise the chain end: type 2)
+ *      and a slot keeps the largest key that asked.  Requested slots are served in ascending hash-index order exactly
+ *      as AllocateSceneFromDepth deals pool slots (the successful request that has v voxel-block slots taken in front
+ *      of it gets voxelAllocationList[lastFree - v]; type 2 also takes the next excess slot; a request that finds a
+ *      pool empty fails and takes nothing); the entry gets the winner's B and is touched, its block holds empty
+ *      voxels.  Blocks that lost a slot ask again in the next pass.  Passes stop when a pass has no miss; or serves
+ *      nothing while misses remain (exhausted = 1, requests_unserved = the slots asked for in that pass); or when
+ *      max_passes have run (exhausted = 1, requests_unserved = the requests of the last pass that were not served);
+ *   3. fusion (pull): every voxel p' of every touched destination block: q' = Y~ p', cell floor(q'), fractions c; all 8
+ *      taps of the cell must lie in resident blocks of the source with w_depth > 0, else the voxel is left alone;
+ *      d = the trilinear blend of raw / 32767 in dslam_register_maps' order; the resampled voxel is packed:
+ *      sdf = (short)(d * 32767), w_depth = min of the 8 taps'; its colour half is live only with with_colour and all 8
+ *      w_color > 0: each channel (unsigned char)(blend((float)c_k) + 0.5f), w_color = min of the taps'; otherwise
+ *      w_color = 0.  With the identity the resampled voxel is the source's voxel at p' as stored (an absent block reads
+ *      as the empty voxel).  It is then merged into the resident voxel exactly as a swapped-out block's host copy is
+ *      (CombineVoxelInformation, dst's max_w); a voxel is stored only if it changed (voxels_changed).
+ * Under a non-identity X the outermost one-voxel layer of what src saw is therefore not transferred.
+ * src is only read.  dst's render states are not touched (their visible lists stay as they were); GetImage memos and
+ * front-end records of dst are invalidated as by dslam_upload_scene_state.  Waits for the stream on synchronous and
+ * asynchronous engines.  DSLAM_ERR_INVALID with nothing changed: a NULL argument other than params, a scene of another
+ * engine, src == dst, voxel_size or mu that differ bitwise, a scene that uses swapping or is sharded, a non-finite X or
+ * one whose rotation block is not orthonormal to 1e-4, a negative max_passes. */
+typedef struct {
+  int32_t max_passes;              /* 0 -> 16 */
+  int32_t with_colour;             /* default 1 */
+} dslam_merge_params;
+typedef struct {
+  int32_t passes, exhausted;       /* allocation passes run; 1 if the pools ran dry (or max_passes was reached) */
+  int32_t src_blocks, blocks_allocated, blocks_touched, requests_unserved;
+  int64_t src_candidates, out_of_range, voxels_changed;
+} dslam_merge_result;
+int dslam_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_dst_from_src[16],
+                     const dslam_merge_params *params /* NULL: defaults */, dslam_merge_result *result);
+/* Bench hook: out_ms (may be NULL) receives the wall clock of the engine's last merge by phase -- [0] the source's live
+ * list, [1] mark kernels, [2] ordered selections (ranks, serve, touched list), [3] block kernel, [4] read-backs -- measured
+ * only while the hook is on, when every phase ends with a wait for the stream (the bytes do not change); then `enable`
+ * turns the hook on or off for the merges that follow. */
+int dslam_debug_merge_phases(dslam_engine *e, int enable, double out_ms[5]);
+
 /* ---- depth tracker (ICP) ---------------------------------------------------------------------- */
 /* trackingController->Track(trackingState, view) (InfiniTamDriver.h:151-163, reached through
  * DenseSlam.cpp:200-206 when the reference runs without ORB-SLAM2 odometry): upstream InfiniTAM v2's
