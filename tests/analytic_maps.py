@@ -155,11 +155,15 @@ class Map:
         self.grid_sdf = np.full(shape, 32767, np.int16)
         self.grid_found = np.zeros(shape, bool)
         self.grid_clr = np.zeros(shape + (3,), np.uint8)
+        self.grid_wd = np.zeros(shape, np.uint8)
+        self.grid_wc = np.zeros(shape, np.uint8)
         v = self.voxels.reshape(-1, 8, 8, 8)  # [n, z, y, x]
         for i, b in enumerate(self.block_pos - lo):
             sl = tuple(slice(int(c) * 8, int(c) * 8 + 8) for c in b)
             self.grid_sdf[sl] = v[i]["sdf"].transpose(2, 1, 0)
             self.grid_clr[sl] = v[i]["clr"].transpose(2, 1, 0, 3)
+            self.grid_wd[sl] = v[i]["w_depth"].transpose(2, 1, 0)
+            self.grid_wc[sl] = v[i]["w_color"].transpose(2, 1, 0)
             self.grid_found[sl] = True
 
     def lookup(self, p):
@@ -174,6 +178,14 @@ class Map:
         clr = np.where(found[..., None], self.grid_clr[idx], 0)
         return sdf, clr, found
 
+    def lookup_weights(self, p):
+        """(w_depth, w_color) of integer voxel coordinates p [..., 3], 0 where the voxel is missing."""
+        q = np.asarray(p, np.int64) - self.grid_lo
+        ok = np.all((q >= 0) & (q < np.array(self.grid_wd.shape)), axis=-1)
+        qc = np.where(ok[..., None], q, 0)
+        idx = (qc[..., 0], qc[..., 1], qc[..., 2])
+        return np.where(ok, self.grid_wd[idx], np.uint8(0)), np.where(ok, self.grid_wc[idx], np.uint8(0))
+
     def scene_params(self, pkg, **over):
         kw = dict(voxel_size=self.vs, mu=self.mu, max_w=100, frustum_min=0.05, frustum_max=5.0,
                   num_local_blocks=self.num_local_blocks, num_buckets=self.num_buckets, num_excess=self.num_excess)
@@ -182,10 +194,17 @@ class Map:
 
 
 def build_map(geom, vs, mu, box_lo, box_hi, band=None, holes=0.0, seed=0, num_buckets=0x400, num_excess=None,
-              colour=None, w_depth=1, local_factor=8, max_blocks=6000):
+              colour=None, w_depth=1, local_factor=8, max_blocks=6000, w_depth_field=None, w_color_field=None,
+              keep_sdf=False):
     """Every block inside the metric box [box_lo, box_hi) with a voxel within `band` (default 1.5 mu) of the surface.
     `holes`: fraction of those blocks left out (seeded).  `colour(x)` -> [..., 3] float in [0, 255] fills clr and
-    sets w_color = 1.  The voxel pool holds `local_factor` times the blocks, so the mesh never saturates."""
+    sets w_color = 1.  The voxel pool holds `local_factor` times the blocks, so the mesh never saturates.
+
+    `w_depth_field(p)` / `w_color_field(p)`: integers in 0 .. 255 per integer voxel coordinate p [..., 3], in place of the
+    one `w_depth` / the w_color of 1.  A voxel whose w_depth is 0 is stored as fusion leaves a voxel it never observed
+    (sdf 32767, no weight, no colour) -- except where `keep_sdf` (True, or a callable on p that returns a mask) says to
+    keep the analytic sdf and the colour under the weight 0: a voxel the law is defined for, which fusion cannot
+    produce, and the only one on which the weight alone decides a read.  A w_color of 0 keeps the voxel's colour bytes."""
     band = 1.5 * mu if band is None else band
     bs = 8 * vs
     blo = np.floor(np.asarray(box_lo) / bs).astype(np.int64)
@@ -214,6 +233,18 @@ def build_map(geom, vs, mu, box_lo, box_hi, band=None, holes=0.0, seed=0, num_bu
         pts = (bpos[:, None, :] * 8 + loc[None]) * vs
         vox["clr"] = np.clip(np.floor(colour(pts)), 0, 255).astype(np.uint8)
         vox["w_color"] = 1
+    if w_depth_field is not None or w_color_field is not None:
+        P = bpos[:, None, :] * 8 + loc[None]
+        if w_color_field is not None:
+            vox["w_color"] = np.asarray(w_color_field(P)).astype(np.uint8)
+        if w_depth_field is not None:
+            wd = np.asarray(w_depth_field(P))
+            assert wd.min() >= 0 and wd.max() <= 255
+            vox["w_depth"] = wd.astype(np.uint8)
+            keep = np.asarray(keep_sdf(P), bool) if callable(keep_sdf) else np.full(wd.shape, bool(keep_sdf))
+            unobserved = np.zeros((), VOXEL_DTYPE)
+            unobserved["sdf"] = 32767
+            vox[(wd == 0) & ~keep] = unobserved
     n = len(bpos)
     nl = max(0x100, local_factor * n)
     nx = num_excess if num_excess is not None else max(0x100, n)

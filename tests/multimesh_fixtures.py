@@ -96,5 +96,12 @@ def seam_wall_offsets(pos):
 @functools.lru_cache(maxsize=None)
 def reference(name):
     """mesh_maps (with colours) of a fixture, computed once per process."""
-    maps = two_spheres()[0] if name == "two_spheres" else seam_planes()
-    return r64.mesh_maps(maps, colour=True)
+    return r64.mesh_maps(fixture(name), colour=True)
+
+
+def fixture(name):
+    """The list of posed maps of a fixture by its name."""
+    if name == "weighted_spheres":   # weights that vary per voxel, and a slab of map 0 that weighs nothing
+        import weighted_fixtures as wf   # (it imports this module)
+        return wf.mesh_spheres()
+    return two_spheres()[0] if name == "two_spheres" else seam_planes()

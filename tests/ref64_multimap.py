@@ -6,8 +6,9 @@ whose blocks project into p's 8x8 tile, in list order, at q_i = T~_i p (T~: tran
 report found are combined: none -> not found (the coarse step takes the 8-voxel block step; a trilinear read returns
 the first candidate's read), one -> its value, several -> sum(w v) / sum(w) (sum(w) = 0: 1.0, or the first
 contributor's normal / colour).  w: the voxel's w_depth (nearest read), the trilinear w_depth (trilinear read, normal),
-the trilinear w_color (colour).  Predicates are evaluated in float64 with the tie flags of ref64.cast_rays, plus the
-cell boundaries where a map's "any tap found" of a trilinear read flips.
+the trilinear w_color (colour) -- each voxel's own stored weights (a missing voxel weighs 0), so a fused map, whose
+weights run from 0 to max_w from one voxel to the next, is read as it is.  Predicates are evaluated in float64 with the
+tie flags of ref64.cast_rays, plus the cell boundaries where a map's "any tap found" of a trilinear read flips.
 """
 import numpy as np
 
@@ -25,21 +26,31 @@ class Posed:
         self.identity = bool(np.array_equal(np.asarray(T, F), np.eye(4, dtype=F)))
         self.R = self.T[:3, :3]
         self.t_vox = self.T[:3, 3] / float(F(m.vs))
-        found = m.voxels["w_depth"]
-        self.w_depth = float(found.flat[0]) if found.size else 0.0
-        self.w_color = float(m.voxels["w_color"].flat[0]) if found.size else 0.0
-        assert (m.voxels["w_depth"] == self.w_depth).all() and (m.voxels["w_color"] == self.w_color).all()
+        # overrides, for the alternative laws the tests hold the kernel away from: a number makes every stored voxel of
+        # the map weigh that much; weight_read = "nearest" gives a trilinear read the weight of its nearest tap;
+        # colour_weight = "w_depth" gives the colour the confidence of the sdf
+        self.w_depth = self.w_color = None
+        self.weight_read = "trilinear"
+        self.colour_weight = "w_color"
 
     def to_map(self, p):
         return p if self.identity else p @ self.R.T + self.t_vox
 
+    def weights(self, p, found):
+        """(w_depth, w_color) as float64 of integer voxel coordinates p, whose `found` the caller has from m.lookup."""
+        wd, wc = self.m.lookup_weights(p)
+        wd = wd.astype(np.float64) if self.w_depth is None else found * float(self.w_depth)
+        wc = wc.astype(np.float64) if self.w_color is None else found * float(self.w_color)
+        return wd, wc
+
 
 def set_weights(m, w_depth, w_color=None):
-    """Give every voxel of map `m` these weights (its uploaded pool `vba` too)."""
+    """Give every voxel of map `m` these weights (its uploaded pool `vba` and its lookup grid too)."""
     m.voxels["w_depth"] = w_depth
     if w_color is not None:
         m.voxels["w_color"] = w_color
     m.vba[m.ptrs] = m.voxels
+    m._build_grid()
     return m
 
 
@@ -75,10 +86,15 @@ def _trilinear(pm, q, colour=False):
     for dz in (0, 1):
         for dy in (0, 1):
             for dx in (0, 1):
-                s, clr, f = pm.m.lookup(q0 + np.array([dx, dy, dz]))
+                tap = q0 + np.array([dx, dy, dz])
+                s, clr, f = pm.m.lookup(tap)
                 w = (c[:, 0] if dx else 1 - c[:, 0]) * (c[:, 1] if dy else 1 - c[:, 1]) * (c[:, 2] if dz else 1 - c[:, 2])
                 acc += (w[:, None] * clr) if colour else w * s
-                wsum += w * f * (pm.w_color if colour else pm.w_depth)
+                wt = pm.weights(tap, f)[1 if colour and pm.colour_weight == "w_color" else 0]
+                if pm.weight_read == "nearest":
+                    wsum += np.where(np.all((c >= 0.5) == np.array([dx, dy, dz], bool), axis=1), wt, 0.0)
+                else:
+                    wsum += w * wt
                 anyf |= f
     return (acc if colour else acc / 32767.0), wsum, anyf
 
@@ -110,7 +126,43 @@ def _floor_tie(q, tol):
     return np.any(np.abs(q - np.round(q)) < tol, axis=1)
 
 
-def multi_trilinear(maps, cand, p, tie, tie_tol):
+def _floor_flip(pm, q, tol):
+    """_floor_tie, kept only where the boundary decides something.  A trilinear read and its trilinear weight are
+    continuous across a cell boundary (the taps that enter or leave have the coefficient 0 there), so the law's result can
+    jump only where one of its predicates flips: the map's `any tap found`, or its weight's `> 0` (with integer weights the
+    sum over the maps is 0 only where every tap with a positive coefficient weighs 0, so `den > 0` can flip nowhere else)."""
+    close = np.abs(q - np.round(q)) < tol
+    tie = close.sum(axis=1) > 1          # near a boundary on two axes at once: flagged as the plain flag does
+    for a in range(3):
+        r = np.round(q[:, a])
+        near = np.nonzero(close[:, a] & ~tie)[0]
+        if len(near):
+            lo, hi = q[near].copy(), q[near].copy()
+            lo[:, a], hi[:, a] = r[near] - 0.25, r[near] + 0.25
+            (_, w0, f0), (_, w1, f1) = _trilinear(pm, lo), _trilinear(pm, hi)
+            tie[near] |= (f0 != f1) | ((w0 > 0) != (w1 > 0))
+    return tie
+
+
+def _round_flip(pm, q, tol):
+    """A coordinate of q within tol of a half, kept only where the two voxels iround chooses between differ in what the
+    nearest read takes from them (found, sdf, w_depth): between two missing voxels nothing is decided."""
+    frac = np.abs(q) - np.floor(np.abs(q))
+    close = np.abs(frac - 0.5) < tol
+    tie = close.sum(axis=1) > 1          # near a half on two axes at once: flagged as the plain flag does
+    for a in range(3):
+        near = np.nonzero(close[:, a] & ~tie)[0]
+        if len(near):
+            lo, hi = q[near].copy(), q[near].copy()
+            lo[:, a] -= 0.25
+            hi[:, a] += 0.25
+            v0, v1 = ref64._iround(lo), ref64._iround(hi)
+            (s0, _, f0), (s1, _, f1) = pm.m.lookup(v0), pm.m.lookup(v1)
+            tie[near] |= (f0 != f1) | (f0 & ((s0 != s1) | (pm.weights(v0, f0)[0] != pm.weights(v1, f1)[0])))
+    return tie
+
+
+def multi_trilinear(maps, cand, p, tie, tie_tol, sharp_ties=False):
     """Combined trilinear sdf read at world points p [n, 3]; cand [n, maps] bool."""
     vals, ws, fs = [], [], []
     first_any = np.full(len(p), np.nan)
@@ -121,15 +173,17 @@ def multi_trilinear(maps, cand, p, tie, tie_tol):
             q = pm.to_map(p[sel])
             v[sel], w[sel], f[sel] = _trilinear(pm, q)
             if cand.sum(1).max() > 1:
-                tie[sel] |= (cand[sel].sum(1) > 1) & _floor_tie(q, tie_tol)
+                tie[sel] |= (cand[sel].sum(1) > 1) & (_floor_flip(pm, q, tie_tol) if sharp_ties else _floor_tie(q, tie_tol))
         first_any = np.where(np.isnan(first_any) & sel, v, first_any)
         vals.append(v), ws.append(w), fs.append(f & sel)
     out, _ = _combine(vals, ws, fs, np.where(np.isnan(first_any), 1.0, first_any), fallback=1.0)
     return out
 
 
-def cast_rays(maps, M, intr, W, H, tie_tol=1e-4, max_steps=4000):
-    """ref64.cast_rays over the composite.  Returns the same dict plus `cand` [H, W, maps] (the pixel's cell mask)."""
+def cast_rays(maps, M, intr, W, H, tie_tol=1e-4, max_steps=4000, sharp_ties=False):
+    """ref64.cast_rays over the composite.  Returns the same dict plus `cand` [H, W, maps] (the pixel's cell mask).
+    sharp_ties: flag a voxel or cell boundary only where it decides something (_round_flip, _floor_flip) -- fewer ties, so
+    more pixels held to the bound."""
     vs, mu = float(F(maps[0].m.vs)), float(F(maps[0].m.mu))
     rng, cmask = front_end(maps, M, intr, W, H)
     fx, fy, cx, cy = (float(F(v)) for v in intr)
@@ -167,11 +221,15 @@ def cast_rays(maps, M, intr, W, H, tie_tol=1e-4, max_steps=4000):
             v, w, f = np.ones(len(idx)), np.zeros(len(idx)), np.zeros(len(idx), bool)
             if sel.any():
                 q = pm.to_map(p[idx[sel]])
-                frac = np.abs(q) - np.floor(np.abs(q))
-                tie[idx[sel]] |= np.any(np.abs(frac - 0.5) < tie_tol, axis=1)
-                s16, _, f[sel] = pm.m.lookup(ref64._iround(q))
+                if sharp_ties:
+                    tie[idx[sel]] |= _round_flip(pm, q, tie_tol)
+                else:
+                    frac = np.abs(q) - np.floor(np.abs(q))
+                    tie[idx[sel]] |= np.any(np.abs(frac - 0.5) < tie_tol, axis=1)
+                near = ref64._iround(q)
+                s16, _, f[sel] = pm.m.lookup(near)
                 v[sel] = s16 / 32767.0
-                w[sel] = pm.w_depth
+                w[sel] = pm.weights(near, f[sel])[0]
             vals.append(v), ws.append(w), fs.append(f)
         s, nf = _combine(vals, ws, fs, np.ones(len(idx)), fallback=1.0)
         found = nf > 0
@@ -180,7 +238,7 @@ def cast_rays(maps, M, intr, W, H, tie_tol=1e-4, max_steps=4000):
         tie[idx] |= found & ((np.abs(s - 0.1) < tie_tol) | (np.abs(s + 0.5) < tie_tol))
         if win.any():
             t_sub = np.zeros(win.sum(), bool)
-            s[win] = multi_trilinear(maps, cand[win], p[idx[win]], t_sub, tie_tol)
+            s[win] = multi_trilinear(maps, cand[win], p[idx[win]], t_sub, tie_tol, sharp_ties)
             tie[idx[win]] |= t_sub
         stop = found & (s <= 0.0)
         tie[idx] |= found & (np.abs(s) < tie_tol)
@@ -199,7 +257,7 @@ def cast_rays(maps, M, intr, W, H, tie_tol=1e-4, max_steps=4000):
     p_stop = p.copy()
     t_sub = np.zeros(len(h), bool)
     p[h] += (sdf[h] * step_scale)[:, None] * d[h]
-    s = multi_trilinear(maps, cand_all[h], p[h], t_sub, tie_tol)
+    s = multi_trilinear(maps, cand_all[h], p[h], t_sub, tie_tol, sharp_ties)
     p[h] += (s * step_scale)[:, None] * d[h]
     tie[h] |= t_sub
     return dict(p=p.reshape(H, W, 3), hit=hit.reshape(H, W), tie=tie.reshape(H, W), dir=d.reshape(H, W, 3),
@@ -216,8 +274,10 @@ def _gradient(pm, q):
     return g
 
 
-def normals(maps, cand, p):
-    """Combined unit normal (world frame) at world points p [n, 3] (voxel units); cand [n, maps]."""
+def normals(maps, cand, p, magnitude=False):
+    """Combined unit normal (world frame) at world points p [n, 3] (voxel units); cand [n, maps].  magnitude=True: also the
+    length of the combined gradient before it is normalised (sdf units per 2 voxels): where it is next to nothing -- inside
+    the region whose sdf is clamped to -1 or 1 -- the direction is rounding noise."""
     vals, ws, fs = [], [], []
     first_any = np.full((len(p), 3), np.nan)
     for i, pm in enumerate(maps):
@@ -233,7 +293,8 @@ def normals(maps, cand, p):
         vals.append(v), ws.append(w), fs.append(f)
     g, _ = _combine(vals, ws, fs, np.nan_to_num(first_any))
     with np.errstate(invalid="ignore", divide="ignore"):
-        return g / np.linalg.norm(g, axis=1, keepdims=True)
+        n = g / np.linalg.norm(g, axis=1, keepdims=True)
+    return (n, np.linalg.norm(g, axis=1)) if magnitude else n
 
 
 def colours(maps, cand, p):

@@ -5,8 +5,9 @@ The law, map i of the list on its own voxel lattice, T~ =
 A_ij = T~_j T~_i^-1, B_i = T~_i^-1:
   own gate       a cube is skipped when one of its 8 corner voxels of map i is missing or holds sdf 32767;
   coverage gate  ... or when a map j < i holds a voxel with w_depth > 0 and sdf != 32767 at iround(A_ij (g + 1/2));
-  corner values  per lattice point: the own voxel (sdf / 32767, w_depth; colour, w_color) and every other map's trilinear
-                 read at A_ij (g + corner), combined in list order: only the own map found -> its value, several ->
+  corner values  per lattice point: the own voxel (sdf / 32767, its w_depth; colour, its w_color) and every other map's
+                 trilinear read (value and trilinear weight) at A_ij (g + corner), combined in list order: only the own
+                 map found -> its value, several ->
                  sum(w v) / sum(w), sum(w) == 0 -> the own value;
   triangles      case table and sdfInterp crossings in map-i voxel coordinates, then (B_i v) * voxel_size.
 Everything is evaluated in float64; a cube is a `tie` when a predicate is within tie_tol of flipping: a blended corner
@@ -93,6 +94,7 @@ def mesh_maps(maps, colour=False, tie_tol=1e-4):
         nb = len(blocks)
         P = (blocks[:, None, :] * 8 + _L[None]).reshape(-1, 3)                      # lattice points, [nb * 729, 3]
         s16, clr, found = m.lookup(P)
+        own_wd, own_wc = pm.weights(P, found)
         own = s16 / 32767.0
         own_c = clr.astype(np.float64)
         bad = ~found | (s16 == 32767)
@@ -102,8 +104,8 @@ def mesh_maps(maps, colour=False, tie_tol=1e-4):
         Pf = P.astype(np.float64)
         for j, pj in enumerate(maps):
             if j == i:
-                v, w, f = own, np.full(len(P), pm.w_depth), found
-                c, wc = own_c, np.full(len(P), pm.w_color)
+                v, w, f = own, own_wd, found
+                c, wc = own_c, own_wc
             else:
                 A = np.eye(4) if _same_pose(pm, pj) else Tv[j] @ B
                 q = Pf @ A[:3, :3].T + A[:3, 3]
@@ -135,8 +137,9 @@ def mesh_maps(maps, colour=False, tie_tol=1e-4):
             same = _same_pose(pm, pj)
             A = np.eye(4) if same else Tv[j] @ B
             c = centre @ A[:3, :3].T + A[:3, 3]
-            s, _, f = pj.m.lookup(ref64._iround(c))
-            covered |= f & (pj.w_depth > 0) & (s != 32767)
+            near = ref64._iround(c)
+            s, _, f = pj.m.lookup(near)
+            covered |= f & (pj.weights(near, f)[0] > 0) & (s != 32767)
             if not same:
                 frac = np.abs(c) - np.floor(np.abs(c))
                 tie |= np.any(np.abs(frac - 0.5) < tie_tol, axis=1)
@@ -179,11 +182,56 @@ def triangles(ref):
     return np.concatenate(parts) if parts else np.zeros((0, 3, 3))
 
 
+def cubes_of_triangles(r, tri, vs, what="map"):
+    """Of triangles [n, 3, 3] (world metres, in mesh order) of the map whose mesh_maps entry is r: the index into r's
+    cubes of the cube each came from.  A triangle belongs to the cube its centroid falls into in the map's frame.
+
+    The one exception is a collapsed triangle on a cube face (two vertices within 1e-5 voxel of each other, centroid within
+    1e-3 voxel of a face): a lattice value within sdfInterp's 1e-5 of 0 pulls the crossings of its edges onto the lattice
+    point, and the centroid of what is left cannot tell the cubes that share the face apart.  Such a triangle goes to a cube
+    that touches the face and holds all three vertices: a tie cube if there is one (a cube with such a lattice value is a
+    tie), and among several the first in mesh order that is not before the preceding triangle's cube -- the mesh lists the
+    cubes in r's order and a cube's triangles together."""
+    vs = float(F(vs))
+    q = (np.asarray(tri, np.float64) / vs) @ r["T"][:3, :3].T + r["T"][:3, 3]     # [n, 3, 3] in the map's voxel frame
+    cen = q.mean(axis=1)
+    gq = np.floor(cen).astype(np.int64)
+    lo = np.minimum(r["g"].min(0), gq.min(0) - 1 if len(gq) else r["g"].min(0))
+    span = np.maximum(r["g"].max(0), gq.max(0) + 1 if len(gq) else r["g"].max(0)) - lo + 1
+    key = lambda a: ((a[..., 0] - lo[0]) * span[1] + (a[..., 1] - lo[1])) * span[2] + (a[..., 2] - lo[2])
+    rk = key(r["g"])
+    order = np.argsort(rk)
+
+    def find(g):
+        """index of the cubes at g, -1 where the map has none"""
+        at = np.minimum(np.searchsorted(rk[order], key(g)), len(rk) - 1)
+        return np.where(rk[order[at]] == key(g), order[at], -1)
+
+    cube = find(gq)
+    frac = cen - gq
+    on_face = np.any((frac < 1e-3) | (frac > 1.0 - 1e-3), axis=1)
+    collapsed = np.zeros(len(q), bool)
+    for a, b in ((0, 1), (1, 2), (0, 2)):
+        collapsed |= np.abs(q[:, a] - q[:, b]).max(axis=1) < 1e-5
+    for t in np.nonzero(on_face & collapsed)[0]:
+        signs = np.array(list(np.ndindex(2, 2, 2))) * 2 - 1
+        options = np.unique(np.floor(cen[t][None] + 2e-3 * signs).astype(np.int64), axis=0)
+        holds = np.all((q[t][None] >= options[:, None, :] - 1e-3) & (q[t][None] <= options[:, None, :] + 1 + 1e-3), axis=(1, 2))
+        idx = find(options)
+        idx = np.sort(idx[holds & (idx >= 0)])
+        assert len(idx), f"{what}: a triangle on a cube face belongs to no cube of the map's live blocks"
+        if r["tie"][idx].any():   # (a collapsed triangle comes from a cube with such a lattice value: a tie)
+            idx = idx[r["tie"][idx]]
+        later = idx[idx >= (cube[t - 1] if t else -1)]
+        cube[t] = later[0] if len(later) else idx[0]
+    assert (cube >= 0).all(), f"{what}: triangles outside every cube of the map's live blocks"
+    return cube
+
+
 def compare(ref, pos, col, counts, vs, vert_tol=1e-3, col_tol=1.0 / 255.0):
     """A triangle list (pos / col [n, 3, 3], counts per map) against a mesh_maps result, cube by cube off the ties: each
-    triangle goes to the cube its centroid falls into in its map's frame; kept / skipped, triangle counts, vertices
-    (within vert_tol voxel) and colours must agree.  Returns dict(cubes compared, max vertex error in voxels, max colour
-    error)."""
+    triangle goes to the cube it came from (cubes_of_triangles); kept / skipped, triangle counts, vertices (within vert_tol
+    voxel) and colours must agree.  Returns dict(cubes compared, max vertex error in voxels, max colour error)."""
     assert int(np.sum(counts)) == len(pos)
     start, n_cmp, worst_v, worst_c = 0, 0, 0.0, 0.0
     vs = float(F(vs))
@@ -191,17 +239,8 @@ def compare(ref, pos, col, counts, vs, vert_tol=1e-3, col_tol=1.0 / 255.0):
         tri = pos[start:start + counts[i]].astype(np.float64)
         tcol = None if col is None else col[start:start + counts[i]].astype(np.float64)
         start += counts[i]
-        cen = tri.mean(axis=1) / vs
-        gq = np.floor(cen @ r["T"][:3, :3].T + r["T"][:3, 3]).astype(np.int64)
-        lo = np.minimum(r["g"].min(0), gq.min(0) if len(gq) else r["g"].min(0))
-        span = np.maximum(r["g"].max(0), gq.max(0) if len(gq) else r["g"].max(0)) - lo + 1
-        key = lambda a: ((a[:, 0] - lo[0]) * span[1] + (a[:, 1] - lo[1])) * span[2] + (a[:, 2] - lo[2])
-        rk = key(r["g"])
-        order = np.argsort(rk)
-        at = np.searchsorted(rk[order], key(gq))
-        at = np.minimum(at, len(rk) - 1)
-        cube = order[at]
-        assert np.array_equal(rk[cube], key(gq)), f"map {i}: triangles outside every cube of the map's live blocks"
+        cube = cubes_of_triangles(r, tri, vs, f"map {i}")
+        rk = r["g"]
         got = np.bincount(cube, minlength=len(rk))
         chk = ~r["tie"]
         wrong = chk & (got != r["ntri"])

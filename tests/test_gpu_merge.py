@@ -15,6 +15,7 @@ import ref64_register as rr
 import ref_merge as rm
 import register_fixtures as fx
 import util
+import weighted_fixtures as wf
 
 pytestmark = pytest.mark.gpu
 
@@ -267,6 +268,39 @@ def test_without_colour_every_colour_half_stays(pkg, gpu, identity):
     assert res["voxels_changed"] > 10000
     res, ref, got2, _ = check_merge(pkg, gpu, "with_colour = 1", src, dst, X)
     assert got2.vba["clr"].tobytes() != dst.vba["clr"].tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 10b. weights that vary from voxel to voxel: the smallest of the taps' weights, the 8-tap gate, the colour gate
+# ---------------------------------------------------------------------------------------------------------------------
+def _shift(v):
+    X = np.eye(4, dtype=np.float32)
+    X[:3, 3] = np.asarray(v, np.float64) * am.VS
+    return X
+
+
+@pytest.mark.parametrize("with_colour", [1, 0])
+@pytest.mark.parametrize("how", ["identity", "translation", "off_lattice"])
+def test_weights_that_vary_per_voxel(pkg, gpu, how, with_colour):
+    """The plane pair re-weighted (weighted_fixtures.weighted_planes): source w_depth 1 .. 7 with one voxel in 37 unobserved
+    inside its blocks and w_color 0 .. 3, destination w_depth up to 99.  Byte for byte against ref_merge.py as every case,
+    and on the merged bytes themselves the weight law voxel by voxel (weighted_fixtures.merge_outcomes): w_depth' =
+    min(w_dst + the smallest of the taps' w_depth, max_w), nothing where a tap weighs nothing, the colour half live exactly
+    where every tap has a w_color -- with at least 1000 voxels of each outcome, so none can go missing."""
+    a, b = wf.weighted_planes()
+    X = {"identity": I4, "translation": _shift((3, -5, 2)), "off_lattice": fx.off_lattice(1.5, 0.45)}[how]
+    src, dst = rm.State.of_map(a), rm.State.of_map(b)
+    res, ref, got, _ = check_merge(pkg, gpu, f"weighted planes, {how}, with_colour = {with_colour}", src, dst, X,
+                                   with_colour=with_colour)
+    counts = wf.merge_outcomes(a, dst, got, X, with_colour)
+    print(counts)
+    assert counts["changed"] == res["voxels_changed"] and counts["clamped"] > 0 and got.vba["w_depth"].max() == 100
+    assert counts["changed"] >= 1000 and counts["gated"] >= 1000
+    if with_colour:
+        assert counts["colour_live"] >= 1000 and counts["colour_idle"] >= 1000
+    else:
+        assert counts["colour_live"] == 0
+        assert got.vba["clr"].tobytes() == dst.vba["clr"].tobytes() and got.vba["w_color"].tobytes() == dst.vba["w_color"].tobytes()
 
 
 def test_targets_outside_the_table_are_counted_and_skipped(pkg, gpu):

@@ -1,5 +1,6 @@
 """dslam_get_image_multi on the MI355X: exact reductions to dslam_get_image, one posed map, the blending law against
-the float64 reference of ref64_multimap.py, maps side by side, argument checks, the GetImage memo and async mode, and
+the float64 reference of ref64_multimap.py on maps of one weight each and on maps whose weights vary per voxel, maps side
+by side, argument checks, the GetImage memo and async mode, and
 the ITMLib mirror's GetImageAllLocalMaps."""
 import os
 import struct
@@ -13,6 +14,7 @@ import ref64
 import ref64_checks as rc
 import ref64_multimap as rm
 import util
+import weighted_fixtures as wf
 
 pytestmark = pytest.mark.gpu
 
@@ -183,6 +185,157 @@ def test_blending_law_against_float64(pkg, gpu):
     want = np.trunc((np.array([220.0, 40.0, 30.0]) + 3 * np.array([30.0, 90.0, 230.0])) / 4.0)
     assert (np.abs(clr[both_maps] - want) <= 1.0).all(axis=1).mean() > 0.9
 
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3b. the blending law on maps whose weights vary from voxel to voxel (weighted_fixtures.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def _render_all(gpu, pkg, maps, M, intr, order=None):
+    """(depth float64, shaded grey float64 [H, W], colour float64 [H, W, 3]) of the composite of `maps` (in `order`)."""
+    order = list(range(len(maps))) if order is None else order
+    scenes = [upload_map(gpu, pkg, maps[i].m) for i in order]
+    Ts = [maps[i].T for i in order]
+    rs = roomiest(gpu, scenes, wf.W, wf.H)
+    depth = gpu.get_image_multi(scenes, Ts, rs, M, intr, pkg.IMAGE_DEPTH).astype(np.float64)
+    grey = gpu.get_image_multi(scenes, Ts, rs, M, intr, pkg.IMAGE_SHADED)[..., 0].astype(np.float64)
+    clr = gpu.get_image_multi(scenes, Ts, rs, M, intr, pkg.IMAGE_COLOUR_FROM_VOLUME)[..., :3].astype(np.float64)
+    return depth, grey, clr, scenes
+
+
+def _against_float64(what, maps, M, intr, ref, depth, grey, clr, min_gradient=0.0):
+    """The acceptance of test_blending_law_against_float64: hits equal off ties, |ddepth| <= 1e-3 voxel off ties and on at
+    most 1 % of the pixels beyond, grey within 2, colour within 1 on the lit pixels.  Returns the pixels compared (hit in
+    both, off ties) and the lit ones among them.  A pixel is lit when n . l > 0.05, as there, and -- on the slab fixture
+    only, which passes min_gradient = 1e-3 -- its combined gradient is longer than that: a ray that
+    passed a surface without weight can stop deep inside, where every sdf is clamped to -1 and the gradient is 0 up to
+    rounding -- 2e-16 in float64, which normalises to some direction, exactly 0 in float32, which draws nothing.  The stored
+    sdf has steps of 3e-5 and a float32 gradient component carries 1e-7 of rounding, so at 1e-3 the direction is good to
+    1e-4, 0.02 grey levels."""
+    vs = am.VS
+    hit, tie = depth > 0, ref["tie"]
+    assert np.array_equal(hit[~tie], ref["hit"][~tie]), f"{what}: {(hit != ref['hit'])[~tie].sum()} pixels off a tie differ in hit"
+    both = hit & ref["hit"]
+    assert both.sum() > 0.1 * wf.W * wf.H
+    err = np.abs(depth - ref64.camera_depth(M, ref["p"], vs)) / vs
+    sel = both & ~tie
+    p_hit, cand = ref["p"][sel], ref["cand"][sel]
+    n, length = rm.normals(maps, cand, p_hit, magnitude=True)
+    ndl = n @ ref64.light_of(M)
+    ok = (ndl > 0.05) & (length > min_gradient)
+    d_grey = np.abs(grey[sel] - ref64.shaded_grey(ndl))[ok]
+    d_clr = np.abs(clr[sel] - np.trunc(rm.colours(maps, cand, p_hit)))[ok]
+    print(f"{what}: {sel.sum()} pixels off a tie ({(tie & ref['hit']).sum() / ref['hit'].sum():.2%} of the hits are ties), "
+          f"|ddepth| <= {err[sel].max():.3g} voxel, grey within {d_grey.max():.3g}, colour within {d_clr.max():.3g} "
+          f"({ok.sum()} lit pixels)")
+    big = both & (err > 1e-3)
+    assert not (big & ~tie).any(), f"{what}: |ddepth| up to {err[big & ~tie].max():.3g} voxel off a tie"
+    assert big.sum() <= 0.01 * both.sum()
+    assert ok.sum() > 0.5 * sel.sum()
+    assert d_grey.max() <= 2.0, f"{what}: grey {d_grey.max()}"
+    assert d_clr.max() <= 1.0, f"{what}: colour {d_clr.max()}"
+    lit = np.zeros(sel.shape, bool)
+    lit[sel] = ok
+    return sel, lit
+
+
+def test_weight_fields_against_float64(pkg, gpu):
+    """Two spheres with radii two voxels apart under the two poses of _two_spheres, w_depth = texture x ramp, w_color =
+    (2x + 3y + 5z) mod 4 (weighted_fixtures.ramp_spheres): depth, hits, shading and colour against the float64 reference
+    that reads every voxel's own weights, and far from the references that blend with each map's mean weight or give a
+    trilinear read its nearest tap's weight."""
+    maps, M, intr, ref = wf.render_reference("ramp")
+    depth, grey, clr, _ = _render_all(gpu, pkg, maps, M, intr)
+    sel, _ = _against_float64("texture x ramp", maps, M, intr, ref, depth, grey, clr)
+    for name, alt in (("per-map mean weights", wf.mean_weight_maps(maps)), ("nearest tap's weight", wf.nearest_weight_maps(maps))):
+        other = ref64.camera_depth(M, rm.cast_rays(alt, M, intr, wf.W, wf.H)["p"], am.VS)
+        med = np.median(np.abs(depth - other)[sel]) / am.VS
+        print(f"texture x ramp: median {med:.3f} voxel from the reference with {name}")
+        assert med > 0.3, name
+    # the colour confidence is w_color, not w_depth: where both maps hold every tap, the w_depth-weighted colour is far
+    p_hit, cand = ref["p"][sel], ref["cand"][sel]
+    by_depth = [rm.Posed(pm.m, pm.T) for pm in maps]
+    for pm in by_depth:
+        pm.colour_weight = "w_depth"
+    wrong = np.trunc(rm.colours(by_depth, cand, p_hit))
+    far = np.abs(clr[sel] - wrong).max(axis=1)
+    print(f"texture x ramp: median colour distance {np.median(far):.1f} from the w_depth-weighted colour")
+    assert np.median(far) > 10.0
+
+
+def test_zero_weight_slabs(pkg, gpu):
+    """weighted_fixtures.slab_spheres: the image against the float64 reference, and region by region what the law says.
+    Where only one map carries a weight the hit lies on that map's sphere, within 0.5 voxel (the other's is 2 voxels away;
+    the two refinement steps of a march leave up to 0.2 voxel at grazing rays, in a single-map render too), and the depth
+    is that map's own render's within 1e-3 voxel wherever the float64 references of the two agree -- not everywhere: in
+    front of the surface one map's blocks reach further than the other's, there it alone is found and its sdf of 1.0 takes
+    the 1 mu step where the single-map march takes the block step, and a march that stops elsewhere is refined to a
+    slightly different point.  Where both maps hold the surface under the
+    weight 0 the sum of the weights is 0, the read gives sdf 1.0 and the ray passes the surface both maps hold (it may stop
+    deeper, at a voxel only one map holds: one found map's value counts whatever it weighs); where neither map has a
+    w_color but both have a w_depth, the colour is the first contributor's, so the order of the list decides it."""
+    maps, M, intr, ref = wf.render_reference("slab")
+    depth, grey, clr, scenes = _render_all(gpu, pkg, maps, M, intr)
+    sel, lit = _against_float64("zero slabs", maps, M, intr, ref, depth, grey, clr, min_gradient=1e-3)
+    vs = am.VS
+    d = ref["dir"].reshape(-1, 3)
+    single = wf.single_references("slab")
+    flat = lambda a: a.reshape(-1)
+
+    ys, xs = (a.reshape(-1).astype(np.float64) for a in np.mgrid[0:wf.H, 0:wf.W])
+
+    def regions(p, along):
+        """slab_regions that hold for the points p and for the points `along` voxels from them on their rays"""
+        rs = [wf.slab_regions(maps, p + k * d) for k in along]
+        return [{key: rs[0][i][key] & rs[1][i][key] & rs[2][i][key] for key in rs[0][i]} for i in range(2)]
+
+    # only one map weighted: that map's surface, and that map's single-map render
+    rA, rB = regions(ref["p"].reshape(-1, 3), (-12.0, 0.0, 4.0))
+    dref = ref64.camera_depth(M, ref["p"], vs)
+    for i, (mine, other) in enumerate(((rA, rB), (rB, rA))):
+        px = flat(sel) & mine["weighted"] & (other["keep"] | other["unobserved"])
+        world = np.stack([flat(depth) * ((xs - float(intr[2])) / float(intr[0])), flat(depth) * ((ys - float(intr[3])) / float(intr[1])),
+                          flat(depth)], -1)
+        world = ref64.mat_vec_f64(np.linalg.inv(np.asarray(M, np.float64)), world)
+        off = np.abs(np.linalg.norm(world - wf.C_WORLD, axis=1) / vs - (wf.RADIUS / vs + 2.0 * i))[px]
+        rs_i = gpu.create_render_state(scenes[i], wf.W, wf.H)
+        own = gpu.get_image(scenes[i], rs_i, rm.camera_of(M, maps[i].T), intr, pkg.IMAGE_DEPTH).astype(np.float64)
+        same = px & flat(own > 0) & ~flat(single[i]["tie"]) & flat(single[i]["hit"]) & (np.abs(flat(dref) - flat(single[i]["depth"])) < 1e-4 * vs)
+        err = np.abs(flat(depth) - flat(own))[same] / vs
+        print(f"zero slabs: only map {i} weighted on {px.sum()} pixels, hits within {off.max():.3g} voxel of its sphere; "
+              f"{same.sum()} of them where the law gives its own render's depth, |ddepth| <= {err.max() if same.any() else 0:.3g} voxel there")
+        assert px.sum() >= 100 and off.max() <= 0.5
+        # (in front of map 0's blocks map 1's reach further, so nearly every ray of map 0's half marches differently
+        # from map 0's own render: 2 pixels of its half agree in the float64 references, 326 of map 1's)
+        assert same.sum() >= (1, 100)[i] and err.max() <= 1e-3
+    # neither weighted, both hold the surface
+    pA = single[0]["p_world"].reshape(-1, 3)
+    rA, rB = regions(pA, (-12.0, 0.0, 16.0))
+    px = flat(single[0]["hit"] & single[1]["hit"]) & rA["keep"] & rB["keep"] & ~flat(ref["tie"])
+    surface = np.maximum(flat(single[0]["depth"]), flat(single[1]["depth"]))
+    passed = (flat(depth) == 0) | (flat(depth) > surface + am.MU)
+    print(f"zero slabs: neither map weighted on {px.sum()} pixels, {(flat(depth) == 0)[px].sum()} without a hit, the others "
+          f"{((flat(depth) - surface)[px & (flat(depth) > 0)] / vs).min() if (px & (flat(depth) > 0)).any() else 0:.3g} voxels and more behind the surface")
+    assert px.sum() >= 100 and passed[px].all()
+    assert np.array_equal((flat(depth) > 0)[px], flat(ref["hit"])[px])
+    # w_color 0 in both maps (their voxels observed, so they hold their colour bytes): the first contributor's colour,
+    # whichever map that is and whatever its w_depth
+    rA, rB = regions(ref["p"].reshape(-1, 3), (-1.0, 0.0, 1.0))
+    px = flat(sel) & rA["no_colour"] & rB["no_colour"] & rA["off_unobserved"] & rB["off_unobserved"] & flat(ref["cand"].all(-1))
+    def first_colour(px, image, ordered, r, want, what):
+        """On the pixels of px where the float64 law gives the first contributor's whole colour (all 8 of its taps hold
+        it; a ray that stopped deep behind the surface may find only the other map), the image shows it."""
+        law = np.trunc(rm.colours(ordered, r["cand"].reshape(-1, 2)[px], r["p"].reshape(-1, 3)[px]))
+        whole = np.zeros(len(px), bool)
+        whole[px] = (np.abs(law - np.trunc(np.array(want))) <= 1.0).all(axis=1)
+        print(f"zero slabs, {what}: neither map has a w_color on {px.sum()} pixels, the first map's colour on {whole.sum()}")
+        assert whole.sum() >= 200
+        assert (np.abs(image.reshape(-1, 3)[whole] - np.trunc(np.array(want))) <= 1.0).all()
+
+    first_colour(px & flat(lit), clr, maps, ref, wf.COLOUR_A, "A first")
+    swapped = [maps[1], maps[0]]
+    ref2 = rm.cast_rays(swapped, M, intr, wf.W, wf.H, sharp_ties=True)
+    depth2, grey2, clr2, _ = _render_all(gpu, pkg, maps, M, intr, order=[1, 0])
+    sel2, lit2 = _against_float64("zero slabs, B first", swapped, M, intr, ref2, depth2, grey2, clr2, min_gradient=1e-3)
+    first_colour(px & flat(lit2), clr2, swapped, ref2, wf.COLOUR_B, "B first")
 
 # ---------------------------------------------------------------------------------------------------------------------
 # 4. maps side by side

@@ -13,6 +13,7 @@ import analytic_maps as am
 import multimesh_fixtures as fx
 import ref64_multimesh as r64
 import util
+import weighted_fixtures as wf
 
 pytestmark = pytest.mark.gpu
 
@@ -130,6 +131,39 @@ def test_overlap_gives_one_blended_surface(pkg, gpu):
     # colour: the w_color-weighted mean (1 : 3) of the two flat colours
     want = (np.array(fx.COLOUR_A) + 3.0 * np.array(fx.COLOUR_B)) / 4.0 / 255.0
     assert np.abs(col.astype(np.float64) - want).max() <= 1.0 / 255.0
+
+
+def test_weight_fields_and_a_slab_without_weight(pkg, gpu):
+    """The two spheres with w_depth = 1 + texture + ramp (1 .. 35), w_color = (2x + 3y + 5z) mod 4, and a slab of map 0, 12
+    voxels thick, whose voxels hold their sdf and colour under the weight 0 (weighted_fixtures.mesh_spheres): cube by cube
+    against the float64 reference that reads every voxel's own weights, with the tolerances and the tie handling of
+    test_overlap_gives_one_blended_surface.  Inside the slab map 0 does not cover map 1, whose cubes leave their triangles;
+    outside it does.  The colours compared are blends by w_color, zeros included."""
+    maps = fx.fixture("weighted_spheres")
+    scenes = [upload_map(gpu, pkg, pm.m) for pm in maps]
+    pos, col, counts = gpu.mesh_scene_multi(scenes, [pm.T for pm in maps], colour=True)
+    assert counts.sum() == len(pos) > 10000
+    ref = fx.reference("weighted_spheres")
+    share = r64.tie_share(ref)
+    assert share <= 0.02, f"tie share {share:.3%}"
+    res = r64.compare(ref, pos, col, counts, am.VS)
+    print(f"weighted spheres: {res['cubes']} cubes compared, vertices within {res['max_vertex']:.3g} voxel, colours within "
+          f"{res['max_colour'] * 255:.3g} / 255, tie share {share:.3%}")
+    assert res["cubes"] > 5000
+    # map 1's cubes by where their centre lies in map 0: well inside the slab, or well outside it, on a voxel map 0 holds
+    r, A = ref[1], maps[0]
+    to_world = np.linalg.inv(r["T"])
+    centre = A.to_map((r["g"] + 0.5) @ to_world[:3, :3].T + to_world[:3, 3])
+    v = centre[:, 1] - (A.T[:3, :3].astype(np.float64) @ wf.C_WORLD + A.T[:3, 3])[1] / am.VS
+    held = A.m.lookup(np.floor(centre + 0.5).astype(np.int64))[2]
+    got = np.bincount(r64.cubes_of_triangles(r, pos[counts[0]:], am.VS), minlength=len(r["g"]))
+    off_tie = ~r["tie"] & r["produce"] & held
+    lo, hi = wf.MESH_SLAB
+    inside, outside = off_tie & (v > lo + 1.5) & (v < hi - 1.5), off_tie & ((v < lo - 1.5) | (v > hi + 1.5))
+    print(f"weighted spheres: map 1 leaves {got[inside].sum()} triangles in {(got[inside] > 0).sum()} of {inside.sum()} cubes "
+          f"inside the slab, {got[outside].sum()} in {outside.sum()} cubes outside it")
+    assert inside.sum() > 1000 and (got[inside] > 0).all() and np.array_equal(got[inside], r["ntri"][inside])
+    assert outside.sum() > 10000 and got[outside].sum() == 0
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ import analytic_maps as am
 import ref64_register as rr
 import register_fixtures as fx
 import util
+import weighted_fixtures as wf
 
 pytestmark = pytest.mark.gpu
 
@@ -67,6 +68,18 @@ def test_single_evaluation_against_the_reference(pkg, gpu, scenes, case):
     what, pair, X0 = fx.single_evaluations()[case]
     ev, _, _ = check_evaluation(pkg, gpu, scenes, what, pair.src, pair.dst, pair.src_map, pair.dst_map, X0)
     assert ev.tie_share < 0.01 and ev.valid > 0.5 * ev.candidates
+
+
+def test_single_evaluation_with_scattered_voxels_without_weight(pkg, gpu, scenes):
+    """The box-corner pair with w_depth 1 + texture and one voxel in 37 unobserved in both maps
+    (weighted_fixtures.weighted_box_pair): the source's candidates and the destination's 8-tap gate both depend on single
+    voxels' weights, and the counts and sums are the reference's."""
+    pair, plain = wf.weighted_box_pair(), fx.box_pair("small")
+    ev, res, _ = check_evaluation(pkg, gpu, scenes, "scattered zero weights", pair.src, pair.dst, pair.src_map, pair.dst_map,
+                                  fx.near_truth(pair))
+    assert ev.tie_share < 0.01
+    assert 0.95 * plain.src.source_voxels()[2].astype(bool).sum() < pair.src.source_voxels()[2].astype(bool).sum()
+    assert 0.7 * ev.candidates < ev.valid < 0.9 * ev.candidates      # 31 of 37 reads pass the gate
 
 
 def test_exact_identity_on_a_map_registered_to_itself(pkg, gpu, scenes):

@@ -11,6 +11,7 @@ import ref_merge as rm
 import refmap
 import register_fixtures as fx
 import util
+import weighted_fixtures as wf
 
 I4 = fx.I4
 
@@ -183,3 +184,63 @@ def test_merging_the_counterpart_does_not_raise_the_error_to_the_analytic_sdf():
     print(f"mean |sdf - analytic| over {len(np.concatenate(err_merged))} changed voxels: merged {merged:.6f}, "
           f"resampled from the source alone {source:.6f} (units of mu)")
     assert merged <= source
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# weights that vary from voxel to voxel: the smallest of the 8 taps' weights, the two gates
+# ---------------------------------------------------------------------------------------------------------------------
+def weighted_transforms():
+    shift = np.eye(4, dtype=np.float32)
+    shift[:3, 3] = np.array((3, -5, 2), np.float64) * am.VS
+    return {"identity": I4, "translation": shift, "off_lattice": fx.off_lattice(1.5, 0.45)}
+
+
+def test_weighted_pair_minimum_of_the_taps_and_both_gates():
+    """ref_merge.merge alone on weighted_fixtures.weighted_planes (source w_depth 1 .. 7 with unobserved voxels inside its
+    blocks, w_color 0 .. 3; destination w_depth up to 99) under the identity, a whole-voxel translation and an off-lattice
+    transform: on a sample, voxel by voxel in a plain loop over the stored source voxels, w_depth' = min(w_dst + the smallest
+    w_depth of the taps, max_w) and the colour half idles exactly where a tap has no w_color; over all voxels
+    (weighted_fixtures.merge_outcomes) the same, and each outcome the GPU cases rely on occurs at least 1000 times."""
+    a, b = wf.weighted_planes()
+    stored = {tuple(int(v) for v in pos): vox for pos, vox in zip(a.block_pos, a.voxels)}
+    for name, X in weighted_transforms().items():
+        src, dst = rm.State.of_map(a), rm.State.of_map(b)
+        before = dst.copy()
+        res = rm.merge(src, dst, X)
+        assert res["exhausted"] == 0
+        check_table(dst)
+        counts = wf.merge_outcomes(a, before, dst, X)
+        print(f"{name}: {res['voxels_changed']} voxels changed, {counts}")
+        assert counts["changed"] == res["voxels_changed"]
+        assert min(counts[k] for k in ("changed", "gated", "colour_live", "colour_idle")) >= 1000 and counts["clamped"] > 0, counts
+        # the sample, tap by tap
+        _, Yt, identity = rm.transforms(X, am.VS)
+        live = dst.live()
+        rng = np.random.default_rng(3)
+        gated = idle = 0
+        for entry, l in zip(live[rng.integers(0, len(live), 1500)], rng.integers(0, 512, 1500)):
+            e = dst.hash[entry]
+            P = e["pos"].astype(np.int64) * 8 + rm.LOCAL[l]
+            if identity:
+                taps = [tuple(P)]
+            else:
+                q = rm.to_map(Yt, False, P.astype(np.float32)[None])[0]
+                x0, y0, z0 = (int(np.floor(v)) for v in q)
+                taps = [(x0 + dx, y0 + dy, z0 + dz) for dz in (0, 1) for dy in (0, 1) for dx in (0, 1)]
+            wds, wcs = [], []
+            for x, y, z in taps:
+                vox = stored.get((x >> 3, y >> 3, z >> 3))
+                v = None if vox is None else vox[(x & 7) + 8 * (y & 7) + 64 * (z & 7)]
+                wds.append(0 if v is None else int(v["w_depth"]))
+                wcs.append(0 if v is None else int(v["w_color"]))
+            r = min(wds)
+            old = before.vba[e["ptr"]][l] if before.hash["ptr"][entry] == e["ptr"] else None
+            old_w = 0 if old is None else int(old["w_depth"])
+            new = dst.vba[e["ptr"]][l]
+            assert int(new["w_depth"]) == min(old_w + r, 100), (name, P, wds)
+            unchanged = (old is None and int(new["w_color"]) == 0 and not new["clr"].any()) or \
+                        (old is not None and new["clr"].tobytes() == old["clr"].tobytes() and new["w_color"] == old["w_color"])
+            assert unchanged == (r == 0 or min(wcs) == 0), (name, P, wds, wcs)
+            gated += r == 0 and max(wds) > 0
+            idle += r > 0 and min(wcs) == 0
+        assert idle > 50 and (identity or gated > 50), (gated, idle)   # (the clamp: counts["clamped"], over all voxels)

@@ -11,6 +11,7 @@ import analytic_maps as am
 import multimesh_fixtures as fx
 import ref64_multimap as rm
 import ref64_multimesh as r64
+import weighted_fixtures as wf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -81,13 +82,70 @@ def test_seam_reference_lies_on_the_wall():
     assert off[~edge].max() <= 0.25 and off[edge].max() <= 1.0, (off[~edge].max(), off[edge].max())
 
 
-@pytest.mark.parametrize("name", ["two_spheres", "seam_planes"])
+@pytest.mark.parametrize("name", ["two_spheres", "seam_planes", "weighted_spheres"])
 def test_tie_share_of_the_gpu_fixtures(name):
     ref = fx.reference(name)
     assert sum(int(r["produce"].sum()) for r in ref) > 5000
     share = r64.tie_share(ref)
     print(f"{name}: tie share {share:.4%}")
     assert share <= 0.02, f"{name}: {share:.3%} of the triangle-producing cubes are ties"
+
+
+def test_weighted_reference_uncovers_the_slab_and_reads_each_voxels_weight():
+    """mesh_maps on weighted_fixtures.mesh_spheres: map 1's cubes whose centre lies in map 0's slab without weight are kept,
+    those on a weighted voxel of map 0 are covered; and a lattice value of map 0, recomputed in a plain loop from the
+    stored voxels (own sdf and w_depth, map 1's 8 taps and their weights), gives the vertex the reference puts on the edge."""
+    maps = fx.fixture("weighted_spheres")
+    ref = fx.reference("weighted_spheres")
+    A, B = maps
+    r = ref[1]
+    to_world = np.linalg.inv(r["T"])
+    centre = A.to_map((r["g"] + 0.5) @ to_world[:3, :3].T + to_world[:3, 3])
+    v = centre[:, 1] - (A.T[:3, :3].astype(np.float64) @ wf.C_WORLD + A.T[:3, 3])[1] / am.VS
+    near = np.floor(centre + 0.5).astype(np.int64)
+    held = A.m.lookup(near)[2]
+    lo, hi = wf.MESH_SLAB
+    prod = r["produce"] & ~r["tie"]
+    inside, outside = prod & held & (v > lo + 1.5) & (v < hi - 1.5), prod & held & ((v < lo - 1.5) | (v > hi + 1.5))
+    assert inside.sum() > 1000 and r["kept"][inside].all() and (A.m.lookup_weights(near[inside])[0] == 0).all()
+    assert outside.sum() > 10000 and not r["kept"][outside].any() and (A.m.lookup_weights(near[outside])[0] > 0).all()
+    # blended lattice values of map 0 on the x edges of some kept cubes, from the stored voxels
+    r0 = ref[0]
+    stored = [{tuple(int(c) for c in pos): vox for pos, vox in zip(pm.m.block_pos, pm.m.voxels)} for pm in maps]
+
+    def voxel(k, p):
+        vox = stored[k].get(tuple(int(c) >> 3 for c in p))
+        return None if vox is None else vox[(int(p[0]) & 7) + 8 * (int(p[1]) & 7) + 64 * (int(p[2]) & 7)]
+
+    T01 = r64.voxel_transform(B) @ np.linalg.inv(r64.voxel_transform(A))
+
+    def blended(g):
+        own = voxel(0, g)
+        q = T01[:3, :3] @ g + T01[:3, 3]
+        q0 = np.floor(q).astype(np.int64)
+        c = q - q0
+        val = wt = 0.0
+        found = False
+        for d in np.ndindex(2, 2, 2):
+            tap = voxel(1, q0 + np.array(d)[::-1])
+            cf = np.prod(np.where(np.array(d)[::-1] == 1, c, 1 - c))
+            val += cf * (1.0 if tap is None else int(tap["sdf"]) / 32767.0)
+            wt += cf * (0 if tap is None else int(tap["w_depth"]))
+            found |= tap is not None
+        s, w = int(own["sdf"]) / 32767.0, int(own["w_depth"])
+        return (w * s + wt * val) / (w + wt) if found and w + wt > 0 else s
+
+    checked = 0
+    for cidx in np.nonzero(r0["kept"] & ~r0["tie"])[0][::97]:
+        g = r0["g"][cidx].astype(np.float64)
+        v0, v1 = blended(g), blended(g + np.array([1.0, 0.0, 0.0]))
+        if (v0 < 0) == (v1 < 0):
+            continue
+        want = (g + np.array([v0 / (v0 - v1), 0.0, 0.0])) @ np.linalg.inv(r0["T"])[:3, :3].T + np.linalg.inv(r0["T"])[:3, 3]
+        dist = np.abs(r0["tris"][cidx, :r0["ntri"][cidx]].reshape(-1, 3) / float(np.float32(am.VS)) - want).max(axis=1).min()
+        assert dist < 1e-9, (g, dist)
+        checked += 1
+    assert checked > 50
 
 
 def test_boundary_exports_declares_and_wraps_the_call(pkg):
