@@ -76,6 +76,29 @@ class RegisterResult(C.Structure):
 
 assert C.sizeof(RegisterParams) == 24 and C.sizeof(RegisterResult) == 32  # the header's layouts
 
+MAX_REGISTER_PAIRS = 128   # DSLAM_MAX_REGISTER_PAIRS
+
+
+class RegisterGraphResult(C.Structure):
+    """dslam_register_graph_result."""
+    _fields_ = [("evaluations", C.c_int32), ("stop_reason", C.c_int32), ("active_pairs", C.c_int32),
+                ("cost_first", C.c_float), ("cost_last", C.c_float), ("conditioning", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class RegisterPairResult(C.Structure):
+    """dslam_register_pair_result."""
+    _fields_ = [("candidates", C.c_int32), ("valid_first", C.c_int32), ("valid_last", C.c_int32), ("active", C.c_int32),
+                ("cost_first", C.c_float), ("cost_last", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+assert C.sizeof(RegisterGraphResult) == 24 and C.sizeof(RegisterPairResult) == 24  # the header's layouts
+
 
 class MergeParams(C.Structure):
     """dslam_merge_params; max_passes = 0 selects its default."""
@@ -674,6 +697,32 @@ class CApi:
         triangle, row by row), 6 gradient, sum of b^2, valid count, 3 sum of q, candidate count."""
         out = np.empty(33, dtype=np.float64)
         self._call("debug_register_sums", self._engine, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
+
+    def register_graph(self, scenes, map_poses, pairs, anchor, params=None):
+        """dslam_register_graph: the poses of N local maps estimated jointly from the voxels of the listed overlapping pairs.
+        `scenes` / `map_poses` as get_image_multi (the starts); `pairs`: (src, dst) indices into `scenes`; `anchor`: the map
+        held fixed.  Returns (the estimates [N, 4, 4] float32, RegisterGraphResult, a list of RegisterPairResult)."""
+        scenes = list(scenes)
+        T = np.asarray(map_poses, dtype=np.float32)
+        if T.ndim != 3 or T.shape[1:] != (4, 4):
+            raise ValueError("map_poses must be N 4x4 matrices")
+        if len(T) != len(scenes):
+            raise ValueError(f"{len(scenes)} scenes but {len(T)} map poses")
+        n = len(scenes)
+        ptrs = (C.c_void_p * max(n, 1))(*[None if s is None else s.ptr for s in scenes])
+        t_abi = np.ascontiguousarray(np.transpose(T, (0, 2, 1))).reshape(-1).copy() if n else np.zeros(16, np.float32)
+        pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        res = RegisterGraphResult()
+        pres = (RegisterPairResult * max(len(pr), 1))()
+        self._call("register_graph", self._engine, ptrs, _fptr(t_abi), C.c_int(n), pr.ctypes.data_as(C.POINTER(C.c_int32)),
+                   C.c_int(len(pr)), C.c_int(int(anchor)), C.byref(params) if params is not None else None, C.byref(res), pres)
+        return np.transpose(t_abi.reshape(n, 4, 4), (0, 2, 1)).copy(), res, list(pres)[:len(pr)]
+
+    def debug_register_graph_sums(self, pair):
+        """The 33 double sums (as debug_register_sums) of pair `pair` at the most recent joint evaluation."""
+        out = np.empty(33, dtype=np.float64)
+        self._call("debug_register_graph_sums", self._engine, C.c_int(int(pair)), out.ctypes.data_as(C.POINTER(C.c_double)))
         return out
 
     # -- map merge -------------------------------------------------------------------------------------

@@ -1597,6 +1597,58 @@ int dslam_debug_register_sums(dslam_engine *e, double out[33]) {
   return DSLAM_OK;
 }
 
+int dslam_register_graph(dslam_engine *e, const dslam_scene *const *scenes, float *T_map_from_world, int num_maps,
+                         const int32_t *pairs, int num_pairs, int anchor, const dslam_register_params *params,
+                         dslam_register_graph_result *result, dslam_register_pair_result *pair_results) {
+  DSLAM_REQUIRE(e && scenes && T_map_from_world && pairs && result, "null argument");
+  DSLAM_REQUIRE(num_maps >= 2 && num_maps <= DSLAM_MAX_RENDER_MAPS, "num_maps must be 2 .. DSLAM_MAX_RENDER_MAPS");
+  DSLAM_REQUIRE(num_pairs >= 1 && num_pairs <= DSLAM_MAX_REGISTER_PAIRS, "num_pairs must be 1 .. DSLAM_MAX_REGISTER_PAIRS");
+  DSLAM_REQUIRE(anchor >= 0 && anchor < num_maps, "the anchor is not a map of the list");
+  for (int i = 0; i < num_maps; i++) {
+    const dslam_scene *s = scenes[i];
+    DSLAM_REQUIRE(s, "a scene in the list is NULL");
+    DSLAM_REQUIRE(s->engine == e, "a scene in the list belongs to another engine");
+    for (int j = 0; j < i; j++) DSLAM_REQUIRE(scenes[j] != s, "a scene is listed twice");
+    DSLAM_REQUIRE(memcmp(&s->p.voxel_size, &scenes[0]->p.voxel_size, sizeof(float)) == 0 &&
+                      memcmp(&s->p.mu, &scenes[0]->p.mu, sizeof(float)) == 0,
+                  "all maps of a joint registration need the same voxel_size and mu");
+    const float *T = T_map_from_world + 16 * i;
+    for (int k = 0; k < 16; k++) DSLAM_REQUIRE(std::isfinite(T[k]), "a map transform is not finite");
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++) {
+        double dot = 0.0;
+        for (int k = 0; k < 3; k++) dot += (double)T[a * 4 + k] * (double)T[b * 4 + k];
+        DSLAM_REQUIRE(fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-4, "a map transform's rotation block is not orthonormal");
+      }
+  }
+  for (int p = 0; p < num_pairs; p++) {
+    const int s = pairs[2 * p], d = pairs[2 * p + 1];
+    DSLAM_REQUIRE(s >= 0 && s < num_maps && d >= 0 && d < num_maps, "a pair names a map that is not in the list");
+    DSLAM_REQUIRE(s != d, "a pair names one map twice");
+    for (int q = 0; q < p; q++) DSLAM_REQUIRE(pairs[2 * q] != s || pairs[2 * q + 1] != d, "an ordered pair is given twice");
+  }
+  dslam_register_params rp = {0.0f, 0.0f, 0, 0, 0.0f, 0.0f};
+  if (params) rp = *params;
+  DSLAM_REQUIRE(rp.band >= 0.0f && rp.residual_gate >= 0.0f && rp.max_evaluations >= 0 && rp.min_valid >= 0 &&
+                    rp.term_rotation >= 0.0f && rp.term_translation_voxels >= 0.0f,
+                "a registration parameter is negative (or not a number)");
+  if (rp.band == 0.0f) rp.band = 0.5f;
+  if (rp.residual_gate == 0.0f) rp.residual_gate = 0.75f;
+  if (rp.max_evaluations == 0) rp.max_evaluations = 30;
+  if (rp.min_valid == 0) rp.min_valid = 500;
+  if (rp.term_rotation == 0.0f) rp.term_rotation = 1e-5f;
+  if (rp.term_translation_voxels == 0.0f) rp.term_translation_voxels = 1e-3f;
+  return launch_register_graph(e, scenes, T_map_from_world, num_maps, pairs, num_pairs, anchor, &rp, result, pair_results);
+}
+
+int dslam_debug_register_graph_sums(dslam_engine *e, int pair, double out[33]) {
+  DSLAM_REQUIRE(e && out, "null argument");
+  DSLAM_REQUIRE(!e->reg_graph_sums.empty(), "no joint registration has run on this engine");
+  DSLAM_REQUIRE(pair >= 0 && (size_t)pair < e->reg_graph_sums.size() / 33, "the pair index is out of range");
+  memcpy(out, e->reg_graph_sums.data() + (size_t)pair * 33, 33 * sizeof(double));
+  return DSLAM_OK;
+}
+
 // ---- map merge --------------------------------------------------------------------------------------------------
 int dslam_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_dst_from_src[16],
                      const dslam_merge_params *params, dslam_merge_result *result) {

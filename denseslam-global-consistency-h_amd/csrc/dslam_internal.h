@@ -111,6 +111,16 @@ struct MergeScratch {
   PinnedBuffer<MergeCounters> counters_host;
   PinnedBuffer<unsigned long long> changed;   // mapped: voxels changed, one count per workgroup of the block kernel
 };
+// dslam_register_graph (register_graph.hip): its own scratch -- allocated by the first call, grown as a whole (built aside,
+// move-assigned); the list and counter slots other calls use are left alone
+struct RegisterGraphScratch {
+  int entries = 0;                       // capacity of live_list
+  DeviceBuffer<int> live_list;           // the resident entries of every distinct source of a call, one range per source
+  DeviceBuffer<int> live_counts;         // [DSLAM_MAX_RENDER_MAPS] entries in each range
+  PinnedBuffer<int> live_counts_host;
+  PinnedBuffer<double> partials;         // mapped: [workgroups][33], one row per workgroup of k_register_graph
+  PinnedBuffer<void> jobs;               // mapped: the pair table and the workgroup -> pair table the kernel reads
+};
 }  // namespace dslam
 
 // (the handles' destructors free memory now: they are not part of the library's exported names)
@@ -187,6 +197,9 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   double reg_last_sums[33] = {0};     // the totals of the most recent evaluation (dslam_debug_register_sums; test hook)
   bool reg_have_sums = false;
   dslam::MergeScratch merge;          // dslam_merge_maps (merge.hip)
+  dslam::RegisterGraphScratch reg_graph;   // dslam_register_graph (register_graph.hip)
+  std::vector<double> reg_graph_sums; // [pairs][33]: each pair's totals at the most recent joint evaluation it took part
+                                      // in (dslam_debug_register_graph_sums; test hook)
   // dslam_debug_merge_phases (bench hook): wall clock of the last merge's phases, each closed by a wait for the stream --
   // [0] the source's live list, [1] mark kernels, [2] ordered selections (ranks, serve, touched list), [3] block kernel,
   // [4] read-backs
@@ -489,6 +502,10 @@ int launch_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, c
 // src / dst / X / params already checked (and defaulted) by dslam_register_maps; X: in the start, out the estimate
 int launch_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_scene *dst, float *X,
                          const dslam_register_params *params, dslam_register_result *result);
+// everything already checked (and params defaulted) by dslam_register_graph; T: in the starts, out the estimates
+int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, float *T_map_from_world, int num_maps,
+                          const int32_t *pairs, int num_pairs, int anchor, const dslam_register_params *params,
+                          dslam_register_graph_result *result, dslam_register_pair_result *pair_results);
 // src / dst / X / params already checked (and defaulted) by dslam_merge_maps
 int launch_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float *X,
                       const dslam_merge_params *params, dslam_merge_result *result);

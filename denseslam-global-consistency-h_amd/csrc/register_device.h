@@ -1,0 +1,26 @@
+// register_device.h -- what the kernels of the map registrations share (register.hip: dslam_register_maps, one pair per
+// launch; register_graph.hip: dslam_register_graph, every pair of a pose graph in one launch): the sizes, the parameters of
+// one source read against one destination, and -- in register_body.h -- the evaluation itself.
+#pragma once
+#include "mesh_device.h"
+#include "multimap_device.h"
+
+namespace dslam {
+
+constexpr int kRegSums = 33;
+constexpr int kRegGrid = 512;      // workgroups of the registration kernels: two per CU of an MI355X
+constexpr int kRegThreads = 256;   // lane t takes voxels t and t + 256 of a block
+constexpr int kRegWaves = kRegThreads / 64;
+
+struct RegisterParams {
+  const HashEntry *hash;     // the source
+  const uint2 *voxels;
+  const int *live_list;      // its resident entries, ascending
+  const int *live_count;
+  MultiMap dst;              // the destination read from the source's voxel frame: T = X~
+  int band_raw;              // (int)(band * 32767)
+  float residual_gate;
+  double *partials;          // [gridDim.x][kRegSums]
+};
+
+}  // namespace dslam

@@ -453,6 +453,37 @@ class ITMMainEngine {
     ms->estimatedGlobalPose.SetM(M);
     return true;
   }
+  /// (extension) Align all local maps jointly from their voxels (dslam_register_graph, law in DESIGN.md section 15): `pairs`
+  /// lists the overlapping maps as (src, dst) indices, `anchor` is the map whose pose is held.  The starts are the maps'
+  /// estimatedGlobalPoses; when the registration converges (stop reason 0) every other map's estimatedGlobalPose is set to
+  /// its estimate and the call returns true, otherwise all poses are left alone, as AlignLocalMap leaves its one.  One
+  /// kernel launch per evaluation however many pairs, and every overlap constrains the result -- where a chain of
+  /// AlignLocalMap calls would add up its errors.  pair_out: one entry per pair.
+  bool AlignLocalMaps(const int (*pairs)[2], int num_pairs, int anchor, dslam_register_graph_result *out = nullptr,
+                      dslam_register_pair_result *pair_out = nullptr) {
+    const int n = mapManager->numLocalMaps();
+    std::vector<const dslam_scene *> scenes(n);
+    std::vector<float> T((size_t)n * 16);
+    for (int i = 0; i < n; i++) {
+      const ITMLocalMap *m = mapManager->getLocalMap(i);
+      scenes[i] = m->scene->handle;
+      memcpy(&T[(size_t)i * 16], m->estimatedGlobalPose.GetM().m, 16 * sizeof(float));
+    }
+    std::vector<int32_t> flat((size_t)(num_pairs > 0 ? num_pairs : 0) * 2);
+    for (size_t i = 0; i < flat.size(); i++) flat[i] = pairs[i / 2][i % 2];
+    dslam_register_graph_result res;
+    dslam_check(dslam_register_graph(engine_, scenes.data(), T.data(), n, flat.data(), num_pairs, anchor, nullptr, &res, pair_out),
+                "dslam_register_graph");
+    if (out) *out = res;
+    if (res.stop_reason != 0) return false;
+    for (int i = 0; i < n; i++) {
+      if (i == anchor) continue;
+      Matrix4f M;
+      memcpy(M.m, &T[(size_t)i * 16], 16 * sizeof(float));
+      mapManager->getLocalMap(i)->estimatedGlobalPose.SetM(M);
+    }
+    return true;
+  }
   /// (extension) Fuse local map `src` into local map `dst` on the device (dslam_merge_maps, law in DESIGN.md section 14)
   /// under X = T_dst T_src^-1 from the two estimatedGlobalPoses, composed as AlignLocalMap composes it -- call that first.
   /// `src` is only read and stays in the graph: dropping it is the caller's decision.  Returns false when the pools of

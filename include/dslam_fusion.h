@@ -572,6 +572,65 @@ int dslam_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_sce
 /* Test hook: the 33 raw sums (pivot at the origin) of the engine's most recent evaluation.  Error if none has run. */
 int dslam_debug_register_sums(dslam_engine *e, double out[33]);
 
+/* Joint alignment of N local maps from a list of overlapping pairs (no counterpart in the reference; the law is this
+ * project's own).  T_i: world -> map i, metres, column-major (estimatedGlobalPose.GetM()); pairs:
+ * (src, dst) indices into the map list, map src read as dslam_register_maps' source against map dst; `anchor`: the map
+ * whose T is held fixed.  T~_i is T_i in double with its translation in voxels (3 x 4, kept by the host through the run).
+ *   pair transform  X~_p = T~_d inv(T~_s) in double, inv = (R^T, -(R^T t)) and the product both with every sum evaluated
+ *                   left to right (the mirror's RigidInverse / RigidProduct); its 12 entries are rounded to float32;
+ *   one evaluation  every pair gets items 1 - 6 of dslam_register_maps at its X~_p, unchanged: 33 sums per pair.  One
+ *                   kernel launch and one wait for the stream, however many pairs;
+ *   active pairs    valid >= min_valid at the start poses; the others are reported and then left out of everything;
+ *   cost            sum over active pairs of (sum b^2 + (N_p - valid_p) gate^2), divided by the sum of their N_p;
+ *   linearisation   map i moves by a left increment about a pivot c_i in its own voxel frame, T~_i' = Inc(y_i, c_i) T~_i
+ *                   (Inc: dslam_register_maps' step), so X~' = Inc_d X~ Inc_s^-1.  With H_p, g_p the pair's 6 x 6 and
+ *                   6-vector at the origin, P(c) = [[I, -[c]x], [0, I]] and Ad(X) = [[R, 0], [[t]x R, R]] (X~ in double,
+ *                   before rounding): J_d = P(c_d), J_s = -P(c_s) Ad(X~)^T; the pair adds J_a H_p J_b^T to block (a, b)
+ *                   and J_a g_p to block a, for a, b in {s, d};
+ *   pivots          c_i = (sum over active pairs with d = i of sum q + sum over active pairs with s = i of
+ *                   valid_p X~_p^-1 (sum q / valid_p)) / (the sum of valid_p over those pairs); 0 if there is none;
+ *   step            the anchor's rows and columns are removed; (H + lambda diag H) y = g over the 6 (N - 1) unknowns,
+ *                   an unknown whose diagonal entry is not positive left out; applied to every free map;
+ *   acceptance      the new evaluation has a lower cost and every active pair still has valid >= min_valid;
+ *   lambda, stop reasons 0 - 2: dslam_register_maps', the termination test on the largest |rotation| and the largest
+ *                   |translation| over the free maps;  stop reason 3: the active pairs do not connect every map to the
+ *                   anchor -- no step is attempted;
+ *   conditioning    the smallest eigenvalue of D^-1/2 H D^-1/2 of the reduced matrix at the last accepted evaluation (0
+ *                   if a diagonal entry is not positive, or on stop reason 3).
+ * On every stop reason the T_i return the last accepted poses (rotation rounded to float32, translation times voxel_size,
+ * then rounded); untouched, byte for byte, if no step was accepted; the anchor's T is never written.  Two maps, the pair
+ * (0, 1), anchor 0 and T_0 the identity is dslam_register_maps(src 0, dst 1, X = T_1), step for step.
+ * All maps are only read (blocks that are swapped out are simply not resident).  Waits for the stream on synchronous and
+ * asynchronous engines.  DSLAM_ERR_INVALID with every T untouched: a NULL argument other than params or pair_results,
+ * num_maps outside 2 .. DSLAM_MAX_RENDER_MAPS, num_pairs outside 1 .. DSLAM_MAX_REGISTER_PAIRS, an index out of range,
+ * src == dst, an ordered pair given twice, a scene listed twice, a scene of another engine, voxel_size or mu that differ
+ * bitwise between two maps, a non-finite T or one whose rotation block is not orthonormal to 1e-4, a negative parameter. */
+#define DSLAM_MAX_REGISTER_PAIRS 128
+typedef struct {
+  int32_t evaluations;
+  int32_t stop_reason;
+  int32_t active_pairs;
+  float cost_first;                /* cost at the start poses */
+  float cost_last;                 /* cost at the returned poses */
+  float conditioning;
+} dslam_register_graph_result;
+typedef struct {
+  int32_t candidates;              /* N_p */
+  int32_t valid_first;             /* valid voxels at the start poses */
+  int32_t valid_last;              /* ... at the returned poses (an inactive pair: valid_first) */
+  int32_t active;
+  float cost_first;                /* the pair's own (sum b^2 + misses gate^2) / N_p at the start poses */
+  float cost_last;                 /* ... at the returned poses */
+} dslam_register_pair_result;
+int dslam_register_graph(dslam_engine *e, const dslam_scene *const *scenes,
+                         float *T_map_from_world /* [num_maps][16]; in: start, out: estimate */, int num_maps,
+                         const int32_t *pairs /* [num_pairs][2] = (src, dst) */, int num_pairs, int anchor,
+                         const dslam_register_params *params /* NULL: defaults */, dslam_register_graph_result *result,
+                         dslam_register_pair_result *pair_results /* [num_pairs], may be NULL */);
+/* Test hook: the 33 raw sums (pivot at the origin) of pair `pair` at the engine's most recent joint evaluation (a pair
+ * that was not active: at the first).  Error if no dslam_register_graph has run or the index is out of range. */
+int dslam_debug_register_graph_sums(dslam_engine *e, int pair, double out[33]);
+
 /* Fuse one local map into another on the device (no counterpart in the reference; the law is this project's own,
  * DESIGN.md section 14).  X is what dslam_register_maps takes and returns: source frame -> destination frame, metres,
  * column-major.  X~ is X with its translation in voxel units, Y~ its inverse (R^T, -R^T t); both are formed on the host

@@ -32,6 +32,7 @@ flags=$(make -s -C "$root/$csrc" --eval='print-flags: ; @echo $(HIPCC) $(HIPFLAG
 flags="$flags -Wno-unused-command-line-argument"
 status=0
 for src in $srcs; do
+  if [ ! -f "$tmp/base/$csrc/$src" ]; then echo "$src: new in the tree (not in $rev)"; continue; fi
   (cd "$tmp/base/$csrc" && $flags --offload-device-only -S "$src" -o "$tmp/asm/${src%.hip}.base.s") &
   (cd "$root/$csrc" && $flags --offload-device-only -S "$src" -o "$tmp/asm/${src%.hip}.new.s") &
   wait
