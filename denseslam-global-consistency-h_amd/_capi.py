@@ -100,6 +100,25 @@ class RegisterPairResult(C.Structure):
 assert C.sizeof(RegisterGraphResult) == 24 and C.sizeof(RegisterPairResult) == 24  # the header's layouts
 
 
+class PairSelectParams(C.Structure):
+    """dslam_pair_select_params; min_shared_octants / max_pairs left at 0 select their defaults."""
+    _fields_ = [("min_shared_octants", C.c_int32), ("one_direction", C.c_int32), ("max_pairs", C.c_int32), ("pad", C.c_int32)]
+
+    def __init__(self, min_shared_octants=0, one_direction=0, max_pairs=0):
+        super().__init__(min_shared_octants, one_direction, max_pairs, 0)
+
+
+class PairSelectResult(C.Structure):
+    """dslam_pair_select_result."""
+    _fields_ = [("qualifying", C.c_int32), ("selected", C.c_int32), ("num_components", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+assert C.sizeof(PairSelectParams) == 16 and C.sizeof(PairSelectResult) == 16  # the header's layouts
+
+
 class MergeParams(C.Structure):
     """dslam_merge_params; max_passes = 0 selects its default."""
     _fields_ = [("max_passes", C.c_int32), ("with_colour", C.c_int32)]
@@ -724,6 +743,44 @@ class CApi:
         out = np.empty(33, dtype=np.float64)
         self._call("debug_register_graph_sums", self._engine, C.c_int(int(pair)), out.ctypes.data_as(C.POINTER(C.c_double)))
         return out
+
+    # -- overlap survey and pair selection ---------------------------------------------------------------
+    def survey_overlaps(self, scenes, map_poses):
+        """dslam_survey_overlaps: which of N local maps overlap, at block granularity.  `scenes` / `map_poses` as
+        register_graph.  Returns (live [N], shared_blocks [N, N], shared_octants [N, N]), int32, row = source map."""
+        scenes = list(scenes)
+        T = np.asarray(map_poses, dtype=np.float32)
+        if T.ndim != 3 or T.shape[1:] != (4, 4):
+            raise ValueError("map_poses must be N 4x4 matrices")
+        if len(T) != len(scenes):
+            raise ValueError(f"{len(scenes)} scenes but {len(T)} map poses")
+        n = len(scenes)
+        ptrs = (C.c_void_p * max(n, 1))(*[None if s is None else s.ptr for s in scenes])
+        t_abi = np.ascontiguousarray(np.transpose(T, (0, 2, 1))).reshape(-1) if n else np.zeros(16, np.float32)
+        live = np.zeros(max(n, 1), dtype=np.int32)
+        blocks = np.zeros((max(n, 1), max(n, 1)), dtype=np.int32)
+        octants = np.zeros((max(n, 1), max(n, 1)), dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._call("survey_overlaps", self._engine, ptrs, _fptr(t_abi), C.c_int(n), live.ctypes.data_as(i32),
+                   blocks.ctypes.data_as(i32), octants.ctypes.data_as(i32))
+        return live, blocks, octants
+
+    def select_register_pairs(self, live, shared_octants, params=None):
+        """dslam_select_register_pairs: the pair list for register_graph from a survey (host only).  Returns (pairs
+        [selected, 2] int32 as (src, dst), component [N] int32, PairSelectResult)."""
+        live = np.ascontiguousarray(np.asarray(live, dtype=np.int32))
+        shared = np.ascontiguousarray(np.asarray(shared_octants, dtype=np.int32))
+        n = len(live)
+        if shared.shape != (n, n):
+            raise ValueError("shared_octants must be N x N for N live counts")
+        pairs = np.zeros((MAX_REGISTER_PAIRS, 2), dtype=np.int32)
+        component = np.zeros(max(n, 1), dtype=np.int32)
+        res = PairSelectResult()
+        i32 = C.POINTER(C.c_int32)
+        self._call("select_register_pairs", live.ctypes.data_as(i32), shared.ctypes.data_as(i32), C.c_int(n),
+                   C.byref(params) if params is not None else None, pairs.ctypes.data_as(i32), component.ctypes.data_as(i32),
+                   C.byref(res))
+        return pairs[:res.selected].copy(), component[:n], res
 
     # -- map merge -------------------------------------------------------------------------------------
     def merge_maps(self, src, dst, X, params=None):

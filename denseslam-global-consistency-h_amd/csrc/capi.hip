@@ -1649,6 +1649,47 @@ int dslam_debug_register_graph_sums(dslam_engine *e, int pair, double out[33]) {
   return DSLAM_OK;
 }
 
+// ---- overlap survey and pair selection ------------------------------------------------------------------------------
+int dslam_survey_overlaps(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                          int32_t *live_blocks_out, int32_t *shared_blocks_out, int32_t *shared_octants_out) {
+  DSLAM_REQUIRE(e && scenes && T_map_from_world && live_blocks_out && shared_octants_out, "null argument");
+  DSLAM_REQUIRE(num_maps >= 2 && num_maps <= DSLAM_MAX_RENDER_MAPS, "num_maps must be 2 .. DSLAM_MAX_RENDER_MAPS");
+  for (int i = 0; i < num_maps; i++) {
+    const dslam_scene *s = scenes[i];
+    DSLAM_REQUIRE(s, "a scene in the list is NULL");
+    DSLAM_REQUIRE(s->engine == e, "a scene in the list belongs to another engine");
+    for (int j = 0; j < i; j++) DSLAM_REQUIRE(scenes[j] != s, "a scene is listed twice");
+    DSLAM_REQUIRE(memcmp(&s->p.voxel_size, &scenes[0]->p.voxel_size, sizeof(float)) == 0 &&
+                      memcmp(&s->p.mu, &scenes[0]->p.mu, sizeof(float)) == 0,
+                  "all maps of an overlap survey need the same voxel_size and mu");
+    const float *T = T_map_from_world + 16 * i;
+    for (int k = 0; k < 16; k++) DSLAM_REQUIRE(std::isfinite(T[k]), "a map transform is not finite");
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++) {
+        double dot = 0.0;
+        for (int k = 0; k < 3; k++) dot += (double)T[a * 4 + k] * (double)T[b * 4 + k];
+        DSLAM_REQUIRE(fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-4, "a map transform's rotation block is not orthonormal");
+      }
+  }
+  return launch_survey_overlaps(e, scenes, T_map_from_world, num_maps, live_blocks_out, shared_blocks_out, shared_octants_out);
+}
+
+int dslam_select_register_pairs(const int32_t *live_blocks, const int32_t *shared_octants, int num_maps,
+                                const dslam_pair_select_params *params, int32_t *pairs_out, int32_t *component_out,
+                                dslam_pair_select_result *result) {
+  DSLAM_REQUIRE(live_blocks && shared_octants && pairs_out && component_out && result, "null argument");
+  DSLAM_REQUIRE(num_maps >= 2 && num_maps <= DSLAM_MAX_RENDER_MAPS, "num_maps must be 2 .. DSLAM_MAX_RENDER_MAPS");
+  dslam_pair_select_params sp = {0, 0, 0, 0};
+  if (params) sp = *params;
+  DSLAM_REQUIRE(sp.min_shared_octants >= 0 && sp.one_direction >= 0 && sp.max_pairs >= 0, "a selection parameter is negative");
+  if (sp.min_shared_octants == 0) sp.min_shared_octants = 64;
+  if (sp.max_pairs == 0) sp.max_pairs = DSLAM_MAX_REGISTER_PAIRS;
+  DSLAM_REQUIRE(sp.max_pairs <= DSLAM_MAX_REGISTER_PAIRS, "max_pairs is above DSLAM_MAX_REGISTER_PAIRS");
+  DSLAM_REQUIRE(sp.max_pairs >= num_maps - 1, "max_pairs is below num_maps - 1: a spanning set of pairs would not fit");
+  select_register_pairs(live_blocks, shared_octants, num_maps, sp, pairs_out, component_out, result);
+  return DSLAM_OK;
+}
+
 // ---- map merge --------------------------------------------------------------------------------------------------
 int dslam_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_dst_from_src[16],
                      const dslam_merge_params *params, dslam_merge_result *result) {

@@ -121,6 +121,17 @@ struct RegisterGraphScratch {
   PinnedBuffer<double> partials;         // mapped: [workgroups][33], one row per workgroup of k_register_graph
   PinnedBuffer<void> jobs;               // mapped: the pair table and the workgroup -> pair table the kernel reads
 };
+// dslam_survey_overlaps (overlap.hip): its own scratch -- allocated by the first call, grown as a whole (built aside,
+// move-assigned); the list and counter slots other calls use and the registration scratch are left alone
+struct OverlapScratch {
+  int entries = 0;                       // capacity of live_list
+  DeviceBuffer<int> live_list;           // the resident entries of every map of a call, one range per map
+  DeviceBuffer<int> live_counts;         // [DSLAM_MAX_RENDER_MAPS] entries in each range
+  PinnedBuffer<int> live_counts_host;
+  PinnedBuffer<int> rows;                // mapped: [workgroups][2 N], one row per workgroup of k_survey_overlaps
+  PinnedBuffer<void> tables_host;        // the tables of a call on their way to the device:
+  DeviceBuffer<void> tables;             // workgroup -> source map, the map descriptors, the N x N pair transforms
+};
 }  // namespace dslam
 
 // (the handles' destructors free memory now: they are not part of the library's exported names)
@@ -198,6 +209,7 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   bool reg_have_sums = false;
   dslam::MergeScratch merge;          // dslam_merge_maps (merge.hip)
   dslam::RegisterGraphScratch reg_graph;   // dslam_register_graph (register_graph.hip)
+  dslam::OverlapScratch overlap;      // dslam_survey_overlaps (overlap.hip)
   std::vector<double> reg_graph_sums; // [pairs][33]: each pair's totals at the most recent joint evaluation it took part
                                       // in (dslam_debug_register_graph_sums; test hook)
   // dslam_debug_merge_phases (bench hook): wall clock of the last merge's phases, each closed by a wait for the stream --
@@ -506,6 +518,13 @@ int launch_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_sc
 int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, float *T_map_from_world, int num_maps,
                           const int32_t *pairs, int num_pairs, int anchor, const dslam_register_params *params,
                           dslam_register_graph_result *result, dslam_register_pair_result *pair_results);
+// scenes / T already checked by dslam_survey_overlaps; the outputs are written only when everything has succeeded
+int launch_survey_overlaps(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                           int32_t *live_blocks_out, int32_t *shared_blocks_out, int32_t *shared_octants_out);
+// arguments already checked (and params defaulted) by dslam_select_register_pairs: the selection law of DESIGN.md section 16
+void select_register_pairs(const int32_t *live_blocks, const int32_t *shared_octants, int num_maps,
+                           const dslam_pair_select_params &params, int32_t *pairs_out, int32_t *component_out,
+                           dslam_pair_select_result *result);
 // src / dst / X / params already checked (and defaulted) by dslam_merge_maps
 int launch_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float *X,
                       const dslam_merge_params *params, dslam_merge_result *result);

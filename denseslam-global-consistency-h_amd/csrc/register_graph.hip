@@ -88,22 +88,6 @@ int ensure_graph_scratch(dslam_engine *e, int entries) {
   return DSLAM_OK;
 }
 
-// The workgroups of the grid over the pairs `use` (list order): G_p = 1 + floor((grid - n) L_p / sum L), the rest handed
-// out one each in list order -- a function of the live counts alone, and all of the grid to a single pair.
-void split_workgroups(const std::vector<int> &use, const std::vector<int> &live_of_pair, std::vector<int> &first, std::vector<int> &count) {
-  const int n = (int)use.size();
-  long long total = 0;
-  for (int p : use) total += live_of_pair[p];
-  int given = 0;
-  for (int p : use) {
-    count[p] = 1 + (total > 0 ? (int)((long long)(kRegGrid - n) * live_of_pair[p] / total) : 0);
-    given += count[p];
-  }
-  for (int k = 0; given < kRegGrid; k = (k + 1) % n, given++) count[use[k]]++;
-  int at = 0;
-  for (int p : use) { first[p] = at; at += count[p]; }
-}
-
 // Ad(X)^T for twists ordered (rotation, translation): Ad = [[R, 0], [[t]x R, R]]
 void adjoint_transposed(const double X[12], double out[36]) {
   const double t[3] = {X[3], X[7], X[11]};
@@ -190,7 +174,7 @@ int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, flo
   // the job table of the pairs `use`: everything but the transforms
   std::vector<int> first_wg(num_pairs, 0), num_wg(num_pairs, 0);
   auto plan = [&](const std::vector<int> &use) {
-    split_workgroups(use, live_of_pair, first_wg, num_wg);
+    split_workgroups(kRegGrid, use, live_of_pair, first_wg, num_wg);
     for (int p : use) {
       const dslam_scene *s = scenes[pairs[2 * p]], *d = scenes[pairs[2 * p + 1]];
       RegisterGraphJob &j = jobs[p];
@@ -209,15 +193,8 @@ int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, flo
   std::vector<double> Xp((size_t)num_pairs * 12);
   auto evaluate = [&](const std::vector<double> &T, const std::vector<int> &use, GraphEvaluation &ev) -> int {
     for (int p : use) {
-      double inv[12];
-      rigid_inverse(&T[(size_t)pairs[2 * p] * 12], inv);
-      rigid_product(&T[(size_t)pairs[2 * p + 1] * 12], inv, &Xp[(size_t)p * 12]);
-      bool identity = true;
-      for (int k = 0; k < 12; k++) {
-        const float v = (float)Xp[(size_t)p * 12 + k];
-        jobs[p].dst.T[k] = v;
-        identity = identity && v == ((k % 5) == 0 ? 1.0f : 0.0f);
-      }
+      const bool identity = pair_transform(&T[(size_t)pairs[2 * p] * 12], &T[(size_t)pairs[2 * p + 1] * 12], &Xp[(size_t)p * 12],
+                                           jobs[p].dst.T);
       jobs[p].dst.identity = identity ? 1 : 0;
     }
     hipLaunchKernelGGL(k_register_graph, dim3(kRegGrid), dim3(kRegThreads), 0, e->stream, kp);
@@ -244,11 +221,7 @@ int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, flo
 
   // ---- the start poses ----
   std::vector<double> T((size_t)num_maps * 12);
-  for (int i = 0; i < num_maps; i++)
-    for (int row = 0; row < 3; row++) {
-      for (int col = 0; col < 3; col++) T[(size_t)i * 12 + row * 4 + col] = (double)T_io[16 * i + col * 4 + row];
-      T[(size_t)i * 12 + row * 4 + 3] = (double)T_io[16 * i + 12 + row] / vs;
-    }
+  for (int i = 0; i < num_maps; i++) voxel_pose(T_io + 16 * i, vs, &T[(size_t)i * 12]);
   std::vector<int> all(num_pairs), active;
   for (int p = 0; p < num_pairs; p++) all[p] = p;
   GraphEvaluation good;

@@ -1,7 +1,8 @@
 // register_host.h -- the host arithmetic of the map registrations (double): the damped solve, the conditioning, the pivot
 // and twist matrices and the rigid compositions.  register.hip (one pair, 6 unknowns) and register_graph.hip (a pose
 // graph, 6 (N - 1) unknowns) run the same functions, so a graph of one pair repeats the pairwise call operation for
-// operation (DESIGN.md sections 13 and 15).
+// operation (DESIGN.md sections 13 and 15).  The pair transform and the split of a fixed grid are also what the overlap
+// survey (overlap.hip) uses.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -156,6 +157,44 @@ inline void rigid_product(const double A[12], const double B[12], double C[12]) 
     for (int c = 0; c < 4; c++)
       C[r * 4 + c] = ((A[r * 4 + 0] * B[0 * 4 + c] + A[r * 4 + 1] * B[1 * 4 + c]) + A[r * 4 + 2] * B[2 * 4 + c]) +
                      A[r * 4 + 3] * (c == 3 ? 1.0 : 0.0);
+}
+
+// T~: a column-major float32 4 x 4 in metres (world -> map) as 3 x 4 row-major double with its translation in voxels
+inline void voxel_pose(const float T[16], double voxel_size, double out[12]) {
+  for (int row = 0; row < 3; row++) {
+    for (int col = 0; col < 3; col++) out[row * 4 + col] = (double)T[col * 4 + row];
+    out[row * 4 + 3] = (double)T[12 + row] / voxel_size;
+  }
+}
+
+// the pair transform X~ = T~_d inv(T~_s) in double (X) and rounded to float32 (Xf); returns whether Xf is the identity
+inline bool pair_transform(const double Ts[12], const double Td[12], double X[12], float Xf[12]) {
+  double inv[12];
+  rigid_inverse(Ts, inv);
+  rigid_product(Td, inv, X);
+  bool identity = true;
+  for (int k = 0; k < 12; k++) {
+    Xf[k] = (float)X[k];
+    identity = identity && Xf[k] == ((k % 5) == 0 ? 1.0f : 0.0f);
+  }
+  return identity;
+}
+
+// The workgroups of a grid over the jobs `use` (list order): G_p = 1 + floor((grid - n) L_p / sum L), the rest handed
+// out one each in list order -- a function of the live counts alone, and all of the grid to a single job.
+inline void split_workgroups(int grid, const std::vector<int> &use, const std::vector<int> &live_of, std::vector<int> &first,
+                             std::vector<int> &count) {
+  const int n = (int)use.size();
+  long long total = 0;
+  for (int p : use) total += live_of[p];
+  int given = 0;
+  for (int p : use) {
+    count[p] = 1 + (total > 0 ? (int)((long long)(grid - n) * live_of[p] / total) : 0);
+    given += count[p];
+  }
+  for (int k = 0; given < grid; k = (k + 1) % n, given++) count[use[k]]++;
+  int at = 0;
+  for (int p : use) { first[p] = at; at += count[p]; }
 }
 
 }  // namespace

@@ -484,6 +484,44 @@ class ITMMainEngine {
     }
     return true;
   }
+  /// (extension) Which local maps overlap (dslam_survey_overlaps, law in DESIGN.md section 16): under the maps'
+  /// estimatedGlobalPoses, `live[i]` becomes map i's resident blocks and `sharedOctants[s * n + d]` the octants of map
+  /// s's blocks that fall into a resident block of map d (n = numLocalMaps(); the diagonal is 8 live[s]).  Only the hash
+  /// tables are read.
+  void SurveyLocalMapOverlaps(std::vector<int32_t> &live, std::vector<int32_t> &sharedOctants) {
+    const int n = mapManager->numLocalMaps();
+    std::vector<const dslam_scene *> scenes(n);
+    std::vector<float> T((size_t)n * 16);
+    for (int i = 0; i < n; i++) {
+      const ITMLocalMap *m = mapManager->getLocalMap(i);
+      scenes[i] = m->scene->handle;
+      memcpy(&T[(size_t)i * 16], m->estimatedGlobalPose.GetM().m, 16 * sizeof(float));
+    }
+    std::vector<int32_t> l((size_t)n), o((size_t)n * n);
+    dslam_check(dslam_survey_overlaps(engine_, scenes.data(), T.data(), n, l.data(), nullptr, o.data()), "dslam_survey_overlaps");
+    live.swap(l);
+    sharedOctants.swap(o);
+  }
+  /// (extension) AlignLocalMaps without a pair list from the caller: the overlaps are surveyed under the maps'
+  /// estimatedGlobalPoses (SurveyLocalMapOverlaps), the pairs selected by dslam_select_register_pairs with its defaults
+  /// (both directions of a pair), and AlignLocalMaps runs on them.  When the qualifying pairs do not join all maps
+  /// (num_components > 1) no registration is attempted: the call returns false and every pose is left alone.
+  /// pairs_out (optional): the selected pairs as (src, dst), by (src, dst) ascending.
+  bool AlignAllLocalMaps(int anchor, dslam_register_graph_result *out = nullptr, std::vector<int32_t> *pairs_out = nullptr,
+                         std::vector<dslam_register_pair_result> *pair_out = nullptr) {
+    const int n = mapManager->numLocalMaps();
+    std::vector<int32_t> live, shared, component((size_t)(n > 0 ? n : 1)), pairs((size_t)DSLAM_MAX_REGISTER_PAIRS * 2);
+    SurveyLocalMapOverlaps(live, shared);
+    dslam_pair_select_result sel;
+    dslam_check(dslam_select_register_pairs(live.data(), shared.data(), n, nullptr, pairs.data(), component.data(), &sel),
+                "dslam_select_register_pairs");
+    pairs.resize((size_t)sel.selected * 2);
+    if (pairs_out) *pairs_out = pairs;
+    if (pair_out) pair_out->assign((size_t)sel.selected, dslam_register_pair_result());
+    if (sel.num_components > 1) return false;
+    return AlignLocalMaps(reinterpret_cast<const int (*)[2]>(pairs.data()), sel.selected, anchor, out,
+                          pair_out ? pair_out->data() : nullptr);
+  }
   /// (extension) Fuse local map `src` into local map `dst` on the device (dslam_merge_maps, law in DESIGN.md section 14)
   /// under X = T_dst T_src^-1 from the two estimatedGlobalPoses, composed as AlignLocalMap composes it -- call that first.
   /// `src` is only read and stays in the graph: dropping it is the caller's decision.  Returns false when the pools of

@@ -631,6 +631,68 @@ int dslam_register_graph(dslam_engine *e, const dslam_scene *const *scenes,
  * that was not active: at the first).  Error if no dslam_register_graph has run or the index is out of range. */
 int dslam_debug_register_graph_sums(dslam_engine *e, int pair, double out[33]);
 
+/* Which local maps overlap: a survey of all N (N - 1) ordered pairs at block granularity (no counterpart in the
+ * reference; the law is this project's own).  It reads only the hash tables, never a voxel, and
+ * produces what dslam_register_graph cannot: the evidence for its list of overlapping pairs.  T_i: world -> map i, metres,
+ * column-major, exactly as dslam_register_graph takes them.
+ *   pair transform  for every ordered pair (s, d), s != d: X~_sd = T~_d inv(T~_s), dslam_register_graph's pair transform
+ *                   (double, translation in voxel units, the sums of inverse and product evaluated left to right, the
+ *                   12 entries rounded to float32);
+ *   live blocks     live[s] = the hash entries of map s with ptr >= 0: resident blocks (a swapped-out block is not);
+ *   octant centres  a resident block of s at block position B (the entry's three shorts) has 8 octants o = (ox, oy, oz)
+ *                   in {0, 1}^3 with centres c = 8 B + (1.5 + 4 ox, 1.5 + 4 oy, 1.5 + 4 oz), exact in float32;
+ *   transform       q = X~_sd c, each row evaluated as ((a x + b y) + c z) + d in float32 without contraction; an X~_sd
+ *                   that rounds to the identity reads at c itself;
+ *   destination     cell = (int)floorf(q) per axis, D = cell >> 3 (floor division, not truncation);
+ *   shared octant   every component of D lies in [-32768, 32767] and map d holds a resident entry (ptr >= 0) at D, found
+ *                   by the ordinary lookup: the bucket of D's hash, then its excess chain.  A q too large for an int, or
+ *                   not a number, is not shared;
+ *   shared_octants[s][d]  the shared octants over all resident blocks of s;
+ *   shared_blocks[s][d]   the resident blocks of s with at least one shared octant;
+ *   the diagonal    shared_octants[s][s] = 8 live[s], shared_blocks[s][s] = live[s], by definition (nothing is probed).
+ * All outputs are integers: exact, and the same on every run.  Both matrices are [N][N] with the source as the row.
+ * Every map is only read; no render state is involved.  Waits for the stream on synchronous and asynchronous engines.
+ * DSLAM_ERR_INVALID with the outputs untouched: a NULL argument other than shared_blocks_out, num_maps outside
+ * 2 .. DSLAM_MAX_RENDER_MAPS, a scene listed twice, a scene of another engine, voxel_size or mu that differ bitwise
+ * between two maps, a non-finite T or one whose rotation block is not orthonormal to 1e-4. */
+int dslam_survey_overlaps(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                          int32_t *live_blocks_out /* [N] */,
+                          int32_t *shared_blocks_out /* [N][N], row = source; may be NULL */,
+                          int32_t *shared_octants_out /* [N][N], row = source */);
+
+/* From a survey to a pair list dslam_register_graph accepts.  A pure host function: no engine, no device.
+ *   1. qualifying   the ordered pairs (s, d), s != d, with shared_octants[s][d] >= min_shared_octants;
+ *   2. one_direction != 0: of an unordered pair {a < b} whose two directions both qualify only one is kept, the one
+ *      whose source is covered more -- shared[s][d] / (8 live[s]), compared exactly as shared[a][b] live[b] against
+ *      shared[b][a] live[a] in 64-bit integers; a tie keeps (a, b).  A pair with one qualifying direction keeps it;
+ *   3. components   the maps joined by the qualifying pairs, undirected: component_out[i] is the smallest index in map
+ *      i's component, num_components their number;
+ *   4. the cap      the kept pairs ordered by shared_octants descending, ties by (s, d) ascending.  Pass 1 takes, in that
+ *      order, every pair that joins two sets of a union-find over the maps; pass 2 takes the others in that order until
+ *      max_pairs pairs are taken.  So the cap never disconnects what step 3 connected;
+ *   5. pairs_out    the selected pairs by (s, d) ascending (entries past `selected` are not written); qualifying = the
+ *      pairs kept after step 2, before the cap; selected = the pairs in pairs_out.
+ * min_shared_octants is a coarse prefilter in units of octants (64 octants = 8 blocks' worth), not a measurement:
+ * dslam_register_graph's own min_valid remains the gate on what a pair contributes.
+ * DSLAM_ERR_INVALID with the outputs untouched: a NULL argument other than params, num_maps outside
+ * 2 .. DSLAM_MAX_RENDER_MAPS, a negative parameter, max_pairs above DSLAM_MAX_REGISTER_PAIRS or below num_maps - 1. */
+typedef struct {
+  int32_t min_shared_octants;      /* 0 -> 64 */
+  int32_t one_direction;
+  int32_t max_pairs;               /* 0 -> DSLAM_MAX_REGISTER_PAIRS */
+  int32_t pad;
+} dslam_pair_select_params;
+typedef struct {
+  int32_t qualifying;
+  int32_t selected;
+  int32_t num_components;
+  int32_t pad;
+} dslam_pair_select_result;
+int dslam_select_register_pairs(const int32_t *live_blocks /* [N] */, const int32_t *shared_octants /* [N][N] */,
+                                int num_maps, const dslam_pair_select_params *params /* NULL: defaults */,
+                                int32_t *pairs_out /* [max_pairs][2] */, int32_t *component_out /* [N] */,
+                                dslam_pair_select_result *result);
+
 /* Fuse one local map into another on the device (no counterpart in the reference; the law is this project's own,
  * DESIGN.md section 14).  X is what dslam_register_maps takes and returns: source frame -> destination frame, metres,
  * column-major.  X~ is X with its translation in voxel units, Y~ its inverse (R^T, -R^T t); both are formed on the host
