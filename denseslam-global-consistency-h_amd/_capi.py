@@ -140,6 +140,27 @@ class MergeResult(C.Structure):
 assert C.sizeof(MergeParams) == 8 and C.sizeof(MergeResult) == 48  # the header's layouts
 
 
+class UnmergeParams(C.Structure):
+    """dslam_unmerge_params."""
+    _fields_ = [("with_colour", C.c_int32), ("reserved", C.c_int32)]
+
+    def __init__(self, with_colour=1):
+        super().__init__(with_colour, 0)
+
+
+class UnmergeResult(C.Structure):
+    """dslam_unmerge_result."""
+    _fields_ = [("src_blocks", C.c_int32), ("blocks_touched", C.c_int32), ("src_candidates", C.c_int64),
+                ("out_of_range", C.c_int64), ("candidates_without_block", C.c_int64), ("voxels_changed", C.c_int64),
+                ("depth_underweight", C.c_int64), ("colour_underweight", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+assert C.sizeof(UnmergeParams) == 8 and C.sizeof(UnmergeResult) == 56  # the header's layouts
+
+
 class WeightParams(C.Structure):
     _fields_ = [("depth_weighting", C.c_int32), ("max_new_w", C.c_int32), ("max_distance", C.c_float)]
 
@@ -790,6 +811,22 @@ class CApi:
         self._call("merge_maps", self._engine, src.ptr, dst.ptr, _fptr(mat_to_abi(X)),
                    C.byref(params) if params is not None else None, C.byref(res))
         return res
+
+    def unmerge_maps(self, src, dst, X, params=None):
+        """dslam_unmerge_maps: remove from `dst` what merge_maps(src, dst, X) added, on the device; `src` is only read.
+        Returns the UnmergeResult."""
+        res = UnmergeResult()
+        self._call("unmerge_maps", self._engine, src.ptr, dst.ptr, _fptr(mat_to_abi(X)),
+                   C.byref(params) if params is not None else None, C.byref(res))
+        return res
+
+    def remerge_maps(self, src, dst, X_old, X_new, params=None):
+        """dslam_remerge_maps: unmerge_maps(src, dst, X_old), then merge_maps(src, dst, X_new, params), in one call.
+        Returns (UnmergeResult, MergeResult); both zeroed when the two transforms are bit-identical."""
+        un, re = UnmergeResult(), MergeResult()
+        self._call("remerge_maps", self._engine, src.ptr, dst.ptr, _fptr(mat_to_abi(X_old)), _fptr(mat_to_abi(X_new)),
+                   C.byref(params) if params is not None else None, C.byref(un), C.byref(re))
+        return un, re
 
     def debug_merge_phases(self, enable):
         """The phase times (ms) of the last merge measured with the hook on; then turns the hook on or off."""

@@ -1691,9 +1691,10 @@ int dslam_select_register_pairs(const int32_t *live_blocks, const int32_t *share
 }
 
 // ---- map merge --------------------------------------------------------------------------------------------------
-int dslam_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_dst_from_src[16],
-                     const dslam_merge_params *params, dslam_merge_result *result) {
-  DSLAM_REQUIRE(e && src && dst && X_dst_from_src && result, "null argument");
+namespace {
+
+// what dslam_merge_maps, dslam_unmerge_maps and dslam_remerge_maps reject alike
+int check_merge_scenes(dslam_engine *e, const dslam_scene *src, const dslam_scene *dst) {
   DSLAM_REQUIRE(src->engine == e && dst->engine == e, "a scene belongs to another engine");
   DSLAM_REQUIRE(src != dst, "a map cannot be merged into itself");
   DSLAM_REQUIRE(memcmp(&src->p.voxel_size, &dst->p.voxel_size, sizeof(float)) == 0 && memcmp(&src->p.mu, &dst->p.mu, sizeof(float)) == 0,
@@ -1701,21 +1702,75 @@ int dslam_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, 
   DSLAM_REQUIRE(!src->p.use_swapping && !dst->p.use_swapping, "maps that use swapping cannot be merged");
   DSLAM_REQUIRE(src->num_shards == 1 && dst->num_shards == 1 && src->shard_count < 0 && dst->shard_count < 0,
                 "sharded maps cannot be merged");
-  for (int i = 0; i < 16; i++) DSLAM_REQUIRE(std::isfinite(X_dst_from_src[i]), "the transform is not finite");
+  return DSLAM_OK;
+}
+
+int check_merge_transform(const float X[16]) {
+  for (int i = 0; i < 16; i++) DSLAM_REQUIRE(std::isfinite(X[i]), "the transform is not finite");
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 3; j++) {
       double dot = 0.0;
-      for (int k = 0; k < 3; k++) dot += (double)X_dst_from_src[i * 4 + k] * (double)X_dst_from_src[j * 4 + k];
+      for (int k = 0; k < 3; k++) dot += (double)X[i * 4 + k] * (double)X[j * 4 + k];
       DSLAM_REQUIRE(fabs(dot - (i == j ? 1.0 : 0.0)) <= 1e-4, "the transform's rotation block is not orthonormal");
     }
+  return DSLAM_OK;
+}
+
+int check_merge_params(const dslam_scene *src, const dslam_merge_params *params, dslam_merge_params *mp) {
   DSLAM_REQUIRE((double)src->p.num_local_blocks * 512.0 < 4294967295.0, "the source has more blocks than the 32-bit order key can name");
-  dslam_merge_params mp = {0, 1};
-  if (params) mp = *params;
-  DSLAM_REQUIRE(mp.max_passes >= 0, "max_passes is negative");
-  if (mp.max_passes == 0) mp.max_passes = 16;
-  dst->version = next_map_version();  // the map changes: GetImage memos of this scene are stale
+  *mp = {0, 1};
+  if (params) *mp = *params;
+  DSLAM_REQUIRE(mp->max_passes >= 0, "max_passes is negative");
+  if (mp->max_passes == 0) mp->max_passes = 16;
+  return DSLAM_OK;
+}
+
+// the map changes: GetImage memos of this scene are stale
+void map_changed(dslam_scene *dst) {
+  dst->version = next_map_version();
   if (dst->front) dst->front->valid = false;
+}
+
+}  // namespace
+
+int dslam_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_dst_from_src[16],
+                     const dslam_merge_params *params, dslam_merge_result *result) {
+  DSLAM_REQUIRE(e && src && dst && X_dst_from_src && result, "null argument");
+  DSLAM_TRY(check_merge_scenes(e, src, dst));
+  DSLAM_TRY(check_merge_transform(X_dst_from_src));
+  dslam_merge_params mp;
+  DSLAM_TRY(check_merge_params(src, params, &mp));
+  map_changed(dst);
   return launch_merge_maps(e, src, dst, X_dst_from_src, &mp, result);
+}
+
+int dslam_unmerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_dst_from_src[16],
+                       const dslam_unmerge_params *params, dslam_unmerge_result *result) {
+  DSLAM_REQUIRE(e && src && dst && X_dst_from_src && result, "null argument");
+  DSLAM_TRY(check_merge_scenes(e, src, dst));
+  DSLAM_TRY(check_merge_transform(X_dst_from_src));
+  map_changed(dst);
+  return launch_unmerge_maps(e, src, dst, X_dst_from_src, params ? params->with_colour : 1, result, false);
+}
+
+int dslam_remerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_old[16],
+                       const float X_new[16], const dslam_merge_params *params, dslam_unmerge_result *unmerged,
+                       dslam_merge_result *merged) {
+  DSLAM_REQUIRE(e && src && dst && X_old && X_new && unmerged && merged, "null argument");
+  DSLAM_TRY(check_merge_scenes(e, src, dst));
+  DSLAM_TRY(check_merge_transform(X_old));
+  DSLAM_TRY(check_merge_transform(X_new));
+  dslam_merge_params mp;
+  DSLAM_TRY(check_merge_params(src, params, &mp));
+  memset(unmerged, 0, sizeof *unmerged);
+  memset(merged, 0, sizeof *merged);
+  if (memcmp(X_old, X_new, 16 * sizeof(float)) == 0) return DSLAM_OK;
+  map_changed(dst);
+  // the unmerge is only enqueued: the merge behind it reuses the source's live list, and its first read-back is the wait
+  DSLAM_TRY(launch_unmerge_maps(e, src, dst, X_old, mp.with_colour, unmerged, true));
+  const int rc = launch_merge_maps(e, src, dst, X_new, &mp, merged, true);
+  if (rc == DSLAM_OK) collect_unmerge_result(e, unmerged);
+  return rc;
 }
 
 int dslam_debug_merge_phases(dslam_engine *e, int enable, double out_ms[5]) {

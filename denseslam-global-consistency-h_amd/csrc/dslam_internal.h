@@ -99,6 +99,7 @@ struct MergeCounters {
   int touched;              // destination entries to fuse into
   int pad[3];
   unsigned long long candidates, out_of_range;
+  unsigned long long without_block;   // dslam_unmerge_maps: candidates whose target block the destination does not hold
 };
 struct MergeScratch {
   int src_entries = 0, dst_entries = 0, words = 0;
@@ -108,8 +109,9 @@ struct MergeScratch {
   DeviceBuffer<int> touched_list;        // [dst_entries]
   DeviceBuffer<int> live_list;           // [src_entries]
   DeviceBuffer<MergeCounters> counters;
-  PinnedBuffer<MergeCounters> counters_host;
-  PinnedBuffer<unsigned long long> changed;   // mapped: voxels changed, one count per workgroup of the block kernel
+  PinnedBuffer<MergeCounters> counters_host;   // [2]: the merge's read-backs, the unmerge's
+  PinnedBuffer<unsigned long long> changed;   // mapped: [workgroups] voxels changed, one count per workgroup of the merge's
+                                              // block kernel; then [workgroups][3], one row per workgroup of the unmerge's
 };
 // dslam_register_graph (register_graph.hip): its own scratch -- allocated by the first call, grown as a whole (built aside,
 // move-assigned); the list and counter slots other calls use are left alone
@@ -527,7 +529,13 @@ void select_register_pairs(const int32_t *live_blocks, const int32_t *shared_oct
                            dslam_pair_select_result *result);
 // src / dst / X / params already checked (and defaulted) by dslam_merge_maps
 int launch_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float *X,
-                      const dslam_merge_params *params, dslam_merge_result *result);
+                      const dslam_merge_params *params, dslam_merge_result *result, bool reuse_live = false);
+int ensure_merge_scratch(dslam_engine *e, int src_entries, int dst_entries);
+// dslam_unmerge_maps / dslam_remerge_maps (unmerge.hip), arguments already checked.  defer: enqueue only -- the caller
+// collects the result (collect_unmerge_result) after a later wait for the stream
+int launch_unmerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float *X, int with_colour,
+                        dslam_unmerge_result *result, bool defer);
+void collect_unmerge_result(dslam_engine *e, dslam_unmerge_result *result);
 int launch_decay(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int max_weight, int min_age, int force_all,
                  int which);
 int launch_slide_pop(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int which);

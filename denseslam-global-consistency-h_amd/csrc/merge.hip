@@ -15,8 +15,9 @@
 //              another pass is needed (different blocks that asked for the same slot).
 //   3. pull    k_merge_blocks: one workgroup per touched destination block at a time (fixed grid, grid-stride over the
 //              ordered list of touched entries), lane t the voxels 2t and 2t + 1 -- the block moves as 16-byte accesses.
-//              Each voxel reads the source trilinearly at Y~ p' (to_map / gather_cell / lerp8 of multimap_device.h), packs
-//              the result as a voxel and merges it with combine_voxel (combine_device.h), as a swap-in does.
+//              Each voxel reads the source trilinearly at Y~ p' (merge_resample of merge_device.h, shared with unmerge.hip:
+//              to_map / gather_cell / lerp8 of multimap_device.h), packs the result as a voxel and merges it with
+//              combine_voxel (combine_device.h), as a swap-in does.
 // No kernel here waits for another workgroup; the pass loop is bounded by max_passes on the host.
 #include <chrono>
 #include <cmath>
@@ -24,6 +25,7 @@
 
 #include "combine_device.h"
 #include "dslam_bits.h"
+#include "merge_device.h"
 #include "mesh_device.h"
 #include "multimap_device.h"
 
@@ -31,23 +33,8 @@
 
 namespace dslam {
 
-constexpr int kMergeGrid = 512;      // workgroups of the mark and block kernels: two per CU of an MI355X
-constexpr int kMergeThreads = 256;
-
 // its own type: the selection kernel of this translation unit is not mesh.hip's
 struct SelLiveMerge : SelLive {};
-
-// the destination block a source voxel falls into; false: outside the table's short range
-__device__ __forceinline__ bool merge_target(const MultiMap &fwd, const HashEntry &he, int l, int B[3]) {
-  const Vec3 p = {(float)(he.pos[0] * kBlock + (l & 7)), (float)(he.pos[1] * kBlock + ((l >> 3) & 7)), (float)(he.pos[2] * kBlock + (l >> 6))};
-  const Vec3 q = to_map(fwd, p);
-  const float tx = floorf(q.x + 0.5f), ty = floorf(q.y + 0.5f), tz = floorf(q.z + 0.5f);
-  const bool ok = tx >= -262144.0f && tx < 262144.0f && ty >= -262144.0f && ty < 262144.0f && tz >= -262144.0f && tz < 262144.0f;
-  B[0] = ok ? (int)tx >> 3 : 0;
-  B[1] = ok ? (int)ty >> 3 : 0;
-  B[2] = ok ? (int)tz >> 3 : 0;
-  return ok;
-}
 
 __global__ void k_merge_begin(SceneCounters *cnt, MergeCounters *mc) {
   cnt->base_free = cnt->last_free;
@@ -191,58 +178,6 @@ struct SelMergeTouched {
   __device__ void finish(int) const {}
 };
 
-struct MergeBlockParams {
-  const HashEntry *dst_hash;
-  uint4 *dst_voxels;         // two voxels per element
-  const int *touched_list;
-  const MergeCounters *mc;
-  MultiMap src;              // the source read from the destination's voxel frame: T = Y~
-  int max_w, with_colour;
-  unsigned long long *changed;   // [gridDim.x]
-};
-
-// the source resampled at the destination voxel (px, py, pz), packed as a voxel; the empty voxel where the source has
-// nothing to give
-__device__ __forceinline__ uint2 merge_resample(const MergeBlockParams &p, const VolumeRef &vol, int px, int py, int pz) {
-  const uint2 empty = make_uint2(kEmptyVoxelLo, kEmptyVoxelHi);
-  if (p.src.identity) {
-    const int ptr = find_block_ptr(vol.hash, vol.num_buckets, vol.mask, px >> 3, py >> 3, pz >> 3);
-    if (ptr < 0) return empty;
-    uint2 v = vol.voxels[(size_t)ptr * kBlock3 + ((px & 7) | ((py & 7) << 3) | ((pz & 7) << 6))];
-    if (!p.with_colour) v.y &= 0xff00ffffu;
-    return v;
-  }
-  const Vec3 pt = {(float)px, (float)py, (float)pz};
-  const Vec3 q = to_map(p.src, pt);
-  // a block coordinate outside the short range is never resident (and this keeps the casts below defined)
-  if (!(fabsf(q.x) < 262144.0f && fabsf(q.y) < 262144.0f && fabsf(q.z) < 262144.0f)) return empty;
-  const float fx = floorf(q.x), fy = floorf(q.y), fz = floorf(q.z);
-  uint2 t[8];
-  if (!gather_cell(vol, (int)fx, (int)fy, (int)fz, t)) return empty;
-  unsigned wd = 255u, wc = 255u;
-  float s[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const unsigned a = (t[k].x >> 16) & 0xffu, c = (t[k].y >> 16) & 0xffu;
-    wd = a < wd ? a : wd;
-    wc = c < wc ? c : wc;
-    s[k] = sdf_to_float((short)(t[k].x & 0xffffu));
-  }
-  if (wd == 0u) return empty;
-  const float cx = q.x - fx, cy = q.y - fy, cz = q.z - fz;
-  uint2 out;
-  out.x = (unsigned)(unsigned short)float_to_sdf(lerp8(s, cx, cy, cz)) | (wd << 16);
-  out.y = 0u;
-  if (p.with_colour && wc != 0u) {
-    float c0[8], c1[8], c2[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) { c0[k] = (float)(t[k].x >> 24); c1[k] = (float)(t[k].y & 0xffu); c2[k] = (float)((t[k].y >> 8) & 0xffu); }
-    out.x |= (unsigned)(unsigned char)(lerp8(c0, cx, cy, cz) + 0.5f) << 24;
-    out.y = (unsigned)(unsigned char)(lerp8(c1, cx, cy, cz) + 0.5f) | ((unsigned)(unsigned char)(lerp8(c2, cx, cy, cz) + 0.5f) << 8) | (wc << 16);
-  }
-  return out;
-}
-
 __global__ __launch_bounds__(kMergeThreads) void k_merge_blocks(MergeBlockParams p) {
   const int n = p.mc->touched;
   const VolumeRef vol = volume_of(p.src);
@@ -277,8 +212,6 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_blocks(MergeBlockParams
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-namespace {
-
 int ensure_merge_scratch(dslam_engine *e, int src_entries, int dst_entries) {
   MergeScratch &have = e->merge;
   if (have.keys && have.src_entries >= src_entries && have.dst_entries >= dst_entries) return DSLAM_OK;
@@ -293,11 +226,13 @@ int ensure_merge_scratch(dslam_engine *e, int src_entries, int dst_entries) {
   DSLAM_TRY(m.touched_list.alloc((size_t)m.dst_entries));
   DSLAM_TRY(m.live_list.alloc((size_t)m.src_entries));
   DSLAM_TRY(m.counters.alloc_zeroed(1, e->stream));
-  DSLAM_TRY(m.counters_host.alloc(1));
-  DSLAM_TRY(m.changed.alloc((size_t)kMergeGrid, hipHostMallocMapped));
+  DSLAM_TRY(m.counters_host.alloc(2));
+  DSLAM_TRY(m.changed.alloc((size_t)kMergeGrid * 4, hipHostMallocMapped));
   have = std::move(m);
   return DSLAM_OK;
 }
+
+namespace {
 
 // dslam_debug_merge_phases: wall clock per phase, each closed by a wait for the stream (only when the hook is on)
 struct PhaseClock {
@@ -316,9 +251,10 @@ struct PhaseClock {
 
 }  // namespace
 
-// src / dst / X / params already checked and defaulted by dslam_merge_maps
+// src / dst / X / params already checked and defaulted by dslam_merge_maps; reuse_live: the source's live list and its
+// count are those an unmerge of the same source has just left in the scratch (dslam_remerge_maps)
 int launch_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float *X_in,
-                      const dslam_merge_params *mp, dslam_merge_result *res) {
+                      const dslam_merge_params *mp, dslam_merge_result *res, bool reuse_live) {
   DSLAM_TRY(ensure_scratch(e, std::max(src->n_entries, dst->n_entries), std::max(src->p.num_local_blocks, dst->p.num_local_blocks)));
   DSLAM_TRY(ensure_merge_scratch(e, src->n_entries, dst->n_entries));
   MergeScratch &m = e->merge;
@@ -326,38 +262,17 @@ int launch_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst,
   unsigned *q1 = m.bits, *q2 = m.bits + m.words, *req = m.bits + 2 * (size_t)m.words, *touched = m.bits + 3 * (size_t)m.words;
   MergeCounters *mc = m.counters;
 
-  // X~ and Y~ = (R^T, -R^T t~): double, rounded to float32
   MultiMap fwd, inv;
-  memset(&fwd, 0, sizeof fwd);
-  memset(&inv, 0, sizeof inv);
-  {
-    const double vs = (double)src->p.voxel_size;
-    double R[3][3], t[3];
-    bool identity = true;
-    for (int i = 0; i < 16; i++) identity = identity && X_in[i] == ((i % 5) == 0 ? 1.0f : 0.0f);
-    for (int row = 0; row < 3; row++) {
-      for (int col = 0; col < 3; col++) R[row][col] = (double)X_in[col * 4 + row];
-      t[row] = (double)X_in[12 + row] / vs;
-    }
-    for (int row = 0; row < 3; row++) {
-      for (int col = 0; col < 3; col++) {
-        fwd.T[row * 4 + col] = (float)R[row][col];
-        inv.T[row * 4 + col] = (float)R[col][row];
-      }
-      fwd.T[row * 4 + 3] = (float)t[row];
-      inv.T[row * 4 + 3] = (float)-((R[0][row] * t[0] + R[1][row] * t[1]) + R[2][row] * t[2]);
-    }
-    fwd.identity = inv.identity = identity ? 1 : 0;
-  }
-  inv.hash = src->hash; inv.voxels = src->voxels;
-  inv.mask = (unsigned)(src->p.num_buckets - 1); inv.num_buckets = src->p.num_buckets;
+  merge_transforms(src, X_in, fwd, inv);
 
   for (double &ms : e->merge_phase_ms) ms = 0.0;
   PhaseClock clock(e);
   DSLAM_HIP(hipMemsetAsync(m.bits, 0, (size_t)m.words * 4 * sizeof(unsigned), e->stream));
-  SelLiveMerge live;
-  live.hash = src->hash;
-  DSLAM_TRY(launch_bits_select(e, src->alloc_bits, src->n_entries, live, m.live_list, src->n_entries, &mc->live, src->counters));
+  if (!reuse_live) {
+    SelLiveMerge live;
+    live.hash = src->hash;
+    DSLAM_TRY(launch_bits_select(e, src->alloc_bits, src->n_entries, live, m.live_list, src->n_entries, &mc->live, src->counters));
+  }
   DSLAM_HIP(hipGetLastError());
   DSLAM_TRY(clock.lap(0));
 

@@ -540,6 +540,47 @@ class ITMMainEngine {
     if (out) *out = res;
     return res.exhausted == 0;
   }
+  /// (extension) X = T_dst T_src^-1 from the two estimatedGlobalPoses, composed exactly as MergeLocalMap composes it
+  /// (double, RigidInverse / RigidProduct, rounded to float32): what a caller records when it merges, in order to undo the
+  /// merge later -- the poses may have moved by then.
+  void LocalMapTransform(int src, int dst, float X[16]) {
+    const ITMLocalMap *ms = mapManager->getLocalMap(src);
+    const ITMLocalMap *md = mapManager->getLocalMap(dst);
+    double Ts[16], Td[16], inv[16], Xd[16];
+    for (int i = 0; i < 16; i++) { Ts[i] = (double)ms->estimatedGlobalPose.GetM().m[i]; Td[i] = (double)md->estimatedGlobalPose.GetM().m[i]; }
+    RigidInverse(Ts, inv);
+    RigidProduct(Td, inv, Xd);
+    for (int i = 0; i < 16; i++) X[i] = (float)Xd[i];
+  }
+  /// (extension) Take local map `src` out of local map `dst` again (dslam_unmerge_maps, law in DESIGN.md section 17):
+  /// X_merged is the transform the merge was made under (LocalMapTransform at that time).  Exact only while nothing
+  /// clamped at max_w during the merge and neither map has changed since.  Returns false when a voxel of `dst` held less
+  /// than was to be taken out of it (such voxels are left alone).
+  bool UnmergeLocalMap(int src, int dst, const float X_merged[16], dslam_unmerge_result *out = nullptr) {
+    const ITMLocalMap *ms = mapManager->getLocalMap(src);
+    ITMLocalMap *md = mapManager->getLocalMap(dst);
+    dslam_unmerge_result res;
+    dslam_check(dslam_unmerge_maps(engine_, ms->scene->handle, md->scene->handle, X_merged, nullptr, &res), "dslam_unmerge_maps");
+    if (out) *out = res;
+    return res.depth_underweight == 0 && res.colour_underweight == 0;
+  }
+  /// (extension) Correct a merge after the poses have moved (dslam_remerge_maps): `src` is taken out of `dst` under
+  /// X_merged and merged again under X = T_dst T_src^-1 from the current estimatedGlobalPoses.  Nothing happens when the
+  /// two are bit-identical.  Returns MergeLocalMap's verdict.
+  bool RemergeLocalMap(int src, int dst, const float X_merged[16], dslam_unmerge_result *un = nullptr,
+                       dslam_merge_result *re = nullptr) {
+    const ITMLocalMap *ms = mapManager->getLocalMap(src);
+    ITMLocalMap *md = mapManager->getLocalMap(dst);
+    float X_new[16];
+    LocalMapTransform(src, dst, X_new);
+    dslam_unmerge_result ures;
+    dslam_merge_result mres;
+    dslam_check(dslam_remerge_maps(engine_, ms->scene->handle, md->scene->handle, X_merged, X_new, nullptr, &ures, &mres),
+                "dslam_remerge_maps");
+    if (un) *un = ures;
+    if (re) *re = mres;
+    return mres.exhausted == 0;
+  }
   /// inverse of a rigid transform (column-major): [R^T | -(R^T t)], each sum evaluated left to right
   static void RigidInverse(const double M[16], double out[16]) {
     for (int r = 0; r < 3; r++) {

@@ -741,6 +741,59 @@ int dslam_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, 
  * turns the hook on or off for the merges that follow. */
 int dslam_debug_merge_phases(dslam_engine *e, int enable, double out_ms[5]);
 
+/* Undo a map merge on the device (no counterpart in the reference; the law is this project's own):
+ * dslam_unmerge_maps(src, dst, X) removes from dst what dslam_merge_maps(src, dst, X) added.  X, X~, Y~ and the identity
+ * flag are formed exactly as dslam_merge_maps forms them.
+ *   1. targets (push): step 1 of the merge, unchanged -- the source's resident entries ascending by hash index, candidates
+ *      have w_depth > 0, q = X~ p with rows evaluated as ((a x + b y) + c z) + d in float32, target voxel floor(q + 0.5f)
+ *      per axis, target block B = t >> 3; a B outside int16 is skipped and counted in out_of_range;
+ *   2. lookup: every candidate's B is looked up in dst.  A hit marks the entry touched; a miss counts the candidate voxel
+ *      in candidates_without_block (one count per source voxel).  Nothing is allocated: the table, both free lists, the
+ *      counters, alloc_bits and the born stamps of dst are not written;
+ *   3. removal (pull): every voxel p' of every touched destination block.  The resampled voxel is step 3 of the merge,
+ *      unchanged: q' = Y~ p', cell floor(q'), all 8 taps in resident blocks of the source with w_depth > 0 (else the voxel
+ *      is left alone), sdf = (short)(blend * 32767), w_depth = min of the 8 taps'; the colour half live only with
+ *      with_colour and all 8 w_color > 0, each channel (unsigned char)(blend((float)c_k) + 0.5f), w_color = min of the
+ *      taps'; under the identity the source's voxel at p' as stored (its w_color read as 0 without with_colour).  It is
+ *      then taken out of the resident voxel by the inverse of CombineVoxelInformation, the two halves independent, in
+ *      float32 with no contraction and IEEE division:
+ *      depth half, ws the resampled w_depth and W the resident one: ws == 0 idles; W < ws idles and is counted in
+ *      depth_underweight (dst does not hold that much: it was decayed, or never merged); otherwise rem = W - ws;
+ *      rem == 0: sdf = 32767, w_depth = 0 (the colour byte that shares the word stays), as removing the last observation
+ *      leaves a voxel; rem > 0: F = ((float)W * (sdf / 32767.0f) - (float)ws * (sdf_s / 32767.0f)) / (float)rem, clamped
+ *      to [-1, 1], sdf = (short)(F * 32767.0f), w_depth = rem;
+ *      colour half, wcs and Wc the w_colors: wcs == 0 idles; Wc < wcs idles and is counted in colour_underweight;
+ *      rem == 0: the three channels and w_color become 0; otherwise per channel
+ *      v = (((float)dc / 255.0f) * (float)Wc - ((float)sc / 255.0f) * (float)wcs) / (float)rem, clamped to [0, 1], the
+ *      channel (unsigned char)(v * 255.0f), w_color = rem.
+ *      A voxel is stored only if it changed (voxels_changed).
+ * What the law does not promise: the removal is the exact inverse of the merge's weights, and of its values to within
+ * (W0 + ws) / W0 + 1 raw sdf units for a voxel of weight W0 before the merge, only while nothing
+ * clamped at max_w during the merge and src and the affected part of dst have not changed since; the call cannot check
+ * any of this.  Blocks the merge allocated stay allocated and hold empty voxels: releasing them is dslam_decay's job.
+ * src is only read.  dst's render states are not touched; GetImage memos and front-end records of dst are invalidated as
+ * by dslam_merge_maps.  Waits for the stream on synchronous and asynchronous engines.  DSLAM_ERR_INVALID with nothing
+ * changed: a NULL argument other than params, a scene of another engine, src == dst, voxel_size or mu that differ bitwise,
+ * a scene that uses swapping or is sharded, a non-finite X or one whose rotation block is not orthonormal to 1e-4. */
+typedef struct {
+  int32_t with_colour;             /* default 1 */
+  int32_t reserved;                /* 0 */
+} dslam_unmerge_params;
+typedef struct {
+  int32_t src_blocks, blocks_touched;
+  int64_t src_candidates, out_of_range, candidates_without_block, voxels_changed, depth_underweight, colour_underweight;
+} dslam_unmerge_result;
+int dslam_unmerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_dst_from_src[16],
+                       const dslam_unmerge_params *params /* NULL: defaults */, dslam_unmerge_result *result);
+/* Correct a merge: dslam_unmerge_maps(src, dst, X_old) with params->with_colour, then dslam_merge_maps(src, dst, X_new,
+ * params), in one call -- dst ends byte-identical to the two calls made one after the other, and the two results are what
+ * they return.  All arguments of both halves are checked before anything is changed (the rejections of both calls).
+ * X_old and X_new bit-identical: nothing is done, both results are zeroed, DSLAM_OK.  The one call validates once,
+ * compacts the source's live list once and saves one wait for the stream. */
+int dslam_remerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_old[16],
+                       const float X_new[16], const dslam_merge_params *params /* NULL: defaults */,
+                       dslam_unmerge_result *unmerged, dslam_merge_result *merged);
+
 /* ---- depth tracker (ICP) ---------------------------------------------------------------------- */
 /* trackingController->Track(trackingState, view) (InfiniTamDriver.h:151-163, reached through
  * DenseSlam.cpp:200-206 when the reference runs without ORB-SLAM2 odometry): upstream InfiniTAM v2's
