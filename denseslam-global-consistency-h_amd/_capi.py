@@ -54,6 +54,31 @@ class TrackerResult(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("valid_points_last", C.c_int32), ("f_last", C.c_float), ("pad", C.c_int32)]
 
 
+class TrackSdfParams(C.Structure):
+    """dslam_track_sdf_params; a field left at 0 selects its default (run_till_level 0 is the full resolution)."""
+    _fields_ = [("no_hierarchy_levels", C.c_int32), ("run_till_level", C.c_int32), ("max_evaluations", C.c_int32),
+                ("min_valid", C.c_int32), ("residual_gate", C.c_float), ("term_rotation", C.c_float),
+                ("term_translation_voxels", C.c_float), ("pad", C.c_int32)]
+
+    def __init__(self, no_hierarchy_levels=0, run_till_level=0, max_evaluations=0, min_valid=0, residual_gate=0.0,
+                 term_rotation=0.0, term_translation_voxels=0.0):
+        super().__init__(no_hierarchy_levels, run_till_level, max_evaluations, min_valid, residual_gate, term_rotation,
+                         term_translation_voxels, 0)
+
+
+class TrackSdfResult(C.Structure):
+    """dslam_track_sdf_result."""
+    _fields_ = [("evaluations", C.c_int32), ("levels_stepped", C.c_int32), ("stop_reason", C.c_int32),
+                ("candidates", C.c_int32), ("valid_last", C.c_int32), ("cost_first", C.c_float), ("cost_last", C.c_float),
+                ("conditioning", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+assert C.sizeof(TrackSdfParams) == 32 and C.sizeof(TrackSdfResult) == 32  # the header's layouts
+
+
 class RegisterParams(C.Structure):
     """dslam_register_params; a field left at 0 selects its default."""
     _fields_ = [("band", C.c_float), ("residual_gate", C.c_float), ("max_evaluations", C.c_int32),
@@ -614,6 +639,33 @@ class CApi:
         row), 6 gradient, sum of b^2, valid count."""
         out = np.empty(29, dtype=np.float64)
         self._call("debug_icp_sums", self._engine, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
+
+    def track_camera_sdf(self, view, scenes, map_poses, pose_M, intr, params=None):
+        """dslam_track_camera_sdf: the camera of `view` tracked against the signed distance fields of several local maps.
+        `scenes` / `map_poses` as get_image_multi; `pose_M`: the start, world -> camera (4x4, metres).  Returns (the
+        estimate as a 4x4 float32 array -- the start's own bytes if no step was accepted --, TrackSdfResult)."""
+        scenes = list(scenes)
+        T = np.asarray(map_poses, dtype=np.float32)
+        if T.ndim != 3 or T.shape[1:] != (4, 4):
+            raise ValueError("map_poses must be N 4x4 matrices")
+        if len(T) != len(scenes):
+            raise ValueError(f"{len(scenes)} scenes but {len(T)} map poses")
+        n = len(scenes)
+        ptrs = (C.c_void_p * max(n, 1))(*[None if s is None else s.ptr for s in scenes])
+        t_abi = np.ascontiguousarray(np.transpose(T, (0, 2, 1))).reshape(-1) if n else np.zeros(16, np.float32)
+        pose, k = self._mi(pose_M, intr)
+        pose = pose.copy()
+        res = TrackSdfResult()
+        self._call("track_camera_sdf", self._engine, view.ptr, ptrs, _fptr(t_abi), C.c_int(n), _fptr(pose), _fptr(k),
+                   C.byref(params) if params is not None else None, C.byref(res))
+        return pose.reshape(4, 4).T.copy(), res
+
+    def debug_track_sdf_sums(self):
+        """The 33 double sums of the most recent depth-to-SDF tracking evaluation (pivot at the world origin), laid out as
+        debug_register_sums: 21 Hessian, 6 gradient, sum of b^2, valid count, 3 sum of p, candidate count."""
+        out = np.empty(33, dtype=np.float64)
+        self._call("debug_track_sdf_sums", self._engine, out.ctypes.data_as(C.POINTER(C.c_double)))
         return out
 
     def _image_call(self, name, scene, rs, M, intr, image_type, download=True, out=None):

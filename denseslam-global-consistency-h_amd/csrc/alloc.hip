@@ -119,6 +119,7 @@ int launch_view_convert(dslam_engine *, dslam_view *v, const void *rgba_dev, con
   v->raw_src = reinterpret_cast<const short *>(depth_dev);
   v->affine_a = a; v->affine_b = b;
   v->depth_dirty = true;
+  v->updated = true;
   return DSLAM_OK;
 }
 

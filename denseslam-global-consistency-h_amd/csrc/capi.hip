@@ -1304,6 +1304,64 @@ int dslam_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state 
   return launch_track_camera(e, v, r, scene_pose_M, pose_M, intr, params, result);
 }
 
+// ---- depth-to-SDF tracker over all local maps --------------------------------------------------------------------
+static bool finite_and_orthonormal(const float *T) {
+  for (int k = 0; k < 16; k++)
+    if (!std::isfinite(T[k])) return false;
+  for (int a = 0; a < 3; a++)
+    for (int b = 0; b < 3; b++) {
+      double dot = 0.0;
+      for (int k = 0; k < 3; k++) dot += (double)T[a * 4 + k] * (double)T[b * 4 + k];
+      if (!(fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-4)) return false;
+    }
+  return true;
+}
+
+int dslam_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T_map_from_world,
+                           int num_maps, float pose_M[16], const float intr[4], const dslam_track_sdf_params *params,
+                           dslam_track_sdf_result *result) {
+  DSLAM_REQUIRE(e && v && scenes && T_map_from_world && pose_M && intr && result, "null argument");
+  DSLAM_REQUIRE(num_maps >= 1 && num_maps <= DSLAM_MAX_RENDER_MAPS, "num_maps must be 1 .. DSLAM_MAX_RENDER_MAPS");
+  DSLAM_REQUIRE(v->engine == e, "the view belongs to another engine");
+  DSLAM_REQUIRE(v->updated, "the view was never updated");
+  for (int i = 0; i < num_maps; i++) {
+    const dslam_scene *s = scenes[i];
+    DSLAM_REQUIRE(s, "a scene in the list is NULL");
+    DSLAM_REQUIRE(s->engine == e, "a scene in the list belongs to another engine");
+    for (int j = 0; j < i; j++) DSLAM_REQUIRE(scenes[j] != s, "a scene is listed twice");
+    DSLAM_REQUIRE(memcmp(&s->p.voxel_size, &scenes[0]->p.voxel_size, sizeof(float)) == 0 &&
+                      memcmp(&s->p.mu, &scenes[0]->p.mu, sizeof(float)) == 0,
+                  "all maps of a tracking call need the same voxel_size and mu");
+    DSLAM_REQUIRE(finite_and_orthonormal(T_map_from_world + 16 * i), "a map transform is not finite or its rotation block is not orthonormal");
+  }
+  DSLAM_REQUIRE(finite_and_orthonormal(pose_M), "the start pose is not finite or its rotation block is not orthonormal");
+  for (int k = 0; k < 4; k++) DSLAM_REQUIRE(std::isfinite(intr[k]), "the intrinsics are not finite");
+  dslam_track_sdf_params tp = {0, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0};
+  if (params) tp = *params;
+  DSLAM_REQUIRE(tp.no_hierarchy_levels >= 0 && tp.run_till_level >= 0 && tp.max_evaluations >= 0 && tp.min_valid >= 0 &&
+                    tp.residual_gate >= 0.0f && tp.term_rotation >= 0.0f && tp.term_translation_voxels >= 0.0f,
+                "a tracking parameter is negative (or not a number)");
+  if (tp.no_hierarchy_levels == 0) tp.no_hierarchy_levels = 3;
+  if (tp.max_evaluations == 0) tp.max_evaluations = 10;
+  if (tp.min_valid == 0) tp.min_valid = 500;
+  if (tp.residual_gate == 0.0f) tp.residual_gate = 0.75f;
+  if (tp.term_rotation == 0.0f) tp.term_rotation = 1e-5f;
+  if (tp.term_translation_voxels == 0.0f) tp.term_translation_voxels = 1e-3f;
+  DSLAM_REQUIRE(tp.no_hierarchy_levels <= DSLAM_TRACKER_MAX_LEVELS, "no_hierarchy_levels must be 1 .. DSLAM_TRACKER_MAX_LEVELS");
+  DSLAM_REQUIRE((v->w_d >> (tp.no_hierarchy_levels - 1)) > 0 && (v->h_d >> (tp.no_hierarchy_levels - 1)) > 0,
+                "too many hierarchy levels for this image size");
+  DSLAM_REQUIRE(tp.run_till_level < tp.no_hierarchy_levels, "run_till_level is not one of the levels");
+  e->view_reads++;  // (see dslam_engine::last_fence)
+  return launch_track_camera_sdf(e, v, scenes, T_map_from_world, num_maps, pose_M, intr, &tp, result);
+}
+
+int dslam_debug_track_sdf_sums(dslam_engine *e, double out[33]) {
+  DSLAM_REQUIRE(e && out, "null argument");
+  DSLAM_REQUIRE(e->track_sdf_have_sums, "no depth-to-SDF tracking evaluation has run on this engine");
+  memcpy(out, e->track_sdf_last_sums, sizeof e->track_sdf_last_sums);
+  return DSLAM_OK;
+}
+
 // ---- decay / sliding window ----------------------------------------------------------------------------------
 int dslam_decay(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int max_weight, int min_age, int force_all) {
   DSLAM_REQUIRE(e && s, "null argument");

@@ -214,6 +214,12 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   dslam::OverlapScratch overlap;      // dslam_survey_overlaps (overlap.hip)
   std::vector<double> reg_graph_sums; // [pairs][33]: each pair's totals at the most recent joint evaluation it took part
                                       // in (dslam_debug_register_graph_sums; test hook)
+  // dslam_track_camera_sdf (track_sdf.hip): the map descriptors of a call (device) and the per-workgroup partial sums in
+  // mapped page-locked memory, as the registration's
+  DeviceBuffer<void> track_sdf_maps;
+  PinnedBuffer<double> track_sdf_partials;
+  double track_sdf_last_sums[33] = {0};   // the totals of the most recent evaluation (dslam_debug_track_sdf_sums; test hook)
+  bool track_sdf_have_sums = false;
   // dslam_debug_merge_phases (bench hook): wall clock of the last merge's phases, each closed by a wait for the stream --
   // [0] the source's live list, [1] mark kernels, [2] ordered selections (ranks, serve, touched list), [3] block kernel,
   // [4] read-backs
@@ -377,6 +383,7 @@ struct DSLAM_INTERNAL dslam_view : ViewLanding {
   float affine_a = 0.001f, affine_b = 0.0f;
   mutable bool depth_dirty = false;  // float depth not yet derived from raw_src (done by the next consumer)
   double timestamp = 0;
+  bool updated = false;         // an UpdateView has given the view a frame (dslam_track_camera_sdf refuses a view without one)
 };
 
 // a marker in the engine's stream (dslam_fence_*): lets a pipelining caller learn when a frame's results have landed
@@ -503,6 +510,12 @@ int launch_find_visible_and_depths(dslam_engine *e, const dslam_scene *s, dslam_
                                    const float *intr);
 int launch_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state *r, const float *scenePose, float *pose_M,
                         const float *intr, const dslam_tracker_params *tp, dslam_tracker_result *res);
+// the depth pyramid of a view whose float depth is current: level pointers and sizes for `levels` levels (track.hip)
+int build_depth_pyramid(dslam_engine *e, const dslam_view *v, int levels, const float **ldepth, int *lw, int *lh);
+// everything already checked (and params defaulted) by dslam_track_camera_sdf; pose_M: in the start, out the estimate
+int launch_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T_map_from_world,
+                            int num_maps, float *pose_M, const float *intr, const dslam_track_sdf_params *params,
+                            dslam_track_sdf_result *result);
 int launch_render(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float *M, const float *intr,
                   int type, bool reuse_raycast = false, void *image_out_override = nullptr);
 // scenes / T (N x 16, world -> map) already checked by dslam_get_image_multi

@@ -178,26 +178,12 @@ void coerce_pose(float *M) {
 constexpr int kIcpGrid = 240;
 }  // namespace
 
-int launch_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state *r, const float *scenePose, float *pose_M,
-                        const float *intr, const dslam_tracker_params *tp, dslam_tracker_result *res) {
-  const int levels = tp->no_hierarchy_levels;
-  DSLAM_REQUIRE(levels >= 1 && levels <= DSLAM_TRACKER_MAX_LEVELS && tp->no_icp_run_till_level >= 0, "bad tracker parameters");
-  DSLAM_REQUIRE(r->icp_points && r->icp_normals, "no ICP maps: call dslam_create_icp_maps first");
-  DSLAM_REQUIRE(v->w_d == r->w && v->h_d == r->h, "view and render state sizes differ");
-  int rc = ensure_view_depth(e, v);
-  if (rc) return rc;
-  // depth pyramid (levels 1.. live in one buffer of the view) and the partial-sum buffers
+// The depth pyramid of a view whose float depth is current (ensure_view_depth): level 0 is the view's depth image, level
+// k FilterSubsampleWithHoles of level k - 1; levels 1.. live in one buffer of the view.  Shared by the ICP tracker below
+// and the depth-to-SDF tracker (track_sdf.hip).
+int build_depth_pyramid(dslam_engine *e, const dslam_view *v, int levels, const float **ldepth, int *lw, int *lh) {
   if (!v->pyramid) DSLAM_TRY(v->pyramid.alloc((size_t)v->w_d * v->h_d));  // sum of levels 1.. < 1/3
-  if (!e->icp_partials) {
-    // the workgroup partials (240 x 29 doubles) are written straight into mapped pinned host memory: one stream
-    // synchronise per iteration instead of a copy launch plus a synchronise
-    DSLAM_TRY(e->icp_partials.alloc((size_t)kIcpGrid * kIcpSums, hipHostMallocMapped));
-  }
-  const float *ldepth[DSLAM_TRACKER_MAX_LEVELS];
-  int lw[DSLAM_TRACKER_MAX_LEVELS], lh[DSLAM_TRACKER_MAX_LEVELS];
-  float lintr[DSLAM_TRACKER_MAX_LEVELS][4];
   ldepth[0] = v->depth; lw[0] = v->w_d; lh[0] = v->h_d;
-  for (int k = 0; k < 4; k++) lintr[0][k] = intr[k];
   float *next = v->pyramid;
   for (int i = 1; i < levels; i++) {
     lw[i] = lw[i - 1] / 2; lh[i] = lh[i - 1] / 2;
@@ -206,8 +192,31 @@ int launch_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state
                        lw[i - 1], next, lw[i], lh[i]);
     ldepth[i] = next;
     next += (size_t)lw[i] * lh[i];
-    for (int k = 0; k < 4; k++) lintr[i][k] = lintr[i - 1][k] * 0.5f;
   }
+  DSLAM_HIP(hipGetLastError());
+  return DSLAM_OK;
+}
+
+int launch_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state *r, const float *scenePose, float *pose_M,
+                        const float *intr, const dslam_tracker_params *tp, dslam_tracker_result *res) {
+  const int levels = tp->no_hierarchy_levels;
+  DSLAM_REQUIRE(levels >= 1 && levels <= DSLAM_TRACKER_MAX_LEVELS && tp->no_icp_run_till_level >= 0, "bad tracker parameters");
+  DSLAM_REQUIRE(r->icp_points && r->icp_normals, "no ICP maps: call dslam_create_icp_maps first");
+  DSLAM_REQUIRE(v->w_d == r->w && v->h_d == r->h, "view and render state sizes differ");
+  int rc = ensure_view_depth(e, v);
+  if (rc) return rc;
+  if (!e->icp_partials) {
+    // the workgroup partials (240 x 29 doubles) are written straight into mapped pinned host memory: one stream
+    // synchronise per iteration instead of a copy launch plus a synchronise
+    DSLAM_TRY(e->icp_partials.alloc((size_t)kIcpGrid * kIcpSums, hipHostMallocMapped));
+  }
+  const float *ldepth[DSLAM_TRACKER_MAX_LEVELS];
+  int lw[DSLAM_TRACKER_MAX_LEVELS], lh[DSLAM_TRACKER_MAX_LEVELS];
+  float lintr[DSLAM_TRACKER_MAX_LEVELS][4];
+  DSLAM_TRY(build_depth_pyramid(e, v, levels, ldepth, lw, lh));
+  for (int k = 0; k < 4; k++) lintr[0][k] = intr[k];
+  for (int i = 1; i < levels; i++)
+    for (int k = 0; k < 4; k++) lintr[i][k] = lintr[i - 1][k] * 0.5f;
   int iters_per_level[DSLAM_TRACKER_MAX_LEVELS];
   float dist_per_level[DSLAM_TRACKER_MAX_LEVELS];
   iters_per_level[0] = 2;

@@ -581,6 +581,46 @@ class ITMMainEngine {
     if (re) *re = mres;
     return mres.exhausted == 0;
   }
+  /// (extension) Track the camera of the current view against ALL local maps under their estimatedGlobalPoses
+  /// (dslam_track_camera_sdf, law in DESIGN.md section 18) -- where the reference's internal odometry prepares and tracks
+  /// currentLocalMap alone (DenseSlam.cpp:198-206), which holds nothing just after createNewLocalMap.  The start is
+  /// world -> camera = pose_d->GetM() T_current from `current`'s tracking state and estimatedGlobalPose; when a step was
+  /// accepted pose_d is written back in the current map's frame, pose_d = (world -> camera) T_current^-1, and the call
+  /// returns true, otherwise pose_d is left alone.  Both compositions are made in double by RigidProduct / RigidInverse,
+  /// so a caller of the C ABI can reproduce them bit for bit.  No Prepare, no render state: call it in place of
+  /// Prepare + Track, after AlignLocalMaps has made the neighbours' poses good.
+  bool TrackAllLocalMaps(ITMLocalMap *current, dslam_track_sdf_result *out = nullptr) {
+    if (view == nullptr) throw std::runtime_error("TrackAllLocalMaps: no view yet (call UpdateView first)");
+    const int n = mapManager->numLocalMaps();
+    std::vector<const dslam_scene *> scenes(n);
+    std::vector<float> T((size_t)n * 16);
+    for (int i = 0; i < n; i++) {
+      const ITMLocalMap *m = mapManager->getLocalMap(i);
+      scenes[i] = m->scene->handle;
+      memcpy(&T[(size_t)i * 16], m->estimatedGlobalPose.GetM().m, 16 * sizeof(float));
+    }
+    double Md[16], Tc[16], Wd[16], inv[16];
+    for (int i = 0; i < 16; i++) {
+      Md[i] = (double)current->trackingState->pose_d->GetM().m[i];
+      Tc[i] = (double)current->estimatedGlobalPose.GetM().m[i];
+    }
+    RigidProduct(Md, Tc, Wd);
+    float Wf[16];
+    for (int i = 0; i < 16; i++) Wf[i] = (float)Wd[i];
+    const Vector4f k = view->calib->intrinsics_d.projectionParamsSimple.all;
+    dslam_track_sdf_result res;
+    dslam_check(dslam_track_camera_sdf(engine_, view->handle, scenes.data(), T.data(), n, Wf, k.v, nullptr, &res),
+                "dslam_track_camera_sdf");
+    if (out) *out = res;
+    if (res.levels_stepped == 0) return false;
+    for (int i = 0; i < 16; i++) Wd[i] = (double)Wf[i];
+    RigidInverse(Tc, inv);
+    RigidProduct(Wd, inv, Md);
+    Matrix4f M;
+    for (int i = 0; i < 16; i++) M.m[i] = (float)Md[i];
+    current->trackingState->pose_d->SetM(M);
+    return true;
+  }
   /// inverse of a rigid transform (column-major): [R^T | -(R^T t)], each sum evaluated left to right
   static void RigidInverse(const double M[16], double out[16]) {
     for (int r = 0; r < 3; r++) {

@@ -831,6 +831,82 @@ int dslam_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state 
  * step stays below).  Error if no evaluation has run. */
 int dslam_debug_icp_sums(dslam_engine *e, double out[29]);
 
+/* ---- depth-to-SDF tracker over all local maps --------------------------------------------------- */
+/* Tracks the camera of a view directly against the signed distance fields of N posed local maps (no counterpart in the
+ * reference, which tracks by ICP against the raycast of the current local map alone, DenseSlam.cpp:198-206; the law is
+ * this project's own).  It back-projects the depth pixels under the pose estimate, reads the
+ * blended SDF and its gradient where the points land and drives the SDF there to zero: no raycast, no render state, no
+ * visible list, and a local map that is still empty is tracked through its neighbours.
+ * T_i: world -> map i in metres, column-major (estimatedGlobalPose.GetM()), as dslam_get_image_multi and
+ * dslam_register_graph take it; T~_i is T_i with its translation in voxel units.  pose_M: world -> camera, metres,
+ * column-major.  P~ is camera -> world: the rigid inverse of pose_M with its translation in voxel units; the host keeps
+ * it in double for the whole call and rounds its 12 entries to float32 for each evaluation.
+ * One evaluation at level l of the depth pyramid (level 0 is the view's float depth, level k FilterSubsampleWithHoles of
+ * level k - 1, the intrinsics halved per level, as dslam_track_camera).  For every pixel (x, y):
+ *   1. candidate: D = depth_l[x, y] > 1e-8f; candidates are counted in N;
+ *   2. camera point in voxel units: c = (D ((x - cx) / fx), D ((y - cy) / fy), D) in float32, each component then
+ *      multiplied by (float)(1.0 / (double)voxel_size);
+ *   3. world point p = P~ c, rows evaluated as ((a x + b y) + c z) + d in float32;
+ *   4. per map i, in list order: q_i = T~_i p in the same row order (a T_i that is exactly the identity reads at p
+ *      itself); a q_i with a coordinate of magnitude >= 262144 is a miss for that map; cell floor(q_i), fractions
+ *      c = q_i - floor(q_i); items 3 and 4 of dslam_register_maps apply unchanged: all 8 taps resident, each with
+ *      w_depth > 0 and a raw sdf other than +-32767, else a miss for that map; the value d_i and the gradient g_i from
+ *      those taps in the float32 expressions stated there; the weight w_i is the same three lerp stages applied to the
+ *      taps' w_depth as floats (x00 = ux w0 + cx w1, ..., w_i = uz (uy x00 + cy x10) + cz (uy x01 + cy x11)); the gradient
+ *      in the world frame is g_i^w = R_i^T g_i, each component (r0 gx + r1 gy) + r2 gz with (r0, r1, r2) a column of
+ *      R_i (an identity map leaves g_i as it is);
+ *   5. combine, by the law of dslam_get_image_multi: no map passed: the pixel is a miss; one map passed: d and g are its
+ *      values unchanged; several: d = sum w_i d_i / sum w_i and g = sum w_i g_i^w / sum w_i, component by component, in
+ *      float32, in list order (sum w > 0 always: every tap weighs at least 1) -- the camera is tracked against the
+ *      field the composite raycast draws;
+ *   6. gate: |d| > residual_gate is a miss;
+ *   7. a valid pixel has b = -d and the row A = [p x g, g] (rotation about the world origin, then translation);
+ *   8. the 33 sums of dslam_register_maps' item 6 with p in place of q: [29..31] sum p over the valid pixels, [32] N;
+ *   9. cost = (sum b^2 + (N - valid) residual_gate^2) / N (residual_gate^2 for N = 0).
+ * Iteration: the levels run from no_hierarchy_levels - 1 down to run_till_level.  Each level runs dslam_register_maps'
+ * iteration word for word on P~: pivot at the centroid c = sum p / valid, (H_c + lambda diag H_c) y = g_c, the step
+ * applied on the left of P~ as p' = c + R(y0..2)(p - c) + y3..5, accepted on valid >= min_valid and a lower cost, the
+ * lambda rules and stop reasons 0 - 3 unchanged.  Each level starts at lambda = 1 from the pose the level above returned;
+ * max_evaluations is per level; a level that stops with reason 3 changes nothing and the next level starts from the same
+ * pose.  pose_M returns the rigid inverse of the last accepted P~ (rotation rounded to float32, translation multiplied
+ * by voxel_size, then rounded); if no step was accepted on any level it is untouched, byte for byte.
+ * Every map is only read (blocks that are swapped out are simply not resident); no render state is involved; no map's
+ * version, GetImage memo or front-end record changes.  Waits for the stream on synchronous and asynchronous engines.
+ * DSLAM_ERR_INVALID with pose_M untouched: a NULL argument other than params, num_maps outside
+ * 1 .. DSLAM_MAX_RENDER_MAPS, a scene listed twice, a scene (or the view) of another engine, voxel_size or mu that differ
+ * bitwise between maps, a non-finite T_i or pose_M or one whose rotation block is not orthonormal to 1e-4, levels outside
+ * 1 .. DSLAM_TRACKER_MAX_LEVELS or too many for the image, run_till_level outside the levels, a negative parameter, a
+ * view that was never updated.
+ * Not promised: convergence from farther away than the truncation band -- a tap at +-32767 is a miss, so a pixel whose
+ * point lies more than mu from every surface contributes nothing and the start pose has to come from the previous frame
+ * or a motion model; anything about dslam_track_camera, which is not touched. */
+typedef struct {
+  int32_t no_hierarchy_levels;     /* 0 -> 3 */
+  int32_t run_till_level;          /* finest level run (0: full resolution) */
+  int32_t max_evaluations;         /* per level; 0 -> 10 */
+  int32_t min_valid;               /* 0 -> 500 */
+  float residual_gate;             /* 0 -> 0.75 */
+  float term_rotation;             /* radians; 0 -> 1e-5 */
+  float term_translation_voxels;   /* 0 -> 1e-3 */
+  int32_t pad;
+} dslam_track_sdf_params;
+typedef struct {
+  int32_t evaluations;             /* of all levels together */
+  int32_t levels_stepped;          /* bit l: level l accepted a step */
+  int32_t stop_reason;             /* this and the fields below: of the finest level run */
+  int32_t candidates;              /* N */
+  int32_t valid_last;              /* valid pixels at the returned pose */
+  float cost_first;                /* cost at the level's start pose */
+  float cost_last;                 /* cost at the returned pose */
+  float conditioning;
+} dslam_track_sdf_result;
+int dslam_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes,
+                           const float *T_map_from_world /* [num_maps][16] */, int num_maps,
+                           float pose_M[16] /* world -> camera; in: start, out: estimate */, const float intrinsics_d[4],
+                           const dslam_track_sdf_params *params /* NULL: defaults */, dslam_track_sdf_result *result);
+/* Test hook: the 33 raw sums (pivot at the world origin) of the engine's most recent evaluation.  Error if none has run. */
+int dslam_debug_track_sdf_sums(dslam_engine *e, double out[33]);
+
 /* ---- state read-back (stats for the driver; bulk downloads for parity tests and checkpoints) ------ */
 int dslam_get_stats(dslam_engine *e, const dslam_scene *s, const dslam_render_state *r, dslam_stats *out);
 int dslam_download_hash_table(dslam_engine *e, const dslam_scene *s, dslam_hash_entry *out_host);
