@@ -641,10 +641,10 @@ class CApi:
         self._call("debug_icp_sums", self._engine, out.ctypes.data_as(C.POINTER(C.c_double)))
         return out
 
-    def track_camera_sdf(self, view, scenes, map_poses, pose_M, intr, params=None):
-        """dslam_track_camera_sdf: the camera of `view` tracked against the signed distance fields of several local maps.
-        `scenes` / `map_poses` as get_image_multi; `pose_M`: the start, world -> camera (4x4, metres).  Returns (the
-        estimate as a 4x4 float32 array -- the start's own bytes if no step was accepted --, TrackSdfResult)."""
+    @staticmethod
+    def _map_list(scenes, map_poses, writable=False):
+        """(scenes, map_poses) of a multi-map call as the ABI wants them: (N, the scene pointers, the N transforms as one
+        column-major float32 array).  writable: an array of its own, for a call that writes its estimates into it."""
         scenes = list(scenes)
         T = np.asarray(map_poses, dtype=np.float32)
         if T.ndim != 3 or T.shape[1:] != (4, 4):
@@ -654,6 +654,13 @@ class CApi:
         n = len(scenes)
         ptrs = (C.c_void_p * max(n, 1))(*[None if s is None else s.ptr for s in scenes])
         t_abi = np.ascontiguousarray(np.transpose(T, (0, 2, 1))).reshape(-1) if n else np.zeros(16, np.float32)
+        return n, ptrs, (t_abi.copy() if writable else t_abi)
+
+    def track_camera_sdf(self, view, scenes, map_poses, pose_M, intr, params=None):
+        """dslam_track_camera_sdf: the camera of `view` tracked against the signed distance fields of several local maps.
+        `scenes` / `map_poses` as get_image_multi; `pose_M`: the start, world -> camera (4x4, metres).  Returns (the
+        estimate as a 4x4 float32 array -- the start's own bytes if no step was accepted --, TrackSdfResult)."""
+        n, ptrs, t_abi = self._map_list(scenes, map_poses)
         pose, k = self._mi(pose_M, intr)
         pose = pose.copy()
         res = TrackSdfResult()
@@ -694,15 +701,7 @@ class CApi:
         """dslam_get_image_multi: one raycast over several local maps.  `scenes`: 1 .. MAX_RENDER_MAPS scenes; `map_poses`:
         one 4x4 world -> map transform per scene (metres, estimatedGlobalPose.GetM()), as a list or an [N, 4, 4] array.
         Otherwise as get_image."""
-        scenes = list(scenes)
-        T = np.asarray(map_poses, dtype=np.float32)
-        if T.ndim != 3 or T.shape[1:] != (4, 4):
-            raise ValueError("map_poses must be N 4x4 matrices")
-        if len(T) != len(scenes):
-            raise ValueError(f"{len(scenes)} scenes but {len(T)} map poses")
-        n = len(scenes)
-        ptrs = (C.c_void_p * max(n, 1))(*[None if s is None else s.ptr for s in scenes])
-        t_abi = np.ascontiguousarray(np.transpose(T, (0, 2, 1))).reshape(-1) if n else np.zeros(16, np.float32)
+        n, ptrs, t_abi = self._map_list(scenes, map_poses)
         m, k = self._mi(M, intr)
         out_rgba = out_f = None
         if download or out is not None:
@@ -756,15 +755,7 @@ class CApi:
         """dslam_mesh_scene_multi: one mesh of several local maps in the world frame.  `scenes` / `map_poses` as
         get_image_multi.  Returns (positions [n, 3, 3] float32 in metres, colours [n, 3, 3] float32 in [0, 1] or None,
         per_map_counts [len(scenes)] int32): the triangles of map 0, then map 1, ..."""
-        scenes = list(scenes)
-        T = np.asarray(map_poses, dtype=np.float32)
-        if T.ndim != 3 or T.shape[1:] != (4, 4):
-            raise ValueError("map_poses must be N 4x4 matrices")
-        if len(T) != len(scenes):
-            raise ValueError(f"{len(scenes)} scenes but {len(T)} map poses")
-        k = len(scenes)
-        ptrs = (C.c_void_p * max(k, 1))(*[None if s is None else s.ptr for s in scenes])
-        t_abi = np.ascontiguousarray(np.transpose(T, (0, 2, 1))).reshape(-1) if k else np.zeros(16, np.float32)
+        k, ptrs, t_abi = self._map_list(scenes, map_poses)
         n = C.c_int(0)
         counts = np.zeros(max(k, 1), dtype=np.int32)
         self._call("mesh_scene_multi", self._engine, ptrs, _fptr(t_abi), C.c_int(k), C.c_int(int(max_triangles)),
@@ -795,15 +786,7 @@ class CApi:
         """dslam_register_graph: the poses of N local maps estimated jointly from the voxels of the listed overlapping pairs.
         `scenes` / `map_poses` as get_image_multi (the starts); `pairs`: (src, dst) indices into `scenes`; `anchor`: the map
         held fixed.  Returns (the estimates [N, 4, 4] float32, RegisterGraphResult, a list of RegisterPairResult)."""
-        scenes = list(scenes)
-        T = np.asarray(map_poses, dtype=np.float32)
-        if T.ndim != 3 or T.shape[1:] != (4, 4):
-            raise ValueError("map_poses must be N 4x4 matrices")
-        if len(T) != len(scenes):
-            raise ValueError(f"{len(scenes)} scenes but {len(T)} map poses")
-        n = len(scenes)
-        ptrs = (C.c_void_p * max(n, 1))(*[None if s is None else s.ptr for s in scenes])
-        t_abi = np.ascontiguousarray(np.transpose(T, (0, 2, 1))).reshape(-1).copy() if n else np.zeros(16, np.float32)
+        n, ptrs, t_abi = self._map_list(scenes, map_poses, writable=True)
         pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
         res = RegisterGraphResult()
         pres = (RegisterPairResult * max(len(pr), 1))()
@@ -821,15 +804,7 @@ class CApi:
     def survey_overlaps(self, scenes, map_poses):
         """dslam_survey_overlaps: which of N local maps overlap, at block granularity.  `scenes` / `map_poses` as
         register_graph.  Returns (live [N], shared_blocks [N, N], shared_octants [N, N]), int32, row = source map."""
-        scenes = list(scenes)
-        T = np.asarray(map_poses, dtype=np.float32)
-        if T.ndim != 3 or T.shape[1:] != (4, 4):
-            raise ValueError("map_poses must be N 4x4 matrices")
-        if len(T) != len(scenes):
-            raise ValueError(f"{len(scenes)} scenes but {len(T)} map poses")
-        n = len(scenes)
-        ptrs = (C.c_void_p * max(n, 1))(*[None if s is None else s.ptr for s in scenes])
-        t_abi = np.ascontiguousarray(np.transpose(T, (0, 2, 1))).reshape(-1) if n else np.zeros(16, np.float32)
+        n, ptrs, t_abi = self._map_list(scenes, map_poses)
         live = np.zeros(max(n, 1), dtype=np.int32)
         blocks = np.zeros((max(n, 1), max(n, 1)), dtype=np.int32)
         octants = np.zeros((max(n, 1), max(n, 1)), dtype=np.int32)

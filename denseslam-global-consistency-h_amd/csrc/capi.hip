@@ -183,6 +183,7 @@ static int engine_allocate(dslam_engine *e) {
   DSLAM_TRY(e->pinned.alloc(e->pinned_bytes));
   memset(e->pinned, 0, e->pinned_bytes);
   DSLAM_TRY(e->misc_counter.alloc(16));
+  DSLAM_TRY(e->map_table.alloc(DSLAM_MAX_RENDER_MAPS * kMapDescriptorBytes));
   DSLAM_TRY(e->ticket.alloc(16));
   DSLAM_HIP(hipMemset(e->ticket, 0, 16 * sizeof(unsigned)));
   e->ticket_base = 0;
@@ -1304,37 +1305,82 @@ int dslam_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state 
   return launch_track_camera(e, v, r, scene_pose_M, pose_M, intr, params, result);
 }
 
-// ---- depth-to-SDF tracker over all local maps --------------------------------------------------------------------
-static bool finite_and_orthonormal(const float *T) {
-  for (int k = 0; k < 16; k++)
-    if (!std::isfinite(T[k])) return false;
+// ---- what the calls that take maps and transforms check alike ----------------------------------------------------------
+namespace {
+
+// a rigid transform (column-major 4 x 4): every entry finite, the rotation block orthonormal to 1e-4
+int check_rigid_transform(const float *T, const char *what) {
+  for (int k = 0; k < 16; k++) DSLAM_REQUIRE(std::isfinite(T[k]), std::string(what) + " is not finite");
   for (int a = 0; a < 3; a++)
     for (int b = 0; b < 3; b++) {
       double dot = 0.0;
       for (int k = 0; k < 3; k++) dot += (double)T[a * 4 + k] * (double)T[b * 4 + k];
-      if (!(fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-4)) return false;
+      DSLAM_REQUIRE(fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-4, std::string(what) + ": the rotation block is not orthonormal");
     }
-  return true;
+  return DSLAM_OK;
 }
+
+// The map list (scenes[], T_map_from_world[], num_maps) of the call `call`; the caller has checked the pointers.  Where the
+// calls differ: min_maps; rigid -- no scene twice and every transform rigid (check_rigid_transform),
+// otherwise a scene may repeat and any transform invert_matrix inverts passes; max_local_blocks -- the most
+// num_local_blocks a scene may have (the composite render's visible-list capacity), 0: any.
+int check_map_list(dslam_engine *e, const char *call, const dslam_scene *const *scenes, const float *T, int num_maps, int min_maps,
+                   bool rigid, int max_local_blocks = 0) {
+  auto msg = [call](const std::string &what) { return std::string(call) + ": " + what; };
+  DSLAM_REQUIRE(num_maps >= min_maps && num_maps <= DSLAM_MAX_RENDER_MAPS,
+                msg("num_maps must be " + std::to_string(min_maps) + " .. DSLAM_MAX_RENDER_MAPS"));
+  for (int i = 0; i < num_maps; i++) {
+    const dslam_scene *s = scenes[i];
+    DSLAM_REQUIRE(s, msg("a scene in the list is NULL"));
+    DSLAM_REQUIRE(s->engine == e, msg("a scene in the list belongs to another engine"));
+    if (rigid)
+      for (int j = 0; j < i; j++) DSLAM_REQUIRE(scenes[j] != s, msg("a scene is listed twice"));
+    // (dslam_scene_create admits only voxel_size > 0 and mu > 0, so equal values are equal bytes)
+    DSLAM_REQUIRE(s->p.voxel_size == scenes[0]->p.voxel_size && s->p.mu == scenes[0]->p.mu,
+                  msg("all maps of the list need the same voxel_size and mu"));
+    DSLAM_REQUIRE(max_local_blocks == 0 || s->p.num_local_blocks <= max_local_blocks,
+                  msg("the render state's visible-list capacity is below a scene's num_local_blocks"));
+    float inv[16];
+    if (rigid) DSLAM_TRY(check_rigid_transform(T + 16 * i, "a map transform"));
+    else DSLAM_REQUIRE(invert_matrix(T + 16 * i, inv), msg("a map transform is singular"));
+  }
+  return DSLAM_OK;
+}
+
+// dslam_register_params with the zeros replaced by the defaults (params NULL: all defaults)
+int default_register_params(const dslam_register_params *params, dslam_register_params *rp) {
+  *rp = {0.0f, 0.0f, 0, 0, 0.0f, 0.0f};
+  if (params) *rp = *params;
+  DSLAM_REQUIRE(rp->band >= 0.0f && rp->residual_gate >= 0.0f && rp->max_evaluations >= 0 && rp->min_valid >= 0 &&
+                    rp->term_rotation >= 0.0f && rp->term_translation_voxels >= 0.0f,
+                "a registration parameter is negative (or not a number)");
+  if (rp->band == 0.0f) rp->band = 0.5f;
+  if (rp->residual_gate == 0.0f) rp->residual_gate = 0.75f;
+  if (rp->max_evaluations == 0) rp->max_evaluations = 30;
+  if (rp->min_valid == 0) rp->min_valid = 500;
+  if (rp->term_rotation == 0.0f) rp->term_rotation = 1e-5f;
+  if (rp->term_translation_voxels == 0.0f) rp->term_translation_voxels = 1e-3f;
+  return DSLAM_OK;
+}
+
+int copy_sums(const SumChannel &ch, const char *none, double out[33]) {
+  DSLAM_REQUIRE(ch.have_sums, none);
+  memcpy(out, ch.last_sums, sizeof ch.last_sums);
+  return DSLAM_OK;
+}
+
+}  // namespace
+
+// ---- depth-to-SDF tracker over all local maps --------------------------------------------------------------------
 
 int dslam_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T_map_from_world,
                            int num_maps, float pose_M[16], const float intr[4], const dslam_track_sdf_params *params,
                            dslam_track_sdf_result *result) {
   DSLAM_REQUIRE(e && v && scenes && T_map_from_world && pose_M && intr && result, "null argument");
-  DSLAM_REQUIRE(num_maps >= 1 && num_maps <= DSLAM_MAX_RENDER_MAPS, "num_maps must be 1 .. DSLAM_MAX_RENDER_MAPS");
+  DSLAM_TRY(check_map_list(e, "dslam_track_camera_sdf", scenes, T_map_from_world, num_maps, 1, true));
   DSLAM_REQUIRE(v->engine == e, "the view belongs to another engine");
   DSLAM_REQUIRE(v->updated, "the view was never updated");
-  for (int i = 0; i < num_maps; i++) {
-    const dslam_scene *s = scenes[i];
-    DSLAM_REQUIRE(s, "a scene in the list is NULL");
-    DSLAM_REQUIRE(s->engine == e, "a scene in the list belongs to another engine");
-    for (int j = 0; j < i; j++) DSLAM_REQUIRE(scenes[j] != s, "a scene is listed twice");
-    DSLAM_REQUIRE(memcmp(&s->p.voxel_size, &scenes[0]->p.voxel_size, sizeof(float)) == 0 &&
-                      memcmp(&s->p.mu, &scenes[0]->p.mu, sizeof(float)) == 0,
-                  "all maps of a tracking call need the same voxel_size and mu");
-    DSLAM_REQUIRE(finite_and_orthonormal(T_map_from_world + 16 * i), "a map transform is not finite or its rotation block is not orthonormal");
-  }
-  DSLAM_REQUIRE(finite_and_orthonormal(pose_M), "the start pose is not finite or its rotation block is not orthonormal");
+  DSLAM_TRY(check_rigid_transform(pose_M, "the start pose"));
   for (int k = 0; k < 4; k++) DSLAM_REQUIRE(std::isfinite(intr[k]), "the intrinsics are not finite");
   dslam_track_sdf_params tp = {0, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0};
   if (params) tp = *params;
@@ -1357,9 +1403,7 @@ int dslam_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_sce
 
 int dslam_debug_track_sdf_sums(dslam_engine *e, double out[33]) {
   DSLAM_REQUIRE(e && out, "null argument");
-  DSLAM_REQUIRE(e->track_sdf_have_sums, "no depth-to-SDF tracking evaluation has run on this engine");
-  memcpy(out, e->track_sdf_last_sums, sizeof e->track_sdf_last_sums);
-  return DSLAM_OK;
+  return copy_sums(e->track_sdf_sums, "no depth-to-SDF tracking evaluation has run on this engine", out);
 }
 
 // ---- decay / sliding window ----------------------------------------------------------------------------------
@@ -1531,20 +1575,11 @@ int dslam_get_image_multi(dslam_engine *e, const dslam_scene *const *scenes, con
                           dslam_render_state *r, const float M[16], const float intr[4], int type, uint8_t *out_rgba,
                           float *out_float) {
   DSLAM_REQUIRE(e && scenes && T_map_from_world && r && M && intr, "null argument");
-  DSLAM_REQUIRE(num_maps >= 1 && num_maps <= DSLAM_MAX_RENDER_MAPS, "num_maps must be 1 .. DSLAM_MAX_RENDER_MAPS");
   DSLAM_REQUIRE(type >= 0 && type <= DSLAM_IMAGE_DEPTH, "unknown image type");
   DSLAM_REQUIRE(r->engine == e, "the render state belongs to another engine");
   float inv[16];
   DSLAM_REQUIRE(invert_matrix(M, inv), "pose matrix is singular");
-  for (int i = 0; i < num_maps; i++) {
-    const dslam_scene *s = scenes[i];
-    DSLAM_REQUIRE(s, "a scene in the list is NULL");
-    DSLAM_REQUIRE(s->engine == e, "a scene in the list belongs to another engine");
-    DSLAM_REQUIRE(s->p.voxel_size == scenes[0]->p.voxel_size && s->p.mu == scenes[0]->p.mu,
-                  "all scenes of a composite render need the same voxel_size and mu");
-    DSLAM_REQUIRE(s->p.num_local_blocks <= r->n_local, "the render state's visible-list capacity is below a scene's num_local_blocks");
-    DSLAM_REQUIRE(invert_matrix(T_map_from_world + 16 * i, inv), "a map transform is singular");
-  }
+  DSLAM_TRY(check_map_list(e, "dslam_get_image_multi", scenes, T_map_from_world, num_maps, 1, false, r->n_local));
   drop_memo(r);   // (and nothing is memoised for several maps)
   void *direct = direct_image(r, type, out_rgba, out_float);
   DSLAM_TRY(launch_render_multi(e, scenes, T_map_from_world, num_maps, r, M, intr, type, direct));
@@ -1606,18 +1641,9 @@ int dslam_mesh_scene(dslam_engine *e, const dslam_scene *s, int max_triangles, i
 int dslam_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
                            int max_triangles, int with_colour, int *out_num_triangles, int32_t *out_map_triangles) {
   DSLAM_REQUIRE(e && scenes && T_map_from_world && out_num_triangles, "null argument");
-  DSLAM_REQUIRE(num_maps >= 1 && num_maps <= DSLAM_MAX_RENDER_MAPS, "num_maps must be 1 .. DSLAM_MAX_RENDER_MAPS");
+  DSLAM_TRY(check_map_list(e, "dslam_mesh_scene_multi", scenes, T_map_from_world, num_maps, 1, false));
   long long blocks = 0;
-  for (int i = 0; i < num_maps; i++) {
-    const dslam_scene *s = scenes[i];
-    float inv[16];
-    DSLAM_REQUIRE(s, "a scene in the list is NULL");
-    DSLAM_REQUIRE(s->engine == e, "a scene in the list belongs to another engine");
-    DSLAM_REQUIRE(s->p.voxel_size == scenes[0]->p.voxel_size && s->p.mu == scenes[0]->p.mu,
-                  "all scenes of a composite mesh need the same voxel_size and mu");
-    DSLAM_REQUIRE(invert_matrix(T_map_from_world + 16 * i, inv), "a map transform is singular");
-    blocks += s->p.num_local_blocks;
-  }
+  for (int i = 0; i < num_maps; i++) blocks += scenes[i]->p.num_local_blocks;
   if (max_triangles <= 0) max_triangles = (int)std::min<long long>(blocks * 32, INT_MAX);  // the maps' noMaxTriangles together
   DSLAM_TRY(launch_mesh_scene_multi(e, scenes, T_map_from_world, num_maps, max_triangles, with_colour, out_num_triangles,
                                     out_map_triangles));
@@ -1634,68 +1660,31 @@ int dslam_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_sce
   for (int i = 0; i < 16; i++) DSLAM_REQUIRE(std::isfinite(X_dst_from_src[i]), "the start transform is not finite");
   float inv[16];
   DSLAM_REQUIRE(invert_matrix(X_dst_from_src, inv), "the start transform is singular");
-  dslam_register_params rp = {0.0f, 0.0f, 0, 0, 0.0f, 0.0f};
-  if (params) rp = *params;
-  DSLAM_REQUIRE(rp.band >= 0.0f && rp.residual_gate >= 0.0f && rp.max_evaluations >= 0 && rp.min_valid >= 0 &&
-                    rp.term_rotation >= 0.0f && rp.term_translation_voxels >= 0.0f,
-                "a registration parameter is negative (or not a number)");
-  if (rp.band == 0.0f) rp.band = 0.5f;
-  if (rp.residual_gate == 0.0f) rp.residual_gate = 0.75f;
-  if (rp.max_evaluations == 0) rp.max_evaluations = 30;
-  if (rp.min_valid == 0) rp.min_valid = 500;
-  if (rp.term_rotation == 0.0f) rp.term_rotation = 1e-5f;
-  if (rp.term_translation_voxels == 0.0f) rp.term_translation_voxels = 1e-3f;
+  dslam_register_params rp;
+  DSLAM_TRY(default_register_params(params, &rp));
   return launch_register_maps(e, src, dst, X_dst_from_src, &rp, result);
 }
 
 int dslam_debug_register_sums(dslam_engine *e, double out[33]) {
   DSLAM_REQUIRE(e && out, "null argument");
-  DSLAM_REQUIRE(e->reg_have_sums, "no registration evaluation has run on this engine");
-  memcpy(out, e->reg_last_sums, sizeof e->reg_last_sums);
-  return DSLAM_OK;
+  return copy_sums(e->reg_sums, "no registration evaluation has run on this engine", out);
 }
 
 int dslam_register_graph(dslam_engine *e, const dslam_scene *const *scenes, float *T_map_from_world, int num_maps,
                          const int32_t *pairs, int num_pairs, int anchor, const dslam_register_params *params,
                          dslam_register_graph_result *result, dslam_register_pair_result *pair_results) {
   DSLAM_REQUIRE(e && scenes && T_map_from_world && pairs && result, "null argument");
-  DSLAM_REQUIRE(num_maps >= 2 && num_maps <= DSLAM_MAX_RENDER_MAPS, "num_maps must be 2 .. DSLAM_MAX_RENDER_MAPS");
+  DSLAM_TRY(check_map_list(e, "dslam_register_graph", scenes, T_map_from_world, num_maps, 2, true));
   DSLAM_REQUIRE(num_pairs >= 1 && num_pairs <= DSLAM_MAX_REGISTER_PAIRS, "num_pairs must be 1 .. DSLAM_MAX_REGISTER_PAIRS");
   DSLAM_REQUIRE(anchor >= 0 && anchor < num_maps, "the anchor is not a map of the list");
-  for (int i = 0; i < num_maps; i++) {
-    const dslam_scene *s = scenes[i];
-    DSLAM_REQUIRE(s, "a scene in the list is NULL");
-    DSLAM_REQUIRE(s->engine == e, "a scene in the list belongs to another engine");
-    for (int j = 0; j < i; j++) DSLAM_REQUIRE(scenes[j] != s, "a scene is listed twice");
-    DSLAM_REQUIRE(memcmp(&s->p.voxel_size, &scenes[0]->p.voxel_size, sizeof(float)) == 0 &&
-                      memcmp(&s->p.mu, &scenes[0]->p.mu, sizeof(float)) == 0,
-                  "all maps of a joint registration need the same voxel_size and mu");
-    const float *T = T_map_from_world + 16 * i;
-    for (int k = 0; k < 16; k++) DSLAM_REQUIRE(std::isfinite(T[k]), "a map transform is not finite");
-    for (int a = 0; a < 3; a++)
-      for (int b = 0; b < 3; b++) {
-        double dot = 0.0;
-        for (int k = 0; k < 3; k++) dot += (double)T[a * 4 + k] * (double)T[b * 4 + k];
-        DSLAM_REQUIRE(fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-4, "a map transform's rotation block is not orthonormal");
-      }
-  }
   for (int p = 0; p < num_pairs; p++) {
     const int s = pairs[2 * p], d = pairs[2 * p + 1];
     DSLAM_REQUIRE(s >= 0 && s < num_maps && d >= 0 && d < num_maps, "a pair names a map that is not in the list");
     DSLAM_REQUIRE(s != d, "a pair names one map twice");
     for (int q = 0; q < p; q++) DSLAM_REQUIRE(pairs[2 * q] != s || pairs[2 * q + 1] != d, "an ordered pair is given twice");
   }
-  dslam_register_params rp = {0.0f, 0.0f, 0, 0, 0.0f, 0.0f};
-  if (params) rp = *params;
-  DSLAM_REQUIRE(rp.band >= 0.0f && rp.residual_gate >= 0.0f && rp.max_evaluations >= 0 && rp.min_valid >= 0 &&
-                    rp.term_rotation >= 0.0f && rp.term_translation_voxels >= 0.0f,
-                "a registration parameter is negative (or not a number)");
-  if (rp.band == 0.0f) rp.band = 0.5f;
-  if (rp.residual_gate == 0.0f) rp.residual_gate = 0.75f;
-  if (rp.max_evaluations == 0) rp.max_evaluations = 30;
-  if (rp.min_valid == 0) rp.min_valid = 500;
-  if (rp.term_rotation == 0.0f) rp.term_rotation = 1e-5f;
-  if (rp.term_translation_voxels == 0.0f) rp.term_translation_voxels = 1e-3f;
+  dslam_register_params rp;
+  DSLAM_TRY(default_register_params(params, &rp));
   return launch_register_graph(e, scenes, T_map_from_world, num_maps, pairs, num_pairs, anchor, &rp, result, pair_results);
 }
 
@@ -1711,24 +1700,7 @@ int dslam_debug_register_graph_sums(dslam_engine *e, int pair, double out[33]) {
 int dslam_survey_overlaps(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
                           int32_t *live_blocks_out, int32_t *shared_blocks_out, int32_t *shared_octants_out) {
   DSLAM_REQUIRE(e && scenes && T_map_from_world && live_blocks_out && shared_octants_out, "null argument");
-  DSLAM_REQUIRE(num_maps >= 2 && num_maps <= DSLAM_MAX_RENDER_MAPS, "num_maps must be 2 .. DSLAM_MAX_RENDER_MAPS");
-  for (int i = 0; i < num_maps; i++) {
-    const dslam_scene *s = scenes[i];
-    DSLAM_REQUIRE(s, "a scene in the list is NULL");
-    DSLAM_REQUIRE(s->engine == e, "a scene in the list belongs to another engine");
-    for (int j = 0; j < i; j++) DSLAM_REQUIRE(scenes[j] != s, "a scene is listed twice");
-    DSLAM_REQUIRE(memcmp(&s->p.voxel_size, &scenes[0]->p.voxel_size, sizeof(float)) == 0 &&
-                      memcmp(&s->p.mu, &scenes[0]->p.mu, sizeof(float)) == 0,
-                  "all maps of an overlap survey need the same voxel_size and mu");
-    const float *T = T_map_from_world + 16 * i;
-    for (int k = 0; k < 16; k++) DSLAM_REQUIRE(std::isfinite(T[k]), "a map transform is not finite");
-    for (int a = 0; a < 3; a++)
-      for (int b = 0; b < 3; b++) {
-        double dot = 0.0;
-        for (int k = 0; k < 3; k++) dot += (double)T[a * 4 + k] * (double)T[b * 4 + k];
-        DSLAM_REQUIRE(fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-4, "a map transform's rotation block is not orthonormal");
-      }
-  }
+  DSLAM_TRY(check_map_list(e, "dslam_survey_overlaps", scenes, T_map_from_world, num_maps, 2, true));
   return launch_survey_overlaps(e, scenes, T_map_from_world, num_maps, live_blocks_out, shared_blocks_out, shared_octants_out);
 }
 
@@ -1763,17 +1735,6 @@ int check_merge_scenes(dslam_engine *e, const dslam_scene *src, const dslam_scen
   return DSLAM_OK;
 }
 
-int check_merge_transform(const float X[16]) {
-  for (int i = 0; i < 16; i++) DSLAM_REQUIRE(std::isfinite(X[i]), "the transform is not finite");
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      double dot = 0.0;
-      for (int k = 0; k < 3; k++) dot += (double)X[i * 4 + k] * (double)X[j * 4 + k];
-      DSLAM_REQUIRE(fabs(dot - (i == j ? 1.0 : 0.0)) <= 1e-4, "the transform's rotation block is not orthonormal");
-    }
-  return DSLAM_OK;
-}
-
 int check_merge_params(const dslam_scene *src, const dslam_merge_params *params, dslam_merge_params *mp) {
   DSLAM_REQUIRE((double)src->p.num_local_blocks * 512.0 < 4294967295.0, "the source has more blocks than the 32-bit order key can name");
   *mp = {0, 1};
@@ -1795,7 +1756,7 @@ int dslam_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, 
                      const dslam_merge_params *params, dslam_merge_result *result) {
   DSLAM_REQUIRE(e && src && dst && X_dst_from_src && result, "null argument");
   DSLAM_TRY(check_merge_scenes(e, src, dst));
-  DSLAM_TRY(check_merge_transform(X_dst_from_src));
+  DSLAM_TRY(check_rigid_transform(X_dst_from_src, "the transform"));
   dslam_merge_params mp;
   DSLAM_TRY(check_merge_params(src, params, &mp));
   map_changed(dst);
@@ -1806,7 +1767,7 @@ int dslam_unmerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst
                        const dslam_unmerge_params *params, dslam_unmerge_result *result) {
   DSLAM_REQUIRE(e && src && dst && X_dst_from_src && result, "null argument");
   DSLAM_TRY(check_merge_scenes(e, src, dst));
-  DSLAM_TRY(check_merge_transform(X_dst_from_src));
+  DSLAM_TRY(check_rigid_transform(X_dst_from_src, "the transform"));
   map_changed(dst);
   return launch_unmerge_maps(e, src, dst, X_dst_from_src, params ? params->with_colour : 1, result, false);
 }
@@ -1816,8 +1777,8 @@ int dslam_remerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst
                        dslam_merge_result *merged) {
   DSLAM_REQUIRE(e && src && dst && X_old && X_new && unmerged && merged, "null argument");
   DSLAM_TRY(check_merge_scenes(e, src, dst));
-  DSLAM_TRY(check_merge_transform(X_old));
-  DSLAM_TRY(check_merge_transform(X_new));
+  DSLAM_TRY(check_rigid_transform(X_old, "the old transform"));
+  DSLAM_TRY(check_rigid_transform(X_new, "the new transform"));
   dslam_merge_params mp;
   DSLAM_TRY(check_merge_params(src, params, &mp));
   memset(unmerged, 0, sizeof *unmerged);

@@ -13,6 +13,7 @@
 #include "../../include/dslam_fusion.h"
 #include "dslam_device.h"
 #include "dslam_memory.h"
+#include "register_host.h"
 
 namespace dslam {
 
@@ -113,27 +114,42 @@ struct MergeScratch {
   PinnedBuffer<unsigned long long> changed;   // mapped: [workgroups] voxels changed, one count per workgroup of the merge's
                                               // block kernel; then [workgroups][3], one row per workgroup of the unmerge's
 };
-// dslam_register_graph (register_graph.hip): its own scratch -- allocated by the first call, grown as a whole (built aside,
-// move-assigned); the list and counter slots other calls use are left alone
-struct RegisterGraphScratch {
+// The resident entries of several maps of one call (fill_live_lists, dslam_bits.h: dslam_register_graph's distinct sources,
+// dslam_survey_overlaps' maps), one range of live_list per map -- allocated by the first call, grown as a whole (built
+// aside, move-assigned); the list and counter slots other calls use are left alone.  One set per engine: both calls
+// enqueue on the engine's one stream and wait for it before they return, so neither sees the other's lists in flight.
+struct LiveLists {
   int entries = 0;                       // capacity of live_list
-  DeviceBuffer<int> live_list;           // the resident entries of every distinct source of a call, one range per source
+  DeviceBuffer<int> live_list;
   DeviceBuffer<int> live_counts;         // [DSLAM_MAX_RENDER_MAPS] entries in each range
   PinnedBuffer<int> live_counts_host;
+};
+// dslam_register_graph (register_graph.hip): its own scratch, allocated by the first call
+struct RegisterGraphScratch {
   PinnedBuffer<double> partials;         // mapped: [workgroups][33], one row per workgroup of k_register_graph
   PinnedBuffer<void> jobs;               // mapped: the pair table and the workgroup -> pair table the kernel reads
 };
-// dslam_survey_overlaps (overlap.hip): its own scratch -- allocated by the first call, grown as a whole (built aside,
-// move-assigned); the list and counter slots other calls use and the registration scratch are left alone
+// dslam_survey_overlaps (overlap.hip): its own scratch, allocated by the first call
 struct OverlapScratch {
-  int entries = 0;                       // capacity of live_list
-  DeviceBuffer<int> live_list;           // the resident entries of every map of a call, one range per map
-  DeviceBuffer<int> live_counts;         // [DSLAM_MAX_RENDER_MAPS] entries in each range
-  PinnedBuffer<int> live_counts_host;
   PinnedBuffer<int> rows;                // mapped: [workgroups][2 N], one row per workgroup of k_survey_overlaps
   PinnedBuffer<void> tables_host;        // the tables of a call on their way to the device:
   DeviceBuffer<void> tables;             // workgroup -> source map, the map descriptors, the N x N pair transforms
 };
+// The reduction channel of an SDF optimiser (dslam_register_maps, dslam_track_camera_sdf): one row of 33 partial sums per
+// workgroup in mapped page-locked memory (kernels: partials.device()), added by the host in index order
+struct SumChannel {
+  PinnedBuffer<double> partials;         // [rows][33], allocated by the first call
+  double last_sums[kRegSums] = {0};      // the totals of the most recent evaluation (dslam_debug_*_sums; test hook)
+  bool have_sums = false;
+  int ensure(int rows) { return partials ? 0 : partials.alloc((size_t)rows * kRegSums, hipHostMallocMapped); }
+  void collect(int rows, Evaluation33 &ev) {
+    ev.sum_rows(partials, 0, rows);
+    memcpy(last_sums, ev.sums, sizeof last_sums);
+    have_sums = true;
+  }
+};
+// bytes of one map descriptor (MultiMap, multimap_device.h) in dslam_engine::map_table
+constexpr size_t kMapDescriptorBytes = 80;
 }  // namespace dslam
 
 // (the handles' destructors free memory now: they are not part of the library's exported names)
@@ -202,24 +218,20 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   int mesh_triangles = 0;
   bool mesh_has_colour = false;
   bool mesh_table_ready = false;      // the case table sits in this device's constant memory
-  // dslam_mesh_scene_multi (multimesh.hip): its copy of the case table, and the per-map descriptor table of one map pass
-  bool multimesh_table_ready = false;
-  DeviceBuffer<void> multimesh_maps;
-  // dslam_register_maps (register.hip): per-workgroup partial sums in mapped page-locked memory, as the tracker's
-  PinnedBuffer<double> reg_partials;
-  double reg_last_sums[33] = {0};     // the totals of the most recent evaluation (dslam_debug_register_sums; test hook)
-  bool reg_have_sums = false;
+  bool multimesh_table_ready = false; // dslam_mesh_scene_multi (multimesh.hip): its copy of the case table is in place
+  // The map descriptors of one multi-map call (dslam_get_image_multi, dslam_mesh_scene_multi per map pass,
+  // dslam_track_camera_sdf): DSLAM_MAX_RENDER_MAPS x MultiMap, device.  One table serves all three: every upload to it
+  // and every kernel that reads it is enqueued on this engine's one stream, so a call's kernels have read the table
+  // before the next call's upload overwrites it.
+  DeviceBuffer<void> map_table;
+  dslam::SumChannel reg_sums;         // dslam_register_maps (register.hip)
+  dslam::SumChannel track_sdf_sums;   // dslam_track_camera_sdf (track_sdf.hip)
   dslam::MergeScratch merge;          // dslam_merge_maps (merge.hip)
+  dslam::LiveLists live_lists;        // dslam_register_graph, dslam_survey_overlaps
   dslam::RegisterGraphScratch reg_graph;   // dslam_register_graph (register_graph.hip)
   dslam::OverlapScratch overlap;      // dslam_survey_overlaps (overlap.hip)
   std::vector<double> reg_graph_sums; // [pairs][33]: each pair's totals at the most recent joint evaluation it took part
                                       // in (dslam_debug_register_graph_sums; test hook)
-  // dslam_track_camera_sdf (track_sdf.hip): the map descriptors of a call (device) and the per-workgroup partial sums in
-  // mapped page-locked memory, as the registration's
-  DeviceBuffer<void> track_sdf_maps;
-  PinnedBuffer<double> track_sdf_partials;
-  double track_sdf_last_sums[33] = {0};   // the totals of the most recent evaluation (dslam_debug_track_sdf_sums; test hook)
-  bool track_sdf_have_sums = false;
   // dslam_debug_merge_phases (bench hook): wall clock of the last merge's phases, each closed by a wait for the stream --
   // [0] the source's live list, [1] mark kernels, [2] ordered selections (ranks, serve, touched list), [3] block kernel,
   // [4] read-backs
@@ -313,9 +325,8 @@ struct RenderIcpMaps {
 };
 struct RenderMulti {
   // dslam_get_image_multi (multimap.hip), allocated by its first call: per range cell the maps whose blocks project into
-  // it (bit i = map i), the per-map descriptor table, per map its visible-block count
+  // it (bit i = map i), per map its visible-block count (the descriptors go to dslam_engine::map_table)
   DeviceBuffer<unsigned long long> multi_mask;
-  DeviceBuffer<void> multi_maps;
   DeviceBuffer<int> multi_counts;
 };
 

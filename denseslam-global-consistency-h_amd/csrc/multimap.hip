@@ -238,18 +238,11 @@ __global__ __launch_bounds__(64) void k_render_multi(MultiRenderParams mp) {
   store_pixel<SHADE>(p, loc, pr, normal, colour);
 }
 
-static bool is_identity(const float *T) {
-  for (int i = 0; i < 16; i++)
-    if (T[i] != ((i % 5) == 0 ? 1.0f : 0.0f)) return false;
-  return true;
-}
-
 static int ensure_multi_buffers(dslam_render_state *r) {
   if (r->multi_mask) return DSLAM_OK;
   const size_t ncell = (size_t)((r->w + 7) / 8) * ((r->h + 7) / 8);
-  RenderMulti n;   // (the render state gets the three together or none)
+  RenderMulti n;   // (the render state gets the two together or none)
   DSLAM_TRY(n.multi_mask.alloc(ncell));
-  DSLAM_TRY(n.multi_maps.alloc(DSLAM_MAX_RENDER_MAPS * sizeof(MultiMap)));
   DSLAM_TRY(n.multi_counts.alloc(DSLAM_MAX_RENDER_MAPS));
   static_cast<RenderMulti &>(*r) = std::move(n);
   return DSLAM_OK;
@@ -260,22 +253,11 @@ int launch_render_multi(dslam_engine *e, const dslam_scene *const *scenes, const
                         const float *M, const float *intr, int type, void *image_out_override) {
   int rc = ensure_multi_buffers(r);
   if (rc) return rc;
-  const float vs = scenes[0]->p.voxel_size;
   const int cw = (r->w + 7) / 8, ch = (r->h + 7) / 8;
   MultiMap maps[DSLAM_MAX_RENDER_MAPS];
-  for (int i = 0; i < n; i++) {
-    const dslam_scene *s = scenes[i];
-    const float *Ti = T + 16 * i;
-    MultiMap &m = maps[i];
-    memset(&m, 0, sizeof(m));
-    m.hash = s->hash; m.voxels = s->voxels; m.mask = (unsigned)(s->p.num_buckets - 1); m.num_buckets = s->p.num_buckets;
-    m.identity = is_identity(Ti) ? 1 : 0;
-    for (int row = 0; row < 3; row++) {
-      for (int col = 0; col < 3; col++) m.T[row * 4 + col] = Ti[col * 4 + row];
-      m.T[row * 4 + 3] = Ti[12 + row] / vs;   // translation in voxel units
-    }
-  }
-  DSLAM_HIP(hipMemcpyAsync(r->multi_maps, maps, (size_t)n * sizeof(MultiMap), hipMemcpyHostToDevice, e->stream));
+  // (posed_map divides the translation in double and rounds; the float32 division this loop used to do gives the same bits)
+  for (int i = 0; i < n; i++) maps[i] = posed_map(scenes[i], T + 16 * i, (double)scenes[0]->p.voxel_size);
+  DSLAM_HIP(hipMemcpyAsync(e->map_table, maps, (size_t)n * sizeof(MultiMap), hipMemcpyHostToDevice, e->stream));
   // front end: map i seen from M is a camera at M T_i^-1 (the identity keeps M bit for bit)
   for (int i = 0; i < n; i++) {
     const dslam_scene *s = scenes[i];
@@ -307,7 +289,7 @@ int launch_render_multi(dslam_engine *e, const dslam_scene *const *scenes, const
     DSLAM_HIP(hipGetLastError());
   }
   MultiRenderParams rp;
-  rp.maps = static_cast<const MultiMap *>(r->multi_maps.get());
+  rp.maps = static_cast<const MultiMap *>(e->map_table.get());
   rp.cell_mask = r->multi_mask;
   rp.cw = cw;
   DSLAM_TRY(fill_ray_camera(rp.cam, scenes[0], r, M, intr, type, image_out_override));

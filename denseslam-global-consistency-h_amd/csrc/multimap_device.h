@@ -1,6 +1,6 @@
 // multimap_device.h -- the posed, weighted cross-map reads shared by multimap.hip (the composite raycast) and multimesh.hip
 // (the composite mesh): a map's descriptor, the transform into its frame, the 8-tap cell gather and the running state of
-// a combined read (DESIGN.md sections 10 and 12).
+// a combined read (DESIGN.md sections 10 and 12); and, for the host, how every launcher fills a descriptor (section 19).
 #pragma once
 #include "raycast_device.h"
 
@@ -18,6 +18,27 @@ struct MultiMap {
   int identity;
   int pad;
 };
+static_assert(sizeof(MultiMap) == kMapDescriptorBytes, "dslam_engine::map_table is sized for this");
+
+// ---- host: a scene's descriptor ----
+// the table and the voxels of a scene; T and identity zero, for the caller to fill
+inline MultiMap map_of(const dslam_scene *s) {
+  MultiMap m;
+  memset(&m, 0, sizeof(m));
+  m.hash = s->hash; m.voxels = s->voxels; m.mask = (unsigned)(s->p.num_buckets - 1); m.num_buckets = s->p.num_buckets;
+  return m;
+}
+// ... under T16 (world -> map, column-major, metres): T is voxel_pose rounded to float32.  (The translation is divided in
+// double and then rounded; a float32 division of the same two float32 values gives the same bits, because a quotient of
+// two 24-bit significands rounded to 53 >= 2 * 24 + 2 bits rounds on to 24 bits as the exact quotient does.)
+inline MultiMap posed_map(const dslam_scene *s, const float *T16, double voxel_size) {
+  MultiMap m = map_of(s);
+  double Tv[12];
+  voxel_pose(T16, voxel_size, Tv);
+  for (int k = 0; k < 12; k++) m.T[k] = (float)Tv[k];
+  m.identity = is_identity16(T16) ? 1 : 0;
+  return m;
+}
 
 // lowest set bit of a wave-uniform mask, as a scalar
 __device__ __forceinline__ int first_map(unsigned long long mk) {

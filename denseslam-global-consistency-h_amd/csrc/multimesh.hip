@@ -270,14 +270,6 @@ __global__ __launch_bounds__(1024) void k_multimesh_scan(const int *block_counts
   if (threadIdx.x == 0) *total_out = totals[0];
 }
 
-// the first three rows of T (column-major, metres) with the translation in voxel units, row-major, in double
-static void voxel_transform(const float *T, double vs, double out[12]) {
-  for (int row = 0; row < 3; row++) {
-    for (int col = 0; col < 3; col++) out[row * 4 + col] = (double)T[col * 4 + row];
-    out[row * 4 + 3] = (double)T[12 + row] / vs;
-  }
-}
-
 // inverse of an affine transform [R | t] (R by its adjugate; the caller has checked that T is not singular)
 static void invert_affine(const double a[12], double out[12]) {
   const double r00 = a[0], r01 = a[1], r02 = a[2], r10 = a[4], r11 = a[5], r12 = a[6], r20 = a[8], r21 = a[9], r22 = a[10];
@@ -300,12 +292,6 @@ static void compose_affine(const double a[12], const double b[12], double c[12])
       for (int k = 0; k < 3; k++) acc += a[row * 4 + k] * b[k * 4 + col];
       c[row * 4 + col] = acc;
     }
-}
-
-static bool is_identity_transform(const float *T) {
-  for (int i = 0; i < 16; i++)
-    if (T[i] != ((i % 5) == 0 ? 1.0f : 0.0f)) return false;
-  return true;
 }
 
 static void set_identity(float T[12]) {
@@ -358,11 +344,10 @@ int launch_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, c
     max_local = std::max(max_local, scenes[i]->p.num_local_blocks);
   }
   DSLAM_TRY(ensure_scratch(e, max_entries, max_local));
-  if (!e->multimesh_maps) DSLAM_TRY(e->multimesh_maps.alloc(DSLAM_MAX_RENDER_MAPS * sizeof(MultiMap)));
   const double vs = (double)scenes[0]->p.voxel_size;
   std::vector<double> Tv((size_t)n * 12), Bv((size_t)n * 12);
   for (int i = 0; i < n; i++) {
-    voxel_transform(T + 16 * i, vs, &Tv[(size_t)i * 12]);
+    voxel_pose(T + 16 * i, vs, &Tv[(size_t)i * 12]);
     invert_affine(&Tv[(size_t)i * 12], &Bv[(size_t)i * 12]);
   }
   int *live_count = e->misc_counter + 8, *total = e->misc_counter + 9;
@@ -379,10 +364,7 @@ int launch_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, c
     if (acc < limit) {
       // row i of the A table: map j read from map i's voxel frame
       for (int j = 0; j < n; j++) {
-        MultiMap &m = row[j];
-        memset(&m, 0, sizeof(m));
-        m.hash = scenes[j]->hash; m.voxels = scenes[j]->voxels;
-        m.mask = (unsigned)(scenes[j]->p.num_buckets - 1); m.num_buckets = scenes[j]->p.num_buckets;
+        MultiMap &m = row[j] = map_of(scenes[j]);
         if (memcmp(T + 16 * i, T + 16 * j, 16 * sizeof(float)) == 0) {
           m.identity = 1;
           set_identity(m.T);
@@ -392,7 +374,7 @@ int launch_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, c
           for (int k = 0; k < 12; k++) m.T[k] = (float)A[k];
         }
       }
-      DSLAM_HIP(hipMemcpyAsync(e->multimesh_maps, row, (size_t)n * sizeof(MultiMap), hipMemcpyHostToDevice, e->stream));
+      DSLAM_HIP(hipMemcpyAsync(e->map_table, row, (size_t)n * sizeof(MultiMap), hipMemcpyHostToDevice, e->stream));
       const int N = s->n_entries;
       SelLiveMulti sel;
       sel.hash = s->hash;
@@ -400,9 +382,9 @@ int launch_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, c
       MultiMeshParams p;
       p.hash = s->hash; p.voxels = s->voxels; p.num_buckets = s->p.num_buckets; p.mask = (unsigned)(s->p.num_buckets - 1);
       p.live_list = e->list_a; p.live_count = live_count; p.block_counts = e->list_b; p.block_offsets = e->list_c;
-      p.maps = static_cast<const MultiMap *>(e->multimesh_maps.get());
+      p.maps = static_cast<const MultiMap *>(e->map_table.get());
       p.self = i; p.num_maps = n;
-      p.b_identity = is_identity_transform(T + 16 * i) ? 1 : 0;
+      p.b_identity = is_identity16(T + 16 * i) ? 1 : 0;
       for (int k = 0; k < 12; k++) p.B[k] = (float)Bv[(size_t)i * 12 + k];
       p.positions = nullptr; p.colours = nullptr; p.factor = s->p.voxel_size; p.limit = 0;
       // (the count pass needs no colours: the case index and both gates come from the sdf values alone)

@@ -7,8 +7,8 @@
 // shared when d holds a resident block at floor(q) >> 3.  Only hash entries are read, never a voxel; all maps are only
 // read; the counts are integers, so the result is exact and the same on every run.
 //
-// Device work per call: one ordered compaction of the resident entries of every map (launch_bits_select) into this
-// feature's own scratch, one read-back of the counts, one copy of the call's tables to the device, and k_survey_overlaps,
+// Device work per call: one ordered compaction of the resident entries of every map (fill_live_lists, dslam_bits.h) into
+// the engine's live lists, one read-back of the counts, one copy of the call's tables to the device, and k_survey_overlaps,
 // once: a fixed grid of kSurveyGrid workgroups, cut by the host into one contiguous range per SOURCE map in proportion to
 // the live counts (split_workgroups, the rule of dslam_register_graph with maps in place of pairs).  A source's live
 // blocks are taken eight at a time; an item is (group of eight blocks, destination map), and wave v of workgroup w of a
@@ -149,19 +149,13 @@ constexpr size_t kMapTableBytes = (size_t)DSLAM_MAX_RENDER_MAPS * sizeof(SurveyM
 constexpr size_t kPairTableBytes = (size_t)DSLAM_MAX_RENDER_MAPS * DSLAM_MAX_RENDER_MAPS * sizeof(SurveyPair);
 static_assert(kWgTableBytes % 16 == 0 && sizeof(SurveyMap) % 8 == 0 && sizeof(SurveyPair) == 64, "table layout");
 
-int ensure_overlap_scratch(dslam_engine *e, int entries) {
-  OverlapScratch &have = e->overlap;
-  if (have.live_list && have.entries >= entries) return DSLAM_OK;
-  DSLAM_HIP(hipStreamSynchronize(e->stream));   // (nothing in flight may still use the old set)
-  OverlapScratch s;
-  s.entries = std::max(entries, have.entries);
-  DSLAM_TRY(s.live_list.alloc((size_t)s.entries));
-  DSLAM_TRY(s.live_counts.alloc_zeroed((size_t)DSLAM_MAX_RENDER_MAPS, e->stream));
-  DSLAM_TRY(s.live_counts_host.alloc((size_t)DSLAM_MAX_RENDER_MAPS));
+int ensure_overlap_scratch(dslam_engine *e) {
+  if (e->overlap.tables) return DSLAM_OK;
+  OverlapScratch s;   // (the engine gets the three together or none)
   DSLAM_TRY(s.rows.alloc((size_t)kSurveyGrid * 2 * DSLAM_MAX_RENDER_MAPS, hipHostMallocMapped));
   DSLAM_TRY(s.tables_host.alloc(kWgTableBytes + kMapTableBytes + kPairTableBytes));
   DSLAM_TRY(s.tables.alloc(kWgTableBytes + kMapTableBytes + kPairTableBytes));
-  have = std::move(s);
+  e->overlap = std::move(s);
   return DSLAM_OK;
 }
 
@@ -171,33 +165,12 @@ int ensure_overlap_scratch(dslam_engine *e, int entries) {
 int launch_survey_overlaps(dslam_engine *e, const dslam_scene *const *scenes, const float *T_in, int num_maps, int32_t *live_out,
                            int32_t *blocks_out, int32_t *octants_out) {
   const int n = num_maps;
-  // ---- the live lists ----
-  std::vector<int> list_offset(n);
-  long long entries = 0;
-  int max_entries = 0, max_blocks = 0;
-  for (int i = 0; i < n; i++) {
-    list_offset[i] = (int)entries;
-    entries += scenes[i]->n_entries;
-    max_entries = std::max(max_entries, scenes[i]->n_entries);
-    max_blocks = std::max(max_blocks, scenes[i]->p.num_local_blocks);
-  }
-  DSLAM_REQUIRE(entries <= 0x7fffffffLL, "the maps' hash tables together exceed the survey's 31-bit list index");
-  DSLAM_TRY(ensure_scratch(e, max_entries, max_blocks));
-  DSLAM_TRY(ensure_overlap_scratch(e, (int)entries));
-  OverlapScratch &sc = e->overlap;
-  for (int i = 0; i < n; i++) {
-    const dslam_scene *s = scenes[i];
-    SelLiveSurvey sel;
-    sel.hash = s->hash;
-    DSLAM_TRY(launch_bits_select(e, s->alloc_bits, s->n_entries, sel, sc.live_list + list_offset[i], s->n_entries,
-                                 sc.live_counts + i, s->counters));
-  }
-  DSLAM_HIP(hipGetLastError());
-  DSLAM_HIP(hipMemcpyAsync(sc.live_counts_host, sc.live_counts, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  DSLAM_HIP(hipStreamSynchronize(e->stream));
-  std::vector<int> live(n), all(n), first_wg(n, 0), num_wg(n, 0);
-  for (int i = 0; i < n; i++) live[i] = std::min(std::max(sc.live_counts_host[i], 0), scenes[i]->n_entries);
+  // ---- the live lists of all maps ----
+  std::vector<int> all(n), list_offset, live, first_wg(n, 0), num_wg(n, 0);
   std::iota(all.begin(), all.end(), 0);
+  DSLAM_TRY(fill_live_lists<SelLiveSurvey>(e, scenes, n, all, list_offset, live));
+  DSLAM_TRY(ensure_overlap_scratch(e));
+  OverlapScratch &sc = e->overlap;
   split_workgroups(kSurveyGrid, all, live, first_wg, num_wg);
 
   // ---- the tables ----
@@ -236,7 +209,7 @@ int launch_survey_overlaps(dslam_engine *e, const dslam_scene *const *scenes, co
   kp.wg_map = reinterpret_cast<const int *>(dev);
   kp.maps = reinterpret_cast<const SurveyMap *>(dev + kWgTableBytes);
   kp.pairs = reinterpret_cast<const SurveyPair *>(dev + kWgTableBytes + kMapTableBytes);
-  kp.live_list = sc.live_list;
+  kp.live_list = e->live_lists.live_list;
   kp.num_maps = n;
   kp.rows = sc.rows.device();
   hipLaunchKernelGGL(k_survey_overlaps, dim3(kSurveyGrid), dim3(kSurveyThreads), 0, e->stream, kp);

@@ -26,7 +26,8 @@
 // order, one row of 33 per workgroup in mapped page-locked memory, rows added by the host in index order.  No atomics;
 // the same bytes on every run.  Bound: gather latency, as the mesh.  The Levenberg-Marquardt iteration (pivot at the
 // centroid, damped 6 x 6 solve, acceptance, stop reasons, conditioning) is a few hundred flops per evaluation and runs
-// on the host in double, like the tracker's.
+// on the host in double: lm_iterate of register_host.h, which the graph and the depth-to-SDF tracker drive too.  What is
+// this file's own is the kernel, its launch and the conversion of X.
 #include <cmath>
 #include <cstring>
 
@@ -50,32 +51,11 @@ __global__ __launch_bounds__(kRegThreads) void k_register(RegisterParams p) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-namespace {
-
-struct Evaluation {
-  double sums[kRegSums];
-  double cost;
-  int valid, candidates;
-};
-
-// the sums re-pivoted to the centroid c = sum q / valid: H_c = P H P^T, g_c = P g with P = [[I, -[c]x], [0, I]]
-void pivot_sums(const double sums[kRegSums], double c[3], double Hc[36], double gc[6]) {
-  double H[36], P[36];
-  unpack_hessian(sums, H);
-  const double valid = sums[28];
-  for (int i = 0; i < 3; i++) c[i] = valid > 0.0 ? sums[29 + i] / valid : 0.0;
-  pivot_matrix(c, P);
-  sandwich6(P, H, P, Hc);
-  mat6_vec(P, sums + 21, gc);
-}
-
-}  // namespace
-
 // src / dst / X / params already checked and defaulted by dslam_register_maps
 int launch_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_scene *dst, float *X_io,
                          const dslam_register_params *rp, dslam_register_result *res) {
   DSLAM_TRY(ensure_scratch(e, std::max(src->n_entries, dst->n_entries), std::max(src->p.num_local_blocks, dst->p.num_local_blocks)));
-  if (!e->reg_partials) DSLAM_TRY(e->reg_partials.alloc((size_t)kRegGrid * kRegSums, hipHostMallocMapped));
+  DSLAM_TRY(e->reg_sums.ensure(kRegGrid));
   int *live_count = e->misc_counter + 8;
   const int N = src->n_entries;
   SelLiveRegister sel;
@@ -86,90 +66,53 @@ int launch_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_sc
   RegisterParams kp;
   memset(&kp, 0, sizeof(kp));
   kp.hash = src->hash; kp.voxels = src->voxels; kp.live_list = e->list_a; kp.live_count = live_count;
-  kp.dst.hash = dst->hash; kp.dst.voxels = dst->voxels;
-  kp.dst.mask = (unsigned)(dst->p.num_buckets - 1); kp.dst.num_buckets = dst->p.num_buckets;
+  kp.dst = map_of(dst);
   kp.band_raw = (int)(rp->band * 32767.0f);
   kp.residual_gate = rp->residual_gate;
-  kp.partials = e->reg_partials.device();
+  kp.partials = e->reg_sums.partials.device();
 
   const double vs = (double)src->p.voxel_size;
   const double gate2 = (double)rp->residual_gate * (double)rp->residual_gate;
-  bool start_is_identity = true;
-  for (int i = 0; i < 16; i++) start_is_identity = start_is_identity && X_io[i] == ((i % 5) == 0 ? 1.0f : 0.0f);
 
-  auto evaluate = [&](const double X[12], bool identity, Evaluation &ev) -> int {
+  // (only the start may be the identity to the kernel: a trial is read through its transform whatever it is)
+  auto evaluate = [&](const double X[12], bool identity, Evaluation33 &ev) -> int {
     for (int k = 0; k < 12; k++) kp.dst.T[k] = (float)X[k];
     kp.dst.identity = identity ? 1 : 0;
     hipLaunchKernelGGL(k_register, dim3(kRegGrid), dim3(kRegThreads), 0, e->stream, kp);
     DSLAM_HIP(hipGetLastError());
     DSLAM_HIP(hipStreamSynchronize(e->stream));
-    for (int i = 0; i < kRegSums; i++) ev.sums[i] = 0.0;
-    for (int g = 0; g < kRegGrid; g++)
-      for (int i = 0; i < kRegSums; i++) ev.sums[i] += e->reg_partials[(size_t)g * kRegSums + i];
-    memcpy(e->reg_last_sums, ev.sums, sizeof ev.sums);
-    e->reg_have_sums = true;
-    ev.valid = (int)ev.sums[28];
-    ev.candidates = (int)ev.sums[32];
-    ev.cost = ev.candidates > 0 ? (ev.sums[27] + (double)(ev.candidates - ev.valid) * gate2) / (double)ev.candidates : gate2;
+    e->reg_sums.collect(kRegGrid, ev);
     return DSLAM_OK;
   };
 
-  double X[12];
-  for (int row = 0; row < 3; row++) {
-    for (int col = 0; col < 3; col++) X[row * 4 + col] = (double)X_io[col * 4 + row];
-    X[row * 4 + 3] = (double)X_io[12 + row] / vs;
-  }
-  Evaluation good;
-  DSLAM_TRY(evaluate(X, start_is_identity, good));
-  int evaluations = 1, stop = -1;
-  bool accepted_any = false;
-  const double cost_first = good.cost;
-  double lambda = 1.0, Hc[36], gc[6], c[3];
-  if (good.valid < rp->min_valid) stop = 3;
-  while (stop < 0) {
-    if (evaluations >= rp->max_evaluations) { stop = 1; break; }
-    pivot_sums(good.sums, c, Hc, gc);
-    double M[36], y[6], trial[12];
-    for (int i = 0; i < 36; i++) M[i] = Hc[i];
-    for (int i = 0; i < 6; i++) M[i * 6 + i] += lambda * Hc[i * 6 + i];
-    solve_damped(M, gc, 6, y);
-    apply_increment(y, c, X, trial);
-    Evaluation ev;
-    DSLAM_TRY(evaluate(trial, false, ev));
-    evaluations++;
-    if (ev.valid >= rp->min_valid && ev.cost < good.cost) {
-      const double used = lambda;
-      memcpy(X, trial, sizeof trial);
-      good = ev;
-      accepted_any = true;
-      lambda = std::max(lambda / 10.0, 1e-6);
-      const double rot = sqrt(y[0] * y[0] + y[1] * y[1] + y[2] * y[2]), tr = sqrt(y[3] * y[3] + y[4] * y[4] + y[5] * y[5]);
-      if (used <= 1.0 && rot < (double)rp->term_rotation && tr < (double)rp->term_translation_voxels) stop = 0;
-    } else {
-      lambda *= 10.0;
-      if (lambda > 1e6) stop = 2;
-    }
-  }
-  double conditioning = 0.0;
-  if (stop != 3) {
-    pivot_sums(good.sums, c, Hc, gc);
-    conditioning = conditioning_of(Hc, 6);
-  }
-  if (accepted_any) {
-    for (int row = 0; row < 3; row++) {
-      for (int col = 0; col < 3; col++) X_io[col * 4 + row] = (float)X[row * 4 + col];
-      X_io[12 + row] = (float)(X[row * 4 + 3] * vs);
-      X_io[row * 4 + 3] = 0.0f;
-    }
-    X_io[15] = 1.0f;
-  }
-  res->evaluations = evaluations;
-  res->stop_reason = stop;
+  double X[12], c[3];
+  voxel_pose(X_io, vs, X);
+  Evaluation33 good;
+  DSLAM_TRY(evaluate(X, is_identity16(X_io), good));
+  const double cost_first = good.gated_cost(gate2);
+  LmOutcome lm;
+  DSLAM_TRY(lm_iterate(
+      6, good.valid >= rp->min_valid, rp->max_evaluations, (double)rp->term_rotation, (double)rp->term_translation_voxels,
+      [&](double *H, double *g) { pivot_sums(good.sums, c, H, g); },
+      [&](const double *y) -> int {
+        double trial[12];
+        Evaluation33 ev;
+        apply_increment(y, c, X, trial);
+        DSLAM_TRY(evaluate(trial, false, ev));
+        if (!(ev.valid >= rp->min_valid && ev.gated_cost(gate2) < good.gated_cost(gate2))) return 0;
+        memcpy(X, trial, sizeof trial);
+        good = ev;
+        return 1;
+      },
+      lm));
+  if (lm.accepted_any) pose_from_voxels(X, vs, X_io);
+  res->evaluations = lm.evaluations;
+  res->stop_reason = lm.stop;
   res->candidates = good.candidates;
   res->valid_last = good.valid;
   res->cost_first = (float)cost_first;
-  res->cost_last = (float)good.cost;
-  res->conditioning = (float)conditioning;
+  res->cost_last = (float)good.gated_cost(gate2);
+  res->conditioning = (float)lm.conditioning;
   res->pad = 0;
   return device_errors(e);
 }

@@ -7,7 +7,7 @@
 
 namespace dslam {
 
-constexpr int kRegSums = 33;
+// (kRegSums, the 33 sums of an evaluation: register_host.h)
 constexpr int kRegGrid = 512;      // workgroups of the registration kernels: two per CU of an MI355X
 constexpr int kRegThreads = 256;   // lane t takes voxels t and t + 256 of a block
 constexpr int kRegWaves = kRegThreads / 64;

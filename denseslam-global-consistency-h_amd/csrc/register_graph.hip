@@ -5,8 +5,8 @@
 // Levenberg-Marquardt problem over the poses of all maps but the anchor, every pair evaluated by dslam_register_maps' law
 // (section 13, register_device.h) at X~_p = T~_d inv(T~_s).  All maps are only read.
 //
-// Device work per call: one ordered compaction of the resident entries of every distinct source map (launch_bits_select)
-// into this feature's own scratch, one read-back of the counts; per evaluation k_register_graph, once: a fixed grid of
+// Device work per call: one ordered compaction of the resident entries of every distinct source map (fill_live_lists,
+// dslam_bits.h) into the engine's live lists, one read-back of the counts; per evaluation k_register_graph, once: a fixed grid of
 // kRegGrid workgroups, cut by the host into one contiguous range per pair in proportion to the sources' live blocks
 // (split_workgroups).  Workgroup w of a pair's range of G takes the live blocks w - first, w - first + G, ... of that
 // pair's source; lanes, gates, arithmetic and reduction are k_register's (register_body.h).  The pair's descriptor -- the
@@ -14,7 +14,8 @@
 // mapped page-locked memory, indexed by a wave-uniform pair index, as k_render_multi reads its maps.  One row of 33 per
 // workgroup in mapped page-locked memory (a workgroup whose share holds no block writes zeros); the host adds each pair's rows in
 // index order.  No atomics, no workgroup waits for another; the same bytes on every run.  The joint system (pivots,
-// Jacobians, damped solve, acceptance, conditioning) is assembled and solved on the host in double (register_host.h).
+// Jacobians) is assembled on the host in double; the damped iteration is lm_iterate of register_host.h, the one the pairwise
+// call runs.  This file's own are the kernel, the plan of the grid, the assembly, the active set and its connectivity.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -73,18 +74,12 @@ namespace {
 
 constexpr size_t kJobTableBytes = (size_t)DSLAM_MAX_REGISTER_PAIRS * sizeof(RegisterGraphJob);
 
-int ensure_graph_scratch(dslam_engine *e, int entries) {
-  RegisterGraphScratch &have = e->reg_graph;
-  if (have.live_list && have.entries >= entries) return DSLAM_OK;
-  DSLAM_HIP(hipStreamSynchronize(e->stream));   // (nothing in flight may still use the old set)
-  RegisterGraphScratch s;
-  s.entries = std::max(entries, have.entries);
-  DSLAM_TRY(s.live_list.alloc((size_t)s.entries));
-  DSLAM_TRY(s.live_counts.alloc_zeroed((size_t)DSLAM_MAX_RENDER_MAPS, e->stream));
-  DSLAM_TRY(s.live_counts_host.alloc((size_t)DSLAM_MAX_RENDER_MAPS));
+int ensure_graph_scratch(dslam_engine *e) {
+  if (e->reg_graph.jobs) return DSLAM_OK;
+  RegisterGraphScratch s;   // (the engine gets the two together or none)
   DSLAM_TRY(s.partials.alloc((size_t)kRegGrid * kRegSums, hipHostMallocMapped));
   DSLAM_TRY(s.jobs.alloc(kJobTableBytes + (size_t)kRegGrid * sizeof(int), hipHostMallocMapped));
-  have = std::move(s);
+  e->reg_graph = std::move(s);
   return DSLAM_OK;
 }
 
@@ -107,14 +102,18 @@ void adjoint_transposed(const double X[12], double out[36]) {
     for (int j = 0; j < 6; j++) out[i * 6 + j] = Ad[j * 6 + i];
 }
 
-struct PairEvaluation {
-  double sums[kRegSums];
-  int valid, candidates;
-};
-
 struct GraphEvaluation {
-  std::vector<PairEvaluation> pairs;   // (entries of pairs that are not evaluated keep what they held)
+  std::vector<Evaluation33> pairs;   // (entries of pairs that are not evaluated keep what they held)
   double cost;
+  // the gated cost of the pairs `use` together
+  void cost_over(const std::vector<int> &use, double gate2) {
+    double num = 0.0, den = 0.0;
+    for (int p : use) {
+      num += pairs[p].gated_sum(gate2);
+      den += (double)pairs[p].candidates;
+    }
+    cost = den > 0.0 ? num / den : gate2;
+  }
 };
 
 }  // namespace
@@ -123,38 +122,15 @@ struct GraphEvaluation {
 int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, float *T_io, int num_maps, const int32_t *pairs,
                           int num_pairs, int anchor, const dslam_register_params *rp, dslam_register_graph_result *res,
                           dslam_register_pair_result *pair_res) {
-  // ---- the live lists of the distinct sources ----
-  std::vector<int> list_offset(num_maps, -1);
-  int entries = 0, max_entries = 0, max_blocks = 0;
-  for (int p = 0; p < num_pairs; p++) {
-    const int s = pairs[2 * p];
-    if (list_offset[s] >= 0) continue;
-    list_offset[s] = entries;
-    entries += scenes[s]->n_entries;
-  }
-  for (int i = 0; i < num_maps; i++) {
-    max_entries = std::max(max_entries, scenes[i]->n_entries);
-    max_blocks = std::max(max_blocks, scenes[i]->p.num_local_blocks);
-  }
-  DSLAM_TRY(ensure_scratch(e, max_entries, max_blocks));
-  DSLAM_TRY(ensure_graph_scratch(e, entries));
+  // ---- the live lists of the distinct sources, in the order the pairs name them ----
+  std::vector<int> sources, list_offset, live;
+  for (int p = 0; p < num_pairs; p++)
+    if (std::find(sources.begin(), sources.end(), pairs[2 * p]) == sources.end()) sources.push_back(pairs[2 * p]);
+  DSLAM_TRY(fill_live_lists<SelLiveRegisterGraph>(e, scenes, num_maps, sources, list_offset, live));
+  DSLAM_TRY(ensure_graph_scratch(e));
   RegisterGraphScratch &sc = e->reg_graph;
-  for (int i = 0; i < num_maps; i++) {
-    if (list_offset[i] < 0) continue;
-    const dslam_scene *s = scenes[i];
-    SelLiveRegisterGraph sel;
-    sel.hash = s->hash;
-    DSLAM_TRY(launch_bits_select(e, s->alloc_bits, s->n_entries, sel, sc.live_list + list_offset[i], s->n_entries,
-                                 sc.live_counts + i, s->counters));
-  }
-  DSLAM_HIP(hipGetLastError());
-  DSLAM_HIP(hipMemcpyAsync(sc.live_counts_host, sc.live_counts, (size_t)num_maps * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  DSLAM_HIP(hipStreamSynchronize(e->stream));
   std::vector<int> live_of_pair(num_pairs);
-  for (int p = 0; p < num_pairs; p++) {
-    const int s = pairs[2 * p];
-    live_of_pair[p] = std::min(std::max(sc.live_counts_host[s], 0), scenes[s]->n_entries);
-  }
+  for (int p = 0; p < num_pairs; p++) live_of_pair[p] = live[pairs[2 * p]];
 
   RegisterGraphJob *jobs = static_cast<RegisterGraphJob *>(sc.jobs.get());
   int *wg_pair = reinterpret_cast<int *>(static_cast<char *>(sc.jobs.get()) + kJobTableBytes);
@@ -162,7 +138,7 @@ int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, flo
   memset(&kp, 0, sizeof kp);
   kp.jobs = static_cast<const RegisterGraphJob *>(sc.jobs.device());
   kp.wg_pair = reinterpret_cast<const int *>(static_cast<const char *>(sc.jobs.device()) + kJobTableBytes);
-  kp.live_list = sc.live_list;
+  kp.live_list = e->live_lists.live_list;
   kp.band_raw = (int)(rp->band * 32767.0f);
   kp.residual_gate = rp->residual_gate;
   kp.partials = sc.partials.device();
@@ -179,8 +155,7 @@ int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, flo
       const dslam_scene *s = scenes[pairs[2 * p]], *d = scenes[pairs[2 * p + 1]];
       RegisterGraphJob &j = jobs[p];
       memset(&j, 0, sizeof j);
-      j.dst.hash = d->hash; j.dst.voxels = d->voxels;
-      j.dst.mask = (unsigned)(d->p.num_buckets - 1); j.dst.num_buckets = d->p.num_buckets;
+      j.dst = map_of(d);
       j.hash = s->hash; j.voxels = s->voxels;
       j.list_offset = list_offset[pairs[2 * p]];
       j.live = live_of_pair[p];
@@ -200,23 +175,12 @@ int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, flo
     hipLaunchKernelGGL(k_register_graph, dim3(kRegGrid), dim3(kRegThreads), 0, e->stream, kp);
     DSLAM_HIP(hipGetLastError());
     DSLAM_HIP(hipStreamSynchronize(e->stream));
-    double num = 0.0, den = 0.0;
     for (int p : use) {
-      PairEvaluation &pe = ev.pairs[p];
-      for (int i = 0; i < kRegSums; i++) pe.sums[i] = 0.0;
-      for (int g = first_wg[p]; g < first_wg[p] + num_wg[p]; g++)
-        for (int i = 0; i < kRegSums; i++) pe.sums[i] += sc.partials[(size_t)g * kRegSums + i];
-      memcpy(&e->reg_graph_sums[(size_t)p * kRegSums], pe.sums, sizeof pe.sums);
-      pe.valid = (int)pe.sums[28];
-      pe.candidates = (int)pe.sums[32];
-      num += pe.sums[27] + (double)(pe.candidates - pe.valid) * gate2;
-      den += (double)pe.candidates;
+      ev.pairs[p].sum_rows(sc.partials, first_wg[p], num_wg[p]);
+      memcpy(&e->reg_graph_sums[(size_t)p * kRegSums], ev.pairs[p].sums, sizeof ev.pairs[p].sums);
     }
-    ev.cost = den > 0.0 ? num / den : gate2;
+    ev.cost_over(use, gate2);
     return DSLAM_OK;
-  };
-  auto pair_cost = [&](const PairEvaluation &pe) {
-    return pe.candidates > 0 ? (pe.sums[27] + (double)(pe.candidates - pe.valid) * gate2) / (double)pe.candidates : gate2;
   };
 
   // ---- the start poses ----
@@ -233,12 +197,7 @@ int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, flo
     if (good.pairs[p].valid >= rp->min_valid) active.push_back(p);
   if ((int)active.size() != num_pairs) {
     // the cost of the active pairs alone, and the grid to them
-    double num = 0.0, den = 0.0;
-    for (int p : active) {
-      num += good.pairs[p].sums[27] + (double)(good.pairs[p].candidates - good.pairs[p].valid) * gate2;
-      den += (double)good.pairs[p].candidates;
-    }
-    good.cost = den > 0.0 ? num / den : gate2;
+    good.cost_over(active, gate2);
     if (!active.empty()) plan(active);
   }
   const double cost_first = good.cost;
@@ -261,16 +220,16 @@ int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, flo
   // unknown block of map i in the reduced system
   const int n_free = num_maps - 1, n = 6 * n_free;
   auto block_of = [&](int i) { return i == anchor ? -1 : (i < anchor ? i : i - 1); };
-  std::vector<double> H((size_t)n * n), g(n), cpiv((size_t)num_maps * 3);
-  // the joint system at an evaluation and the poses it was made at (Xp holds their pair transforms)
-  auto assemble = [&](const GraphEvaluation &ev) {
-    std::fill(H.begin(), H.end(), 0.0);
-    std::fill(g.begin(), g.end(), 0.0);
+  std::vector<double> cpiv((size_t)num_maps * 3);
+  // the joint system (H: n x n, g: n) at an evaluation and the poses it was made at (Xp holds their pair transforms)
+  auto assemble = [&](const GraphEvaluation &ev, double *H, double *g) {
+    std::fill_n(H, (size_t)n * n, 0.0);
+    std::fill_n(g, n, 0.0);
     // pivots
     for (int i = 0; i < num_maps; i++) {
       double acc[3] = {0.0, 0.0, 0.0}, weight = 0.0;
       for (int p : active) {
-        const PairEvaluation &pe = ev.pairs[p];
+        const Evaluation33 &pe = ev.pairs[p];
         const double valid = pe.sums[28];
         if (pairs[2 * p + 1] == i) {
           for (int k = 0; k < 3; k++) acc[k] += pe.sums[29 + k];
@@ -287,7 +246,7 @@ int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, flo
       for (int k = 0; k < 3; k++) cpiv[(size_t)i * 3 + k] = weight > 0.0 ? acc[k] / weight : 0.0;
     }
     for (int p : active) {
-      const PairEvaluation &pe = ev.pairs[p];
+      const Evaluation33 &pe = ev.pairs[p];
       const int maps_of[2] = {pairs[2 * p], pairs[2 * p + 1]};   // s, d
       double Hp[36], J[2][36], P[36], AdT[36];
       unpack_hessian(pe.sums, Hp);
@@ -319,72 +278,40 @@ int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, flo
     }
   };
 
-  int evaluations = 1, stop = -1;
-  bool accepted_any = false;
-  double lambda = 1.0;
-  if (!connected) stop = 3;
-  std::vector<double> M((size_t)n * n), y(n), trial((size_t)num_maps * 12), Xp_good;
+  // a step: the poses the increment leads to, evaluated on the active pairs; adopted if every pair stays valid and the
+  // joint cost falls, otherwise the pair transforms go back to those of the accepted poses (what the next system is made at)
+  std::vector<double> trial((size_t)num_maps * 12), Xp_good;
   GraphEvaluation ev;
   ev.pairs.resize(num_pairs);
-  while (stop < 0) {
-    if (evaluations >= rp->max_evaluations) { stop = 1; break; }
-    assemble(good);
+  auto step = [&](const double *y) -> int {
     Xp_good = Xp;
-    M = H;
-    for (int i = 0; i < n; i++) M[(size_t)i * n + i] += lambda * H[(size_t)i * n + i];
-    solve_damped(M.data(), g.data(), n, y.data());
     trial = T;
     for (int i = 0; i < num_maps; i++) {
       const int b = block_of(i);
-      if (b >= 0) apply_increment(&y[(size_t)b * 6], &cpiv[(size_t)i * 3], &T[(size_t)i * 12], &trial[(size_t)i * 12]);
+      if (b >= 0) apply_increment(y + (size_t)b * 6, &cpiv[(size_t)i * 3], &T[(size_t)i * 12], &trial[(size_t)i * 12]);
     }
     DSLAM_TRY(evaluate(trial, active, ev));
-    evaluations++;
     bool all_valid = true;
     for (int p : active) all_valid = all_valid && ev.pairs[p].valid >= rp->min_valid;
-    if (all_valid && ev.cost < good.cost) {
-      const double used = lambda;
-      T = trial;
-      for (int p : active) good.pairs[p] = ev.pairs[p];
-      good.cost = ev.cost;
-      accepted_any = true;
-      lambda = std::max(lambda / 10.0, 1e-6);
-      double rot = 0.0, tr = 0.0;
-      for (int b = 0; b < n_free; b++) {
-        const double *yb = &y[(size_t)b * 6];
-        rot = std::max(rot, sqrt(yb[0] * yb[0] + yb[1] * yb[1] + yb[2] * yb[2]));
-        tr = std::max(tr, sqrt(yb[3] * yb[3] + yb[4] * yb[4] + yb[5] * yb[5]));
-      }
-      if (used <= 1.0 && rot < (double)rp->term_rotation && tr < (double)rp->term_translation_voxels) stop = 0;
-    } else {
-      Xp = Xp_good;   // (the pair transforms of the last accepted poses: what the next system is made at)
-      lambda *= 10.0;
-      if (lambda > 1e6) stop = 2;
-    }
-  }
-  double conditioning = 0.0;
-  if (stop != 3) {
-    assemble(good);
-    conditioning = conditioning_of(H.data(), n);
-  }
-  if (accepted_any)
-    for (int i = 0; i < num_maps; i++) {
-      if (i == anchor) continue;
-      float *out = T_io + 16 * i;
-      const double *Ti = &T[(size_t)i * 12];
-      for (int row = 0; row < 3; row++) {
-        for (int col = 0; col < 3; col++) out[col * 4 + row] = (float)Ti[row * 4 + col];
-        out[12 + row] = (float)(Ti[row * 4 + 3] * vs);
-        out[row * 4 + 3] = 0.0f;
-      }
-      out[15] = 1.0f;
-    }
-  res->evaluations = evaluations;
-  res->stop_reason = stop;
+    if (!(all_valid && ev.cost < good.cost)) { Xp = Xp_good; return 0; }
+    T = trial;
+    for (int p : active) good.pairs[p] = ev.pairs[p];
+    good.cost = ev.cost;
+    return 1;
+  };
+  LmOutcome lm;
+  DSLAM_TRY(lm_iterate(
+      n, connected, rp->max_evaluations, (double)rp->term_rotation, (double)rp->term_translation_voxels,
+      [&](double *H, double *g) { assemble(good, H, g); }, step, lm));
+  if (lm.accepted_any)
+    for (int i = 0; i < num_maps; i++)
+      if (i != anchor) pose_from_voxels(&T[(size_t)i * 12], vs, T_io + 16 * i);
+  res->evaluations = lm.evaluations;
+  res->stop_reason = lm.stop;
   res->active_pairs = (int)active.size();
   res->cost_first = (float)cost_first;
   res->cost_last = (float)good.cost;
-  res->conditioning = (float)conditioning;
+  res->conditioning = (float)lm.conditioning;
   if (pair_res) {
     std::vector<char> is_active(num_pairs, 0);
     for (int p : active) is_active[p] = 1;
@@ -394,8 +321,8 @@ int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, flo
       pr.valid_first = first.pairs[p].valid;
       pr.valid_last = good.pairs[p].valid;
       pr.active = is_active[p];
-      pr.cost_first = (float)pair_cost(first.pairs[p]);
-      pr.cost_last = (float)pair_cost(good.pairs[p]);
+      pr.cost_first = (float)first.pairs[p].gated_cost(gate2);
+      pr.cost_last = (float)good.pairs[p].gated_cost(gate2);
     }
   }
   return device_errors(e);

@@ -1,15 +1,40 @@
-// register_host.h -- the host arithmetic of the map registrations (double): the damped solve, the conditioning, the pivot
-// and twist matrices and the rigid compositions.  register.hip (one pair, 6 unknowns) and register_graph.hip (a pose
-// graph, 6 (N - 1) unknowns) run the same functions, so a graph of one pair repeats the pairwise call operation for
-// operation (DESIGN.md sections 13 and 15).  The pair transform and the split of a fixed grid are also what the overlap
-// survey (overlap.hip) uses.
+// register_host.h -- the host arithmetic of the SDF optimisers (double): the 33 sums of an evaluation and their pivot, the
+// damped iteration (lm_iterate), the damped solve, the conditioning, the twist matrices and the rigid compositions.
+// register.hip (one pair, 6 unknowns), track_sdf.hip (the camera, 6 unknowns per pyramid level) and register_graph.hip (a
+// pose graph, 6 (N - 1) unknowns) run the same functions, so a graph of one pair repeats the pairwise call operation for
+// operation (DESIGN.md sections 13, 15, 18 and 19).  The pair transform and the split of a fixed grid are also what the
+// overlap survey (overlap.hip) uses.  Plain C++: nothing here needs HIP (tests/stubs/lm_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <utility>
 #include <vector>
 
 namespace dslam {
+
+// the sums of one evaluation (register_body.h): [0..20] lower triangle of sum A^T A row by row, [21..26] sum b A,
+// [27] sum b^2, [28] valid, [29..31] sum q over valid points, [32] candidates
+constexpr int kRegSums = 33;
+
+// the totals of one evaluation
+struct Evaluation33 {
+  double sums[kRegSums];
+  int valid, candidates;
+  // rows first_row .. first_row + num_rows of the per-workgroup partials, added in index order
+  void sum_rows(const double *partials, int first_row, int num_rows) {
+    for (int i = 0; i < kRegSums; i++) sums[i] = 0.0;
+    for (int g = first_row; g < first_row + num_rows; g++)
+      for (int i = 0; i < kRegSums; i++) sums[i] += partials[(size_t)g * kRegSums + i];
+    valid = (int)sums[28];
+    candidates = (int)sums[32];
+  }
+  // sum b^2 with every candidate that is not valid counted at the gate ...
+  double gated_sum(double gate2) const { return sums[27] + (double)(candidates - valid) * gate2; }
+  // ... per candidate
+  double gated_cost(double gate2) const { return candidates > 0 ? gated_sum(gate2) / (double)candidates : gate2; }
+};
+
 namespace {
 
 // solve M y = r (n x n, symmetric positive definite up to rounding) by Gaussian elimination with partial pivoting; a
@@ -119,6 +144,17 @@ inline void mat6_vec(const double A[36], const double *v, double out[6]) {
   }
 }
 
+// the sums re-pivoted to the centroid c = sum q / valid: H_c = P H P^T, g_c = P g with P = [[I, -[c]x], [0, I]]
+inline void pivot_sums(const double sums[kRegSums], double c[3], double Hc[36], double gc[6]) {
+  double H[36], P[36];
+  unpack_hessian(sums, H);
+  const double valid = sums[28];
+  for (int i = 0; i < 3; i++) c[i] = valid > 0.0 ? sums[29 + i] / valid : 0.0;
+  pivot_matrix(c, P);
+  sandwich6(P, H, P, Hc);
+  mat6_vec(P, sums + 21, gc);
+}
+
 // X' = Inc X with Inc: q -> c + R(w)(q - c) + t (Rodrigues); X, out: 3 x 4 row-major
 inline void apply_increment(const double y[6], const double c[3], const double X[12], double out[12]) {
   const double th = sqrt(y[0] * y[0] + y[1] * y[1] + y[2] * y[2]);
@@ -178,6 +214,79 @@ inline bool pair_transform(const double Ts[12], const double Td[12], double X[12
     identity = identity && Xf[k] == ((k % 5) == 0 ? 1.0f : 0.0f);
   }
   return identity;
+}
+
+// a column-major float32 4 x 4, exactly the identity?
+inline bool is_identity16(const float *T) {
+  for (int i = 0; i < 16; i++)
+    if (T[i] != ((i % 5) == 0 ? 1.0f : 0.0f)) return false;
+  return true;
+}
+
+// the estimate X (3 x 4 row-major double, translation in voxels) as a column-major float32 4 x 4 in metres
+inline void pose_from_voxels(const double X[12], double voxel_size, float out[16]) {
+  for (int row = 0; row < 3; row++) {
+    for (int col = 0; col < 3; col++) out[col * 4 + row] = (float)X[row * 4 + col];
+    out[12 + row] = (float)(X[row * 4 + 3] * voxel_size);
+    out[row * 4 + 3] = 0.0f;
+  }
+  out[15] = 1.0f;
+}
+
+// The damped (Levenberg-Marquardt) iteration over n = 6 B unknowns, B blocks of (rotation, translation), from a state
+// that has been evaluated once; start_ok: that evaluation allows a step at all.
+//   system(H, g)   fills the n x n system at the accepted state;
+//   step(y)        evaluates the state the increment y leads to and adopts it if it is valid and cheaper: 1 adopted,
+//                  0 rejected (the accepted state is as before), negative: a failure, handed on.
+// The driver damps (H + lambda diag H) y = g, lambda from 1: an adopted step divides it by 10 (not below 1e-6), a rejected
+// one multiplies it by 10.  Stop reasons: 0 an adopted step taken with lambda <= 1 whose rotation and translation norms
+// are below the thresholds in every block, 1 max_evaluations reached, 2 lambda above 1e6, 3 no step possible at the start.
+struct LmOutcome {
+  int evaluations;       // the start's included
+  int stop;
+  bool accepted_any;
+  double conditioning;   // conditioning_of the system at the accepted state; 0 for stop reason 3
+};
+template <class System, class Step>
+int lm_iterate(int n, bool start_ok, int max_evaluations, double term_rotation, double term_translation, System &&system,
+               Step &&step, LmOutcome &out) {
+  out.evaluations = 1;
+  out.stop = start_ok ? -1 : 3;
+  out.accepted_any = false;
+  out.conditioning = 0.0;
+  double lambda = 1.0;
+  std::vector<double> H((size_t)n * n), g(n), M, y(n);
+  while (out.stop < 0) {
+    if (out.evaluations >= max_evaluations) { out.stop = 1; break; }
+    system(H.data(), g.data());
+    M = H;
+    for (int i = 0; i < n; i++) M[(size_t)i * n + i] += lambda * H[(size_t)i * n + i];
+    solve_damped(M.data(), g.data(), n, y.data());
+    const int adopted = step(y.data());
+    if (adopted < 0) return adopted;
+    out.evaluations++;
+    if (adopted) {
+      const double used = lambda;
+      out.accepted_any = true;
+      lambda = std::max(lambda / 10.0, 1e-6);
+      // (the largest block norm is below a threshold exactly when every block's is)
+      bool small = true;
+      for (int b = 0; b < n; b += 6) {
+        const double rot = sqrt(y[b] * y[b] + y[b + 1] * y[b + 1] + y[b + 2] * y[b + 2]);
+        const double tr = sqrt(y[b + 3] * y[b + 3] + y[b + 4] * y[b + 4] + y[b + 5] * y[b + 5]);
+        small = small && rot < term_rotation && tr < term_translation;
+      }
+      if (used <= 1.0 && small) out.stop = 0;
+    } else {
+      lambda *= 10.0;
+      if (lambda > 1e6) out.stop = 2;
+    }
+  }
+  if (out.stop != 3) {
+    system(H.data(), g.data());
+    out.conditioning = conditioning_of(H.data(), n);
+  }
+  return 0;
 }
 
 // The workgroups of a grid over the jobs `use` (list order): G_p = 1 + floor((grid - n) L_p / sum L), the rest handed

@@ -23,7 +23,8 @@
 // pixel pays for the maps that hold its point and not for num_maps.  Accumulation and reduction are register_body.h's:
 // per-lane doubles of float32 products, wave shuffle tree, the four wave partials through LDS in index order, one row of
 // 33 per workgroup in mapped page-locked memory (a workgroup without a pixel writes zeros), rows added by the host in
-// index order.  No atomics; the same bytes on every run.  The iteration is register.hip's, on the host in double.
+// index order.  No atomics; the same bytes on every run.  The iteration is lm_iterate of register_host.h, on the host in
+// double, once per pyramid level; this file's own are the kernel, the level loop and levels_stepped.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -185,29 +186,6 @@ __global__ __launch_bounds__(kTrackSdfThreads) void k_track_sdf(TrackSdfParams p
 // ---- host side ------------------------------------------------------------------------------------------------
 namespace {
 
-struct Evaluation {
-  double sums[kRegSums];
-  double cost;
-  int valid, candidates;
-};
-
-// the sums re-pivoted to the centroid c = sum p / valid: H_c = P H P^T, g_c = P g with P = [[I, -[c]x], [0, I]]
-void pivot_sums(const double sums[kRegSums], double c[3], double Hc[36], double gc[6]) {
-  double H[36], P[36];
-  unpack_hessian(sums, H);
-  const double valid = sums[28];
-  for (int i = 0; i < 3; i++) c[i] = valid > 0.0 ? sums[29 + i] / valid : 0.0;
-  pivot_matrix(c, P);
-  sandwich6(P, H, P, Hc);
-  mat6_vec(P, sums + 21, gc);
-}
-
-bool is_identity16(const float *T) {
-  for (int i = 0; i < 16; i++)
-    if (T[i] != ((i % 5) == 0 ? 1.0f : 0.0f)) return false;
-  return true;
-}
-
 // Which pixel takes which lane.  Measured on the MI355X (harness/track_sdf_bench.py); the
 // environment variable DSLAM_TRACK_SDF_PIXELS=rows|tiles is that measurement's switch and nothing else reads it.
 bool pixels_in_tiles() {
@@ -232,34 +210,24 @@ int launch_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_sc
   for (int k = 0; k < 4; k++) lintr[0][k] = intr[k];
   for (int i = 1; i < levels; i++)
     for (int k = 0; k < 4; k++) lintr[i][k] = lintr[i - 1][k] * 0.5f;
-  if (!e->track_sdf_partials) DSLAM_TRY(e->track_sdf_partials.alloc((size_t)kTrackSdfGrid * kRegSums, hipHostMallocMapped));
-  if (!e->track_sdf_maps) DSLAM_TRY(e->track_sdf_maps.alloc(DSLAM_MAX_RENDER_MAPS * sizeof(MultiMap)));
+  DSLAM_TRY(e->track_sdf_sums.ensure(kTrackSdfGrid));
 
   const double vs = (double)scenes[0]->p.voxel_size;
   MultiMap maps[DSLAM_MAX_RENDER_MAPS];
-  for (int i = 0; i < n; i++) {
-    const dslam_scene *s = scenes[i];
-    MultiMap &m = maps[i];
-    memset(&m, 0, sizeof(m));
-    m.hash = s->hash; m.voxels = s->voxels; m.mask = (unsigned)(s->p.num_buckets - 1); m.num_buckets = s->p.num_buckets;
-    m.identity = is_identity16(T + 16 * i) ? 1 : 0;
-    double Tv[12];
-    voxel_pose(T + 16 * i, vs, Tv);
-    for (int k = 0; k < 12; k++) m.T[k] = (float)Tv[k];
-  }
-  DSLAM_HIP(hipMemcpyAsync(e->track_sdf_maps, maps, (size_t)n * sizeof(MultiMap), hipMemcpyHostToDevice, e->stream));
+  for (int i = 0; i < n; i++) maps[i] = posed_map(scenes[i], T + 16 * i, vs);
+  DSLAM_HIP(hipMemcpyAsync(e->map_table, maps, (size_t)n * sizeof(MultiMap), hipMemcpyHostToDevice, e->stream));
 
   TrackSdfParams kp;
   memset(&kp, 0, sizeof(kp));
   kp.inv_vs = (float)(1.0 / vs);
-  kp.maps = static_cast<const MultiMap *>(e->track_sdf_maps.get());
+  kp.maps = static_cast<const MultiMap *>(e->map_table.get());
   kp.num_maps = n;
   kp.residual_gate = tp->residual_gate;
-  kp.partials = e->track_sdf_partials.device();
+  kp.partials = e->track_sdf_sums.partials.device();
   const double gate2 = (double)tp->residual_gate * (double)tp->residual_gate;
   const bool tiles = pixels_in_tiles();
 
-  auto evaluate = [&](int level, const double P[12], Evaluation &ev) -> int {
+  auto evaluate = [&](int level, const double P[12], Evaluation33 &ev) -> int {
     kp.depth = ldepth[level]; kp.lw = lw[level]; kp.lh = lh[level];
     kp.fx = lintr[level][0]; kp.fy = lintr[level][1]; kp.cx = lintr[level][2]; kp.cy = lintr[level][3];
     for (int k = 0; k < 12; k++) kp.P[k] = (float)P[k];
@@ -267,83 +235,53 @@ int launch_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_sc
     else hipLaunchKernelGGL(k_track_sdf<false>, dim3(kTrackSdfGrid), dim3(kTrackSdfThreads), 0, e->stream, kp);
     DSLAM_HIP(hipGetLastError());
     DSLAM_HIP(hipStreamSynchronize(e->stream));
-    for (int i = 0; i < kRegSums; i++) ev.sums[i] = 0.0;
-    for (int g = 0; g < kTrackSdfGrid; g++)
-      for (int i = 0; i < kRegSums; i++) ev.sums[i] += e->track_sdf_partials[(size_t)g * kRegSums + i];
-    memcpy(e->track_sdf_last_sums, ev.sums, sizeof ev.sums);
-    e->track_sdf_have_sums = true;
-    ev.valid = (int)ev.sums[28];
-    ev.candidates = (int)ev.sums[32];
-    ev.cost = ev.candidates > 0 ? (ev.sums[27] + (double)(ev.candidates - ev.valid) * gate2) / (double)ev.candidates : gate2;
+    e->track_sdf_sums.collect(kTrackSdfGrid, ev);
     return DSLAM_OK;
   };
 
-  double Mv[12], P[12];
+  double Mv[12], P[12], c[3];
   voxel_pose(pose_M, vs, Mv);
   rigid_inverse(Mv, P);
   bool accepted_any = false;
-  int total_evaluations = 0, levels_stepped = 0, stop_last = 3;
-  Evaluation good_last;
-  memset(&good_last, 0, sizeof good_last);
-  double cost_first_last = 0.0, conditioning_last = 0.0;
+  int total_evaluations = 0, levels_stepped = 0;
+  // the last level's outcome is the call's (no level at all: stop reason 3, everything else zero)
+  LmOutcome lm = {0, 3, false, 0.0};
+  Evaluation33 good;
+  memset(&good, 0, sizeof good);
+  double cost_first = 0.0, cost_last = 0.0;
   for (int level = levels - 1; level >= tp->run_till_level; level--) {
-    Evaluation good;
     DSLAM_TRY(evaluate(level, P, good));
-    int evaluations = 1, stop = -1;
-    bool accepted_here = false;
-    const double cost_first = good.cost;
-    double lambda = 1.0, Hc[36], gc[6], c[3];
-    if (good.valid < tp->min_valid) stop = 3;
-    while (stop < 0) {
-      if (evaluations >= tp->max_evaluations) { stop = 1; break; }
-      pivot_sums(good.sums, c, Hc, gc);
-      double M[36], y[6], trial[12];
-      for (int i = 0; i < 36; i++) M[i] = Hc[i];
-      for (int i = 0; i < 6; i++) M[i * 6 + i] += lambda * Hc[i * 6 + i];
-      solve_damped(M, gc, 6, y);
-      apply_increment(y, c, P, trial);
-      Evaluation ev;
-      DSLAM_TRY(evaluate(level, trial, ev));
-      evaluations++;
-      if (ev.valid >= tp->min_valid && ev.cost < good.cost) {
-        const double used = lambda;
-        memcpy(P, trial, sizeof trial);
-        good = ev;
-        accepted_here = true;
-        lambda = std::max(lambda / 10.0, 1e-6);
-        const double rot = sqrt(y[0] * y[0] + y[1] * y[1] + y[2] * y[2]), tr = sqrt(y[3] * y[3] + y[4] * y[4] + y[5] * y[5]);
-        if (used <= 1.0 && rot < (double)tp->term_rotation && tr < (double)tp->term_translation_voxels) stop = 0;
-      } else {
-        lambda *= 10.0;
-        if (lambda > 1e6) stop = 2;
-      }
-    }
-    total_evaluations += evaluations;
-    if (accepted_here) { accepted_any = true; levels_stepped |= 1 << level; }
-    double conditioning = 0.0;
-    if (stop != 3) {
-      pivot_sums(good.sums, c, Hc, gc);
-      conditioning = conditioning_of(Hc, 6);
-    }
-    stop_last = stop; good_last = good; cost_first_last = cost_first; conditioning_last = conditioning;
+    cost_first = good.gated_cost(gate2);
+    DSLAM_TRY(lm_iterate(
+        6, good.valid >= tp->min_valid, tp->max_evaluations, (double)tp->term_rotation, (double)tp->term_translation_voxels,
+        [&](double *H, double *g) { pivot_sums(good.sums, c, H, g); },
+        [&](const double *y) -> int {
+          double trial[12];
+          Evaluation33 ev;
+          apply_increment(y, c, P, trial);
+          DSLAM_TRY(evaluate(level, trial, ev));
+          if (!(ev.valid >= tp->min_valid && ev.gated_cost(gate2) < good.gated_cost(gate2))) return 0;
+          memcpy(P, trial, sizeof trial);
+          good = ev;
+          return 1;
+        },
+        lm));
+    total_evaluations += lm.evaluations;
+    if (lm.accepted_any) { accepted_any = true; levels_stepped |= 1 << level; }
+    cost_last = good.gated_cost(gate2);
   }
   if (accepted_any) {
     rigid_inverse(P, Mv);
-    for (int row = 0; row < 3; row++) {
-      for (int col = 0; col < 3; col++) pose_M[col * 4 + row] = (float)Mv[row * 4 + col];
-      pose_M[12 + row] = (float)(Mv[row * 4 + 3] * vs);
-      pose_M[row * 4 + 3] = 0.0f;
-    }
-    pose_M[15] = 1.0f;
+    pose_from_voxels(Mv, vs, pose_M);
   }
   res->evaluations = total_evaluations;
   res->levels_stepped = levels_stepped;
-  res->stop_reason = stop_last;
-  res->candidates = good_last.candidates;
-  res->valid_last = good_last.valid;
-  res->cost_first = (float)cost_first_last;
-  res->cost_last = (float)good_last.cost;
-  res->conditioning = (float)conditioning_last;
+  res->stop_reason = lm.stop;
+  res->candidates = good.candidates;
+  res->valid_last = good.valid;
+  res->cost_first = (float)cost_first;
+  res->cost_last = (float)cost_last;
+  res->conditioning = (float)lm.conditioning;
   return device_errors(e);
 }
 
