@@ -11,10 +11,10 @@ import os
 import subprocess
 
 from ._capi import (BLOCK_SIZE3, HASH_ENTRY_DTYPE, IMAGE_COLOUR_FROM_NORMAL, IMAGE_COLOUR_FROM_VOLUME, IMAGE_DEPTH,
-                    IMAGE_SHADED, MAX_REGISTER_PAIRS, MAX_RENDER_MAPS, VOXEL_DTYPE, CApi, DslamError, MergeParams, MergeResult,
+                    IMAGE_SHADED, MAX_REGISTER_PAIRS, MAX_RENDER_MAPS, MAX_SURVEY_MAPS, MAX_SURVEY_VIEWS, VOXEL_DTYPE, CApi, DslamError, MergeParams, MergeResult,
                     PairSelectParams, PairSelectResult, RegisterGraphResult, RegisterPairResult, RegisterParams, RegisterResult,
-                    SceneParams, Stats, TrackerParams, TrackerResult, TrackSdfParams, TrackSdfResult, UnmergeParams, UnmergeResult,
-                    WeightParams, mat_to_abi)
+                    SceneParams, Stats, SurveyView, TrackerParams, TrackerResult, TrackSdfParams, TrackSdfResult, UnmergeParams,
+                    UnmergeResult, ViewSelectParams, ViewSelectResult, ViewSurveyParams, WeightParams, mat_to_abi)
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")

@@ -144,6 +144,50 @@ class PairSelectResult(C.Structure):
 assert C.sizeof(PairSelectParams) == 16 and C.sizeof(PairSelectResult) == 16  # the header's layouts
 
 
+MAX_SURVEY_MAPS, MAX_SURVEY_VIEWS = 256, 16   # DSLAM_MAX_SURVEY_MAPS, DSLAM_MAX_SURVEY_VIEWS
+
+
+class SurveyView(C.Structure):
+    """dslam_survey_view: M world -> camera as the ABI stores it (column-major), intrinsics (fx, fy, cx, cy), image size,
+    near and far distance in metres (far_m 0: no far plane)."""
+    _fields_ = [("M", C.c_float * 16), ("intrinsics", C.c_float * 4), ("width", C.c_int32), ("height", C.c_int32),
+                ("near_m", C.c_float), ("far_m", C.c_float)]
+
+    @classmethod
+    def of(cls, M, intr, width, height, near_m, far_m):
+        """From a 4x4 math matrix (M[row, col]) and (fx, fy, cx, cy)."""
+        return cls((C.c_float * 16)(*mat_to_abi(M).tolist()), (C.c_float * 4)(*np.asarray(intr, np.float32).tolist()),
+                   int(width), int(height), float(near_m), float(far_m))
+
+
+class ViewSurveyParams(C.Structure):
+    """dslam_view_survey_params; margin_voxels left at 0 selects its default."""
+    _fields_ = [("margin_voxels", C.c_float), ("pad", C.c_int32 * 3)]
+
+    def __init__(self, margin_voxels=0.0):
+        super().__init__(margin_voxels, (C.c_int32 * 3)(0, 0, 0))
+
+
+class ViewSelectParams(C.Structure):
+    """dslam_view_select_params; min_blocks / max_maps left at 0 select their defaults, always_keep -1: no map."""
+    _fields_ = [("min_blocks", C.c_int32), ("max_maps", C.c_int32), ("always_keep", C.c_int32), ("pad", C.c_int32)]
+
+    def __init__(self, min_blocks=0, max_maps=0, always_keep=-1):
+        super().__init__(min_blocks, max_maps, always_keep, 0)
+
+
+class ViewSelectResult(C.Structure):
+    """dslam_view_select_result."""
+    _fields_ = [("reaching", C.c_int32), ("selected", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+assert C.sizeof(SurveyView) == 96 and C.sizeof(ViewSurveyParams) == 16  # the header's layouts
+assert C.sizeof(ViewSelectParams) == 16 and C.sizeof(ViewSelectResult) == 8
+
+
 class MergeParams(C.Structure):
     """dslam_merge_params; max_passes = 0 selects its default."""
     _fields_ = [("max_passes", C.c_int32), ("with_colour", C.c_int32)]
@@ -829,6 +873,49 @@ class CApi:
                    C.byref(params) if params is not None else None, pairs.ctypes.data_as(i32), component.ctypes.data_as(i32),
                    C.byref(res))
         return pairs[:res.selected].copy(), component[:n], res
+
+    # -- view survey and map selection -------------------------------------------------------------------
+    def view_frustum_planes(self, view, voxel_size):
+        """dslam_view_frustum_planes (host only): the [7, 4] float32 rows of a SurveyView in the world frame, voxel units."""
+        out = np.zeros((7, 4), dtype=np.float32)
+        self._call("view_frustum_planes", C.byref(view), C.c_float(voxel_size), _fptr(out))
+        return out
+
+    def survey_views(self, scenes, map_poses, views, params=None):
+        """dslam_survey_views: which of N local maps reach V camera views, at block granularity.  `scenes` / `map_poses` as
+        register_graph (up to MAX_SURVEY_MAPS); `views`: SurveyView objects.  Returns (live [N], reach [V, N], nearest
+        [V, N], farthest [V, N]), int32."""
+        n, ptrs, t_abi = self._map_list(scenes, map_poses)
+        views = list(views)
+        nv = len(views)
+        varr = (SurveyView * max(nv, 1))(*views)
+        live = np.zeros(max(n, 1), dtype=np.int32)
+        reach, nearest, farthest = (np.zeros((max(nv, 1), max(n, 1)), dtype=np.int32) for _ in range(3))
+        i32 = C.POINTER(C.c_int32)
+        self._call("survey_views", self._engine, ptrs, _fptr(t_abi), C.c_int(n), varr, C.c_int(nv),
+                   C.byref(params) if params is not None else None, live.ctypes.data_as(i32), reach.ctypes.data_as(i32),
+                   nearest.ctypes.data_as(i32), farthest.ctypes.data_as(i32))
+        return live, reach, nearest, farthest
+
+    def debug_survey_views_launches(self):
+        n = C.c_longlong(0)
+        self._call("debug_survey_views_launches", self._engine, C.byref(n))
+        return n.value
+
+    def select_view_maps(self, reach, nearest, params=None):
+        """dslam_select_view_maps: the maps to list for a view from a survey (host only).  Returns (the kept map indices,
+        ascending, int32, ViewSelectResult)."""
+        reach = np.ascontiguousarray(np.asarray(reach, dtype=np.int32))
+        nearest = np.ascontiguousarray(np.asarray(nearest, dtype=np.int32))
+        if reach.ndim != 2 or nearest.shape != reach.shape:
+            raise ValueError("reach and nearest must both be V x N")
+        nv, n = reach.shape
+        maps = np.zeros(MAX_RENDER_MAPS, dtype=np.int32)
+        res = ViewSelectResult()
+        i32 = C.POINTER(C.c_int32)
+        self._call("select_view_maps", reach.ctypes.data_as(i32), nearest.ctypes.data_as(i32), C.c_int(nv), C.c_int(n),
+                   C.byref(params) if params is not None else None, maps.ctypes.data_as(i32), C.byref(res))
+        return maps[:res.selected].copy(), res
 
     # -- map merge -------------------------------------------------------------------------------------
     def merge_maps(self, src, dst, X, params=None):

@@ -1323,12 +1323,14 @@ int check_rigid_transform(const float *T, const char *what) {
 // The map list (scenes[], T_map_from_world[], num_maps) of the call `call`; the caller has checked the pointers.  Where the
 // calls differ: min_maps; rigid -- no scene twice and every transform rigid (check_rigid_transform),
 // otherwise a scene may repeat and any transform invert_matrix inverts passes; max_local_blocks -- the most
-// num_local_blocks a scene may have (the composite render's visible-list capacity), 0: any.
+// num_local_blocks a scene may have (the composite render's visible-list capacity), 0: any; max_maps -- the longest list
+// (DSLAM_MAX_RENDER_MAPS for every call but the view survey).
 int check_map_list(dslam_engine *e, const char *call, const dslam_scene *const *scenes, const float *T, int num_maps, int min_maps,
-                   bool rigid, int max_local_blocks = 0) {
+                   bool rigid, int max_local_blocks = 0, int max_maps = DSLAM_MAX_RENDER_MAPS) {
   auto msg = [call](const std::string &what) { return std::string(call) + ": " + what; };
-  DSLAM_REQUIRE(num_maps >= min_maps && num_maps <= DSLAM_MAX_RENDER_MAPS,
-                msg("num_maps must be " + std::to_string(min_maps) + " .. DSLAM_MAX_RENDER_MAPS"));
+  DSLAM_REQUIRE(num_maps >= min_maps && num_maps <= max_maps,
+                msg("num_maps must be " + std::to_string(min_maps) + " .. " +
+                    (max_maps == DSLAM_MAX_RENDER_MAPS ? std::string("DSLAM_MAX_RENDER_MAPS") : std::to_string(max_maps))));
   for (int i = 0; i < num_maps; i++) {
     const dslam_scene *s = scenes[i];
     DSLAM_REQUIRE(s, msg("a scene in the list is NULL"));
@@ -1717,6 +1719,71 @@ int dslam_select_register_pairs(const int32_t *live_blocks, const int32_t *share
   DSLAM_REQUIRE(sp.max_pairs <= DSLAM_MAX_REGISTER_PAIRS, "max_pairs is above DSLAM_MAX_REGISTER_PAIRS");
   DSLAM_REQUIRE(sp.max_pairs >= num_maps - 1, "max_pairs is below num_maps - 1: a spanning set of pairs would not fit");
   select_register_pairs(live_blocks, shared_octants, num_maps, sp, pairs_out, component_out, result);
+  return DSLAM_OK;
+}
+
+// ---- view survey and map selection ----------------------------------------------------------------------------------
+namespace {
+
+// what dslam_view_frustum_planes rejects (and dslam_survey_views with it)
+int check_survey_view(const dslam_survey_view &v, float voxel_size) {
+  DSLAM_REQUIRE(std::isfinite(voxel_size) && voxel_size > 0.0f, "voxel_size must be positive and finite");
+  DSLAM_TRY(check_rigid_transform(v.M, "a view's pose"));
+  for (int k = 0; k < 4; k++) DSLAM_REQUIRE(std::isfinite(v.intrinsics[k]), "a view's intrinsics are not finite");
+  DSLAM_REQUIRE(v.intrinsics[0] > 0.0f && v.intrinsics[1] > 0.0f, "a view's focal lengths must be positive");
+  DSLAM_REQUIRE(v.width >= 1 && v.height >= 1, "a view's image size must be at least 1 x 1");
+  DSLAM_REQUIRE(std::isfinite(v.near_m) && std::isfinite(v.far_m) && v.near_m >= 0.0f && v.far_m >= 0.0f,
+                "a view's near and far distances must be finite and not negative");
+  DSLAM_REQUIRE(v.far_m == 0.0f || v.far_m > v.near_m, "a view's far plane must lie beyond its near plane (or be 0: none)");
+  return DSLAM_OK;
+}
+
+}  // namespace
+
+int dslam_view_frustum_planes(const dslam_survey_view *view, float voxel_size, float out[28]) {
+  DSLAM_REQUIRE(view && out, "null argument");
+  DSLAM_TRY(check_survey_view(*view, voxel_size));
+  view_frustum_planes(*view, voxel_size, out);
+  return DSLAM_OK;
+}
+
+int dslam_survey_views(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                       const dslam_survey_view *views, int num_views, const dslam_view_survey_params *params,
+                       int32_t *live_blocks_out, int32_t *reach_blocks_out, int32_t *nearest_out, int32_t *farthest_out) {
+  DSLAM_REQUIRE(e && scenes && T_map_from_world && views && live_blocks_out && reach_blocks_out, "null argument");
+  DSLAM_TRY(check_map_list(e, "dslam_survey_views", scenes, T_map_from_world, num_maps, 1, true, 0, DSLAM_MAX_SURVEY_MAPS));
+  DSLAM_REQUIRE(num_views >= 1 && num_views <= DSLAM_MAX_SURVEY_VIEWS, "num_views must be 1 .. DSLAM_MAX_SURVEY_VIEWS");
+  const float margin = params ? params->margin_voxels : 0.0f;
+  DSLAM_REQUIRE(std::isfinite(margin) && margin >= 0.0f, "the margin is negative (or not a number)");
+  float planes[DSLAM_MAX_SURVEY_VIEWS * 28];
+  for (int v = 0; v < num_views; v++) {
+    DSLAM_TRY(check_survey_view(views[v], scenes[0]->p.voxel_size));
+    view_frustum_planes(views[v], scenes[0]->p.voxel_size, planes + 28 * v);
+  }
+  const float rho = (float)(6.92820323027550917 + (double)(margin == 0.0f ? 2.0f : margin));
+  return launch_survey_views(e, scenes, T_map_from_world, num_maps, planes, num_views, rho, live_blocks_out, reach_blocks_out,
+                             nearest_out, farthest_out);
+}
+
+int dslam_debug_survey_views_launches(dslam_engine *e, long long *count_out) {
+  DSLAM_REQUIRE(e && count_out, "null argument");
+  *count_out = e->view_survey_launches;
+  return DSLAM_OK;
+}
+
+int dslam_select_view_maps(const int32_t *reach_blocks, const int32_t *nearest, int num_views, int num_maps,
+                           const dslam_view_select_params *params, int32_t *maps_out, dslam_view_select_result *result) {
+  DSLAM_REQUIRE(reach_blocks && nearest && maps_out && result, "null argument");
+  DSLAM_REQUIRE(num_views >= 1 && num_views <= DSLAM_MAX_SURVEY_VIEWS, "num_views must be 1 .. DSLAM_MAX_SURVEY_VIEWS");
+  DSLAM_REQUIRE(num_maps >= 1 && num_maps <= DSLAM_MAX_SURVEY_MAPS, "num_maps must be 1 .. DSLAM_MAX_SURVEY_MAPS");
+  dslam_view_select_params sp = {0, 0, -1, 0};
+  if (params) sp = *params;
+  DSLAM_REQUIRE(sp.min_blocks >= 0 && sp.max_maps >= 0 && sp.always_keep >= -1 && sp.pad >= 0, "a selection parameter is negative");
+  DSLAM_REQUIRE(sp.always_keep < num_maps, "always_keep is not one of the maps");
+  if (sp.min_blocks == 0) sp.min_blocks = 1;
+  if (sp.max_maps == 0) sp.max_maps = DSLAM_MAX_RENDER_MAPS;
+  DSLAM_REQUIRE(sp.max_maps <= DSLAM_MAX_RENDER_MAPS, "max_maps is above DSLAM_MAX_RENDER_MAPS");
+  select_view_maps(reach_blocks, nearest, num_views, num_maps, sp, maps_out, result);
   return DSLAM_OK;
 }
 

@@ -135,6 +135,13 @@ struct OverlapScratch {
   PinnedBuffer<void> tables_host;        // the tables of a call on their way to the device:
   DeviceBuffer<void> tables;             // workgroup -> source map, the map descriptors, the N x N pair transforms
 };
+// dslam_survey_views (view_survey.hip): its own scratch, allocated by the first call
+struct ViewSurveyScratch {
+  PinnedBuffer<void> tables_host;        // the tables of a call on their way to the device:
+  DeviceBuffer<void> tables;             // first tile of each map, the map descriptors, the views' planes
+  DeviceBuffer<int> results;             // live [N], reach [V][N], nearest and farthest [V][N] (encoded): zeroed per call
+  PinnedBuffer<int> results_host;
+};
 // The reduction channel of an SDF optimiser (dslam_register_maps, dslam_track_camera_sdf): one row of 33 partial sums per
 // workgroup in mapped page-locked memory (kernels: partials.device()), added by the host in index order
 struct SumChannel {
@@ -230,6 +237,8 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   dslam::LiveLists live_lists;        // dslam_register_graph, dslam_survey_overlaps
   dslam::RegisterGraphScratch reg_graph;   // dslam_register_graph (register_graph.hip)
   dslam::OverlapScratch overlap;      // dslam_survey_overlaps (overlap.hip)
+  dslam::ViewSurveyScratch view_survey;   // dslam_survey_views (view_survey.hip)
+  long long view_survey_launches = 0; // kernel launches dslam_survey_views has enqueued (test hook)
   std::vector<double> reg_graph_sums; // [pairs][33]: each pair's totals at the most recent joint evaluation it took part
                                       // in (dslam_debug_register_graph_sums; test hook)
   // dslam_debug_merge_phases (bench hook): wall clock of the last merge's phases, each closed by a wait for the stream --
@@ -551,6 +560,16 @@ int launch_survey_overlaps(dslam_engine *e, const dslam_scene *const *scenes, co
 void select_register_pairs(const int32_t *live_blocks, const int32_t *shared_octants, int num_maps,
                            const dslam_pair_select_params &params, int32_t *pairs_out, int32_t *component_out,
                            dslam_pair_select_result *result);
+// the law of dslam_view_frustum_planes; the view already checked
+void view_frustum_planes(const dslam_survey_view &view, float voxel_size, float out[28]);
+// everything already checked by dslam_survey_views (planes: [num_views][28], rho: the loosened radius); the outputs are
+// written only when everything has succeeded
+int launch_survey_views(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                        const float *planes, int num_views, float rho, int32_t *live_blocks_out, int32_t *reach_blocks_out,
+                        int32_t *nearest_out, int32_t *farthest_out);
+// arguments already checked (and params defaulted) by dslam_select_view_maps: the selection law of DESIGN.md section 20
+void select_view_maps(const int32_t *reach_blocks, const int32_t *nearest, int num_views, int num_maps,
+                      const dslam_view_select_params &params, int32_t *maps_out, dslam_view_select_result *result);
 // src / dst / X / params already checked (and defaulted) by dslam_merge_maps
 int launch_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float *X,
                       const dslam_merge_params *params, dslam_merge_result *result, bool reuse_live = false);

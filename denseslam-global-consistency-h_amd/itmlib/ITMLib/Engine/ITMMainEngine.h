@@ -388,33 +388,12 @@ class ITMMainEngine {
       throw std::runtime_error("GetImageAllLocalMaps: " + std::to_string(n) + " local maps, at most " +
                                std::to_string(DSLAM_MAX_RENDER_MAPS) + " can be drawn in one image");
     int t;
-    switch (type) {
-      case InfiniTAM_IMAGE_FREECAMERA_SHADED: t = DSLAM_IMAGE_SHADED; break;
-      case InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME: t = DSLAM_IMAGE_COLOUR_FROM_VOLUME; break;
-      case InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL: t = DSLAM_IMAGE_COLOUR_FROM_NORMAL; break;
-      case InfiniTAM_IMAGE_FREECAMERA_DEPTH: t = DSLAM_IMAGE_DEPTH; break;
-      default: return;
-    }
-    const Vector2i sz = (t == DSLAM_IMAGE_DEPTH) ? (outFloat ? outFloat->noDims : Vector2i(0, 0)) : (out ? out->noDims : Vector2i(0, 0));
-    if (sz.x <= 0) return;
-    const ITMLocalMap *first = mapManager->getLocalMap(0);
-    if (renderState_allmaps_ == nullptr || allmapsSize_.x != sz.x || allmapsSize_.y != sz.y) {
-      delete renderState_allmaps_;
-      renderState_allmaps_ = visualisationEngine->CreateRenderState(first->scene, sz);
-      allmapsSize_ = sz;
-    }
-    std::vector<const dslam_scene *> scenes(n);
-    std::vector<float> T((size_t)n * 16);
-    for (int i = 0; i < n; i++) {
-      const ITMLocalMap *m = mapManager->getLocalMap(i);
-      scenes[i] = m->scene->handle;
-      memcpy(&T[(size_t)i * 16], m->estimatedGlobalPose.GetM().m, 16 * sizeof(float));
-    }
-    dslam_check(dslam_get_image_multi(engine_, scenes.data(), T.data(), n, renderState_allmaps_->handle, pose->GetM().m,
-                                      intrinsics->projectionParamsSimple.all.v, t,
-                                      t == DSLAM_IMAGE_DEPTH ? nullptr : &out->GetData(MEMORYDEVICE_CPU)->x,
-                                      t == DSLAM_IMAGE_DEPTH ? outFloat->GetData(MEMORYDEVICE_CPU) : nullptr), "dslam_get_image_multi");
-    if (deferred_) dslam_check(dslam_engine_synchronize(engine_), "dslam_engine_synchronize");
+    Vector2i sz;
+    if (!FreeCameraImage(type, out, outFloat, t, sz)) return;
+    std::vector<const dslam_scene *> scenes;
+    std::vector<float> T;
+    ListLocalMaps(scenes, T);
+    DrawLocalMaps(scenes, T, t, sz, out, outFloat, pose, intrinsics);
   }
 
   /// SaveCurrSceneToMesh(objFileName, scene) (DenseSlam.cpp:641): meshingEngine->MeshScene(mesh, scene), then
@@ -591,35 +570,65 @@ class ITMMainEngine {
   /// Prepare + Track, after AlignLocalMaps has made the neighbours' poses good.
   bool TrackAllLocalMaps(ITMLocalMap *current, dslam_track_sdf_result *out = nullptr) {
     if (view == nullptr) throw std::runtime_error("TrackAllLocalMaps: no view yet (call UpdateView first)");
-    const int n = mapManager->numLocalMaps();
-    std::vector<const dslam_scene *> scenes(n);
-    std::vector<float> T((size_t)n * 16);
-    for (int i = 0; i < n; i++) {
-      const ITMLocalMap *m = mapManager->getLocalMap(i);
-      scenes[i] = m->scene->handle;
-      memcpy(&T[(size_t)i * 16], m->estimatedGlobalPose.GetM().m, 16 * sizeof(float));
-    }
-    double Md[16], Tc[16], Wd[16], inv[16];
-    for (int i = 0; i < 16; i++) {
-      Md[i] = (double)current->trackingState->pose_d->GetM().m[i];
-      Tc[i] = (double)current->estimatedGlobalPose.GetM().m[i];
-    }
-    RigidProduct(Md, Tc, Wd);
+    std::vector<const dslam_scene *> scenes;
+    std::vector<float> T;
+    ListLocalMaps(scenes, T);
     float Wf[16];
-    for (int i = 0; i < 16; i++) Wf[i] = (float)Wd[i];
-    const Vector4f k = view->calib->intrinsics_d.projectionParamsSimple.all;
-    dslam_track_sdf_result res;
-    dslam_check(dslam_track_camera_sdf(engine_, view->handle, scenes.data(), T.data(), n, Wf, k.v, nullptr, &res),
-                "dslam_track_camera_sdf");
-    if (out) *out = res;
-    if (res.levels_stepped == 0) return false;
-    for (int i = 0; i < 16; i++) Wd[i] = (double)Wf[i];
-    RigidInverse(Tc, inv);
-    RigidProduct(Wd, inv, Md);
-    Matrix4f M;
-    for (int i = 0; i < 16; i++) M.m[i] = (float)Md[i];
-    current->trackingState->pose_d->SetM(M);
-    return true;
+    WorldPoseOf(current, Wf);
+    return TrackListedMaps(current, scenes, T, Wf, out);
+  }
+  /// (extension) Which local maps a camera view reaches (dslam_survey_views, law in DESIGN.md section 20): under the
+  /// maps' estimatedGlobalPoses, `reach[i]` becomes the resident blocks of map i whose loosened sphere meets the frustum of
+  /// the camera `M` (world -> camera, metres, column-major) with the image `size`, between nearM and farM metres (farM 0:
+  /// no far plane), and `nearest[i]` the smallest depth, in voxels, among them (INT32_MAX for none).  Up to
+  /// DSLAM_MAX_SURVEY_MAPS local maps; only the hash tables are read.
+  void SurveyLocalMapsInView(const float M[16], const float intrinsics[4], Vector2i size, float nearM, float farM,
+                             std::vector<int32_t> &reach, std::vector<int32_t> &nearest) {
+    std::vector<const dslam_scene *> scenes;
+    std::vector<float> T;
+    ListLocalMaps(scenes, T);
+    SurveyListedMaps(M, intrinsics, size, nearM, farM, scenes, T, reach, nearest);
+  }
+  /// (extension) TrackAllLocalMaps against the local maps the camera can reach: the maps are surveyed at the start pose
+  /// (SurveyLocalMapsInView with the depth image's size, nearM and farM), dslam_select_view_maps keeps at most
+  /// DSLAM_MAX_RENDER_MAPS of them -- `current` always, so the map being fused into stays listed while it is empty -- and
+  /// dslam_track_camera_sdf runs on that sub-list, in list order.  With nearM < D <= farM for every depth pixel a map the
+  /// survey drops holds no block at any pixel, and the result is TrackAllLocalMaps' bit for bit;
+  /// the defaults, no near and no far plane, cover every depth.  Unlike TrackAllLocalMaps it takes more than
+  /// DSLAM_MAX_RENDER_MAPS local maps.  kept (optional): the indices of the listed maps, ascending.
+  bool TrackVisibleLocalMaps(ITMLocalMap *current, float nearM = 0.0f, float farM = 0.0f, dslam_track_sdf_result *out = nullptr,
+                             std::vector<int32_t> *kept = nullptr) {
+    if (view == nullptr) throw std::runtime_error("TrackVisibleLocalMaps: no view yet (call UpdateView first)");
+    std::vector<const dslam_scene *> scenes;
+    std::vector<float> T;
+    const int cur = ListLocalMaps(scenes, T, current);
+    if (cur < 0) throw std::runtime_error("TrackVisibleLocalMaps: `current` is not one of the local maps");
+    float Wf[16];
+    WorldPoseOf(current, Wf);
+    std::vector<int32_t> keep;
+    SelectLocalMapsInView(Wf, view->calib->intrinsics_d.projectionParamsSimple.all.v, view->depth->noDims, nearM, farM, cur, scenes, T, keep);
+    if (kept) *kept = keep;
+    return TrackListedMaps(current, scenes, T, Wf, out);
+  }
+  /// (extension) GetImageAllLocalMaps of the local maps the free camera can reach: the maps are surveyed at `pose`
+  /// (the image's size, nearM, farM), at most DSLAM_MAX_RENDER_MAPS are kept -- the nearest first -- and
+  /// dslam_get_image_multi draws that sub-list.  Every ray sample in a block of a dropped map lies outside the view, but
+  /// the renderer's range image is bounded by projected block corners and the renderer draws whatever its rays meet, so
+  /// the image is GetImageAllLocalMaps' only where no dropped block's bounding box touches the image and nothing lies
+  /// beyond farM.  When no map reaches, map 0 is drawn.  kept (optional): the listed maps.
+  void GetImageVisibleLocalMaps(ITMUChar4Image *out, ITMFloatImage *outFloat, GetImageType type, ITMPose *pose,
+                                ITMIntrinsics *intrinsics, float nearM = 0.0f, float farM = 0.0f, std::vector<int32_t> *kept = nullptr) {
+    if (mapManager->numLocalMaps() == 0 || pose == nullptr || intrinsics == nullptr) return;
+    int t;
+    Vector2i sz;
+    if (!FreeCameraImage(type, out, outFloat, t, sz)) return;
+    std::vector<const dslam_scene *> scenes;
+    std::vector<float> T;
+    ListLocalMaps(scenes, T);
+    std::vector<int32_t> keep;
+    SelectLocalMapsInView(pose->GetM().m, intrinsics->projectionParamsSimple.all.v, sz, nearM, farM, -1, scenes, T, keep);
+    if (kept) *kept = keep;
+    DrawLocalMaps(scenes, T, t, sz, out, outFloat, pose, intrinsics);
   }
   /// inverse of a rigid transform (column-major): [R^T | -(R^T t)], each sum evaluated left to right
   static void RigidInverse(const double M[16], double out[16]) {
@@ -700,6 +709,115 @@ class ITMMainEngine {
   ITMActiveMapManager *mActiveDataManger;
 
  private:
+  /// every local map's scene handle and estimatedGlobalPose.GetM(), in mapManager's order; returns the index of `which`
+  /// (-1: not among them)
+  int ListLocalMaps(std::vector<const dslam_scene *> &scenes, std::vector<float> &T, const ITMLocalMap *which = nullptr) const {
+    const int n = mapManager->numLocalMaps();
+    int at = -1;
+    scenes.resize((size_t)n);
+    T.resize((size_t)n * 16);
+    for (int i = 0; i < n; i++) {
+      const ITMLocalMap *m = mapManager->getLocalMap(i);
+      if (m == which) at = i;
+      scenes[(size_t)i] = m->scene->handle;
+      memcpy(&T[(size_t)i * 16], m->estimatedGlobalPose.GetM().m, 16 * sizeof(float));
+    }
+    return at;
+  }
+  /// the dslam image type and the size of a FREECAMERA_* request; false: nothing to draw (another type, no image)
+  static bool FreeCameraImage(GetImageType type, const ITMUChar4Image *out, const ITMFloatImage *outFloat, int &t, Vector2i &sz) {
+    switch (type) {
+      case InfiniTAM_IMAGE_FREECAMERA_SHADED: t = DSLAM_IMAGE_SHADED; break;
+      case InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_VOLUME: t = DSLAM_IMAGE_COLOUR_FROM_VOLUME; break;
+      case InfiniTAM_IMAGE_FREECAMERA_COLOUR_FROM_NORMAL: t = DSLAM_IMAGE_COLOUR_FROM_NORMAL; break;
+      case InfiniTAM_IMAGE_FREECAMERA_DEPTH: t = DSLAM_IMAGE_DEPTH; break;
+      default: return false;
+    }
+    sz = (t == DSLAM_IMAGE_DEPTH) ? (outFloat ? outFloat->noDims : Vector2i(0, 0)) : (out ? out->noDims : Vector2i(0, 0));
+    return sz.x > 0;
+  }
+  /// dslam_get_image_multi of the listed maps into the caller's image, through the all-maps render state
+  void DrawLocalMaps(const std::vector<const dslam_scene *> &scenes, const std::vector<float> &T, int t, Vector2i sz,
+                     ITMUChar4Image *out, ITMFloatImage *outFloat, ITMPose *pose, ITMIntrinsics *intrinsics) {
+    if (renderState_allmaps_ == nullptr || allmapsSize_.x != sz.x || allmapsSize_.y != sz.y) {
+      delete renderState_allmaps_;
+      renderState_allmaps_ = visualisationEngine->CreateRenderState(mapManager->getLocalMap(0)->scene, sz);
+      allmapsSize_ = sz;
+    }
+    dslam_check(dslam_get_image_multi(engine_, scenes.data(), T.data(), (int)scenes.size(), renderState_allmaps_->handle,
+                                      pose->GetM().m, intrinsics->projectionParamsSimple.all.v, t,
+                                      t == DSLAM_IMAGE_DEPTH ? nullptr : &out->GetData(MEMORYDEVICE_CPU)->x,
+                                      t == DSLAM_IMAGE_DEPTH ? outFloat->GetData(MEMORYDEVICE_CPU) : nullptr), "dslam_get_image_multi");
+    if (deferred_) dslam_check(dslam_engine_synchronize(engine_), "dslam_engine_synchronize");
+  }
+  /// world -> camera = pose_d->GetM() T_current of `current`, composed in double (RigidProduct) and rounded to float32
+  static void WorldPoseOf(const ITMLocalMap *current, float Wf[16]) {
+    double Md[16], Tc[16], Wd[16];
+    for (int i = 0; i < 16; i++) {
+      Md[i] = (double)current->trackingState->pose_d->GetM().m[i];
+      Tc[i] = (double)current->estimatedGlobalPose.GetM().m[i];
+    }
+    RigidProduct(Md, Tc, Wd);
+    for (int i = 0; i < 16; i++) Wf[i] = (float)Wd[i];
+  }
+  /// dslam_track_camera_sdf of the current view against the listed maps from the start Wf (world -> camera); when a step
+  /// was accepted, pose_d = (world -> camera) T_current^-1 is written back and the call returns true
+  bool TrackListedMaps(ITMLocalMap *current, const std::vector<const dslam_scene *> &scenes, const std::vector<float> &T,
+                       float Wf[16], dslam_track_sdf_result *out) {
+    const Vector4f k = view->calib->intrinsics_d.projectionParamsSimple.all;
+    dslam_track_sdf_result res;
+    dslam_check(dslam_track_camera_sdf(engine_, view->handle, scenes.data(), T.data(), (int)scenes.size(), Wf, k.v, nullptr, &res),
+                "dslam_track_camera_sdf");
+    if (out) *out = res;
+    if (res.levels_stepped == 0) return false;
+    double Md[16], Tc[16], Wd[16], inv[16];
+    for (int i = 0; i < 16; i++) {
+      Wd[i] = (double)Wf[i];
+      Tc[i] = (double)current->estimatedGlobalPose.GetM().m[i];
+    }
+    RigidInverse(Tc, inv);
+    RigidProduct(Wd, inv, Md);
+    Matrix4f M;
+    for (int i = 0; i < 16; i++) M.m[i] = (float)Md[i];
+    current->trackingState->pose_d->SetM(M);
+    return true;
+  }
+  /// dslam_survey_views of the listed maps from one camera: reach and nearest per map
+  void SurveyListedMaps(const float M[16], const float intrinsics[4], Vector2i size, float nearM, float farM,
+                        const std::vector<const dslam_scene *> &scenes, const std::vector<float> &T, std::vector<int32_t> &reach,
+                        std::vector<int32_t> &nearest) {
+    const int n = (int)scenes.size();
+    dslam_survey_view v;
+    memcpy(v.M, M, sizeof v.M);
+    memcpy(v.intrinsics, intrinsics, sizeof v.intrinsics);
+    v.width = size.x; v.height = size.y;
+    v.near_m = nearM; v.far_m = farM;
+    std::vector<int32_t> live((size_t)n), r((size_t)n), z((size_t)n);
+    dslam_check(dslam_survey_views(engine_, scenes.data(), T.data(), n, &v, 1, nullptr, live.data(), r.data(), z.data(), nullptr),
+                "dslam_survey_views");
+    reach.swap(r);
+    nearest.swap(z);
+  }
+  /// survey (scenes, T) from the camera M and cut both down to the maps dslam_select_view_maps keeps (`keep`, ascending;
+  /// alwaysKeep: an index or -1); when none is kept, map 0 stays
+  void SelectLocalMapsInView(const float M[16], const float intrinsics[4], Vector2i size, float nearM, float farM, int alwaysKeep,
+                             std::vector<const dslam_scene *> &scenes, std::vector<float> &T, std::vector<int32_t> &keep) {
+    std::vector<int32_t> reach, nearest;
+    SurveyListedMaps(M, intrinsics, size, nearM, farM, scenes, T, reach, nearest);
+    dslam_view_select_params sp = {0, 0, alwaysKeep, 0};
+    dslam_view_select_result res;
+    keep.assign(DSLAM_MAX_RENDER_MAPS, 0);
+    dslam_check(dslam_select_view_maps(reach.data(), nearest.data(), 1, (int)scenes.size(), &sp, keep.data(), &res), "dslam_select_view_maps");
+    keep.resize((size_t)res.selected);
+    if (keep.empty()) keep.push_back(0);
+    for (size_t k = 0; k < keep.size(); k++) {   // (ascending, so an entry is never overwritten before it is read)
+      scenes[k] = scenes[(size_t)keep[k]];
+      memmove(&T[k * 16], &T[(size_t)keep[k] * 16], 16 * sizeof(float));
+    }
+    scenes.resize(keep.size());
+    T.resize(keep.size() * 16);
+  }
+
   dslam_engine *engine_;
   bool deferred_;   ///< the engine runs asynchronously (default; DSLAM_MIRROR_SYNC=1 turns it off)
   const ITMScene<ITMVoxel, ITMVoxelIndex> *freeviewScene_;

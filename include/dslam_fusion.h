@@ -693,6 +693,107 @@ int dslam_select_register_pairs(const int32_t *live_blocks /* [N] */, const int3
                                 int32_t *pairs_out /* [max_pairs][2] */, int32_t *component_out /* [N] */,
                                 dslam_pair_select_result *result);
 
+/* ---- which local maps a camera view reaches (no counterpart in the reference) ---------------- */
+#define DSLAM_MAX_SURVEY_MAPS 256
+#define DSLAM_MAX_SURVEY_VIEWS 16
+typedef struct {
+  float M[16];                     /* world -> camera, metres, column-major (as pose_M of dslam_track_camera_sdf) */
+  float intrinsics[4];             /* fx, fy, cx, cy */
+  int32_t width, height;
+  float near_m, far_m;             /* far_m == 0: no far plane */
+} dslam_survey_view;
+/* The frustum of a view as seven rows of four float32 in the world frame, in voxel units: rows 0..5 the inward unit-normal
+ * planes left, right, top, bottom, near, far (a point p is inside when n . p + d >= 0), row 6 the camera's z row.  A pure
+ * host function: no engine, no device.  Everything below is double; each of the 28 numbers is rounded to float32 once, at
+ * the end.  R[r][c] = M[4 c + r], t[r] = M[12 + r], vs = voxel_size, each converted to double first.
+ *   t~[r] = t[r] / vs;
+ *   the image bounds are one pixel wider than the image, x from -1 to width, y from -1 to height, so the integer pixel
+ *   coordinates of the tracker and the renderer lie strictly inside;
+ *   camera-frame normals before scaling: left (fx, 0, cx + 1), right (-fx, 0, width - cx), top (0, fy, cy + 1),
+ *   bottom (0, -fy, height - cy), where cx + 1, width - cx, cy + 1 and height - cy are formed in double; for each, with
+ *   (a, b) its two non-zero entries in that order, len = sqrt(a a + b b) and the unit normal is (a / len, 0, b / len)
+ *   (respectively (0, a / len, b / len)); their d_c is 0.  near: n_c = (0, 0, 1), d_c = -(near_m / vs).  far:
+ *   n_c = (0, 0, -1), d_c = far_m / vs;
+ *   world frame, for each of the six: n_w[j] = (R[0][j] n_c[0] + R[1][j] n_c[1]) + R[2][j] n_c[2] for j = 0, 1, 2 (all
+ *   three products are formed, the zero ones included) and d_w = ((n_c[0] t~[0] + n_c[1] t~[1]) + n_c[2] t~[2]) + d_c;
+ *   with far_m == 0 row 5 is (0, 0, 0, +INFINITY): it always passes;
+ *   row 6 = (R[2][0], R[2][1], R[2][2], t~[2]).
+ * DSLAM_ERR_INVALID with `out` untouched: a NULL argument, a non-finite entry of the view or voxel_size, a rotation block of
+ * M that is not orthonormal to 1e-4, fx or fy <= 0, width or height < 1, near_m < 0, far_m < 0, 0 < far_m <= near_m,
+ * voxel_size <= 0. */
+int dslam_view_frustum_planes(const dslam_survey_view *view, float voxel_size, float out[28]);
+
+/* Which of N local maps reach V camera views, at block granularity, from the hash tables alone (never a voxel).
+ * T_i: world -> map i, metres, column-major, as the other multi-map calls take it.
+ *   inverse pose    T~_i is T_i with its translation in voxel units; Y~_i = (R^T, -(R^T t)) is its rigid inverse, formed
+ *                   in double (each translation entry -((r0 t0 + r1 t1) + r2 t2) with (r0, r1, r2) a column of R), its 12
+ *                   entries rounded to float32 -- as dslam_merge_maps forms its Y~;
+ *   resident block  a hash entry of map i with ptr >= 0; its block position B is the entry's three shorts, its centre
+ *                   c = 8 B + 4, exact in float32;
+ *   world point     p = Y~_i c, rows evaluated as ((a x + b y) + c z) + d in float32 without contraction; a T_i that is
+ *                   exactly the identity reads at c itself;
+ *   planes          the 28 floats of dslam_view_frustum_planes(view v, the maps' voxel_size); for rows k = 0..5
+ *                   s_k = ((n_x p_x + n_y p_y) + n_z p_z) + d in float32;
+ *   reach           the block reaches view v when s_k >= -rho for all six rows, rho = (float)(6.92820323027550917 +
+ *                   (double)margin_voxels): 4 sqrt(3), the radius of the sphere around the block's cube
+ *                   [8 B, 8 B + 8]^3, plus the margin.  A NaN s_k does not reach;
+ *   depth           z = ((r20 p_x + r21 p_y) + r22 p_z) + t~_z from row 6, zi = (int)floorf(z) with floorf(z) first
+ *                   clamped to [-2147483648, 2147483520] (both exact in float32), so the cast is always defined;
+ *   live_blocks[i]      the resident entries of map i;
+ *   reach_blocks[v][i]  its reaching blocks;
+ *   nearest[v][i], farthest[v][i]  the minimum and the maximum of zi over the reaching blocks; INT32_MAX and INT32_MIN
+ *                   when no block reaches.
+ * All outputs are integers: exact, the same bytes on every run, and independent of how the work is split.
+ * The six half-spaces, loosened by the block's radius, are conservative: a point inside the frustum lies in no block the
+ * test rejects (DESIGN.md section 20 gives the float32 rounding bound the margin has to cover).  So a map with
+ * reach_blocks[v][i] == 0 holds no resident block at any depth pixel of view v with near_m < D <= far_m, fails the
+ * base-corner probe of dslam_track_camera_sdf at every such pixel, and can be dropped from that call's list without
+ * changing a bit of its sums.  Nothing is promised about the images of dslam_get_image_multi: its range image lists
+ * blocks by the bounding box of their projected corners, which can touch the image for a block that misses the frustum.
+ * Every map is only read (a block that is swapped out is not resident); no render state is involved; no map's version,
+ * GetImage memo or front-end record changes.  One kernel launch whatever N and V.  Waits for the stream on synchronous
+ * and asynchronous engines.
+ * DSLAM_ERR_INVALID with all outputs untouched: a NULL argument other than params, nearest_out or farthest_out, num_maps
+ * outside 1 .. DSLAM_MAX_SURVEY_MAPS, num_views outside 1 .. DSLAM_MAX_SURVEY_VIEWS, a scene listed twice, a scene of
+ * another engine, voxel_size or mu that differ between maps, a non-finite T_i or one whose rotation block is not
+ * orthonormal to 1e-4, a view dslam_view_frustum_planes rejects, a negative or non-finite margin. */
+typedef struct {
+  float margin_voxels;             /* 0 -> 2.0 */
+  int32_t pad[3];
+} dslam_view_survey_params;
+int dslam_survey_views(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                       const dslam_survey_view *views, int num_views, const dslam_view_survey_params *params /* NULL: defaults */,
+                       int32_t *live_blocks_out /* [N] */, int32_t *reach_blocks_out /* [V][N] */,
+                       int32_t *nearest_out /* [V][N]; may be NULL */, int32_t *farthest_out /* [V][N]; may be NULL */);
+/* Test hook: the kernel launches all dslam_survey_views calls of this engine have enqueued so far (one per call). */
+int dslam_debug_survey_views_launches(dslam_engine *e, long long *count_out);
+
+/* From a view survey to a list of at most max_maps maps the multi-map calls accept.  A pure host function.
+ *   candidates  the maps with max_v reach_blocks[v][i] >= min_blocks; always_keep, if >= 0, is a candidate regardless
+ *               (the map being fused into stays listed even while it is empty); reaching = their number;
+ *   the cap     with more than max_maps candidates: always_keep is taken first, then the candidates in the order of the
+ *               smaller min_v nearest[v][i], ties to the larger sum_v reach_blocks[v][i] (64-bit), then to the smaller
+ *               index, until max_maps are taken;
+ *   maps_out    the taken indices ascending (entries past `selected` are not written), so a sub-list built from them
+ *               keeps the list order the blend laws depend on; selected = their number.
+ * DSLAM_ERR_INVALID with the outputs untouched: a NULL argument other than params, num_views outside
+ * 1 .. DSLAM_MAX_SURVEY_VIEWS, num_maps outside 1 .. DSLAM_MAX_SURVEY_MAPS, a negative parameter other than
+ * always_keep == -1 (pad counts as a parameter: it must not be negative), always_keep >= num_maps, max_maps above
+ * DSLAM_MAX_RENDER_MAPS. */
+typedef struct {
+  int32_t min_blocks;              /* 0 -> 1 */
+  int32_t max_maps;                /* 0 -> DSLAM_MAX_RENDER_MAPS */
+  int32_t always_keep;             /* index, or -1 */
+  int32_t pad;
+} dslam_view_select_params;
+typedef struct {
+  int32_t reaching;
+  int32_t selected;
+} dslam_view_select_result;
+int dslam_select_view_maps(const int32_t *reach_blocks /* [V][N] */, const int32_t *nearest /* [V][N] */, int num_views,
+                           int num_maps, const dslam_view_select_params *params /* NULL: defaults */,
+                           int32_t *maps_out /* [max_maps] */, dslam_view_select_result *result);
+
 /* Fuse one local map into another on the device (no counterpart in the reference; the law is this project's own,
  * DESIGN.md section 14).  X is what dslam_register_maps takes and returns: source frame -> destination frame, metres,
  * column-major.  X~ is X with its translation in voxel units, Y~ its inverse (R^T, -R^T t); both are formed on the host
