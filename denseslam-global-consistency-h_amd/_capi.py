@@ -230,6 +230,19 @@ class UnmergeResult(C.Structure):
 assert C.sizeof(UnmergeParams) == 8 and C.sizeof(UnmergeResult) == 56  # the header's layouts
 
 
+class PackInfo(C.Structure):
+    """dslam_pack_info: the 64-byte header of a packed map, as it lies in the buffer."""
+    _fields_ = [("magic", C.c_char * 4), ("version", C.c_uint32), ("num_buckets", C.c_int32), ("num_excess", C.c_int32),
+                ("blocks", C.c_int32), ("free_excess", C.c_int32), ("voxel_size_bits", C.c_uint32), ("mu_bits", C.c_uint32),
+                ("blocks_offset", C.c_int64), ("total_bytes", C.c_int64), ("bbox_min", C.c_int16 * 3),
+                ("bbox_max", C.c_int16 * 3), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["bbox_min"], d["bbox_max"] = list(self.bbox_min), list(self.bbox_max)
+        return d
+
+
 class WeightParams(C.Structure):
     _fields_ = [("depth_weighting", C.c_int32), ("max_new_w", C.c_int32), ("max_distance", C.c_float)]
 
@@ -947,6 +960,22 @@ class CApi:
         out = np.zeros(5, dtype=np.float64)
         self._call("debug_merge_phases", self._engine, C.c_int(int(enable)), out.ctypes.data_as(C.POINTER(C.c_double)))
         return out
+
+    # -- packed maps: the host half ------------------------------------------------------------------------
+    def pack_layout(self, blocks, free_excess):
+        """dslam_pack_layout (host only): (blocks_offset, total_bytes) of a packed map of n blocks and f free excess slots."""
+        off, total = C.c_int64(), C.c_int64()
+        self._call("pack_layout", C.c_int32(blocks), C.c_int32(free_excess), C.byref(off), C.byref(total))
+        return off.value, total.value
+
+    def pack_header_read(self, first_64_bytes):
+        """dslam_pack_header_read (host only): the PackInfo in the first 64 bytes of a packed map; raises if it is none."""
+        raw = bytes(first_64_bytes)
+        if len(raw) < C.sizeof(PackInfo):
+            raise ValueError("a packed map's header is 64 bytes")
+        info = PackInfo()
+        self._call("pack_header_read", C.c_char_p(raw), C.byref(info))
+        return info
 
     # -- page-locked host images -----------------------------------------------------------------------
     def host_alloc(self, shape, dtype):

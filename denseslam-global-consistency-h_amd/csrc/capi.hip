@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "dslam_internal.h"
+#include "pack_host.h"
 
 #pragma clang fp contract(off)
 
@@ -1857,6 +1858,23 @@ int dslam_remerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst
   const int rc = launch_merge_maps(e, src, dst, X_new, &mp, merged, true);
   if (rc == DSLAM_OK) collect_unmerge_result(e, unmerged);
   return rc;
+}
+
+// ---- packed maps: the host half (pack_host.h) ------------------------------------------------------------------
+int dslam_pack_layout(int32_t blocks, int32_t free_excess, int64_t *blocks_offset_out, int64_t *total_bytes_out) {
+  DSLAM_REQUIRE(blocks_offset_out && total_bytes_out, "null argument");
+  DSLAM_REQUIRE(blocks >= 0 && free_excess >= 0, "a packed map has no negative count");
+  pack_layout(blocks, free_excess, blocks_offset_out, total_bytes_out);
+  return DSLAM_OK;
+}
+
+int dslam_pack_header_read(const void *first_64_bytes, dslam_pack_info *out) {
+  DSLAM_REQUIRE(first_64_bytes && out, "null argument");
+  dslam_pack_info h;
+  memcpy(&h, first_64_bytes, sizeof h);
+  DSLAM_REQUIRE(pack_header_valid(h), "not the header of a packed map (magic, version, counts or layout)");
+  *out = h;
+  return DSLAM_OK;
 }
 
 int dslam_debug_merge_phases(dslam_engine *e, int enable, double out_ms[5]) {

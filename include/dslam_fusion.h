@@ -895,6 +895,43 @@ int dslam_remerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst
                        const float X_new[16], const dslam_merge_params *params /* NULL: defaults */,
                        dslam_unmerge_result *unmerged, dslam_merge_result *merged);
 
+/* ---- packed maps: the layout and its host half ---------------------------------------------------- */
+/* A compact, self-describing, deterministic image of a map (DESIGN.md section 21 states the law in full: which entries are
+ * packed, what an unpack into a pool of any size leaves, what is checked before its first write).  The library holds the
+ * host half only -- the two functions below, callable without a device, as dslam_view_frustum_planes is; the device
+ * calls that write and read such an image are not part of it yet (section 21 says why).
+ * Layout, little-endian; every byte up to total_bytes is defined.  n: the resident entries (ptr >= 0), in ascending hash
+ * index (rank order); f = last_free_excess_id + 1:
+ *   offset 0                64-byte header: dslam_pack_info as it lies in memory
+ *   offset 64               n records of 16 bytes, rank order: a dslam_hash_entry with pos and offset as stored,
+ *                           _pad = 0, and ptr = THE ENTRY'S HASH INDEX
+ *   offset 64 + 16 n        f values of int32: excess_list[0 .. f-1] verbatim (the order of the free stack decides
+ *                           future allocations, so it is carried)
+ *   up to blocks_offset     zeros; blocks_offset = 64 + 16 n + 4 f rounded up to a multiple of 4096
+ *   offset blocks_offset    n voxel blocks of 4096 bytes, rank order, as stored
+ *   total_bytes = blocks_offset + 4096 n.
+ * bbox_min / bbox_max: componentwise minimum and maximum of pos over the packed entries (n = 0: 32767 and -32768), so a
+ * host can test a parked map against dslam_view_frustum_planes without a table on the device. */
+typedef struct {
+  char magic[4];                   /* "DSPK" */
+  uint32_t version;                /* 1 */
+  int32_t num_buckets, num_excess; /* the geometry of the table the indices refer to */
+  int32_t blocks;                  /* n */
+  int32_t free_excess;             /* f */
+  uint32_t voxel_size_bits, mu_bits;  /* the bit patterns of the scene's float32 voxel_size and mu */
+  int64_t blocks_offset, total_bytes;
+  int16_t bbox_min[3], bbox_max[3];
+  uint32_t reserved;               /* 0 */
+} dslam_pack_info;
+/* Host only: the two layout functions of (n, f) above, in 64 bits.  DSLAM_ERR_INVALID, with both outputs untouched, for a
+ * negative n or f or a NULL output. */
+int dslam_pack_layout(int32_t blocks, int32_t free_excess, int64_t *blocks_offset_out, int64_t *total_bytes_out);
+/* Host only: reads the header of a packed map from its first 64 bytes (host memory, any alignment).  Validates magic,
+ * version, the reserved word, that num_buckets, num_excess, n and f are not negative, f <= num_excess, and that
+ * blocks_offset and total_bytes are the functions of n and f above; DSLAM_ERR_INVALID leaves *out untouched.  voxel_size,
+ * mu and the bounding box pass through unjudged: comparing them with a scene is the caller's. */
+int dslam_pack_header_read(const void *first_64_bytes, dslam_pack_info *out);
+
 /* ---- depth tracker (ICP) ---------------------------------------------------------------------- */
 /* trackingController->Track(trackingState, view) (InfiniTamDriver.h:151-163, reached through
  * DenseSlam.cpp:200-206 when the reference runs without ORB-SLAM2 odometry): upstream InfiniTAM v2's
