@@ -20,7 +20,8 @@ swap-in / swap-out calls and SaveToGlobalMemory (`save_to_global`).  Every merge
 `events`, in order, so that a caller who carries voxel values (refmap_checks.Rig, with ref64.combine_stored) can move them
 the same way.  Both list rings are driven: q = 1 is the defusion ring of ProcessFrame(isDefusion), SlideWindowDefusionPart
 and DecayDefusionPart.  Out of the model: voxel values (sdf, colour), the transfer buffers, the batched re-integration,
-sharding, FindVisibleBlocks.
+sharding.  FindVisibleBlocks and CreateExpectedDepths (the visible list of a free view, the projected boxes, the render-tile
+budget and the range image) are stated in ref_range.py, which takes `block_visibility` from here.
 """
 import numpy as np
 
