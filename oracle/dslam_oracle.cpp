@@ -566,7 +566,11 @@ extern "C" int oracle_scene_set_shard_range(oracle_scene *s, int first, int coun
 // ---- the exchange step of the sharded re-integration (same contract as dslam_scene_track_dirty / dslam_shard_dirty_*;
 // the "device" buffers are host memory here) --------------------------------------------------------------------------
 extern "C" int oracle_scene_track_dirty(oracle_engine *, oracle_scene *s, int enable) {
-  if (enable) s->dirty.assign((size_t)s->p.num_local_blocks, 0);
+  if (enable) {  // new marks: the plan of the old ones is forgotten, as the engine forgets it (pack and unpack want a new plan)
+    s->dirty.assign((size_t)s->p.num_local_blocks, 0);
+    s->dirty_list.clear();
+    s->dirty_counts.clear();
+  }
   s->dirty_tracking = enable != 0;
   return 0;
 }
