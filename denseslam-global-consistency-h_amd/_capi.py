@@ -977,6 +977,35 @@ class CApi:
         self._call("pack_header_read", C.c_char_p(raw), C.byref(info))
         return info
 
+    # -- packed maps: the device half ----------------------------------------------------------------------
+    def pack_scene(self, scene, buf_ptr=None, capacity=0):
+        """dslam_pack_scene: the map's packed image into `capacity` bytes at `buf_ptr` (an address in device or
+        page-locked host memory, 16-byte aligned); buf_ptr None is the size query.  Returns the header as a PackInfo."""
+        info = PackInfo()
+        self._call("pack_scene", self._engine, scene.ptr, C.c_void_p(buf_ptr or 0), C.c_int64(int(capacity)), C.byref(info))
+        return info
+
+    def unpack_scene(self, scene, buf_ptr, nbytes):
+        """dslam_unpack_scene: the packed image of `nbytes` bytes at `buf_ptr` into `scene`.  Returns its header."""
+        info = PackInfo()
+        self._call("unpack_scene", self._engine, scene.ptr, C.c_void_p(buf_ptr), C.c_int64(int(nbytes)), C.byref(info))
+        return info
+
+    def device_alloc(self, nbytes):
+        """dslam_device_alloc: the address of `nbytes` of device memory on the engine's device; release with device_free."""
+        p = C.c_void_p()
+        self._call("device_alloc", self._engine, C.c_size_t(int(nbytes)), C.byref(p))
+        return p.value
+
+    def device_free(self, ptr):
+        self._call("device_free", self._engine, C.c_void_p(ptr))
+
+    def debug_live_engines(self):
+        """dslam_debug_live_engines: engine objects of this process not yet freed (needs no engine)."""
+        out = C.c_int(-1)
+        self._call("debug_live_engines", C.byref(out))
+        return out.value
+
     # -- page-locked host images -----------------------------------------------------------------------
     def host_alloc(self, shape, dtype):
         """A zero-filled numpy array over page-locked memory (dslam_host_alloc): view_update* in synchronous mode

@@ -69,6 +69,11 @@ int launch_scene_reset(dslam_engine *e, dslam_scene *s) {
   const size_t n16 = (size_t)s->p.num_local_blocks * kBlock3 / 2;
   const unsigned fill_wgs = (unsigned)((n16 + 256 * kFillUnroll - 1) / (256 * kFillUnroll));
   hipLaunchKernelGGL(k_fill_voxels, dim3(fill_wgs), dim3(256), 0, e->stream, reinterpret_cast<uint4 *>(s->voxels), n16);
+  return launch_scene_reset_tables(e, s);
+}
+
+// everything of a reset but the voxel pool (an unpack writes every slot of the pool itself, pack.hip)
+int launch_scene_reset_tables(dslam_engine *e, dslam_scene *s) {
   hipLaunchKernelGGL(k_reset_tables, dim3(2048), dim3(256), 0, e->stream, s->hash, s->n_entries, s->alloc_list,
                      s->last_seen, s->p.num_local_blocks, s->excess_list, s->p.num_excess, s->counters, e->err_host);
   DSLAM_HIP(hipMemsetAsync(s->masks, 0, (size_t)s->p.num_local_blocks * 2 * s->history_words * sizeof(unsigned long long),

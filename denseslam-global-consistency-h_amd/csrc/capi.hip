@@ -177,6 +177,43 @@ extern "C" {
 const char *dslam_last_error(void) { return g_last_error.c_str(); }
 const char *dslam_version(void) { return "dslam_fusion 0.1 (gfx950)"; }
 
+// ---- an engine outlives the handles made from it ---------------------------------------------------------------
+// Every destroy call of a scene, render state, view or frame store selects the engine's device and waits for its
+// stream, so the engine object and its streams must be there for it.  A create call adopts its handle the moment the
+// handle points at the engine (so the destroy call that clears away a half-built one balances it), every destroy call
+// releases it; dslam_engine_destroy frees the engine only if no handle is left, and otherwise leaves that to the last
+// release.  Plain counters: the engine and its handles are used from one thread (dslam_fusion.h, conventions).
+static std::atomic<int> g_live_engines{0};   // engine objects not yet freed (dslam_debug_live_engines)
+static void engine_adopt(dslam_engine *e) { e->children++; }
+// Fences the caller still holds forget the engine, destroyed ones go -- except those a view still waits on: they stay
+// attached until that view lets go, which the engine waits for anyway.  The invariant this rests on: lent_count > 0 only
+// while a VIEW of this engine holds the fence in up_lender (dslam_view_destroy lets go of both before it releases the
+// engine), so lent_count > 0 implies children > 0 through that view -- `children` counts every handle kind and is only
+// the guard for the final call (engine_free, children == 0, where nothing can be lent any more and every fence goes).
+// A fence kept this way still names the closed engine: dslam_fence_wait reads its error word through it, which is sound
+// because the object lives exactly as long as the fence stays attached.
+static void engine_detach_fences(dslam_engine *e) {
+  std::vector<dslam_fence *> kept;
+  for (dslam_fence *f : e->fences) {
+    if (f->lent_count > 0 && e->children > 0) kept.push_back(f);
+    else if (f->zombie) delete f;
+    else f->engine = nullptr;   // the caller still holds it: its destroy call must not look for this engine
+  }
+  e->fences.swap(kept);
+  e->last_fence = nullptr;
+}
+static void engine_free(dslam_engine *e) {
+  (void)hipSetDevice(e->device);
+  engine_detach_fences(e);
+  if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
+  if (e->stream) (void)hipStreamDestroy(e->stream);
+  delete e;
+  g_live_engines.fetch_sub(1, std::memory_order_relaxed);
+}
+static void engine_release(dslam_engine *e) {
+  if (--e->children == 0 && e->closed) engine_free(e);
+}
+
 static int engine_allocate(dslam_engine *e) {
   DSLAM_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
   DSLAM_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
@@ -227,6 +264,7 @@ int dslam_engine_create(int device_index, dslam_engine **out) {
   DSLAM_REQUIRE(device_index >= 0 && device_index < n, "device index out of range");
   DSLAM_HIP(hipSetDevice(device_index));
   dslam_engine *e = new dslam_engine();
+  g_live_engines.fetch_add(1, std::memory_order_relaxed);
   e->device = device_index;
   if (const char *v = getenv("DSLAM_SPECULATIVE_FRONT_END")) e->speculate_front = atoi(v) != 0;
   const int rc = engine_allocate(e);
@@ -243,15 +281,21 @@ int dslam_engine_create(int device_index, dslam_engine **out) {
 int dslam_engine_destroy(dslam_engine *e) {
   if (!e) return DSLAM_OK;
   (void)hipSetDevice(e->device);
+  if (e->closed) return DSLAM_OK;   // (a second destroy of an engine its handles keep alive: nothing left to do)
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  if (e->copy_stream) { (void)hipStreamSynchronize(e->copy_stream); (void)hipStreamDestroy(e->copy_stream); }
-  for (dslam_fence *f : e->fences) {
-    if (f->zombie) delete f;
-    else f->engine = nullptr;   // the caller still holds it: its destroy call must not look for this engine
+  if (e->copy_stream) (void)hipStreamSynchronize(e->copy_stream);
+  if (e->children > 0) {   // handles are left: their destroy calls need the object and its streams
+    engine_detach_fences(e);
+    e->closed = true;
+    return DSLAM_OK;
   }
-  e->fences.clear();
-  if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
+  engine_free(e);
+  return DSLAM_OK;
+}
+
+int dslam_debug_live_engines(int *out) {
+  DSLAM_REQUIRE(out, "null argument");
+  *out = g_live_engines.load(std::memory_order_relaxed);
   return DSLAM_OK;
 }
 
@@ -405,6 +449,7 @@ int dslam_scene_create(dslam_engine *e, const dslam_scene_params *p, void *ext_v
   dslam_scene *s = new dslam_scene();
   s->version = next_map_version();
   s->engine = e;
+  engine_adopt(e);
   s->p = *p;
   if (s->p.num_local_blocks <= 0) s->p.num_local_blocks = DSLAM_DEFAULT_LOCAL_BLOCK_NUM;
   if (s->p.num_buckets <= 0) s->p.num_buckets = DSLAM_DEFAULT_BUCKET_NUM;
@@ -414,6 +459,7 @@ int dslam_scene_create(dslam_engine *e, const dslam_scene_params *p, void *ext_v
   if ((s->p.num_buckets & (s->p.num_buckets - 1)) || ((s->p.num_buckets + s->p.num_excess) & 15) ||
       s->p.max_w < 1 || s->p.max_w > 255 || !(s->p.voxel_size > 0) || !(s->p.mu > 0)) {
     delete s;
+    engine_release(e);
     set_last_error("invalid scene parameters (buckets must be a power of two, entries a multiple of 16, 1<=max_w<=255)");
     return DSLAM_ERR_INVALID;
   }
@@ -454,8 +500,16 @@ int dslam_scene_destroy(dslam_scene *s) {
   if (!s) return DSLAM_OK;
   (void)hipSetDevice(s->engine->device);
   (void)hipStreamSynchronize(s->engine->stream);
+  dslam_engine *e = s->engine;
   delete s;
+  engine_release(e);
   return DSLAM_OK;
+}
+
+// the host's share of a reset map: rings, decay cursors, frame counter (dslam_scene_reset, dslam_unpack_scene)
+static void reset_host_cursors(dslam_scene *s) {
+  for (int q = 0; q < 2; q++) { s->ring_head[q] = 0; s->ring_next[q] = 0; s->decay_cursor[q] = 0; }
+  s->frame_counter = 0;
 }
 
 int dslam_scene_reset(dslam_engine *e, dslam_scene *s) {
@@ -463,8 +517,7 @@ int dslam_scene_reset(dslam_engine *e, dslam_scene *s) {
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   int rc = launch_scene_reset(e, s);
   if (rc) return rc;
-  for (int q = 0; q < 2; q++) { s->ring_head[q] = 0; s->ring_next[q] = 0; s->decay_cursor[q] = 0; }
-  s->frame_counter = 0;
+  reset_host_cursors(s);
   if (s->slot_dev) {  // the slabs stay; their slots are dealt again from the start (the counters were just zeroed)
     DSLAM_HIP(hipMemsetAsync(s->slot_dev, 0xff, (size_t)s->n_entries * sizeof(int), e->stream));
     DSLAM_HIP(hipStreamSynchronize(e->stream));
@@ -554,7 +607,7 @@ int dslam_render_state_create(dslam_engine *e, const dslam_scene *s, int w, int 
   DSLAM_REQUIRE(e && s && out && w > 0 && h > 0, "bad argument");
   *out = nullptr;
   dslam_render_state *r = new dslam_render_state();
-  r->engine = e; r->w = w; r->h = h; r->n_entries = s->n_entries; r->n_local = s->p.num_local_blocks;
+  r->engine = e; engine_adopt(e); r->w = w; r->h = h; r->n_entries = s->n_entries; r->n_local = s->p.num_local_blocks;
   const int rc = render_state_allocate(e, r);
   if (rc) {
     (void)dslam_render_state_destroy(r);
@@ -568,7 +621,9 @@ int dslam_render_state_destroy(dslam_render_state *r) {
   if (!r) return DSLAM_OK;
   (void)hipSetDevice(r->engine->device);
   (void)hipStreamSynchronize(r->engine->stream);
+  dslam_engine *e = r->engine;
   delete r;
+  engine_release(e);
   return DSLAM_OK;
 }
 
@@ -592,7 +647,7 @@ int dslam_view_create(dslam_engine *e, int w_rgb, int h_rgb, int w_d, int h_d, d
   DSLAM_REQUIRE(e && out && w_rgb > 0 && h_rgb > 0 && w_d > 0 && h_d > 0, "bad argument");
   *out = nullptr;
   dslam_view *v = new dslam_view();
-  v->engine = e; v->w_rgb = w_rgb; v->h_rgb = h_rgb; v->w_d = w_d; v->h_d = h_d;
+  v->engine = e; engine_adopt(e); v->w_rgb = w_rgb; v->h_rgb = h_rgb; v->w_d = w_d; v->h_d = h_d;
   const int rc = view_allocate(e, v);
   if (rc) {
     (void)dslam_view_destroy(v);
@@ -608,7 +663,9 @@ int dslam_view_destroy(dslam_view *v) {
   (void)hipStreamSynchronize(v->engine->stream);
   if (v->engine->copy_stream) (void)hipStreamSynchronize(v->engine->copy_stream);
   for (int b = 0; b < 2; b++) release_lender(v, b);
+  dslam_engine *e = v->engine;
   delete v;
+  engine_release(e);
   return DSLAM_OK;
 }
 
@@ -867,6 +924,7 @@ int dslam_frame_store_create(dslam_engine *e, int w_rgb, int h_rgb, int w_d, int
   fs->rgba_bytes = ((size_t)w_rgb * h_rgb * 4 + 255) & ~(size_t)255;
   fs->depth_bytes = ((size_t)w_d * h_d * 2 + 255) & ~(size_t)255;
   DSLAM_TRY(fs->rgba.alloc(fs->rgba_bytes * capacity)); DSLAM_TRY(fs->depth.alloc(fs->depth_bytes * capacity));
+  engine_adopt(e);   // (only a complete store is a handle: a half-built one goes with `fs`, without a destroy call)
   *out = fs.release();
   return DSLAM_OK;
 }
@@ -875,7 +933,9 @@ int dslam_frame_store_destroy(dslam_frame_store *fs) {
   if (!fs) return DSLAM_OK;
   (void)hipSetDevice(fs->engine->device);
   (void)hipStreamSynchronize(fs->engine->stream);
+  dslam_engine *e = fs->engine;
   delete fs;
+  engine_release(e);
   return DSLAM_OK;
 }
 
@@ -1874,6 +1934,77 @@ int dslam_pack_header_read(const void *first_64_bytes, dslam_pack_info *out) {
   memcpy(&h, first_64_bytes, sizeof h);
   DSLAM_REQUIRE(pack_header_valid(h), "not the header of a packed map (magic, version, counts or layout)");
   *out = h;
+  return DSLAM_OK;
+}
+
+// ---- packed maps: the device half (pack.hip) ---------------------------------------------------------------------
+// the scene kinds neither call takes: their maps are more than resident entries plus a free excess list, or in motion
+static int check_pack_scene(dslam_engine *e, const dslam_scene *s) {
+  DSLAM_REQUIRE(s->engine == e, "the scene belongs to another engine");
+  DSLAM_REQUIRE(!s->p.use_swapping, "a scene that uses swapping cannot be packed or unpacked into");
+  DSLAM_REQUIRE(s->num_shards == 1 && s->shard_count < 0, "a sharded scene cannot be packed or unpacked into");
+  DSLAM_REQUIRE(!s->alloc_born, "the scene's re-integration batch is being planned");
+  return DSLAM_OK;
+}
+
+int dslam_device_alloc(dslam_engine *e, size_t bytes, void **out) {
+  DSLAM_REQUIRE(e && out && bytes > 0, "bad argument");
+  *out = nullptr;
+  DSLAM_HIP(hipSetDevice(e->device));
+  DSLAM_HIP(hipMalloc(out, bytes));
+  return DSLAM_OK;
+}
+int dslam_device_free(dslam_engine *e, void *p) {
+  DSLAM_REQUIRE(e, "null engine");
+  if (!p) return DSLAM_OK;
+  DSLAM_HIP(hipSetDevice(e->device));
+  DSLAM_HIP(hipStreamSynchronize(e->stream));
+  DSLAM_HIP(hipFree(p));
+  return DSLAM_OK;
+}
+
+int dslam_pack_scene(dslam_engine *e, const dslam_scene *s, void *buf, int64_t capacity, dslam_pack_info *info_out) {
+  DSLAM_REQUIRE(e && s && info_out, "null argument");
+  DSLAM_TRY(check_pack_scene(e, s));
+  DSLAM_HIP(hipSetDevice(e->device));
+  dslam_pack_info info;
+  memset(&info, 0, sizeof info);
+  const int rc = launch_pack_scene(e, s, buf, capacity, &info);
+  if (rc == DSLAM_OK || info.total_bytes > 0) *info_out = info;   // (total_bytes > 0: the counts were read)
+  return rc;
+}
+
+int dslam_unpack_scene(dslam_engine *e, dslam_scene *s, const void *buf, int64_t bytes, dslam_pack_info *info_out) {
+  DSLAM_REQUIRE(e && s && buf, "null argument");
+  DSLAM_TRY(check_pack_scene(e, s));
+  DSLAM_REQUIRE(bytes >= kPackHeaderBytes, "shorter than the header of a packed map");
+  DSLAM_HIP(hipSetDevice(e->device));
+  void *buf_dev = nullptr;
+  DSLAM_TRY(pack_buffer_address(e, buf, kPackHeaderBytes, &buf_dev));
+  // the header: read by the host, judged as dslam_pack_header_read judges it, compared with the scene
+  dslam_pack_info h;
+  DSLAM_HIP(hipMemcpyAsync(e->pinned, buf_dev, sizeof h, hipMemcpyDefault, e->stream));
+  DSLAM_TRY(sync_check(e));
+  DSLAM_TRY(dslam_pack_header_read(e->pinned, &h));
+  DSLAM_REQUIRE(h.num_buckets == s->p.num_buckets && h.num_excess == s->p.num_excess, "the packed map's table geometry is not the scene's");
+  DSLAM_REQUIRE(memcmp(&h.voxel_size_bits, &s->p.voxel_size, 4) == 0 && memcmp(&h.mu_bits, &s->p.mu, 4) == 0,
+                "the packed map's voxel_size or mu is not the scene's");
+  DSLAM_REQUIRE(h.blocks <= s->p.num_local_blocks, "the packed map holds more blocks than the scene's pool");
+  DSLAM_REQUIRE(bytes >= h.total_bytes, "the buffer is shorter than the packed map");
+  DSLAM_TRY(pack_buffer_address(e, buf, h.total_bytes, &buf_dev));
+  DSLAM_TRY(launch_unpack_validate(e, s, buf_dev, &h));
+  // ---- the first write: from here on a failure leaves the scene reset ----
+  map_changed(s);
+  reset_host_cursors(s);
+  int rc = launch_unpack_write(e, s, buf_dev, &h);
+  if (rc == DSLAM_OK) rc = sync_check(e);
+  if (rc != DSLAM_OK) {   // whatever failed (a HIP call, or a device report the wait heard): never a half-written scene
+    const std::string why = g_last_error;
+    if (launch_scene_reset(e, s) == DSLAM_OK) (void)hipStreamSynchronize(e->stream);
+    g_last_error = why;
+    return rc;
+  }
+  if (info_out) *info_out = h;
   return DSLAM_OK;
 }
 

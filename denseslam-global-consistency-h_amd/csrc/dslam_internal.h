@@ -167,6 +167,11 @@ using dslam::DeviceBuffer, dslam::Event, dslam::PinnedBuffer;
 struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   int device = 0;
   hipStream_t stream = nullptr;
+  // Handles made from this engine that still exist (scenes, render states, views, frame stores: everything that keeps a
+  // pointer to it and reads it in its destroy call).  dslam_engine_destroy with children left only closes the engine:
+  // object and streams stay until the last child's destroy call (capi.hip engine_adopt / engine_release).
+  int children = 0;
+  bool closed = false;
   // A caller's fence recorded behind the last call that read a view is also that view's "consumed" mark: the pipelined
   // upload then records no event of its own (an event record costs the compute stream ~3.5 us per frame, measured).
   unsigned long long view_reads = 0;   // calls that enqueued kernels reading a view's images, so far
@@ -485,6 +490,12 @@ class DiagDump {
 };
 // kernels' host launchers (one translation unit per subsystem)
 int launch_scene_reset(dslam_engine *e, dslam_scene *s);
+int launch_scene_reset_tables(dslam_engine *e, dslam_scene *s);   // ... without the voxel pool
+// packed maps (pack.hip); the scene already checked by the entry point.  buf: the caller's pointer (pack: null = size query)
+int pack_buffer_address(dslam_engine *e, const void *p, int64_t bytes, void **dev_out);
+int launch_pack_scene(dslam_engine *e, const dslam_scene *s, void *buf, int64_t capacity, dslam_pack_info *info);
+int launch_unpack_validate(dslam_engine *e, const dslam_scene *s, const void *buf_dev, const dslam_pack_info *h);
+int launch_unpack_write(dslam_engine *e, dslam_scene *s, const void *buf_dev, const dslam_pack_info *h);   // enqueues only
 int launch_inject_error(dslam_engine *e, dslam_scene *s, int bits);
 int launch_build_alloc_bits(dslam_engine *e, dslam_scene *s);  // alloc_bits from an uploaded table
 int launch_view_convert(dslam_engine *e, dslam_view *v, const void *rgba_dev, const void *depth_dev, float a, float b);

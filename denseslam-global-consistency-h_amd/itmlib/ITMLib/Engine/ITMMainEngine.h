@@ -305,7 +305,7 @@ class ITMMainEngine {
 
   ITMMainEngine(const ITMLibSettings *settings_, const ITMRGBDCalib *calib, Vector2i imgSize_rgb, Vector2i imgSize_d = Vector2i(-1, -1))
       : settings(settings_), view(nullptr), engine_(nullptr), freeviewScene_(nullptr), renderState_freeview_(nullptr),
-        renderState_allmaps_(nullptr) {
+        renderState_allmaps_(nullptr), allmapsBlocks_(0), allmapsScene_(nullptr) {
     if (imgSize_d.x == -1 || imgSize_d.y == -1) imgSize_d = imgSize_rgb;
     dslam_check(dslam_engine_create(settings->hipDeviceIndex, &engine_), "dslam_engine_create");
     // calls enqueue; the calls that hand data to the host wait (see the head of this file)
@@ -560,6 +560,49 @@ class ITMMainEngine {
     if (re) *re = mres;
     return mres.exhausted == 0;
   }
+  /// (extension) Shrink a finished local map's voxel pool to what the map holds plus `headroomBlocks` (dslam_pack_scene,
+  /// dslam_unpack_scene; law in DESIGN.md section 21): the map is packed into device memory, its scene is replaced by
+  /// one of n + headroomBlocks blocks with the same table geometry, and the image is unpacked into it.  Entries keep
+  /// their hash indices, the free excess stack its order; blocks move to new slots.  The map's render state is sized by
+  /// the old pool and is made anew (its visible list starts empty, as a new map's); the free-view and all-maps render
+  /// states go if they were made from the old scene and are made again by the next image (DrawLocalMaps sizes the
+  /// all-maps one by the largest pool among the maps it draws, so maps of different pools draw together).  Tracking
+  /// state and estimatedGlobalPose stay.  Not for maps that use swapping.  Everything new -- image, scene, render state --
+  /// is complete before anything old is let go: on failure the map is left as it was and the call throws.
+  void CompactLocalMap(int mapIdx, int headroomBlocks, dslam_pack_info *out = nullptr) {
+    ITMLocalMap *m = mapManager->getLocalMap(mapIdx);
+    if (headroomBlocks < 0) throw std::runtime_error("CompactLocalMap: negative headroom");
+    dslam_pack_info info;
+    dslam_check(dslam_pack_scene(engine_, m->scene->handle, nullptr, 0, &info), "dslam_pack_scene (size query)");
+    void *buf = nullptr;
+    dslam_check(dslam_device_alloc(engine_, (size_t)info.total_bytes, &buf), "dslam_device_alloc");
+    ITMScene<ITMVoxel, ITMVoxelIndex> *compact = nullptr;
+    ITMRenderState *renderState = nullptr;
+    try {
+      dslam_check(dslam_pack_scene(engine_, m->scene->handle, buf, info.total_bytes, &info), "dslam_pack_scene");
+      const long long blocks = std::max(1LL, (long long)info.blocks + headroomBlocks);
+      if (blocks > 0x7fffffffLL) throw std::runtime_error("CompactLocalMap: headroom too large");
+      compact = new ITMScene<ITMVoxel, ITMVoxelIndex>(settings, engine_, (int)blocks);
+      dslam_check(dslam_unpack_scene(engine_, compact->handle, buf, info.total_bytes, nullptr), "dslam_unpack_scene");
+      renderState = new ITMRenderState_VH(engine_, compact->handle, m->renderState->raycastImage->noDims);
+      void *image = buf;
+      buf = nullptr;
+      dslam_check(dslam_device_free(engine_, image), "dslam_device_free");
+    } catch (...) {
+      delete renderState;
+      delete compact;
+      if (buf) dslam_device_free(engine_, buf);
+      throw;
+    }
+    // nothing below throws: the old objects go, the new ones take their place
+    if (freeviewScene_ == m->scene) { delete renderState_freeview_; renderState_freeview_ = nullptr; freeviewScene_ = nullptr; }
+    if (allmapsScene_ == m->scene->handle) { delete renderState_allmaps_; renderState_allmaps_ = nullptr; allmapsScene_ = nullptr; }
+    delete m->renderState;
+    delete m->scene;
+    m->scene = compact;
+    m->renderState = renderState;
+    if (out) *out = info;
+  }
   /// (extension) Track the camera of the current view against ALL local maps under their estimatedGlobalPoses
   /// (dslam_track_camera_sdf, law in DESIGN.md section 18) -- where the reference's internal odometry prepares and tracks
   /// currentLocalMap alone (DenseSlam.cpp:198-206), which holds nothing just after createNewLocalMap.  The start is
@@ -739,10 +782,22 @@ class ITMMainEngine {
   /// dslam_get_image_multi of the listed maps into the caller's image, through the all-maps render state
   void DrawLocalMaps(const std::vector<const dslam_scene *> &scenes, const std::vector<float> &T, int t, Vector2i sz,
                      ITMUChar4Image *out, ITMFloatImage *outFloat, ITMPose *pose, ITMIntrinsics *intrinsics) {
-    if (renderState_allmaps_ == nullptr || allmapsSize_.x != sz.x || allmapsSize_.y != sz.y) {
+    // The render state's visible list has to hold the largest pool among the listed maps (dslam_get_image_multi rejects
+    // a list otherwise), and pools differ once maps have been compacted: it is made from the listed scene with the
+    // largest pool (the first of them), and made again when the image size changes or a listed pool exceeds it.
+    const dslam_scene *largest = nullptr;
+    int largestBlocks = 0;
+    for (size_t i = 0; i < scenes.size(); i++) {
+      dslam_scene_params p;
+      dslam_check(dslam_scene_get_params(scenes[i], &p), "dslam_scene_get_params");
+      if (p.num_local_blocks > largestBlocks) { largestBlocks = p.num_local_blocks; largest = scenes[i]; }
+    }
+    if (largest == nullptr) return;
+    if (renderState_allmaps_ == nullptr || allmapsSize_.x != sz.x || allmapsSize_.y != sz.y || largestBlocks > allmapsBlocks_) {
       delete renderState_allmaps_;
-      renderState_allmaps_ = visualisationEngine->CreateRenderState(mapManager->getLocalMap(0)->scene, sz);
-      allmapsSize_ = sz;
+      renderState_allmaps_ = nullptr; allmapsScene_ = nullptr;
+      renderState_allmaps_ = new ITMRenderState_VH(engine_, largest, sz);
+      allmapsSize_ = sz; allmapsBlocks_ = largestBlocks; allmapsScene_ = largest;
     }
     dslam_check(dslam_get_image_multi(engine_, scenes.data(), T.data(), (int)scenes.size(), renderState_allmaps_->handle,
                                       pose->GetM().m, intrinsics->projectionParamsSimple.all.v, t,
@@ -825,6 +880,8 @@ class ITMMainEngine {
   Vector2i freeviewSize_;
   ITMRenderState *renderState_allmaps_;   ///< GetImageAllLocalMaps' own render state
   Vector2i allmapsSize_;
+  int allmapsBlocks_;                     ///< ... the pool size its visible list holds
+  const dslam_scene *allmapsScene_;       ///< ... the scene it was made from (its counters read that scene: gone with it)
 };
 
 }  // namespace Engine

@@ -271,16 +271,19 @@ template <class TVoxel, class TIndex> class ITMScene {
   TIndex index;
   ITMLocalVBA localVBA;
   dslam_scene *handle;
-  ITMScene(const ITMLibSettings *settings, dslam_engine *eng) : counters_(nullptr), sceneParams(&settings->sceneParams), index(settings->numLocalBlocks), handle(nullptr) {
+  ITMScene(const ITMLibSettings *settings, dslam_engine *eng) : ITMScene(settings, eng, settings->numLocalBlocks) {}
+  /// (extension) ... with a voxel pool of `numLocalBlocks` blocks instead of the settings' (ITMMainEngine::CompactLocalMap:
+  /// a finished map in a pool as large as it needs); table geometry and scene parameters are the settings'
+  ITMScene(const ITMLibSettings *settings, dslam_engine *eng, int numLocalBlocks) : counters_(nullptr), sceneParams(&settings->sceneParams), index(numLocalBlocks), handle(nullptr) {
     dslam_scene_params p;
     memset(&p, 0, sizeof(p));
     p.voxel_size = sceneParams->voxelSize; p.mu = sceneParams->mu; p.max_w = sceneParams->maxW;
     p.frustum_min = sceneParams->viewFrustum_min; p.frustum_max = sceneParams->viewFrustum_max;
     p.stop_integrating_at_max_w = sceneParams->stopIntegratingAtMaxW;
-    p.num_local_blocks = settings->numLocalBlocks; p.num_buckets = settings->numBuckets; p.num_excess = settings->numExcess;
+    p.num_local_blocks = numLocalBlocks; p.num_buckets = settings->numBuckets; p.num_excess = settings->numExcess;
     p.use_swapping = settings->useSwapping;
     dslam_check(dslam_scene_create(eng, &p, nullptr, &handle), "dslam_scene_create");
-    localVBA.allocatedSize = settings->numLocalBlocks;
+    localVBA.allocatedSize = numLocalBlocks;
     counters_ = new DeviceCounters(eng, handle, nullptr);
     localVBA.lastFreeBlockId.Bind(counters_, &dslam_stats::last_free_block_id);
     index.lastFreeExcessListId.Bind(counters_, &dslam_stats::last_free_excess_id);

@@ -141,7 +141,17 @@ int dslam_engine_create(int device_index, dslam_engine **out);
  * 640x480 frame takes ~60 us there and ~160 us from the other socket of a two-socket host.  May be
  * called before any engine exists. */
 int dslam_device_numa_node(int device_index, int *node_out);
+/* Waits for both streams of the engine and ends its life for the caller.  Handles may be destroyed in any order: the
+ * scenes, render states, views and frame stores made from the engine may still exist, and each of them is destroyed by
+ * its own destroy call as before, whether that comes before or after this one -- the engine's object and streams are
+ * kept until the last of them has gone, and freed by that call.  Fences the caller still holds are detached as before
+ * (dslam_fence_wait / _query / _destroy on them stay valid).  No other call may be given a destroyed engine, nor a
+ * handle of one for anything but its destroy call.  The threading rule above holds unchanged: the engine and its
+ * handles, their destroy calls included, are used from one thread. */
 int dslam_engine_destroy(dslam_engine *e);
+/* Test hook: engine objects of this process that have not been freed yet -- created and not destroyed, or destroyed
+ * while handles made from them are left (see dslam_engine_destroy).  Needs no engine. */
+int dslam_debug_live_engines(int *out);
 int dslam_engine_set_async(dslam_engine *e, int async_mode);
 /* waits for everything enqueued so far; returns what kernels reported since the last synchronising call (above) */
 int dslam_engine_synchronize(dslam_engine *e);
@@ -897,9 +907,9 @@ int dslam_remerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst
 
 /* ---- packed maps: the layout and its host half ---------------------------------------------------- */
 /* A compact, self-describing, deterministic image of a map (DESIGN.md section 21 states the law in full: which entries are
- * packed, what an unpack into a pool of any size leaves, what is checked before its first write).  The library holds the
- * host half only -- the two functions below, callable without a device, as dslam_view_frustum_planes is; the device
- * calls that write and read such an image are not part of it yet (section 21 says why).
+ * packed, what an unpack into a pool of any size leaves, what is checked before its first write).  The host half -- the
+ * two layout functions, callable without a device, as dslam_view_frustum_planes is -- comes first; the device calls that
+ * write and read such an image, dslam_pack_scene and dslam_unpack_scene, follow.
  * Layout, little-endian; every byte up to total_bytes is defined.  n: the resident entries (ptr >= 0), in ascending hash
  * index (rank order); f = last_free_excess_id + 1:
  *   offset 0                64-byte header: dslam_pack_info as it lies in memory
@@ -931,6 +941,39 @@ int dslam_pack_layout(int32_t blocks, int32_t free_excess, int64_t *blocks_offse
  * blocks_offset and total_bytes are the functions of n and f above; DSLAM_ERR_INVALID leaves *out untouched.  voxel_size,
  * mu and the bounding box pass through unjudged: comparing them with a scene is the caller's. */
 int dslam_pack_header_read(const void *first_64_bytes, dslam_pack_info *out);
+/* Device memory of the engine's device for a packed map, for callers without a HIP runtime of their own (the ITMLib
+ * mirror's CompactLocalMap): hipMalloc / hipFree, 256-byte aligned at least; the free waits for the engine's stream. */
+int dslam_device_alloc(dslam_engine *e, size_t bytes, void **out);
+int dslam_device_free(dslam_engine *e, void *p);
+/* The device half (csrc/pack.hip).  `buf` is device memory of the engine's device or page-locked host memory
+ * (dslam_host_alloc, hipHostMalloc, hipHostRegister), 16-byte aligned: the kernels write and read it directly.  The
+ * library asks hipPointerGetAttributes about its first and its last byte and rejects, before anything is launched, a
+ * pointer the device cannot address (ordinary pageable memory).  Both calls reject (DSLAM_ERR_INVALID, nothing written)
+ * a scene that uses swapping, a sharded scene (num_shards > 1 or a shard range), a scene whose re-integration batch is
+ * being planned, and a scene of another engine.
+ *
+ * dslam_pack_scene writes the image of `s` to buf[0 .. total_bytes): every byte of that range and none outside, the same
+ * bytes on every run.  It runs on the engine's stream, so it sees everything enqueued before it, and it returns with the
+ * buffer complete on synchronous and asynchronous engines alike.  `s` is only read: version, front-end record and GetImage
+ * memos stay.  buf == NULL is the size query: *info_out is filled (it is the header a pack would write) and nothing is
+ * written; capacity is ignored.  capacity < total_bytes: DSLAM_ERR_INVALID, nothing written, *info_out still filled.
+ *
+ * dslam_unpack_scene reads the image in buf[0 .. bytes) into `s`, a scene of N = num_local_blocks blocks, and leaves
+ * what DESIGN.md section 21 states: record k at the entry its index names with ptr = N-1-k, block k in slot N-1-k,
+ * every other slot empty, every other entry the reset entry, the free excess stack as packed, everything else as
+ * dslam_scene_reset leaves it; the version is advanced, front-end record and memos are dropped.  Before the first write
+ * to `s` the host validates the header (dslam_pack_header_read) and compares it with the scene -- num_buckets and
+ * num_excess equal, voxel_size and mu equal bitwise, 0 <= n <= N, bytes >= total_bytes -- and a read-only device pass
+ * checks that the record indices lie in the table and ascend strictly, every offset in [0, num_excess], every free
+ * value in [0, num_excess); its verdict is read back first.  A failure of any of these leaves `s` as it was
+ * (DSLAM_ERR_INVALID).  The kernels that write judge every record index, offset and free value again as they read it,
+ * so even if the buffer changes under the call no address depends on an unchecked value and no value outside these
+ * ranges reaches the table or the free list (a record or free value that fails then is skipped: the reset's stays).
+ * If anything fails after the first write -- a HIP call, or a device report heard by the wait -- `s` is left as
+ * dslam_scene_reset leaves it and the failure's code is returned.  Returns with the scene complete; buf may be released
+ * then.  info_out (may be NULL for unpack): the header read, filled only on success. */
+int dslam_pack_scene(dslam_engine *e, const dslam_scene *s, void *buf, int64_t capacity, dslam_pack_info *info_out);
+int dslam_unpack_scene(dslam_engine *e, dslam_scene *s, const void *buf, int64_t bytes, dslam_pack_info *info_out);
 
 /* ---- depth tracker (ICP) ---------------------------------------------------------------------- */
 /* trackingController->Track(trackingState, view) (InfiniTamDriver.h:151-163, reached through
