@@ -79,6 +79,31 @@ class TrackSdfResult(C.Structure):
 assert C.sizeof(TrackSdfParams) == 32 and C.sizeof(TrackSdfResult) == 32  # the header's layouts
 
 
+MAX_TRACK_STARTS = 256   # DSLAM_MAX_TRACK_STARTS
+
+
+class PoseScore(C.Structure):
+    """dslam_pose_score."""
+    _fields_ = [("candidates", C.c_int32), ("valid", C.c_int32), ("cost", C.c_float), ("pad", C.c_int32)]
+
+
+class PoseLattice(C.Structure):
+    """dslam_pose_lattice: nt translation nodes to each side per world axis, step_t metres apart; nr rotation nodes to each
+    side about `axis`, step_r radians apart."""
+    _fields_ = [("nt", C.c_int32 * 3), ("step_t", C.c_float), ("nr", C.c_int32), ("step_r", C.c_float), ("axis", C.c_float * 3),
+                ("pad", C.c_int32)]
+
+    def __init__(self, nt=(0, 0, 0), step_t=0.0, nr=0, step_r=0.0, axis=(0.0, 0.0, 0.0)):
+        super().__init__((C.c_int32 * 3)(*nt), step_t, nr, step_r, (C.c_float * 3)(*axis), 0)
+
+    @property
+    def count(self):
+        return (2 * self.nr + 1) * (2 * self.nt[0] + 1) * (2 * self.nt[1] + 1) * (2 * self.nt[2] + 1)
+
+
+assert C.sizeof(PoseScore) == 16 and C.sizeof(PoseLattice) == 40  # the header's layouts
+
+
 class RegisterParams(C.Structure):
     """dslam_register_params; a field left at 0 selects its default."""
     _fields_ = [("band", C.c_float), ("residual_gate", C.c_float), ("max_evaluations", C.c_int32),
@@ -731,6 +756,60 @@ class CApi:
         out = np.empty(33, dtype=np.float64)
         self._call("debug_track_sdf_sums", self._engine, out.ctypes.data_as(C.POINTER(C.c_double)))
         return out
+
+    @staticmethod
+    def _pose_list(poses_M):
+        """[K] 4x4 world -> camera poses as one column-major float32 array of the caller's own."""
+        P = np.asarray(poses_M, dtype=np.float32)
+        if P.ndim != 3 or P.shape[1:] != (4, 4):
+            raise ValueError("poses_M must be K 4x4 matrices")
+        return len(P), np.ascontiguousarray(np.transpose(P, (0, 2, 1))).reshape(-1).copy()
+
+    def score_camera_poses(self, view, scenes, map_poses, poses_M, intr, level=0, residual_gate=0.0):
+        """dslam_score_camera_poses: one evaluation of dslam_track_camera_sdf's law per pose of `poses_M` ([K] 4x4, world ->
+        camera) on `level` of the view's pyramid, all in one launch.  Returns a ctypes array of K PoseScore."""
+        n, ptrs, t_abi = self._map_list(scenes, map_poses)
+        k, poses = self._pose_list(poses_M)
+        intr = np.ascontiguousarray(intr, dtype=np.float32)
+        scores = (PoseScore * max(k, 1))()
+        self._call("score_camera_poses", self._engine, view.ptr, ptrs, _fptr(t_abi), C.c_int(n), _fptr(poses), C.c_int(k),
+                   _fptr(intr), C.c_int(level), C.c_float(residual_gate), scores)
+        return scores
+
+    def track_camera_sdf_starts(self, view, scenes, map_poses, poses_M, intr, params=None):
+        """dslam_track_camera_sdf_starts: track_camera_sdf from every start of `poses_M` ([K] 4x4) in lock-step.  Returns (the
+        estimates [K, 4, 4] float32 -- a start's own bytes where no step was accepted --, a ctypes array of K TrackSdfResult)."""
+        n, ptrs, t_abi = self._map_list(scenes, map_poses)
+        k, poses = self._pose_list(poses_M)
+        intr = np.ascontiguousarray(intr, dtype=np.float32)
+        res = (TrackSdfResult * max(k, 1))()
+        self._call("track_camera_sdf_starts", self._engine, view.ptr, ptrs, _fptr(t_abi), C.c_int(n), _fptr(poses), C.c_int(k),
+                   _fptr(intr), C.byref(params) if params is not None else None, res)
+        return np.transpose(poses.reshape(k, 4, 4), (0, 2, 1)).copy(), res
+
+    def debug_track_sdf_start_sums(self, start):
+        """The 33 double sums of start `start`'s last evaluation in the most recent track_camera_sdf_starts."""
+        out = np.empty(33, dtype=np.float64)
+        self._call("debug_track_sdf_start_sums", self._engine, C.c_int(start), out.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
+
+    def select_start_poses(self, scores, min_valid, max_keep):
+        """dslam_select_start_poses (host only): the indices of the max_keep cheapest scores with valid >= min_valid."""
+        num = len(scores)
+        arr = scores if isinstance(scores, C.Array) else (PoseScore * max(num, 1))(*scores)
+        kept = np.zeros(max(max_keep, 1), dtype=np.int32)
+        count = C.c_int32(0)
+        self._call("select_start_poses", arr, C.c_int(num), C.c_int(min_valid), C.c_int(max_keep),
+                   kept.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(count))
+        return kept[:count.value].copy()
+
+    def camera_pose_lattice(self, pose_M, lattice):
+        """dslam_camera_pose_lattice (host only): the lattice's poses around pose_M as [count, 4, 4] float32."""
+        count = C.c_int32(0)
+        cap = max(lattice.count, 1)
+        out = np.zeros(cap * 16, dtype=np.float32)
+        self._call("camera_pose_lattice", _fptr(mat_to_abi(pose_M)), C.byref(lattice), _fptr(out), C.c_int(cap), C.byref(count))
+        return np.transpose(out[:16 * count.value].reshape(-1, 4, 4), (0, 2, 1)).copy()
 
     def _image_call(self, name, scene, rs, M, intr, image_type, download=True, out=None):
         """`out`: an existing (H, W) float32 / (H, W, 4) uint8 array to fill instead of a fresh one (e.g. a page-locked

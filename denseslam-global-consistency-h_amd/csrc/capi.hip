@@ -1426,6 +1426,40 @@ int default_register_params(const dslam_register_params *params, dslam_register_
   return DSLAM_OK;
 }
 
+// dslam_track_sdf_params with the zeros replaced by the defaults (params NULL: all defaults), checked against the view's size
+int default_track_sdf_params(const dslam_view *v, const dslam_track_sdf_params *params, dslam_track_sdf_params *out) {
+  dslam_track_sdf_params tp = {0, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0};
+  if (params) tp = *params;
+  DSLAM_REQUIRE(tp.no_hierarchy_levels >= 0 && tp.run_till_level >= 0 && tp.max_evaluations >= 0 && tp.min_valid >= 0 &&
+                    tp.residual_gate >= 0.0f && tp.term_rotation >= 0.0f && tp.term_translation_voxels >= 0.0f,
+                "a tracking parameter is negative (or not a number)");
+  if (tp.no_hierarchy_levels == 0) tp.no_hierarchy_levels = 3;
+  if (tp.max_evaluations == 0) tp.max_evaluations = 10;
+  if (tp.min_valid == 0) tp.min_valid = 500;
+  if (tp.residual_gate == 0.0f) tp.residual_gate = 0.75f;
+  if (tp.term_rotation == 0.0f) tp.term_rotation = 1e-5f;
+  if (tp.term_translation_voxels == 0.0f) tp.term_translation_voxels = 1e-3f;
+  DSLAM_REQUIRE(tp.no_hierarchy_levels <= DSLAM_TRACKER_MAX_LEVELS, "no_hierarchy_levels must be 1 .. DSLAM_TRACKER_MAX_LEVELS");
+  DSLAM_REQUIRE((v->w_d >> (tp.no_hierarchy_levels - 1)) > 0 && (v->h_d >> (tp.no_hierarchy_levels - 1)) > 0,
+                "too many hierarchy levels for this image size");
+  DSLAM_REQUIRE(tp.run_till_level < tp.no_hierarchy_levels, "run_till_level is not one of the levels");
+  *out = tp;
+  return DSLAM_OK;
+}
+
+// what dslam_score_camera_poses and dslam_track_camera_sdf_starts check alike: dslam_track_camera_sdf's checks, on a pose list
+int check_pose_list_call(dslam_engine *e, const char *call, const dslam_view *v, const dslam_scene *const *scenes, const float *T,
+                         int num_maps, const float *poses_M, int num_poses, const float *intr) {
+  DSLAM_REQUIRE(num_poses >= 1 && num_poses <= DSLAM_MAX_TRACK_STARTS,
+                std::string(call) + ": the number of poses must be 1 .. DSLAM_MAX_TRACK_STARTS");
+  DSLAM_TRY(check_map_list(e, call, scenes, T, num_maps, 1, true));
+  DSLAM_REQUIRE(v->engine == e, "the view belongs to another engine");
+  DSLAM_REQUIRE(v->updated, "the view was never updated");
+  for (int k = 0; k < num_poses; k++) DSLAM_TRY(check_rigid_transform(poses_M + 16 * k, "a pose of the list"));
+  for (int k = 0; k < 4; k++) DSLAM_REQUIRE(std::isfinite(intr[k]), "the intrinsics are not finite");
+  return DSLAM_OK;
+}
+
 int copy_sums(const SumChannel &ch, const char *none, double out[33]) {
   DSLAM_REQUIRE(ch.have_sums, none);
   memcpy(out, ch.last_sums, sizeof ch.last_sums);
@@ -1445,21 +1479,8 @@ int dslam_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_sce
   DSLAM_REQUIRE(v->updated, "the view was never updated");
   DSLAM_TRY(check_rigid_transform(pose_M, "the start pose"));
   for (int k = 0; k < 4; k++) DSLAM_REQUIRE(std::isfinite(intr[k]), "the intrinsics are not finite");
-  dslam_track_sdf_params tp = {0, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0};
-  if (params) tp = *params;
-  DSLAM_REQUIRE(tp.no_hierarchy_levels >= 0 && tp.run_till_level >= 0 && tp.max_evaluations >= 0 && tp.min_valid >= 0 &&
-                    tp.residual_gate >= 0.0f && tp.term_rotation >= 0.0f && tp.term_translation_voxels >= 0.0f,
-                "a tracking parameter is negative (or not a number)");
-  if (tp.no_hierarchy_levels == 0) tp.no_hierarchy_levels = 3;
-  if (tp.max_evaluations == 0) tp.max_evaluations = 10;
-  if (tp.min_valid == 0) tp.min_valid = 500;
-  if (tp.residual_gate == 0.0f) tp.residual_gate = 0.75f;
-  if (tp.term_rotation == 0.0f) tp.term_rotation = 1e-5f;
-  if (tp.term_translation_voxels == 0.0f) tp.term_translation_voxels = 1e-3f;
-  DSLAM_REQUIRE(tp.no_hierarchy_levels <= DSLAM_TRACKER_MAX_LEVELS, "no_hierarchy_levels must be 1 .. DSLAM_TRACKER_MAX_LEVELS");
-  DSLAM_REQUIRE((v->w_d >> (tp.no_hierarchy_levels - 1)) > 0 && (v->h_d >> (tp.no_hierarchy_levels - 1)) > 0,
-                "too many hierarchy levels for this image size");
-  DSLAM_REQUIRE(tp.run_till_level < tp.no_hierarchy_levels, "run_till_level is not one of the levels");
+  dslam_track_sdf_params tp;
+  DSLAM_TRY(default_track_sdf_params(v, params, &tp));
   e->view_reads++;  // (see dslam_engine::last_fence)
   return launch_track_camera_sdf(e, v, scenes, T_map_from_world, num_maps, pose_M, intr, &tp, result);
 }
@@ -1467,6 +1488,70 @@ int dslam_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_sce
 int dslam_debug_track_sdf_sums(dslam_engine *e, double out[33]) {
   DSLAM_REQUIRE(e && out, "null argument");
   return copy_sums(e->track_sdf_sums, "no depth-to-SDF tracking evaluation has run on this engine", out);
+}
+
+// ---- depth-to-SDF tracking from many start poses at once -----------------------------------------------------------
+
+int dslam_score_camera_poses(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T_map_from_world,
+                             int num_maps, const float *poses_M, int num_poses, const float intr[4], int level,
+                             float residual_gate, dslam_pose_score *scores_out) {
+  DSLAM_REQUIRE(e && v && scenes && T_map_from_world && poses_M && intr && scores_out, "null argument");
+  DSLAM_TRY(check_pose_list_call(e, "dslam_score_camera_poses", v, scenes, T_map_from_world, num_maps, poses_M, num_poses, intr));
+  DSLAM_REQUIRE(level >= 0 && level < DSLAM_TRACKER_MAX_LEVELS && (v->w_d >> level) > 0 && (v->h_d >> level) > 0,
+                "level is not a level of this view's pyramid");
+  DSLAM_REQUIRE(residual_gate >= 0.0f, "residual_gate is negative (or not a number)");
+  if (residual_gate == 0.0f) residual_gate = 0.75f;
+  e->view_reads++;  // (see dslam_engine::last_fence)
+  return launch_score_camera_poses(e, v, scenes, T_map_from_world, num_maps, poses_M, num_poses, intr, level, residual_gate,
+                                   scores_out);
+}
+
+int dslam_track_camera_sdf_starts(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes,
+                                  const float *T_map_from_world, int num_maps, float *poses_M, int num_starts, const float intr[4],
+                                  const dslam_track_sdf_params *params, dslam_track_sdf_result *results) {
+  DSLAM_REQUIRE(e && v && scenes && T_map_from_world && poses_M && intr && results, "null argument");
+  DSLAM_TRY(check_pose_list_call(e, "dslam_track_camera_sdf_starts", v, scenes, T_map_from_world, num_maps, poses_M, num_starts, intr));
+  dslam_track_sdf_params tp;
+  DSLAM_TRY(default_track_sdf_params(v, params, &tp));
+  e->view_reads++;  // (see dslam_engine::last_fence)
+  return launch_track_camera_sdf_starts(e, v, scenes, T_map_from_world, num_maps, poses_M, num_starts, intr, &tp, results);
+}
+
+int dslam_debug_track_sdf_start_sums(dslam_engine *e, int start, double out[33]) {
+  DSLAM_REQUIRE(e && out, "null argument");
+  const std::vector<double> &last = e->track_starts.last_sums;
+  DSLAM_REQUIRE(!last.empty(), "no dslam_track_camera_sdf_starts has run on this engine");
+  DSLAM_REQUIRE(start >= 0 && (size_t)start < last.size() / kRegSums, "start is not one of the most recent call's starts");
+  memcpy(out, &last[(size_t)start * kRegSums], kRegSums * sizeof(double));
+  return DSLAM_OK;
+}
+
+int dslam_select_start_poses(const dslam_pose_score *scores, int num, int min_valid, int max_keep, int32_t *kept_out,
+                             int32_t *num_kept_out) {
+  DSLAM_REQUIRE(scores && kept_out && num_kept_out, "null argument");
+  DSLAM_REQUIRE(num >= 1 && min_valid >= 0 && max_keep >= 0, "num must be at least 1, min_valid and max_keep not negative");
+  select_start_poses(scores, num, min_valid, max_keep, kept_out, num_kept_out);
+  return DSLAM_OK;
+}
+
+int dslam_camera_pose_lattice(const float pose_M[16], const dslam_pose_lattice *l, float *poses_out, int capacity,
+                              int32_t *count_out) {
+  DSLAM_REQUIRE(pose_M && l && poses_out && count_out, "null argument");
+  *count_out = 0;
+  DSLAM_REQUIRE(l->nr >= 0 && l->nt[0] >= 0 && l->nt[1] >= 0 && l->nt[2] >= 0, "a lattice count is negative");
+  long long count = 2LL * l->nr + 1;
+  for (int a = 0; a < 3; a++) count = std::min(count * (2LL * l->nt[a] + 1), (long long)INT32_MAX);
+  *count_out = (int32_t)count;
+  DSLAM_REQUIRE(l->step_t >= 0.0f && l->step_r >= 0.0f && std::isfinite(l->step_t) && std::isfinite(l->step_r),
+                "a lattice step is negative or not finite");
+  if (l->nr > 0) {
+    const double len2 = (double)l->axis[0] * l->axis[0] + (double)l->axis[1] * l->axis[1] + (double)l->axis[2] * l->axis[2];
+    DSLAM_REQUIRE(std::isfinite(len2) && len2 > 0.0, "the lattice's rotation axis is zero or not finite");
+  }
+  DSLAM_TRY(check_rigid_transform(pose_M, "the lattice's centre pose"));
+  DSLAM_REQUIRE(capacity >= 0 && count <= (long long)capacity, "the lattice has more nodes than poses_out holds");
+  camera_pose_lattice(pose_M, *l, poses_out);
+  return DSLAM_OK;
 }
 
 // ---- decay / sliding window ----------------------------------------------------------------------------------

@@ -155,6 +155,19 @@ struct SumChannel {
     have_sums = true;
   }
 };
+// dslam_score_camera_poses / dslam_track_camera_sdf_starts (track_sdf_starts.hip): their own scratch.  The tables exist
+// from the first call on; the rows grow on demand (a larger level or more poses in a round) and are never allocated per call.
+struct TrackStartsScratch {
+  DeviceBuffer<double> rows;             // [poses of a round][workgroups per pose][33], one row per workgroup of k_track_sdf_starts
+  size_t rows_capacity = 0;              // ... in doubles
+  PinnedBuffer<double> rows_host;        // mapped: the same rows when the host adds them (DSLAM_TRACK_STARTS_ROWS=host, a
+  size_t rows_host_capacity = 0;         // measurement's switch); never allocated otherwise
+  PinnedBuffer<float> poses_host;        // [DSLAM_MAX_TRACK_STARTS][12]: the P~ of a round on their way to the device
+  DeviceBuffer<float> poses;             // ... where the kernel reads them by scalar loads
+  PinnedBuffer<double> sums;             // mapped: [DSLAM_MAX_TRACK_STARTS][33], the totals k_track_sdf_row_sum writes
+  std::vector<double> last_sums;         // [starts][33]: each start's most recent evaluation in the most recent _starts call
+                                         // (dslam_debug_track_sdf_start_sums; test hook)
+};
 // bytes of one map descriptor (MultiMap, multimap_device.h) in dslam_engine::map_table
 constexpr size_t kMapDescriptorBytes = 80;
 }  // namespace dslam
@@ -238,6 +251,7 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   DeviceBuffer<void> map_table;
   dslam::SumChannel reg_sums;         // dslam_register_maps (register.hip)
   dslam::SumChannel track_sdf_sums;   // dslam_track_camera_sdf (track_sdf.hip)
+  dslam::TrackStartsScratch track_starts;   // dslam_score_camera_poses, dslam_track_camera_sdf_starts (track_sdf_starts.hip)
   dslam::MergeScratch merge;          // dslam_merge_maps (merge.hip)
   dslam::LiveLists live_lists;        // dslam_register_graph, dslam_survey_overlaps
   dslam::RegisterGraphScratch reg_graph;   // dslam_register_graph (register_graph.hip)
@@ -547,6 +561,18 @@ int build_depth_pyramid(dslam_engine *e, const dslam_view *v, int levels, const 
 int launch_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T_map_from_world,
                             int num_maps, float *pose_M, const float *intr, const dslam_track_sdf_params *params,
                             dslam_track_sdf_result *result);
+// arguments already checked by dslam_select_start_poses / dslam_camera_pose_lattice (host only)
+void select_start_poses(const dslam_pose_score *scores, int num, int min_valid, int max_keep, int32_t *kept_out, int32_t *num_kept_out);
+void camera_pose_lattice(const float pose_M[16], const dslam_pose_lattice &l, float *poses_out);
+bool track_sdf_pixels_in_tiles();   // which pixel takes which lane in the tracker's kernels (track_sdf.hip)
+// everything already checked (and params defaulted) by dslam_score_camera_poses / dslam_track_camera_sdf_starts; outputs are
+// written only by a call that succeeds
+int launch_score_camera_poses(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T_map_from_world,
+                              int num_maps, const float *poses_M, int num_poses, const float *intr, int level, float residual_gate,
+                              dslam_pose_score *scores_out);
+int launch_track_camera_sdf_starts(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes,
+                                   const float *T_map_from_world, int num_maps, float *poses_M, int num_starts, const float *intr,
+                                   const dslam_track_sdf_params *params, dslam_track_sdf_result *results);
 int launch_render(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float *M, const float *intr,
                   int type, bool reuse_raycast = false, void *image_out_override = nullptr);
 // scenes / T (N x 16, world -> map) already checked by dslam_get_image_multi

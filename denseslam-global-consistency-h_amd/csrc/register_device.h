@@ -11,6 +11,10 @@ namespace dslam {
 constexpr int kRegGrid = 512;      // workgroups of the registration kernels: two per CU of an MI355X
 constexpr int kRegThreads = 256;   // lane t takes voxels t and t + 256 of a block
 constexpr int kRegWaves = kRegThreads / 64;
+// the depth-to-SDF tracker's kernels (track_sdf.hip, track_sdf_starts.hip; the body of both is track_sdf_device.h)
+constexpr int kTrackSdfGrid = 512;      // workgroups: two per CU of an MI355X.  512 x 256 = 131072 lanes, so a level of
+                                        // more than 131072 pixels (640 x 480 has 307200) takes further trips of the loop
+constexpr int kTrackSdfThreads = kRegThreads;
 
 struct RegisterParams {
   const HashEntry *hash;     // the source

@@ -247,45 +247,85 @@ struct LmOutcome {
   bool accepted_any;
   double conditioning;   // conditioning_of the system at the accepted state; 0 for stop reason 3
 };
-template <class System, class Step>
-int lm_iterate(int n, bool start_ok, int max_evaluations, double term_rotation, double term_translation, System &&system,
-               Step &&step, LmOutcome &out) {
-  out.evaluations = 1;
-  out.stop = start_ok ? -1 : 3;
-  out.accepted_any = false;
-  out.conditioning = 0.0;
-  double lambda = 1.0;
-  std::vector<double> H((size_t)n * n), g(n), M, y(n);
-  while (out.stop < 0) {
-    if (out.evaluations >= max_evaluations) { out.stop = 1; break; }
-    system(H.data(), g.data());
-    M = H;
-    for (int i = 0; i < n; i++) M[(size_t)i * n + i] += lambda * H[(size_t)i * n + i];
-    solve_damped(M.data(), g.data(), n, y.data());
-    const int adopted = step(y.data());
-    if (adopted < 0) return adopted;
+// The iteration as a resumable stepper, for a caller that has the trials of many problems evaluated together
+// (track_sdf_starts.hip): begin(); then, while propose(system) returns true, have the state increment() leads to evaluated
+// and hand its outcome to verdict(adopted); then finish(system).  lm_iterate below is that loop around one problem.
+class LmStepper {
+ public:
+  LmOutcome out = {0, 3, false, 0.0};
+  void begin(int n, bool start_ok, int max_evaluations, double term_rotation, double term_translation) {
+    n_ = n; max_evaluations_ = max_evaluations; term_rotation_ = term_rotation; term_translation_ = term_translation;
+    out.evaluations = 1;
+    out.stop = start_ok ? -1 : 3;
+    out.accepted_any = false;
+    out.conditioning = 0.0;
+    lambda_ = 1.0;
+    H_.assign((size_t)n * n, 0.0);
+    g_.assign(n, 0.0);
+    y_.assign(n, 0.0);
+  }
+  // false: the iteration has stopped (out.stop says why); true: increment() is the step to try next
+  template <class System>
+  bool propose(System &&system) {
+    if (out.stop >= 0) return false;
+    if (out.evaluations >= max_evaluations_) { out.stop = 1; return false; }
+    const int n = n_;
+    system(H_.data(), g_.data());
+    M_ = H_;
+    for (int i = 0; i < n; i++) M_[(size_t)i * n + i] += lambda_ * H_[(size_t)i * n + i];
+    solve_damped(M_.data(), g_.data(), n, y_.data());
+    return true;
+  }
+  const double *increment() const { return y_.data(); }
+  // the proposed step has been evaluated: adopted (the caller's accepted state is now the trial) or rejected
+  void verdict(bool adopted) {
+    const int n = n_;
+    const std::vector<double> &y = y_;
     out.evaluations++;
     if (adopted) {
-      const double used = lambda;
+      const double used = lambda_;
       out.accepted_any = true;
-      lambda = std::max(lambda / 10.0, 1e-6);
+      lambda_ = std::max(lambda_ / 10.0, 1e-6);
       // (the largest block norm is below a threshold exactly when every block's is)
       bool small = true;
       for (int b = 0; b < n; b += 6) {
         const double rot = sqrt(y[b] * y[b] + y[b + 1] * y[b + 1] + y[b + 2] * y[b + 2]);
         const double tr = sqrt(y[b + 3] * y[b + 3] + y[b + 4] * y[b + 4] + y[b + 5] * y[b + 5]);
-        small = small && rot < term_rotation && tr < term_translation;
+        small = small && rot < term_rotation_ && tr < term_translation_;
       }
       if (used <= 1.0 && small) out.stop = 0;
     } else {
-      lambda *= 10.0;
-      if (lambda > 1e6) out.stop = 2;
+      lambda_ *= 10.0;
+      if (lambda_ > 1e6) out.stop = 2;
     }
   }
-  if (out.stop != 3) {
-    system(H.data(), g.data());
-    out.conditioning = conditioning_of(H.data(), n);
+  // after the stop: the conditioning at the accepted state
+  template <class System>
+  void finish(System &&system) {
+    if (out.stop != 3) {
+      system(H_.data(), g_.data());
+      out.conditioning = conditioning_of(H_.data(), n_);
+    }
   }
+  double lambda() const { return lambda_; }
+
+ private:
+  int n_ = 0, max_evaluations_ = 0;
+  double term_rotation_ = 0.0, term_translation_ = 0.0, lambda_ = 1.0;
+  std::vector<double> H_, g_, M_, y_;
+};
+template <class System, class Step>
+int lm_iterate(int n, bool start_ok, int max_evaluations, double term_rotation, double term_translation, System &&system,
+               Step &&step, LmOutcome &out) {
+  LmStepper lm;
+  lm.begin(n, start_ok, max_evaluations, term_rotation, term_translation);
+  while (lm.propose(system)) {
+    const int adopted = step(lm.increment());
+    if (adopted < 0) { out = lm.out; return adopted; }
+    lm.verdict(adopted != 0);
+  }
+  lm.finish(system);
+  out = lm.out;
   return 0;
 }
 

@@ -620,6 +620,57 @@ class ITMMainEngine {
     WorldPoseOf(current, Wf);
     return TrackListedMaps(current, scenes, T, Wf, out);
   }
+  /// (extension) Find the camera again from a pose that may be farther off than the truncation band -- after a tracking
+  /// loss, at a loop closure, against maps AlignLocalMaps has just moved -- where TrackAllLocalMaps finds no valid pixel
+  /// (DESIGN.md section 24).  The start is TrackAllLocalMaps' world -> camera pose of `current`.  In this order:
+  /// dslam_camera_pose_lattice builds `lattice` around it (world axes); dslam_score_camera_poses evaluates every node on
+  /// pyramid level scoreLevel in one launch; dslam_select_start_poses keeps the `keep` cheapest nodes with at least the
+  /// default parameters' min_valid (500) valid pixels; dslam_track_camera_sdf_starts tracks them in lock-step with the
+  /// default parameters.  The winner is the start with the lowest cost_last among those that end with valid_last >= 500
+  /// and a stop reason other than 3, ties to the lower index; pose_d = (its world -> camera) T_current^-1 is written back as
+  /// TrackAllLocalMaps writes it, `out` receives its result and the call returns true.  Without a winner pose_d is left
+  /// alone, `out` is zeroed and the call returns false.  Throws on a lattice of more than DSLAM_MAX_TRACK_STARTS nodes.
+  bool RelocaliseAllLocalMaps(ITMLocalMap *current, const dslam_pose_lattice &lattice, int scoreLevel, int keep,
+                              dslam_track_sdf_result *out = nullptr) {
+    if (view == nullptr) throw std::runtime_error("RelocaliseAllLocalMaps: no view yet (call UpdateView first)");
+    if (keep < 1 || keep > DSLAM_MAX_TRACK_STARTS) throw std::runtime_error("RelocaliseAllLocalMaps: keep must be 1 .. DSLAM_MAX_TRACK_STARTS");
+    std::vector<const dslam_scene *> scenes;
+    std::vector<float> T;
+    ListLocalMaps(scenes, T);
+    float Wf[16];
+    WorldPoseOf(current, Wf);
+    const int minValid = 500;   // dslam_track_sdf_params' default
+    const Vector4f k = view->calib->intrinsics_d.projectionParamsSimple.all;
+    std::vector<float> nodes((size_t)DSLAM_MAX_TRACK_STARTS * 16);
+    int32_t count = 0;
+    if (dslam_camera_pose_lattice(Wf, &lattice, nodes.data(), DSLAM_MAX_TRACK_STARTS, &count) != DSLAM_OK) {
+      if (count > DSLAM_MAX_TRACK_STARTS) throw std::runtime_error("RelocaliseAllLocalMaps: the lattice has more than DSLAM_MAX_TRACK_STARTS nodes");
+      dslam_check(DSLAM_ERR_INVALID, "dslam_camera_pose_lattice");
+    }
+    std::vector<dslam_pose_score> scores((size_t)count);
+    dslam_check(dslam_score_camera_poses(engine_, view->handle, scenes.data(), T.data(), (int)scenes.size(), nodes.data(), count, k.v,
+                                         scoreLevel, 0.0f, scores.data()), "dslam_score_camera_poses");
+    std::vector<int32_t> kept((size_t)keep);
+    int32_t numKept = 0;
+    dslam_check(dslam_select_start_poses(scores.data(), count, minValid, keep, kept.data(), &numKept), "dslam_select_start_poses");
+    if (out) memset(out, 0, sizeof *out);
+    if (numKept == 0) return false;
+    std::vector<float> starts((size_t)numKept * 16);
+    for (int s = 0; s < numKept; s++) memcpy(&starts[(size_t)s * 16], &nodes[(size_t)kept[(size_t)s] * 16], 16 * sizeof(float));
+    std::vector<dslam_track_sdf_result> results((size_t)numKept);
+    dslam_check(dslam_track_camera_sdf_starts(engine_, view->handle, scenes.data(), T.data(), (int)scenes.size(), starts.data(), numKept,
+                                              k.v, nullptr, results.data()), "dslam_track_camera_sdf_starts");
+    int winner = -1;
+    for (int s = 0; s < numKept; s++) {
+      const dslam_track_sdf_result &r = results[(size_t)s];
+      if (r.valid_last < minValid || r.stop_reason == 3) continue;
+      if (winner < 0 || r.cost_last < results[(size_t)winner].cost_last) winner = s;
+    }
+    if (winner < 0) return false;
+    if (out) *out = results[(size_t)winner];
+    WritePoseBack(current, &starts[(size_t)winner * 16]);
+    return true;
+  }
   /// (extension) Which local maps a camera view reaches (dslam_survey_views, law in DESIGN.md section 20): under the
   /// maps' estimatedGlobalPoses, `reach[i]` becomes the resident blocks of map i whose loosened sphere meets the frustum of
   /// the camera `M` (world -> camera, metres, column-major) with the image `size`, between nearM and farM metres (farM 0:
@@ -825,6 +876,11 @@ class ITMMainEngine {
                 "dslam_track_camera_sdf");
     if (out) *out = res;
     if (res.levels_stepped == 0) return false;
+    WritePoseBack(current, Wf);
+    return true;
+  }
+  /// pose_d = (world -> camera) T_current^-1 of `current`, composed in double (RigidInverse, RigidProduct), rounded to float32
+  static void WritePoseBack(ITMLocalMap *current, const float Wf[16]) {
     double Md[16], Tc[16], Wd[16], inv[16];
     for (int i = 0; i < 16; i++) {
       Wd[i] = (double)Wf[i];
@@ -835,7 +891,6 @@ class ITMMainEngine {
     Matrix4f M;
     for (int i = 0; i < 16; i++) M.m[i] = (float)Md[i];
     current->trackingState->pose_d->SetM(M);
-    return true;
   }
   /// dslam_survey_views of the listed maps from one camera: reach and nearest per map
   void SurveyListedMaps(const float M[16], const float intrinsics[4], Vector2i size, float nearM, float farM,

@@ -1088,6 +1088,77 @@ int dslam_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_sce
 /* Test hook: the 33 raw sums (pivot at the world origin) of the engine's most recent evaluation.  Error if none has run. */
 int dslam_debug_track_sdf_sums(dslam_engine *e, double out[33]);
 
+/* ---- depth-to-SDF tracking from many start poses at once ---------------------------------------- */
+/* dslam_track_camera_sdf promises nothing from farther away than the truncation band.  After a tracking loss, at a loop
+ * closure or against maps dslam_register_graph has just moved, a caller has a region of poses and not a pose; these calls
+ * try many of them for the price of a few: one kernel launch per round of evaluations, however
+ * many poses take part in it.  No counterpart in the reference.
+ *
+ * dslam_score_camera_poses: element k of scores_out is one evaluation (items 1 - 9 above) of poses_M[k] on `level` of the
+ * view's pyramid: candidates = N, valid, cost.  They are exactly the candidates, valid_last and cost_first
+ * dslam_track_camera_sdf returns for that pose with no_hierarchy_levels = level + 1, run_till_level = level,
+ * max_evaluations = 1 and the same residual_gate (0 -> 0.75): the kernel keeps the single call's partition of the pixels
+ * over 512 workgroups, its reduction order inside a workgroup, and adds a pose's workgroup rows in index order from +0.0.
+ * An element depends on its own pose alone: permuting the list permutes the outputs and changes nothing else.
+ *
+ * dslam_track_camera_sdf_starts: poses_M[k] and results[k] are, byte for byte, what dslam_track_camera_sdf returns when
+ * called alone from start k with the same arguments; a start whose single call would leave its pose untouched is left
+ * untouched.  Per pyramid level, coarse to fine, the iterations of all starts advance in lock-step, one launch per round
+ * over the starts that have not stopped at that level; a start that has stopped idles until the level ends (the
+ * trajectories do not depend on each other, so idling changes no outcome).
+ *
+ * Both are read-only on every map, touch no render state, version, memo or front-end record, and wait for the stream on
+ * synchronous and asynchronous engines.  DSLAM_ERR_INVALID with poses_M, results and scores_out untouched: every rejection
+ * of dslam_track_camera_sdf (a pose of the list in place of pose_M); num_poses / num_starts outside
+ * 1 .. DSLAM_MAX_TRACK_STARTS; level outside 0 .. DSLAM_TRACKER_MAX_LEVELS - 1 or with no pixel at this image size; a
+ * negative (or NaN) residual_gate. */
+#define DSLAM_MAX_TRACK_STARTS 256
+typedef struct {
+  int32_t candidates, valid;       /* N and the valid pixels of the evaluation */
+  float cost;                      /* item 9 */
+  int32_t pad;
+} dslam_pose_score;
+int dslam_score_camera_poses(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes,
+                             const float *T_map_from_world /* [num_maps][16] */, int num_maps,
+                             const float *poses_M /* [num_poses][16], world -> camera */, int num_poses,
+                             const float intrinsics_d[4], int level, float residual_gate /* 0 -> 0.75 */,
+                             dslam_pose_score *scores_out /* [num_poses] */);
+int dslam_track_camera_sdf_starts(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes,
+                                  const float *T_map_from_world /* [num_maps][16] */, int num_maps,
+                                  float *poses_M /* [num_starts][16]; in: starts, out: estimates */, int num_starts,
+                                  const float intrinsics_d[4], const dslam_track_sdf_params *params /* NULL: defaults */,
+                                  dslam_track_sdf_result *results /* [num_starts] */);
+/* Test hook: the 33 raw sums of the last evaluation of start `start` in the engine's most recent
+ * dslam_track_camera_sdf_starts -- what dslam_debug_track_sdf_sums gives after the single call from that start.  Error if
+ * no such call has run or `start` is not one of its starts. */
+int dslam_debug_track_sdf_start_sums(dslam_engine *e, int start, double out[33]);
+
+/* Host only, callable without a device (as dslam_select_view_maps is).
+ * dslam_select_start_poses: of scores[0 .. num), the poses with valid >= min_valid and a cost that is not NaN, ordered by
+ * cost ascending (ties: the lower index first); the first max_keep of them go to kept_out, their number to num_kept_out.
+ * DSLAM_ERR_INVALID: a NULL argument, num < 1, min_valid or max_keep negative. */
+int dslam_select_start_poses(const dslam_pose_score *scores, int num, int min_valid, int max_keep,
+                             int32_t *kept_out /* [max_keep] */, int32_t *num_kept_out);
+/* dslam_camera_pose_lattice: poses on a lattice of camera centres and of rotations about one axis around pose_M (world ->
+ * camera).  All arithmetic in double.  (R, c): the camera -> world rotation and the camera centre from the rigid inverse
+ * of pose_M; a^ = axis / |axis|.  Node (ir, iz, iy, ix), ir in [-nr, nr], ia in [-nt[a], nt[a]] (nt[0] counts x), has the
+ * centre c + step_t (ix, iy, iz) and the orientation Rot(a^, ir step_r) R (Rodrigues); its pose is the rigid inverse
+ * (R'^T, -R'^T c'), rounded to float32.  Nodes are listed with ir slowest and ix fastest; the node with all indices 0 is
+ * pose_M byte for byte.  count_out = (2 nr + 1)(2 nt[2] + 1)(2 nt[1] + 1)(2 nt[0] + 1) is always filled (0 when a count is
+ * negative).  DSLAM_ERR_INVALID with poses_out untouched: a NULL argument, a count above capacity, a negative count or a
+ * negative or non-finite step, a zero or non-finite axis with nr > 0, a non-finite pose_M or one whose rotation block is
+ * not orthonormal to 1e-4. */
+typedef struct {
+  int32_t nt[3];                   /* translation nodes to each side, per axis x, y, z (world) */
+  float step_t;                    /* metres */
+  int32_t nr;                      /* rotation nodes to each side */
+  float step_r;                    /* radians */
+  float axis[3];                   /* world; need not be normalised */
+  int32_t pad;
+} dslam_pose_lattice;
+int dslam_camera_pose_lattice(const float pose_M[16], const dslam_pose_lattice *l, float *poses_out /* [capacity][16] */,
+                              int capacity, int32_t *count_out);
+
 /* ---- state read-back (stats for the driver; bulk downloads for parity tests and checkpoints) ------ */
 int dslam_get_stats(dslam_engine *e, const dslam_scene *s, const dslam_render_state *r, dslam_stats *out);
 int dslam_download_hash_table(dslam_engine *e, const dslam_scene *s, dslam_hash_entry *out_host);
