@@ -463,6 +463,17 @@ int dslam_scene_create(dslam_engine *e, const dslam_scene_params *p, void *ext_v
     set_last_error("invalid scene parameters (buckets must be a power of two, entries a multiple of 16, 1<=max_w<=255)");
     return DSLAM_ERR_INVALID;
   }
+  // the march's 32-bit byte offsets (raycast.hip, gather_taps_batched) reach slot DSLAM_MAX_LOCAL_BLOCKS - 1 and no further
+  if (s->p.num_local_blocks > DSLAM_MAX_LOCAL_BLOCKS) {
+    const int asked = s->p.num_local_blocks;
+    delete s;
+    engine_release(e);
+    char msg[160];
+    snprintf(msg, sizeof msg, "num_local_blocks %d exceeds DSLAM_MAX_LOCAL_BLOCKS (%d blocks, 4 GiB of voxels)", asked,
+             DSLAM_MAX_LOCAL_BLOCKS);
+    set_last_error(msg);
+    return DSLAM_ERR_INVALID;
+  }
   s->n_entries = s->p.num_buckets + s->p.num_excess;
   const int rc = scene_allocate(e, s, ext_voxels);
   if (rc) {

@@ -372,7 +372,7 @@ __device__ __forceinline__ bool cast_ray(Vec4 &out, int x, int y, const RenderPa
       const unsigned ly[2] = {((unsigned)y0 & 7u) << 3, ((unsigned)(y0 + 1) & 7u) << 3};
       const unsigned lz[2] = {((unsigned)z0 & 7u) << 6, ((unsigned)(z0 + 1) & 7u) << 6};
       const char *vbytes = reinterpret_cast<const char *>(p.vol.voxels);
-      const unsigned off0 = (unsigned)base * 8u;  // base < 2^27 voxels -> < 2^30 bytes
+      const unsigned off0 = (unsigned)base * 8u;  // base < 2^29 voxels -> < 2^32 bytes (DSLAM_MAX_LOCAL_BLOCKS)
 #pragma unroll
       for (int k = 0; k < 8; k++) {
         const unsigned off = off0 + ((lx[k & 1] | ly[(k >> 1) & 1] | lz[k >> 2]) << 3);

@@ -273,7 +273,8 @@ template <class TVoxel, class TIndex> class ITMScene {
   dslam_scene *handle;
   ITMScene(const ITMLibSettings *settings, dslam_engine *eng) : ITMScene(settings, eng, settings->numLocalBlocks) {}
   /// (extension) ... with a voxel pool of `numLocalBlocks` blocks instead of the settings' (ITMMainEngine::CompactLocalMap:
-  /// a finished map in a pool as large as it needs); table geometry and scene parameters are the settings'
+  /// a finished map in a pool as large as it needs); table geometry and scene parameters are the settings'.  More than
+  /// DSLAM_MAX_LOCAL_BLOCKS blocks is refused by dslam_scene_create, which dslam_check turns into an exception
   ITMScene(const ITMLibSettings *settings, dslam_engine *eng, int numLocalBlocks) : counters_(nullptr), sceneParams(&settings->sceneParams), index(numLocalBlocks), handle(nullptr) {
     dslam_scene_params p;
     memset(&p, 0, sizeof(p));

@@ -43,6 +43,10 @@ extern "C" {
 #define DSLAM_DEFAULT_LOCAL_BLOCK_NUM 0x40000 /* SDF_LOCAL_BLOCK_NUM   */
 #define DSLAM_DEFAULT_BUCKET_NUM 0x100000     /* SDF_BUCKET_NUM        */
 #define DSLAM_DEFAULT_EXCESS_LIST_SIZE 0x20000 /* SDF_EXCESS_LIST_SIZE */
+/* Largest voxel pool of one scene: 4 GiB of voxels.  The ray march and its straddling-cell gather address a voxel by a
+ * 32-bit byte offset from the pool's base (4096 * slot + at most 4092, below 2^32 up to slot 0xfffff); dslam_scene_create
+ * refuses a larger num_local_blocks, for a pool of its own and for a caller's buffer alike. */
+#define DSLAM_MAX_LOCAL_BLOCKS 0x100000
 #define DSLAM_TRANSFER_BLOCK_NUM 0x1000       /* SDF_TRANSFER_BLOCK_NUM */
 #define DSLAM_MAX_RENDERING_BLOCKS (65536 * 4)
 /* local maps one dslam_get_image_multi call can draw (a bit each in a 64-bit mask per 8x8 pixel tile) */
@@ -84,7 +88,7 @@ typedef struct {
   float frustum_min;  /* viewFrustum_min, metres    (0.2)  */
   float frustum_max;  /* viewFrustum_max, metres    (3.0)  */
   int32_t stop_integrating_at_max_w;
-  int32_t num_local_blocks; /* SDF_LOCAL_BLOCK_NUM; 0 -> default */
+  int32_t num_local_blocks; /* SDF_LOCAL_BLOCK_NUM; 0 -> default; at most DSLAM_MAX_LOCAL_BLOCKS */
   int32_t num_buckets;      /* SDF_BUCKET_NUM, power of two; 0 -> default */
   int32_t num_excess;       /* SDF_EXCESS_LIST_SIZE; 0 -> default */
   int32_t use_swapping;     /* ITMLibSettings::useSwapping: allocate the host-side global cache */
@@ -208,7 +212,8 @@ int dslam_debug_inject_device_error(dslam_engine *e, dslam_scene *s, int bits);
 /* ---- scene ------------------------------------------------------------------------------------- */
 /* new ITMScene(sceneParams, useSwapping, memoryType) + ResetScene.  ext_voxel_blocks_dev may be NULL
  * (library allocates) or a caller-owned device buffer of num_local_blocks*512*8 bytes (e.g. a torch
- * tensor used as the RCCL all-gather buffer). */
+ * tensor used as the RCCL all-gather buffer).  DSLAM_ERR_INVALID, before anything is allocated: num_local_blocks above
+ * DSLAM_MAX_LOCAL_BLOCKS (with either kind of pool), or the parameters the error message names. */
 int dslam_scene_create(dslam_engine *e, const dslam_scene_params *p, void *ext_voxel_blocks_dev,
                        dslam_scene **out);
 int dslam_scene_destroy(dslam_scene *s);

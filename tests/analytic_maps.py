@@ -253,7 +253,10 @@ def build_map(geom, vs, mu, box_lo, box_hi, band=None, holes=0.0, seed=0, num_bu
 
 
 def upload(api, scene, m):
-    """Load map `m` into `scene` (HIP engine or oracle): hash table, pools, every voxel block."""
+    """Load map `m` into `scene` (HIP engine or oracle): hash table, pools, every voxel block.  A map that brings its own
+    `upload` (highslot_fixtures.relocate: no whole-pool `vba`) is loaded by that."""
+    if getattr(m, "upload", None) is not None:
+        return m.upload(api, scene, m)
     api.upload_scene_state(scene, m.hash, m.alloc_list, m.last_free, m.excess_list, m.last_free_ex)
     api.upload_voxel_blocks(scene, 0, m.vba)
 

@@ -22,7 +22,31 @@ def _entries(api, scene, rs):
     return e["ptr"].astype(np.int64), e["pos"].astype(np.int64)
 
 
+def _pool(api, scene, slots=None):
+    """The voxel pool as (voxels, slots): every slot (slots None), or -- for a pool too large to bring to the host -- the
+    blocks of `slots` (ascending), downloaded one contiguous run at a time."""
+    if slots is None:
+        return api.download_voxel_blocks(scene), None
+    import highslot_fixtures as hs
+    return hs.download_blocks(api, scene, slots), slots
+
+
+def _live_slots(api, scene):
+    h = api.download_hash_table(scene)
+    return np.sort(h["ptr"][h["ptr"] >= 0].astype(np.int64))
+
+
+def _places(slots, ptrs):
+    """Rows of a _pool download that hold the blocks `ptrs`."""
+    if slots is None:
+        return ptrs
+    at = np.searchsorted(slots, ptrs)
+    assert np.array_equal(slots[at], ptrs), "a visible block is not a live block"
+    return at
+
+
 def _compare_step(before, after, ptrs, pos, ref, what):
+    """`before`, `after`: the pool, or the rows of the live blocks with `ptrs` already mapped to rows (_places)."""
     got = after[ptrs]
     assert np.array_equal(got["w_depth"], ref["w_depth"]), f"{what}: depth weights differ ({(got['w_depth'] != ref['w_depth']).sum()} voxels)"
     assert np.array_equal(got["w_color"], ref["w_color"]), f"{what}: colour weights differ ({(got['w_color'] != ref['w_color']).sum()} voxels)"
@@ -35,14 +59,20 @@ def _compare_step(before, after, ptrs, pos, ref, what):
     assert np.array_equal(before[rest].view(np.uint64), after[rest].view(np.uint64)), f"{what}: a block outside the visible list changed"
 
 
-def check_integration(api, pkg, wl, frames, params, M_rgb_of=None, intr_rgb=None, wp=None, deintegrate=()):
+def check_integration(api, pkg, wl, frames, params, M_rgb_of=None, intr_rgb=None, wp=None, deintegrate=(), alloc_list=None,
+                      live_only=False):
     """Fuse `frames` one at a time; before each integrate the voxels are downloaded and the float64 update A.5 is
     applied to them.  Frames listed in `deintegrate` are then taken out again (A.11) and checked the same way.
-    Returns (updated voxel count, tie count, ties of axis-aligned poses) summed over the steps."""
+    Returns (updated voxel count, tie count, ties of axis-aligned poses) summed over the steps.
+    `alloc_list`: a full allocation list the fresh scene starts from, in place of the ascending one.  `live_only`: the
+    pool is too large for the host; each step downloads the live blocks by slot run, and "every other block unchanged"
+    then speaks of the live blocks outside the visible list."""
     if wp is not None:
         api.set_fusion_weight_params(*wp)
     try:
         scene = api.create_scene(params)
+        if alloc_list is not None:
+            api.upload_scene_state(scene, allocation_list=alloc_list, last_free_block_id=len(alloc_list) - 1)
         rs = api.create_render_state(scene, wl.W, wl.H)
         view = api.create_view(wl.W, wl.H)
         vs, mu, mw, stop = params.voxel_size, params.mu, params.max_w, bool(params.stop_integrating_at_max_w)
@@ -55,14 +85,15 @@ def check_integration(api, pkg, wl, frames, params, M_rgb_of=None, intr_rgb=None
             depth = api.download_view_depth(view)
             assert np.array_equal(depth, ref64.depth_to_float(mm).astype(np.float32)), "depth conversion (A.3)"
             if de:
-                before = api.download_voxel_blocks(scene)
+                before, slots = _pool(api, scene, _live_slots(api, scene) if live_only else None)
                 api.deprocess_frame(scene, view, rs, M, wl.intr, M_rgb=M_rgb, intr_rgb=intr_rgb)
             else:
                 api.allocate_scene_from_depth(scene, view, rs, M, wl.intr)
-                before = api.download_voxel_blocks(scene)
+                before, slots = _pool(api, scene, _live_slots(api, scene) if live_only else None)
                 api.integrate_into_scene(scene, view, rs, M, wl.intr, M_rgb=M_rgb, intr_rgb=intr_rgb)
-            after = api.download_voxel_blocks(scene)
+            after, _ = _pool(api, scene, slots)
             ptrs, pos = _entries(api, scene, rs)
+            ptrs = _places(slots, ptrs)
             ref, ties = ref64.integrate(before[ptrs], pos, depth, rgba, M, wl.intr, vs, mu, mw, M_rgb=M_rgb,
                                         intr_rgb=intr_rgb, stop_at_max=stop, wp=wp, deintegrate=de)
             what = f"{wl.name} frame {i}{' de-integrated' if de else ''}"
@@ -353,15 +384,16 @@ def _check_shading(api, pkg, scene, rs, m, M, intr, ref, a, sel, dist, xw):
 # ---------------------------------------------------------------------------------------------------------------------
 # mesh
 # ---------------------------------------------------------------------------------------------------------------------
-def check_mesh(api, pkg, m, surface_bound=None):
+def check_mesh(api, pkg, m, surface_bound=None, max_triangles=0):
     """The mesh triangle for triangle, in upstream's order (hash entries, voxels, table slots), against the float64
-    re-derivation; then its vertices against the analytic surface."""
+    re-derivation; then its vertices against the analytic surface.  `max_triangles`: the list's size, where the default
+    of 32 per pool slot would be sized by the pool and not by the map."""
     scene = api.create_scene(m.scene_params(pkg))
     am.upload(api, scene, m)
-    pos, _ = api.mesh_scene(scene)
+    pos, _ = api.mesh_scene(scene, max_triangles=max_triangles)
     ec, co = mct.load_small_tables()
     ref = ref64.mesh(m, co, ec, mct.load_table())
-    assert len(pos) < m.num_local_blocks * 32 - 1, "mesh saturated: size the map"
+    assert len(pos) < (max_triangles or m.num_local_blocks * 32) - 1, "mesh saturated: size the map"
     assert len(pos) == len(ref), f"{len(pos)} triangles, float64 re-derivation has {len(ref)}"
     got = pos.astype(np.float64) / np.float64(np.float32(m.vs))
     # 1e-5 voxel, plus the float32 rounding of the metric output (one ulp of the largest coordinate, in voxels)
