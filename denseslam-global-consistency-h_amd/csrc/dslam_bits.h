@@ -307,49 +307,4 @@ inline int launch_bits_select(dslam_engine *e, const unsigned *src_bits, int n_e
   return dump.write(e);
 }
 
-// The live lists of several maps of one call, in dslam_engine::live_lists: for every map of `wanted`, in that order, one
-// ordered compaction of its resident entries (Sel: the caller's own live-entry selection, a SelLive) into a range of its
-// own.  list_offset[i]: where map i's range begins (-1: not wanted); live[i]: how many entries it holds -- read back
-// behind a wait for the stream and clamped to [0, n_entries].
-template <class Sel>
-inline int fill_live_lists(dslam_engine *e, const dslam_scene *const *scenes, int n, const std::vector<int> &wanted,
-                           std::vector<int> &list_offset, std::vector<int> &live) {
-  list_offset.assign(n, -1);
-  live.assign(n, 0);
-  long long entries = 0;
-  int max_entries = 0, max_blocks = 0;
-  for (int i : wanted) {
-    list_offset[i] = (int)entries;
-    entries += scenes[i]->n_entries;
-  }
-  for (int i = 0; i < n; i++) {
-    max_entries = std::max(max_entries, scenes[i]->n_entries);
-    max_blocks = std::max(max_blocks, scenes[i]->p.num_local_blocks);
-  }
-  DSLAM_REQUIRE(entries <= 0x7fffffffLL, "the maps' hash tables together exceed the survey's 31-bit list index");
-  DSLAM_TRY(ensure_scratch(e, max_entries, max_blocks));
-  LiveLists &ll = e->live_lists;
-  if (!ll.live_list || ll.entries < (int)entries) {
-    DSLAM_HIP(hipStreamSynchronize(e->stream));   // (nothing in flight may still use the old set)
-    LiveLists grown;
-    grown.entries = std::max((int)entries, ll.entries);
-    DSLAM_TRY(grown.live_list.alloc((size_t)grown.entries));
-    DSLAM_TRY(grown.live_counts.alloc_zeroed((size_t)DSLAM_MAX_RENDER_MAPS, e->stream));
-    DSLAM_TRY(grown.live_counts_host.alloc((size_t)DSLAM_MAX_RENDER_MAPS));
-    ll = std::move(grown);
-  }
-  for (int i : wanted) {
-    const dslam_scene *s = scenes[i];
-    Sel sel;
-    sel.hash = s->hash;
-    DSLAM_TRY(launch_bits_select(e, s->alloc_bits, s->n_entries, sel, ll.live_list + list_offset[i], s->n_entries,
-                                 ll.live_counts + i, s->counters));
-  }
-  DSLAM_HIP(hipGetLastError());
-  DSLAM_HIP(hipMemcpyAsync(ll.live_counts_host, ll.live_counts, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  DSLAM_HIP(hipStreamSynchronize(e->stream));
-  for (int i : wanted) live[i] = std::min(std::max(ll.live_counts_host[i], 0), scenes[i]->n_entries);
-  return DSLAM_OK;
-}
-
 }  // namespace dslam

@@ -114,7 +114,7 @@ struct MergeScratch {
   PinnedBuffer<unsigned long long> changed;   // mapped: [workgroups] voxels changed, one count per workgroup of the merge's
                                               // block kernel; then [workgroups][3], one row per workgroup of the unmerge's
 };
-// The resident entries of several maps of one call (fill_live_lists, dslam_bits.h: dslam_register_graph's distinct sources,
+// The resident entries of several maps of one call (fill_live_lists, live_list.hip: dslam_register_graph's distinct sources,
 // dslam_survey_overlaps' maps), one range of live_list per map -- allocated by the first call, grown as a whole (built
 // aside, move-assigned); the list and counter slots other calls use are left alone.  One set per engine: both calls
 // enqueue on the engine's one stream and wait for it before they return, so neither sees the other's lists in flight.
@@ -607,6 +607,16 @@ int launch_survey_views(dslam_engine *e, const dslam_scene *const *scenes, const
 // arguments already checked (and params defaulted) by dslam_select_view_maps: the selection law of DESIGN.md section 20
 void select_view_maps(const int32_t *reach_blocks, const int32_t *nearest, int num_views, int num_maps,
                       const dslam_view_select_params &params, int32_t *maps_out, dslam_view_select_result *result);
+// live_list.hip: a bitmap of the hash table as an ordered list (one launch of k_bits_select each; enqueue only).
+// list_out[0 .. *count_out) = the entries of s with ptr >= 0, ascending; capacity s->n_entries, errors to s->counters
+int launch_live_list(dslam_engine *e, const dslam_scene *s, int *list_out, int *count_out);
+// list_out[0 .. *count_out) = the set bits of `bits`, ascending; capacity n_entries
+int launch_bits_list(dslam_engine *e, const unsigned *bits, int n_entries, int *list_out, int *count_out, SceneCounters *err_cnt);
+// The live lists of several maps of one call, in dslam_engine::live_lists: for every map of `wanted`, in that order, one
+// launch_live_list into a range of its own.  list_offset[i]: where map i's range begins (-1: not wanted); live[i]: how
+// many entries it holds -- read back behind a wait for the stream and clamped to [0, n_entries].
+int fill_live_lists(dslam_engine *e, const dslam_scene *const *scenes, int n, const std::vector<int> &wanted,
+                    std::vector<int> &list_offset, std::vector<int> &live);
 // src / dst / X / params already checked (and defaulted) by dslam_merge_maps
 int launch_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float *X,
                       const dslam_merge_params *params, dslam_merge_result *result, bool reuse_live = false);

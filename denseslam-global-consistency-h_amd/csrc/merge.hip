@@ -6,15 +6,17 @@
 //   X~ : source voxels -> destination voxels, Y~ its inverse; the first three rows, row-major, float32 (host: double).
 //   1. push    every source voxel with w_depth > 0, in the order (rank r of its entry among the resident entries, linear
 //              index l), key r * 512 + l + 1, names the destination block B = floor(X~ p + 0.5) >> 3 it falls into;
-//   2. passes  k_merge_mark looks every B up in the destination: a hit sets the entry's bit in `touched`, a miss does
-//              atomicMax(keys[slot], key) on the slot AllocateSceneFromDepth would use and sets the slot's request bits.
+//   2. passes  k_merge_mark (merge_walk of merge_device.h, shared with unmerge.hip) looks every B up in the destination:
+//              a hit sets the entry's bit in `touched`, a miss does atomicMax(keys[slot], key) on the slot
+//              AllocateSceneFromDepth would use and sets the slot's request bits.
 //              Three ordered selections (dslam_bits.h) then serve the requests in hash-index order: over q1 and over q2
 //              to give every request its rank among those of its own type, over q1 | q2 to give it its rank among all --
 //              with both the closed form of DESIGN.md section 3 says whether the pools still hold a block for it and
 //              which.  The winner's B is recomputed from its key.  One small read-back per pass tells the host whether
 //              another pass is needed (different blocks that asked for the same slot).
-//   3. pull    k_merge_blocks: one workgroup per touched destination block at a time (fixed grid, grid-stride over the
-//              ordered list of touched entries), lane t the voxels 2t and 2t + 1 -- the block moves as 16-byte accesses.
+//   3. pull    k_merge_blocks (merge_pull of merge_device.h, shared with unmerge.hip): one workgroup per touched
+//              destination block at a time (fixed grid, grid-stride over the ordered list of touched entries), lane t
+//              the voxels 2t and 2t + 1 -- the block moves as 16-byte accesses.
 //              Each voxel reads the source trilinearly at Y~ p' (merge_resample of merge_device.h, shared with unmerge.hip:
 //              to_map / gather_cell / lerp8 of multimap_device.h), packs the result as a voxel and merges it with
 //              combine_voxel (combine_device.h), as a swap-in does.
@@ -33,9 +35,6 @@
 
 namespace dslam {
 
-// its own type: the selection kernel of this translation unit is not mesh.hip's
-struct SelLiveMerge : SelLive {};
-
 __global__ void k_merge_begin(SceneCounters *cnt, MergeCounters *mc) {
   cnt->base_free = cnt->last_free;
   cnt->base_free_ex = cnt->last_free_ex;
@@ -50,64 +49,23 @@ __global__ void k_merge_end(SceneCounters *cnt, const MergeCounters *mc) {
   cnt->last_free_ex = cnt->base_free_ex - mc->served2;
 }
 
-struct MergeMarkParams {
-  const HashEntry *src_hash;
-  const uint2 *src_voxels;
-  const int *live_list;
-  MultiMap fwd;              // T = X~ (its map pointers are not used)
-  const HashEntry *dst_hash;
-  unsigned mask;
-  int num_buckets;
+struct MergeMarkParams : MergeWalkParams {
   unsigned *keys, *q1, *q2, *req, *touched;
   MergeCounters *mc;
 };
 
+// a hit sets the entry's bit in `touched`; a miss asks for the slot the probe stopped at, with the voxel's key
 __global__ __launch_bounds__(kMergeThreads) void k_merge_mark(MergeMarkParams p) {
-  const int live = p.mc->live;
-  const int lane = threadIdx.x & 63;
-  int n_cand = 0, n_oor = 0;
-  for (int job = blockIdx.x * 2; job < live * 2; job += (job & 1) ? gridDim.x * 2 - 1 : 1) {
-    const int r = job >> 1, l = (int)threadIdx.x + kMergeThreads * (job & 1);
-    const HashEntry he = load_entry(p.src_hash, p.live_list[r]);
-    bool cand = false;
-    int B[3] = {0, 0, 0};
-    if (he.ptr >= 0) {  // (uniform; a live entry holds a block)
-      const unsigned own = p.src_voxels[(size_t)he.ptr * kBlock3 + l].x;
-      if (((own >> 16) & 0xffu) != 0u) {
-        n_cand++;
-        cand = merge_target(p.fwd, he, l, B);
-        n_oor += cand ? 0 : 1;
-      }
-    }
-    // Neighbouring lanes are neighbouring voxels of a row and mostly fall into the same block: a lane whose right
-    // neighbour asks for the same block leaves the probe to it (keys grow with the lane, so the prober's is the largest)
-    const int rc = __shfl_down((int)cand, 1, 64), rx = __shfl_down(B[0], 1, 64), ry = __shfl_down(B[1], 1, 64), rz = __shfl_down(B[2], 1, 64);
-    if (!cand || (lane < 63 && rc && rx == B[0] && ry == B[1] && rz == B[2])) continue;
-    int h = hash_index(B[0], B[1], B[2], p.mask);
-    HashEntry e = load_entry(p.dst_hash, h);   // one 16-byte load per chain step
-    bool found = e.pos[0] == B[0] && e.pos[1] == B[1] && e.pos[2] == B[2] && e.ptr >= -1;
-    if (!found && e.ptr >= -1) {
-      while (e.offset >= 1) {
-        h = p.num_buckets + e.offset - 1;
-        e = load_entry(p.dst_hash, h);
-        if (e.pos[0] == B[0] && e.pos[1] == B[1] && e.pos[2] == B[2] && e.ptr >= -1) { found = true; break; }
-      }
-    }
-    const unsigned bit = 1u << (h & 31);
-    if (found) {
-      if (!(p.touched[h >> 5] & bit)) atomicOr(&p.touched[h >> 5], bit);
+  merge_walk<2>(p, p.mc, [&](const MergeProbe &pr, int r, int l, int, int *) {
+    if (pr.found) {
+      merge_touch(p.touched, pr.h);
     } else {
-      atomicMax(&p.keys[h], (unsigned)r * (unsigned)kBlock3 + (unsigned)l + 1u);
-      atomicOr(&(e.ptr >= -1 ? p.q2 : p.q1)[h >> 5], bit);
-      atomicOr(&p.req[h >> 5], bit);
+      const unsigned bit = 1u << (pr.h & 31);
+      atomicMax(&p.keys[pr.h], (unsigned)r * (unsigned)kBlock3 + (unsigned)l + 1u);
+      atomicOr(&(pr.in_use ? p.q2 : p.q1)[pr.h >> 5], bit);
+      atomicOr(&p.req[pr.h >> 5], bit);
     }
-  }
-  // integer counts: the order of the additions does not matter
-  for (int d = 32; d > 0; d >>= 1) { n_cand += __shfl_xor(n_cand, d, 64); n_oor += __shfl_xor(n_oor, d, 64); }
-  if (lane == 0 && n_cand) {
-    atomicAdd(&p.mc->candidates, (unsigned long long)n_cand);
-    if (n_oor) atomicAdd(&p.mc->out_of_range, (unsigned long long)n_oor);
-  }
+  });
 }
 
 // rank of a request among the requests of its own type
@@ -170,45 +128,9 @@ struct SelMergeServe {
   __device__ void finish(int) const {}
 };
 
-struct SelMergeTouched {
-  DSLAM_SEL_NO_LOAD
-  __device__ bool test(int, const NoPayload &) const { return true; }
-  __device__ void prologue() const {}
-  __device__ int emit(int, int, bool, const NoPayload &) const { return 0; }
-  __device__ void finish(int) const {}
-};
-
+// p.changed: [gridDim.x] voxels changed, summed by the host
 __global__ __launch_bounds__(kMergeThreads) void k_merge_blocks(MergeBlockParams p) {
-  const int n = p.mc->touched;
-  const VolumeRef vol = volume_of(p.src);
-  const int tid = threadIdx.x;
-  const int x = (tid & 3) * 2, y = (tid >> 2) & 7, z = tid >> 5;
-  int changed = 0;
-  for (int i = blockIdx.x; i < n; i += gridDim.x) {
-    const HashEntry he = load_entry(p.dst_hash, p.touched_list[i]);
-    if (he.ptr < 0) continue;  // (uniform; a touched entry holds a block)
-    uint4 *blk = p.dst_voxels + (size_t)he.ptr * (kBlock3 / 2);
-    const uint4 was = blk[tid];
-    uint4 d = was;
-    const int px = he.pos[0] * kBlock + x, py = he.pos[1] * kBlock + y, pz = he.pos[2] * kBlock + z;
-    const uint2 s0 = merge_resample(p, vol, px, py, pz);
-    const uint2 s1 = merge_resample(p, vol, px + 1, py, pz);
-    combine_voxel(s0.x, s0.y, d.x, d.y, p.max_w);
-    combine_voxel(s1.x, s1.y, d.z, d.w, p.max_w);
-    const int c = (int)(d.x != was.x || d.y != was.y) + (int)(d.z != was.z || d.w != was.w);
-    if (c) blk[tid] = d;
-    changed += c;
-  }
-  // one count per workgroup, summed by the host (a workgroup without a block writes its zero)
-  __shared__ int red[kMergeThreads / 64];
-  for (int dlt = 32; dlt > 0; dlt >>= 1) changed += __shfl_xor(changed, dlt, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = changed;
-  __syncthreads();
-  if (tid == 0) {
-    unsigned long long v = 0;
-    for (int w = 0; w < kMergeThreads / 64; w++) v += (unsigned long long)red[w];
-    p.changed[blockIdx.x] = v;
-  }
+  merge_pull<1>(p, [max_w = p.max_w](unsigned slo, unsigned shi, unsigned &dlo, unsigned &dhi, int *) { combine_voxel(slo, shi, dlo, dhi, max_w); });
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
@@ -255,32 +177,22 @@ struct PhaseClock {
 // count are those an unmerge of the same source has just left in the scratch (dslam_remerge_maps)
 int launch_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float *X_in,
                       const dslam_merge_params *mp, dslam_merge_result *res, bool reuse_live) {
-  DSLAM_TRY(ensure_scratch(e, std::max(src->n_entries, dst->n_entries), std::max(src->p.num_local_blocks, dst->p.num_local_blocks)));
-  DSLAM_TRY(ensure_merge_scratch(e, src->n_entries, dst->n_entries));
+  MultiMap fwd, inv;
+  DSLAM_TRY(merge_begin(e, src, dst, X_in, fwd, inv));
   MergeScratch &m = e->merge;
   const int N = dst->n_entries;
   unsigned *q1 = m.bits, *q2 = m.bits + m.words, *req = m.bits + 2 * (size_t)m.words, *touched = m.bits + 3 * (size_t)m.words;
   MergeCounters *mc = m.counters;
 
-  MultiMap fwd, inv;
-  merge_transforms(src, X_in, fwd, inv);
-
   for (double &ms : e->merge_phase_ms) ms = 0.0;
   PhaseClock clock(e);
   DSLAM_HIP(hipMemsetAsync(m.bits, 0, (size_t)m.words * 4 * sizeof(unsigned), e->stream));
-  if (!reuse_live) {
-    SelLiveMerge live;
-    live.hash = src->hash;
-    DSLAM_TRY(launch_bits_select(e, src->alloc_bits, src->n_entries, live, m.live_list, src->n_entries, &mc->live, src->counters));
-  }
+  if (!reuse_live) DSLAM_TRY(launch_live_list(e, src, m.live_list, &mc->live));
   DSLAM_HIP(hipGetLastError());
   DSLAM_TRY(clock.lap(0));
 
   MergeMarkParams kp;
-  memset(&kp, 0, sizeof kp);
-  kp.src_hash = src->hash; kp.src_voxels = src->voxels; kp.live_list = m.live_list;
-  kp.fwd = fwd;
-  kp.dst_hash = dst->hash; kp.mask = (unsigned)(dst->p.num_buckets - 1); kp.num_buckets = dst->p.num_buckets;
+  merge_fill_walk(kp, e, src, dst, fwd);
   kp.keys = m.keys; kp.q1 = q1; kp.q2 = q2; kp.req = req; kp.touched = touched; kp.mc = mc;
 
   SelMergeRank rank;
@@ -325,19 +237,8 @@ int launch_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst,
       break;
     }
   }
-  SelMergeTouched sel_touched;
-  DSLAM_TRY(launch_bits_select(e, touched, N, sel_touched, m.touched_list, N, &mc->touched, dst->counters));
-  MergeBlockParams bp;
-  memset(&bp, 0, sizeof bp);
-  bp.dst_hash = dst->hash; bp.dst_voxels = reinterpret_cast<uint4 *>(dst->voxels);
-  bp.touched_list = m.touched_list; bp.mc = mc;
-  bp.src = inv;
-  bp.max_w = dst->p.max_w; bp.with_colour = mp->with_colour;
-  bp.changed = m.changed.device();
-  DSLAM_TRY(clock.lap(2));   // (the ordered list of touched entries counts as selection work)
-  hipLaunchKernelGGL(k_merge_blocks, dim3(kMergeGrid), dim3(kMergeThreads), 0, e->stream, bp);
-  dbg_sync(e, "k_merge_blocks");
-  DSLAM_HIP(hipGetLastError());
+  // (the ordered list of touched entries counts as selection work)
+  DSLAM_TRY(merge_pull_touched(e, dst, inv, mp->with_colour, k_merge_blocks, "k_merge_blocks", m.changed.device(), [&] { return clock.lap(2); }));
   DSLAM_TRY(clock.lap(3));
   DSLAM_HIP(hipMemcpyAsync(host, mc, sizeof(MergeCounters), hipMemcpyDeviceToHost, e->stream));
   DSLAM_HIP(hipStreamSynchronize(e->stream));

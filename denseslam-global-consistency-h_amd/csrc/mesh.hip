@@ -4,7 +4,7 @@
 // Upstream's CPU engine walks the hash table in entry order, each block in z, y, x order, and appends each cube's
 // triangles in table order; its CUDA engine appends with one atomicAdd per triangle, so its output order changes
 // from run to run.  Here the order is the CPU engine's, reproduced without atomics:
-//   live list   the entries with ptr >= 0, ascending: one ordered selection over the scene's alloc_bits
+//   live list   the entries with ptr >= 0, ascending: launch_live_list (live_list.hip)
 //   count       one 512-thread workgroup per live block, one voxel per thread: cube case -> triangles per block
 //   scan        exclusive scan of the per-block counts (one workgroup)
 //   emit        same cube evaluation; an in-workgroup scan in voxel order gives every triangle its final slot
@@ -15,7 +15,7 @@
 // path -- no roofline claim.
 #include <hip/hip_runtime.h>
 
-#include "dslam_bits.h"
+#include "dslam_internal.h"
 #include "mc_tables.h"
 #include "mesh_device.h"
 
@@ -162,7 +162,7 @@ int launch_mesh_scene(dslam_engine *e, const dslam_scene *s, int max_triangles, 
   int rc = ensure_scratch(e, N, s->p.num_local_blocks);
   if (rc) return rc;
   int *live_count = e->misc_counter + 8, *total = e->misc_counter + 9;
-  launch_bits_select(e, s->alloc_bits, N, SelLive{s->hash}, e->list_a, N, live_count, s->counters);
+  DSLAM_TRY(launch_live_list(e, s, e->list_a, live_count));
   MeshParams p;
   p.hash = s->hash; p.voxels = s->voxels; p.num_buckets = s->p.num_buckets; p.mask = (unsigned)(s->p.num_buckets - 1);
   p.live_list = e->list_a; p.live_count = live_count; p.block_counts = e->list_b; p.block_offsets = e->list_c;

@@ -1,23 +1,13 @@
 // mesh_device.h -- what mesh.hip (one scene) and multimesh.hip (several posed scenes) share of the marching-cubes export:
-// the live-list selection, findVoxel's block search and sdfInterp's zero crossing.
+// findVoxel's block search and sdfInterp's zero crossing.  (The live list both walk comes from launch_live_list, live_list.hip.)
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "dslam_bits.h"
+#include "dslam_internal.h"
 
 #pragma clang fp contract(off)
 
 namespace dslam {
-
-// the live list: every entry with a resident block, ascending -- the scene's alloc_bits as a list (dslam_bits.h)
-struct SelLive {
-  DSLAM_SEL_NO_LOAD
-  const HashEntry *hash;
-  __device__ bool test(int t, const NoPayload &) const { return hash[t].ptr >= 0; }
-  __device__ void prologue() const {}
-  __device__ int emit(int, int, bool, const NoPayload &) const { return 0; }
-  __device__ void finish(int) const {}
-};
 
 // findVoxel's block search: walk the bucket's chain for a resident block at (bx, by, bz); -1 when there is none
 __device__ __forceinline__ int find_block_ptr(const HashEntry *hash, int num_buckets, unsigned mask, int bx, int by, int bz) {

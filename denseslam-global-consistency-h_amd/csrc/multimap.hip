@@ -254,16 +254,14 @@ int launch_render_multi(dslam_engine *e, const dslam_scene *const *scenes, const
   int rc = ensure_multi_buffers(r);
   if (rc) return rc;
   const int cw = (r->w + 7) / 8, ch = (r->h + 7) / 8;
-  MultiMap maps[DSLAM_MAX_RENDER_MAPS];
-  // (posed_map divides the translation in double and rounds; the float32 division this loop used to do gives the same bits)
-  for (int i = 0; i < n; i++) maps[i] = posed_map(scenes[i], T + 16 * i, (double)scenes[0]->p.voxel_size);
-  DSLAM_HIP(hipMemcpyAsync(e->map_table, maps, (size_t)n * sizeof(MultiMap), hipMemcpyHostToDevice, e->stream));
+  // (posed_map divides the translation in double and rounds; the float32 division this call used to do gives the same bits)
+  DSLAM_TRY(upload_posed_maps(e, scenes, T, n, (double)scenes[0]->p.voxel_size));
   // front end: map i seen from M is a camera at M T_i^-1 (the identity keeps M bit for bit)
   for (int i = 0; i < n; i++) {
     const dslam_scene *s = scenes[i];
     const float *Ti = T + 16 * i;
     float Mi[16];
-    if (maps[i].identity) {
+    if (is_identity16(Ti)) {
       memcpy(Mi, M, sizeof(Mi));
     } else {
       float Tinv[16];

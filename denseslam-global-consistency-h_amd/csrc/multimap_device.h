@@ -39,6 +39,13 @@ inline MultiMap posed_map(const dslam_scene *s, const float *T16, double voxel_s
   m.identity = is_identity16(T16) ? 1 : 0;
   return m;
 }
+// the posed descriptors of a call's n maps, in list order, to dslam_engine::map_table (enqueued on the engine's stream)
+inline int upload_posed_maps(dslam_engine *e, const dslam_scene *const *scenes, const float *T, int n, double voxel_size) {
+  MultiMap maps[DSLAM_MAX_RENDER_MAPS];
+  for (int i = 0; i < n; i++) maps[i] = posed_map(scenes[i], T + 16 * i, voxel_size);
+  DSLAM_HIP(hipMemcpyAsync(e->map_table, maps, (size_t)n * sizeof(MultiMap), hipMemcpyHostToDevice, e->stream));
+  return DSLAM_OK;
+}
 
 // lowest set bit of a wave-uniform mask, as a scalar
 __device__ __forceinline__ int first_map(unsigned long long mk) {

@@ -28,7 +28,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "dslam_bits.h"
+#include "dslam_internal.h"
 #include "mc_tables.h"
 #include "mesh_device.h"
 #include "multimap_device.h"
@@ -60,9 +60,6 @@ struct MultiMeshParams {
   float factor;
   int limit;                 // triangles of this map with rank >= limit are dropped
 };
-
-// its own type: the selection kernel of this translation unit is not mesh.hip's
-struct SelLiveMulti : SelLive {};
 
 __device__ __forceinline__ int mm_triangles_of_case(int cube) {
   int n = 0;
@@ -375,10 +372,7 @@ int launch_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, c
         }
       }
       DSLAM_HIP(hipMemcpyAsync(e->map_table, row, (size_t)n * sizeof(MultiMap), hipMemcpyHostToDevice, e->stream));
-      const int N = s->n_entries;
-      SelLiveMulti sel;
-      sel.hash = s->hash;
-      launch_bits_select(e, s->alloc_bits, N, sel, e->list_a, N, live_count, s->counters);
+      DSLAM_TRY(launch_live_list(e, s, e->list_a, live_count));
       MultiMeshParams p;
       p.hash = s->hash; p.voxels = s->voxels; p.num_buckets = s->p.num_buckets; p.mask = (unsigned)(s->p.num_buckets - 1);
       p.live_list = e->list_a; p.live_count = live_count; p.block_counts = e->list_b; p.block_offsets = e->list_c;

@@ -7,7 +7,7 @@
 // shared when d holds a resident block at floor(q) >> 3.  Only hash entries are read, never a voxel; all maps are only
 // read; the counts are integers, so the result is exact and the same on every run.
 //
-// Device work per call: one ordered compaction of the resident entries of every map (fill_live_lists, dslam_bits.h) into
+// Device work per call: one ordered compaction of the resident entries of every map (fill_live_lists, live_list.hip) into
 // the engine's live lists, one read-back of the counts, one copy of the call's tables to the device, and k_survey_overlaps,
 // once: a fixed grid of kSurveyGrid workgroups, cut by the host into one contiguous range per SOURCE map in proportion to
 // the live counts (split_workgroups, the rule of dslam_register_graph with maps in place of pairs).  A source's live
@@ -24,7 +24,7 @@
 #include <numeric>
 #include <vector>
 
-#include "dslam_bits.h"
+#include "dslam_internal.h"
 #include "mesh_device.h"
 #include "register_host.h"
 
@@ -63,8 +63,6 @@ struct SurveyParams {
   int *rows;                 // [gridDim.x][2 N]: shared blocks, then shared octants, per destination
 };
 
-// its own type: the selection kernel of this translation unit is not mesh.hip's
-struct SelLiveSurvey : SelLive {};
 
 // Does the map hold a resident entry at block (bx, by, bz)?  The ordinary walk -- bucket head, then the excess chain --
 // with two guards a well-formed table never meets: a link that leaves the table ends the walk, and so does a chain longer
@@ -168,7 +166,7 @@ int launch_survey_overlaps(dslam_engine *e, const dslam_scene *const *scenes, co
   // ---- the live lists of all maps ----
   std::vector<int> all(n), list_offset, live, first_wg(n, 0), num_wg(n, 0);
   std::iota(all.begin(), all.end(), 0);
-  DSLAM_TRY(fill_live_lists<SelLiveSurvey>(e, scenes, n, all, list_offset, live));
+  DSLAM_TRY(fill_live_lists(e, scenes, n, all, list_offset, live));
   DSLAM_TRY(ensure_overlap_scratch(e));
   OverlapScratch &sc = e->overlap;
   split_workgroups(kSurveyGrid, all, live, first_wg, num_wg);

@@ -4,7 +4,7 @@
 // Reference: none; the law is this project's own.  Every value moved is an integer or a bit pattern.
 //
 // Pack, all on the engine's stream:
-//   ranks     one ordered selection over alloc_bits (launch_bits_select, SelLive): list_a[k] = hash index of the k-th
+//   ranks     the live list (launch_live_list, live_list.hip): list_a[k] = hash index of the k-th
 //             resident entry, its length n read back together with the scene's counters (f = last_free_ex + 1) -- the one
 //             wait of a size query, and what a pack needs before it can name blocks_offset;
 //   records   k_pack_records: record k = the entry's pos and offset with ptr = its hash index (one 16-byte store per lane),
@@ -24,14 +24,12 @@
 // Bound: bytes.  2 to 37 VGPRs, no scratch (the compiler's table).
 #include <cstring>
 
-#include "dslam_bits.h"
+#include "dslam_internal.h"
 #include "mesh_device.h"
 #include "pack_host.h"
 
 namespace dslam {
 
-// its own type: the selection kernel of this translation unit is not mesh.hip's
-struct SelLivePack : SelLive {};
 
 constexpr int kPackGrid = 512;       // workgroups of the block kernels (two per CU: 128 KiB in flight per trip and CU)
 constexpr int kPackThreads = 256;    // one 4096-byte block = 256 lanes x 16 bytes
@@ -125,9 +123,7 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_blocks(const HashEntry *_
 static int pack_counts(dslam_engine *e, const dslam_scene *s, int *n_out, int *f_out) {
   DSLAM_TRY(ensure_scratch(e, s->n_entries, s->p.num_local_blocks));
   int *count = e->misc_counter + 8;
-  SelLivePack sel;
-  sel.hash = s->hash;
-  DSLAM_TRY(launch_bits_select(e, s->alloc_bits, s->n_entries, sel, e->list_a, s->n_entries, count, s->counters));
+  DSLAM_TRY(launch_live_list(e, s, e->list_a, count));
   DSLAM_HIP(hipGetLastError());
   char *host = reinterpret_cast<char *>(e->pinned.get());
   SceneCounters *sc = reinterpret_cast<SceneCounters *>(host);

@@ -19,7 +19,7 @@
 //   sums              33 doubles of float32 products: [0..20] lower triangle of sum A^T A row by row, [21..26] sum b A,
 //                     [27] sum b^2, [28] valid, [29..31] sum q over valid voxels, [32] N.
 //
-// Device work per call: one ordered compaction of the source's resident entries (launch_bits_select) and, per
+// Device work per call: one ordered compaction of the source's resident entries (launch_live_list, live_list.hip) and, per
 // evaluation, k_register: a fixed grid, workgroup i takes live blocks i, i + grid, ..., lane t voxels t and t + 256 of the
 // block (coalesced 8-byte loads); the candidate gate comes first, so only the band's voxels gather.  The reduction is
 // the tracker's: per-lane doubles, wave shuffle tree (32, 16, ..., 1), the four wave partials through LDS in index
@@ -31,7 +31,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "dslam_bits.h"
+#include "dslam_internal.h"
 #include "register_device.h"
 #include "register_host.h"
 
@@ -39,8 +39,6 @@
 
 namespace dslam {
 
-// its own type: the selection kernel of this translation unit is not mesh.hip's
-struct SelLiveRegister : SelLive {};
 
 __global__ __launch_bounds__(kRegThreads) void k_register(RegisterParams p) {
 #define DSLAM_REG_FIRST blockIdx.x
@@ -57,10 +55,7 @@ int launch_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_sc
   DSLAM_TRY(ensure_scratch(e, std::max(src->n_entries, dst->n_entries), std::max(src->p.num_local_blocks, dst->p.num_local_blocks)));
   DSLAM_TRY(e->reg_sums.ensure(kRegGrid));
   int *live_count = e->misc_counter + 8;
-  const int N = src->n_entries;
-  SelLiveRegister sel;
-  sel.hash = src->hash;
-  DSLAM_TRY(launch_bits_select(e, src->alloc_bits, N, sel, e->list_a, N, live_count, src->counters));
+  DSLAM_TRY(launch_live_list(e, src, e->list_a, live_count));
   DSLAM_HIP(hipGetLastError());
 
   RegisterParams kp;

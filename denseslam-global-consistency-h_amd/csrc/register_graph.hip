@@ -6,7 +6,7 @@
 // (section 13, register_device.h) at X~_p = T~_d inv(T~_s).  All maps are only read.
 //
 // Device work per call: one ordered compaction of the resident entries of every distinct source map (fill_live_lists,
-// dslam_bits.h) into the engine's live lists, one read-back of the counts; per evaluation k_register_graph, once: a fixed grid of
+// live_list.hip) into the engine's live lists, one read-back of the counts; per evaluation k_register_graph, once: a fixed grid of
 // kRegGrid workgroups, cut by the host into one contiguous range per pair in proportion to the sources' live blocks
 // (split_workgroups).  Workgroup w of a pair's range of G takes the live blocks w - first, w - first + G, ... of that
 // pair's source; lanes, gates, arithmetic and reduction are k_register's (register_body.h).  The pair's descriptor -- the
@@ -20,7 +20,7 @@
 #include <cstring>
 #include <vector>
 
-#include "dslam_bits.h"
+#include "dslam_internal.h"
 #include "register_device.h"
 #include "register_host.h"
 
@@ -47,8 +47,6 @@ struct RegisterGraphParams {
   double *partials;          // [gridDim.x][kRegSums]
 };
 
-// its own type: the selection kernel of this translation unit is not mesh.hip's
-struct SelLiveRegisterGraph : SelLive {};
 
 __global__ __launch_bounds__(kRegThreads) void k_register_graph(RegisterGraphParams gp) {
   // (split_workgroups hands out the whole grid, so every workgroup has a pair; one whose share holds no block writes zeros
@@ -126,7 +124,7 @@ int launch_register_graph(dslam_engine *e, const dslam_scene *const *scenes, flo
   std::vector<int> sources, list_offset, live;
   for (int p = 0; p < num_pairs; p++)
     if (std::find(sources.begin(), sources.end(), pairs[2 * p]) == sources.end()) sources.push_back(pairs[2 * p]);
-  DSLAM_TRY(fill_live_lists<SelLiveRegisterGraph>(e, scenes, num_maps, sources, list_offset, live));
+  DSLAM_TRY(fill_live_lists(e, scenes, num_maps, sources, list_offset, live));
   DSLAM_TRY(ensure_graph_scratch(e));
   RegisterGraphScratch &sc = e->reg_graph;
   std::vector<int> live_of_pair(num_pairs);

@@ -31,6 +31,7 @@
 
 #include "register_device.h"
 #include "register_host.h"
+#include "track_sdf_host.h"
 
 #pragma clang fp contract(off)
 
@@ -77,21 +78,13 @@ bool track_sdf_pixels_in_tiles() {
 // everything already checked (and params defaulted) by dslam_track_camera_sdf
 int launch_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T, int n,
                             float *pose_M, const float *intr, const dslam_track_sdf_params *tp, dslam_track_sdf_result *res) {
-  DSLAM_TRY(ensure_view_depth(e, v));
   const int levels = tp->no_hierarchy_levels;
-  const float *ldepth[DSLAM_TRACKER_MAX_LEVELS];
-  int lw[DSLAM_TRACKER_MAX_LEVELS], lh[DSLAM_TRACKER_MAX_LEVELS];
-  float lintr[DSLAM_TRACKER_MAX_LEVELS][4];
-  DSLAM_TRY(build_depth_pyramid(e, v, levels, ldepth, lw, lh));
-  for (int k = 0; k < 4; k++) lintr[0][k] = intr[k];
-  for (int i = 1; i < levels; i++)
-    for (int k = 0; k < 4; k++) lintr[i][k] = lintr[i - 1][k] * 0.5f;
+  TrackSdfPyramid pyr;
+  DSLAM_TRY(pyr.prepare(e, v, intr, levels));
   DSLAM_TRY(e->track_sdf_sums.ensure(kTrackSdfGrid));
 
   const double vs = (double)scenes[0]->p.voxel_size;
-  MultiMap maps[DSLAM_MAX_RENDER_MAPS];
-  for (int i = 0; i < n; i++) maps[i] = posed_map(scenes[i], T + 16 * i, vs);
-  DSLAM_HIP(hipMemcpyAsync(e->map_table, maps, (size_t)n * sizeof(MultiMap), hipMemcpyHostToDevice, e->stream));
+  DSLAM_TRY(upload_posed_maps(e, scenes, T, n, vs));
 
   TrackSdfParams kp;
   memset(&kp, 0, sizeof(kp));
@@ -104,8 +97,7 @@ int launch_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_sc
   const bool tiles = track_sdf_pixels_in_tiles();
 
   auto evaluate = [&](int level, const double P[12], Evaluation33 &ev) -> int {
-    kp.depth = ldepth[level]; kp.lw = lw[level]; kp.lh = lh[level];
-    kp.fx = lintr[level][0]; kp.fy = lintr[level][1]; kp.cx = lintr[level][2]; kp.cy = lintr[level][3];
+    pyr.set_level(kp, level);
     for (int k = 0; k < 12; k++) kp.P[k] = (float)P[k];
     if (tiles) hipLaunchKernelGGL(k_track_sdf<true>, dim3(kTrackSdfGrid), dim3(kTrackSdfThreads), 0, e->stream, kp);
     else hipLaunchKernelGGL(k_track_sdf<false>, dim3(kTrackSdfGrid), dim3(kTrackSdfThreads), 0, e->stream, kp);
@@ -150,14 +142,7 @@ int launch_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_sc
     rigid_inverse(P, Mv);
     pose_from_voxels(Mv, vs, pose_M);
   }
-  res->evaluations = total_evaluations;
-  res->levels_stepped = levels_stepped;
-  res->stop_reason = lm.stop;
-  res->candidates = good.candidates;
-  res->valid_last = good.valid;
-  res->cost_first = (float)cost_first;
-  res->cost_last = (float)cost_last;
-  res->conditioning = (float)lm.conditioning;
+  fill_track_sdf_result(res, total_evaluations, levels_stepped, lm, good, cost_first, cost_last);
   return device_errors(e);
 }
 

@@ -24,6 +24,7 @@
 
 #include "register_device.h"
 #include "register_host.h"
+#include "track_sdf_host.h"
 
 #pragma clang fp contract(off)
 
@@ -95,20 +96,14 @@ bool rows_added_on_host() {
 // what a call evaluates on: the pyramid, the maps' table, the kernel's constant arguments
 struct StartsCall {
   dslam_engine *e;
-  const float *ldepth[DSLAM_TRACKER_MAX_LEVELS];
-  int lw[DSLAM_TRACKER_MAX_LEVELS], lh[DSLAM_TRACKER_MAX_LEVELS];
-  float lintr[DSLAM_TRACKER_MAX_LEVELS][4];
+  TrackSdfPyramid pyr;
   TrackSdfStartsParams kp;
   bool tiles, rows_to_host;
 
   int prepare(dslam_engine *engine, const dslam_view *v, const dslam_scene *const *scenes, const float *T, int n, const float *intr,
               int levels, float residual_gate) {
     e = engine;
-    DSLAM_TRY(ensure_view_depth(e, v));
-    DSLAM_TRY(build_depth_pyramid(e, v, levels, ldepth, lw, lh));
-    for (int k = 0; k < 4; k++) lintr[0][k] = intr[k];
-    for (int i = 1; i < levels; i++)
-      for (int k = 0; k < 4; k++) lintr[i][k] = lintr[i - 1][k] * 0.5f;
+    DSLAM_TRY(pyr.prepare(e, v, intr, levels));
     TrackStartsScratch &sc = e->track_starts;
     if (!sc.sums) {
       TrackStartsScratch made;
@@ -119,9 +114,7 @@ struct StartsCall {
       sc = std::move(made);
     }
     const double vs = (double)scenes[0]->p.voxel_size;
-    MultiMap maps[DSLAM_MAX_RENDER_MAPS];
-    for (int i = 0; i < n; i++) maps[i] = posed_map(scenes[i], T + 16 * i, vs);
-    DSLAM_HIP(hipMemcpyAsync(e->map_table, maps, (size_t)n * sizeof(MultiMap), hipMemcpyHostToDevice, e->stream));
+    DSLAM_TRY(upload_posed_maps(e, scenes, T, n, vs));
     memset(&kp, 0, sizeof(kp));
     kp.inv_vs = (float)(1.0 / vs);
     kp.poses = sc.poses;
@@ -135,7 +128,8 @@ struct StartsCall {
 
   // workgroups per pose on `level`: those of the single call's 512 that have a job
   int workgroups(int level) const {
-    const long long jobs = tiles ? (long long)((lw[level] + 7) >> 3) * ((lh[level] + 7) >> 3) * 64 : (long long)lw[level] * lh[level];
+    const int lw = pyr.lw[level], lh = pyr.lh[level];
+    const long long jobs = tiles ? (long long)((lw + 7) >> 3) * ((lh + 7) >> 3) * 64 : (long long)lw * lh;
     return (int)std::max(1LL, std::min((long long)kTrackSdfGrid, (jobs + kTrackSdfThreads - 1) / kTrackSdfThreads));
   }
 
@@ -158,8 +152,7 @@ struct StartsCall {
     for (int k = 0; k < poses; k++)
       for (int i = 0; i < 12; i++) ph[12 * k + i] = (float)P[k][i];
     DSLAM_HIP(hipMemcpyAsync(sc.poses, ph, (size_t)poses * 12 * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    kp.depth = ldepth[level]; kp.lw = lw[level]; kp.lh = lh[level];
-    kp.fx = lintr[level][0]; kp.fy = lintr[level][1]; kp.cx = lintr[level][2]; kp.cy = lintr[level][3];
+    pyr.set_level(kp, level);
     kp.partials = rows_to_host ? sc.rows_host.device() : sc.rows.get();
     if (tiles) hipLaunchKernelGGL(k_track_sdf_starts<true>, dim3(G, poses), dim3(kTrackSdfThreads), 0, e->stream, kp);
     else hipLaunchKernelGGL(k_track_sdf_starts<false>, dim3(G, poses), dim3(kTrackSdfThreads), 0, e->stream, kp);
@@ -290,15 +283,7 @@ int launch_track_camera_sdf_starts(dslam_engine *e, const dslam_view *v, const d
       rigid_inverse(s.P, Mv);
       pose_from_voxels(Mv, vs, poses_M + 16 * k);
     }
-    dslam_track_sdf_result *res = results + k;
-    res->evaluations = s.total_evaluations;
-    res->levels_stepped = s.levels_stepped;
-    res->stop_reason = s.lm.out.stop;
-    res->candidates = s.good.candidates;
-    res->valid_last = s.good.valid;
-    res->cost_first = (float)s.cost_first;
-    res->cost_last = (float)s.cost_last;
-    res->conditioning = (float)s.lm.out.conditioning;
+    fill_track_sdf_result(results + k, s.total_evaluations, s.levels_stepped, s.lm.out, s.good, s.cost_first, s.cost_last);
   }
   e->track_starts.last_sums = std::move(last);
   return DSLAM_OK;
