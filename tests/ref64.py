@@ -20,6 +20,23 @@ FAR_AWAY, VERY_CLOSE = F(999999.9), F(0.05)
 MEAN_SIGMA_L = 1.2232
 
 
+class Scale:
+    """How a bound grows with the size of the coordinates.  `P` is the largest |voxel coordinate| of a fixture and `u`
+    float32's spacing there; `scale(origin, c)` is max(origin, c u): the bound that holds at the world origin, or c
+    float32 roundings of a position-sized quantity, whichever is larger.  Up to P = 256 (every fixture at the origin) u
+    counts as 0, so each bound is exactly the origin's."""
+
+    def __init__(self, P=0):
+        self.P = int(P)
+        self.u = float(np.spacing(F(P))) if P > 256 else 0.0
+
+    def __call__(self, origin, c):
+        return max(origin, c * self.u)
+
+
+ORIGIN = Scale(0)
+
+
 def mat_vec_f32(M, p):
     """ORUtils Matrix4f * Vector4f(p, 1) in float32: row r = ((m_r0 x + m_r1 y) + m_r2 z) + m_r3 (no FMA)."""
     M = np.asarray(M, F)
@@ -163,7 +180,9 @@ def integrate(vox, block_pos, depth, rgba, M_d, intr, vs, mu, max_w, M_rgb=None,
     ok &= upd
     oldF = v["sdf"].astype(np.float64) / 32767.0
     oldW = v["w_depth"].astype(np.int64)
-    newF = np.minimum(1.0, eta64 / mu64)
+    # (the spec takes a voxel only with eta32 >= -mu32, so its newF is >= -1; eta64 may lie below -mu64 where the two
+    # disagree -- a tie -- and the value stored for it must not leave int16's range)
+    newF = np.clip(eta64 / mu64, -1.0, 1.0)
     newW = new_weight(dm32, wp)
     if not deintegrate:
         Wsum = oldW + newW
@@ -633,9 +652,10 @@ def visible_blocks(m, M, intr, W, H):
     return vis
 
 
-def expected_depths(m, M, intr, W, H):
+def expected_depths(m, M, intr, W, H, z32=False):
     """A.7 CreateExpectedDepths on the visible blocks: per 8x8 tile the (min, max) camera z of the blocks whose
-    projected corner bbox covers it.  Returns [ceil(H/8), ceil(W/8), 2]; no block = (FAR_AWAY, VERY_CLOSE)."""
+    projected corner bbox covers it.  Returns [ceil(H/8), ceil(W/8), 2]; no block = (FAR_AWAY, VERY_CLOSE).
+    `z32`: the corners' camera z from the float32 mat-vec, as an engine forms it, in place of the float64 one."""
     tw, th = -(-W // 8), -(-H // 8)
     rng = np.empty((th, tw, 2))
     rng[..., 0], rng[..., 1] = FAR_AWAY, VERY_CLOSE
@@ -651,7 +671,7 @@ def expected_depths(m, M, intr, W, H):
         good = pc[:, 2] >= F(1e-6)
         with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
             u, v = project_f32(intr, pc)
-        zs.append(mat_vec_f64(M, (bp + d) * float(fac))[:, 2])
+        zs.append(pc[:, 2].astype(np.float64) if z32 else mat_vec_f64(M, (bp + d) * float(fac))[:, 2])
         us.append(u / F(8))
         vs_.append(v / F(8))
         goods.append(good)
@@ -683,10 +703,22 @@ def _iround(x):
     return np.trunc(np.where(x < 0, x - 0.5, x + 0.5)).astype(np.int64)
 
 
-def cast_rays(m, M, intr, W, H, tie_tol=1e-4, max_steps=4000):
+def cast_rays(m, M, intr, W, H, tie_tol=1e-4, max_steps=4000, by_outcome=False):
     """A.7 castRay for every pixel on map `m`.  Returns dict(p [H, W, 3] hit position in voxel units (world), hit
     [H, W], tie [H, W], miss_cell [H, W]: a read at the stop point or after either refinement touched a missing voxel, dir: the unit ray,
-    p_stop / sdf_stop: where the march stopped and the read that stopped it, before the two refinement steps)."""
+    p_stop / sdf_stop: where the march stopped and the read that stopped it, before the two refinement steps).
+
+    `tie_tol` (voxels) is how far a float32 march position may lie from this one; every branch test uses it.  Far from the
+    origin it grows with float32's spacing (placement_checks.py), and the plain rule -- a tie wherever a position comes
+    within tie_tol of a nearest-voxel rounding boundary or a read within tie_tol of a threshold -- would call most rays
+    ties.  `by_outcome` states the same tests by what they decide:
+      * a nearest-voxel rounding within tie_tol of its boundary on one axis is a tie only if the voxel on the other side
+        would make the march do something else: the two differ in being found, or in lying inside the interpolation
+        window (inside it the trilinear read replaces the value, whichever voxel), or, both outside it, in value (the
+        value is the step); two axes near their boundaries at once are a tie;
+      * the nearest-voxel value is an integer / 32767 and meets 0.1, -0.5 and 0 the same way in float32 and float64: no
+        tolerance applies to it; a trilinear read moves with the position by at most sqrt(3) vs / mu per voxel, so its
+        hit test is a tie within sqrt(3) (vs / mu) tie_tol of 0."""
     vs, mu = float(F(m.vs)), float(F(m.mu))
     rng = expected_depths(m, M, intr, W, H)
     fx, fy, cx, cy = (float(F(v)) for v in intr)
@@ -705,6 +737,7 @@ def cast_rays(m, M, intr, W, H, tie_tol=1e-4, max_steps=4000):
     with np.errstate(invalid="ignore", divide="ignore"):
         d = d / np.linalg.norm(d, axis=1, keepdims=True)
     step_scale = mu / vs
+    sdf_tol = np.sqrt(3.0) * tie_tol / step_scale
     n = len(xs)
     p = ps.copy()
     sdf = np.ones(n)
@@ -718,16 +751,32 @@ def cast_rays(m, M, intr, W, H, tie_tol=1e-4, max_steps=4000):
             break
         q = p[idx]
         frac = np.abs(q) - np.floor(np.abs(q))
-        tie[idx] |= np.any(np.abs(frac - 0.5) < tie_tol, axis=1)
-        s16, _, found = m.lookup(_iround(q))
+        near = np.abs(frac - 0.5) < tie_tol
+        r = _iround(q)
+        s16, _, found = m.lookup(r)
         s = s16 / 32767.0
         step = np.full(len(idx), 8.0)
         win = found & (s <= 0.1) & (s >= -0.5)
-        tie[idx] |= found & ((np.abs(s - 0.1) < tie_tol) | (np.abs(s + 0.5) < tie_tol))
+        if not by_outcome:
+            tie[idx] |= np.any(near, axis=1)
+            tie[idx] |= found & ((np.abs(s - 0.1) < tie_tol) | (np.abs(s + 0.5) < tie_tol))
+        else:
+            tie[idx] |= near.sum(axis=1) > 1
+            for ax in range(3):
+                k = np.nonzero(near[:, ax])[0]
+                if len(k) == 0:
+                    continue
+                alt = r[k].copy()
+                alt[:, ax] += np.where(q[k, ax] > r[k, ax], 1, -1)
+                a16, _, afound = m.lookup(alt)
+                sa = a16 / 32767.0
+                awin = afound & (sa <= 0.1) & (sa >= -0.5)
+                same = (afound == found[k]) & (~afound | (awin & win[k]) | (~awin & ~win[k] & (a16 == s16[k])))
+                tie[idx[k]] |= ~same
         if win.any():
             s[win] = read_trilinear(m, q[win])[0]
         stop = found & (s <= 0.0)
-        tie[idx] |= found & (np.abs(s) < tie_tol)
+        tie[idx] |= (win & (np.abs(s) < sdf_tol)) if by_outcome else (found & (np.abs(s) < tie_tol))
         step[found] = np.maximum(s[found] * step_scale, 1.0)
         sdf[idx] = s
         hit[idx[stop]] = True

@@ -9,6 +9,16 @@ import test_mc_tables as mct
 import util
 
 TIE_LIMIT = 1e-3  # fraction of updated voxels allowed to sit on a float32 / float64 branch tie
+# Far from the origin (ref64.Scale), in units of u, float32's spacing at the largest voxel coordinate:
+C_TIE = 8.0        # how far a float32 march position may lie from the float64 one when a branch is taken
+C_RAY = 27.0       # a hit's position, and its depth, against the float64 march on rays that are no tie: twice the 13.4 u
+                   # the float32 restatement of the march (ref32_march.py) shows at the worst (test_placement_fixtures.py)
+C_TAPS = 1.5       # the direction of a 6-tap normal: each tap's position is rounded once (u / 2 per component, sqrt(3) u / 2
+                   # per tap, sqrt(3) u on the difference of two taps two voxels apart: sqrt(3) u / 2 relative, times
+                   # sqrt(3) for the three components)
+C_MESH = 0.5       # a mesh vertex a + t (b - a) in voxels: one addition at the size of a (the product by the voxel
+                   # size is the output ulp the check already counts)
+C_MESH_SURFACE = 1.5 * np.sqrt(3.0)  # both roundings, (0.5 + 1) u per component, along a unit normal
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -204,11 +214,19 @@ def tier_b_bound(m, cos_t, d0, s0):
     return b
 
 
-def check_raycast(api, pkg, m, M, intr, W, H, colour=False, icp=True):
+def reference_rays(m, M, intr, W, H, scale=ref64.ORIGIN):
+    """The float64 march with the tie tolerance of the fixture's size (at the origin: cast_rays' own default)."""
+    return ref64.cast_rays(m, M, intr, W, H, tie_tol=scale(1e-4, C_TIE), by_outcome=scale.u > 0)
+
+
+def check_raycast(api, pkg, m, M, intr, W, H, colour=False, icp=True, scale=ref64.ORIGIN, ref=None, extras=False):
     """Tier (a): the kernel against the float64 castRay on the same uploaded map.  Tier (b): the kernel's hit points
-    against the closed-form surface.  Returns measured figures."""
+    against the closed-form surface.  Returns measured figures.  `scale`: the size of the fixture's coordinates;
+    `ref`: reference_rays of the same arguments, where a caller has them already.  `extras`: the raycast result
+    (positions in voxels) against the float64 march too, and get_depth_image_int16 against (int16)(depth * 1000)."""
     scene, rs = load_map(api, pkg, m, W, H)
-    ref = ref64.cast_rays(m, M, intr, W, H)
+    ref = reference_rays(m, M, intr, W, H, scale) if ref is None else ref
+    thr_a = scale(1e-3, C_RAY)
     depth = api.get_image(scene, rs, M, intr, pkg.IMAGE_DEPTH).astype(np.float64)
     hit = depth > 0
     tie = ref["tie"]
@@ -217,18 +235,28 @@ def check_raycast(api, pkg, m, M, intr, W, H, colour=False, icp=True):
     assert both.sum() > 0.1 * W * H, f"only {both.sum()} hits"
     dref = ref64.camera_depth(M, ref["p"], m.vs)
     err = np.abs(depth - dref) / m.vs  # voxels
-    big = both & (err > 1e-3)
+    big = both & (err > thr_a)
     assert not (big & ~tie).any(), f"tier (a): |ddepth| up to {err[big & ~tie].max():.3g} voxel with no threshold tie"
-    assert big.sum() <= 0.01 * both.sum(), f"tier (a): {big.sum()} of {both.sum()} hits beyond 1e-3 voxel"
+    assert big.sum() <= 0.01 * both.sum(), f"tier (a): {big.sum()} of {both.sum()} hits beyond {thr_a:.3g} voxel"
     out = dict(hits=int(both.sum()), ties=int((tie & both).sum()), a_max=float(err[both & ~tie].max()),
                a_p99=float(np.percentile(err[both], 99)))
+    if extras:
+        res = api.download_raycast_result(rs)
+        assert np.array_equal(res[..., 3] > 0, hit), "the raycast result and the depth image disagree on the hits"
+        rerr = np.abs(res[..., :3].astype(np.float64) - ref["p"]).max(-1)
+        assert rerr[both & ~tie].max() <= thr_a, f"raycast result {rerr[both & ~tie].max():.3g} voxel from the float64 march"
+        mm = api.get_depth_image_int16(scene, rs, M, intr, 1000)
+        want = (depth.astype(np.float32) * np.float32(1000)).astype(np.int32).astype(np.int16)
+        assert np.array_equal(mm, want), "get_depth_image_int16 is not (int16)(depth * 1000)"
+        out["result_max"] = float(rerr[both & ~tie].max())
     # tier (b): distance of the kernel's hit along the normal
     xw = world_points_from_depth(M, intr, depth)
     dist = np.abs(m.geom.sdf(xw)) / m.vs
     nrm = m.geom.normal(xw)
     cos_t = np.abs(np.sum(nrm * ref["dir"], -1))
     d0 = m.geom.sdf(ref["p_stop"] * m.vs) / m.vs
-    bound = tier_b_bound(m, cos_t, d0, ref["sdf_stop"] * (m.mu / m.vs))
+    # (far from the origin the engine's ray lies up to C_RAY u beside the float64 ray the depth is put back on)
+    bound = tier_b_bound(m, cos_t, d0, ref["sdf_stop"] * (m.mu / m.vs)) + scale(0.0, C_RAY)
     # the reads are linear in the distance only while every corner of their cells lies inside the truncation band:
     # a stop point more than mu/vs - sqrt(3) voxels behind the surface (after an 8-voxel step through a missing
     # block) reads clamped values, and the derivation above does not apply to it
@@ -243,8 +271,8 @@ def check_raycast(api, pkg, m, M, intr, W, H, colour=False, icp=True):
     out["b_max"] = float(dist[sel].max())
     out["b_bound_max"] = float(bound[sel].max())
     if icp:
-        out.update(_check_icp(api, scene, rs, m, M, intr, ref, hit, sel, bound))
-    out.update(_check_shading(api, pkg, scene, rs, m, M, intr, ref, both & ~tie, sel, dist, xw))
+        out.update(_check_icp(api, scene, rs, m, M, intr, ref, hit, sel, bound, thr_a))
+    out.update(_check_shading(api, pkg, scene, rs, m, M, intr, ref, both & ~tie, sel, dist, xw, scale))
     if colour:
         img = api.get_image(scene, rs, M, intr, pkg.IMAGE_COLOUR_FROM_VOLUME)
         chit = img[..., 3] > 0
@@ -268,7 +296,54 @@ def check_raycast(api, pkg, m, M, intr, W, H, colour=False, icp=True):
     return out
 
 
-def _check_icp(api, scene, rs, m, M, intr, ref, hit, sel, bound):
+def check_raycast_untied(api, pkg, m, M, intr, W, H, scale, ref, min_rays=40):
+    """The ray march where the float64 march calls most rays ties (the full FAR placements, the table's ends): what holds
+    ray by ray, asserted on every ray that is no tie, with no cap on the ties and a floor on the rays left.  The hit masks
+    agree; depth, raycast result and ICP point lie within the scaled tier (a) bound of the float64 hit; the hit lies within
+    the tier (b) bound of the closed-form surface; get_depth_image_int16 is (int16)(depth * 1000); no image type draws a
+    pixel the march did not hit.  What needs whole neighbourhoods or counts of rays (the ICP normals, the shading's drawn
+    set, the colours, the 1 % rule) stays with check_raycast at the D its tie cap allows."""
+    scene, rs = load_map(api, pkg, m, W, H)
+    thr_a = scale(1e-3, C_RAY)
+    depth = api.get_image(scene, rs, M, intr, pkg.IMAGE_DEPTH).astype(np.float64)
+    hit, tie = depth > 0, ref["tie"]
+    assert np.array_equal(hit[~tie], ref["hit"][~tie]), f"hit masks differ on {(hit != ref['hit'])[~tie].sum()} non-tie pixels"
+    ok = hit & ref["hit"] & ~tie
+    assert ok.sum() >= min_rays, f"only {ok.sum()} hits that are no tie"
+    err = np.abs(depth - ref64.camera_depth(M, ref["p"], m.vs)) / m.vs
+    assert err[ok].max() <= thr_a, f"tier (a): |ddepth| up to {err[ok].max():.3g} voxel with no threshold tie"
+    res = api.download_raycast_result(rs)
+    assert np.array_equal(res[..., 3] > 0, hit), "the raycast result and the depth image disagree on the hits"
+    rerr = np.abs(res[..., :3].astype(np.float64) - ref["p"]).max(-1)
+    assert rerr[ok].max() <= thr_a, f"raycast result {rerr[ok].max():.3g} voxel from the float64 march"
+    mm = api.get_depth_image_int16(scene, rs, M, intr, 1000)
+    want = (depth.astype(np.float32) * np.float32(1000)).astype(np.int32).astype(np.int16)
+    assert np.array_equal(mm, want), "get_depth_image_int16 is not (int16)(depth * 1000)"
+    xw = world_points_from_depth(M, intr, depth)
+    dist = np.abs(m.geom.sdf(xw)) / m.vs
+    cos_t = np.abs(np.sum(m.geom.normal(xw) * ref["dir"], -1))
+    d0 = m.geom.sdf(ref["p_stop"] * m.vs) / m.vs
+    bound = tier_b_bound(m, cos_t, d0, ref["sdf_stop"] * (m.mu / m.vs)) + scale(0.0, C_RAY)
+    sel = ok & ~ref["miss_cell"] & (np.abs(d0) + np.sqrt(3.0) < m.mu / m.vs)  # (as in check_raycast)
+    if isinstance(m.geom, am.BoxCorner):
+        g = np.sort(m.geom.k - xw, -1)
+        sel &= (g[..., 1] - g[..., 0]) > 3.0 * m.vs
+    assert sel.sum() >= min_rays // 2, f"only {sel.sum()} rays for tier (b)"
+    over = sel & (dist > bound)
+    assert not over.any(), f"tier (b): {over.sum()} hits beyond the bound, worst {(dist - bound)[over].max():.3g} voxel over"
+    api.find_visible_blocks(scene, rs, M, intr)
+    pts, nrms = api.create_icp_maps(scene, rs, M, intr)
+    pok = pts[..., 3] > 0
+    assert not (pok & ~hit).any(), "ICP point where the raycast found nothing"
+    perr = np.linalg.norm(pts[..., :3] - ref["p"] * float(np.float32(m.vs)), axis=-1) / m.vs
+    assert (pok & ok).sum() >= min_rays // 4 and perr[pok & ok].max() <= np.sqrt(3.0) * thr_a, "ICP points"
+    for t in (pkg.IMAGE_SHADED, pkg.IMAGE_COLOUR_FROM_NORMAL, pkg.IMAGE_COLOUR_FROM_VOLUME):
+        assert not ((api.get_image(scene, rs, M, intr, t)[..., 3] > 0) & ~hit).any(), f"image type {t} draws a pixel that is no hit"
+    return dict(hits=int(hit.sum()), untied=int(ok.sum()), tier_b_rays=int(sel.sum()), a_max=float(err[ok].max()),
+                result_max=float(rerr[ok].max()), b_max=float(dist[sel].max()), b_bound_max=float(bound[sel].max()))
+
+
+def _check_icp(api, scene, rs, m, M, intr, ref, hit, sel, bound, thr_a=1e-3):
     """CreateICPMaps: points and normals against the float64 restatement built from the float64 march points
     (tier a), and the normals against the analytic surface with a bound derived from the tap points' tier-(b)
     bounds (tier b)."""
@@ -284,11 +359,13 @@ def _check_icp(api, scene, rs, m, M, intr, ref, hit, sel, bound):
     # points: the raycast points in metres, so the depth's tier (a) -- 1e-3 voxel -- holds for them too (the float32
     # rounding of a metric coordinate below 1 m is < 6e-8 m = 1.2e-5 voxel, inside that figure)
     perr = np.linalg.norm(pts[..., :3] - ref["p"] * float(np.float32(m.vs)), axis=-1) / m.vs
-    assert perr[a].max() <= 1e-3, f"ICP points: {perr[a].max():.3g} voxel from the float64 march"
+    # (far from the origin: within thr_a per component, sqrt(3) thr_a as a distance)
+    tap_err = np.sqrt(3.0) * thr_a if thr_a > 1e-3 else 1e-3
+    assert perr[a].max() <= tap_err, f"ICP points: {perr[a].max():.3g} voxel from the float64 march"
     # normals, tier (a): each tap point is within 1e-3 voxel of its float64 twin, so each difference vector is within
     # 2e-3 voxel and the cross product's direction tilts by at most 2e-3 (1/|dx| + 1/|dy|) / sin(angle(dx, dy))
     dxv, dyv, sphi = _tap_geometry(ref["p"], tap)
-    lim_a = 2e-3 * (1.0 / dxv + 1.0 / dyv) / sphi + 1e-6
+    lim_a = 2.0 * tap_err * (1.0 / dxv + 1.0 / dyv) / sphi + 1e-6
     ang_a = _angle(nrms[..., :3], n_ref)
     assert (ang_a[a] <= lim_a[a]).all(), f"ICP normals: {np.degrees(ang_a[a]).max():.3g} deg from the float64 restatement"
     out = dict(icp_points=int(ok.sum()), icp_ties=int((t_icp & (ok | f_ref)).sum()), icp_a_deg=float(np.degrees(ang_a[a]).max()))
@@ -338,7 +415,7 @@ def _tap_geometry(p, tap):
     return lx, ly, sphi
 
 
-def _check_shading(api, pkg, scene, rs, m, M, intr, ref, a, sel, dist, xw):
+def _check_shading(api, pkg, scene, rs, m, M, intr, ref, a, sel, dist, xw, scale=ref64.ORIGIN):
     """SHADED and COLOUR_FROM_NORMAL: the 6-tap normal at the hit, shaded against the camera's viewing axis.
     Tier (a): against the float64 normal at the float64 hit (+-1 for the output truncation).  Tier (b): against the
     analytic normal.  The taps read the field one voxel either side along each axis; for a plane the difference is
@@ -362,10 +439,17 @@ def _check_shading(api, pkg, scene, rs, m, M, intr, ref, a, sel, dist, xw):
     c_ref = ref64.normal_colour(n64)
     dg = np.abs(sh[..., 0].astype(np.float64) - g_ref)
     dc = np.abs(cn[..., :3].astype(np.float64) - c_ref).max(-1)
-    assert dg[ta].max() <= 1, f"SHADED off by {dg[ta].max()} from the float64 grey"
+    # far from the origin the kernel's normal turns by up to C_TAPS u (its taps' positions are rounded) and, on a sphere
+    # of radius r voxels, by the hit's distance from the float64 hit (sqrt(3) C_RAY u) / r; the truncated outputs then
+    # differ by one more than the whole levels that turn is worth
+    turn = scale(0.0, C_TAPS)
+    if isinstance(m.geom, am.Sphere):
+        turn += np.sqrt(3.0) * scale(0.0, C_RAY) / (m.geom.r / m.vs)
+    lim_g, lim_c = 1 + np.floor(0.8 * 255.0 * turn), 1 + np.floor(0.35 * 255.0 * turn)
+    assert dg[ta].max() <= lim_g, f"SHADED off by {dg[ta].max()} from the float64 grey"
     assert (sh[ta][:, :4] == sh[ta][:, :1]).all(), "SHADED: grey channels differ"
-    assert dc[ta].max() <= 1, f"COLOUR_FROM_NORMAL off by {dc[ta].max()} from the float64 encoding"
-    eps = np.sqrt(3.0) * 2.0 / 32767.0 / (2.0 * m.vs / m.mu)
+    assert dc[ta].max() <= lim_c, f"COLOUR_FROM_NORMAL off by {dc[ta].max()} from the float64 encoding"
+    eps = np.sqrt(3.0) * 2.0 / 32767.0 / (2.0 * m.vs / m.mu) + scale(0.0, C_TAPS)
     if isinstance(m.geom, am.Sphere):
         r = m.geom.r / m.vs
         eps += np.sqrt(3.0) / (4.0 * r) + 1.0 / r ** 2
@@ -384,13 +468,15 @@ def _check_shading(api, pkg, scene, rs, m, M, intr, ref, a, sel, dist, xw):
 # ---------------------------------------------------------------------------------------------------------------------
 # mesh
 # ---------------------------------------------------------------------------------------------------------------------
-def check_mesh(api, pkg, m, surface_bound=None, max_triangles=0):
+def check_mesh(api, pkg, m, surface_bound=None, max_triangles=0, scale=ref64.ORIGIN, colour=False):
     """The mesh triangle for triangle, in upstream's order (hash entries, voxels, table slots), against the float64
     re-derivation; then its vertices against the analytic surface.  `max_triangles`: the list's size, where the default
-    of 32 per pool slot would be sized by the pool and not by the map."""
+    of 32 per pool slot would be sized by the pool and not by the map.  `scale`: the size of the fixture's coordinates.
+    `colour`: the vertex colours too, each within [0, 1] and, where the map has a linear colour field, within 1 / 255
+    (the floor on storage of the edge's two ends) of the field at the vertex."""
     scene = api.create_scene(m.scene_params(pkg))
     am.upload(api, scene, m)
-    pos, _ = api.mesh_scene(scene, max_triangles=max_triangles)
+    pos, col = api.mesh_scene(scene, max_triangles=max_triangles, colour=colour)
     ec, co = mct.load_small_tables()
     ref = ref64.mesh(m, co, ec, mct.load_table())
     assert len(pos) < (max_triangles or m.num_local_blocks * 32) - 1, "mesh saturated: size the map"
@@ -399,12 +485,22 @@ def check_mesh(api, pkg, m, surface_bound=None, max_triangles=0):
     # 1e-5 voxel, plus the float32 rounding of the metric output (one ulp of the largest coordinate, in voxels)
     ulp = np.spacing(np.abs(pos).max().astype(np.float32)) / m.vs
     d = np.abs(got - ref).max()
-    assert d <= 1e-5 + ulp, f"mesh vertices {d:.3g} voxel from the float64 edge interpolation"
+    assert d <= 1e-5 + ulp + scale(0.0, C_MESH), f"mesh vertices {d:.3g} voxel from the float64 edge interpolation"
     out = dict(triangles=len(pos), vertex_max=float(d))
     if surface_bound is not None:
         dist = np.abs(m.geom.sdf(pos.reshape(-1, 3).astype(np.float64))) / m.vs
-        assert dist.max() <= surface_bound, f"mesh vertex {dist.max():.3g} voxel off the analytic surface"
+        lim = surface_bound + scale(0.0, C_MESH_SURFACE)
+        assert dist.max() <= lim, f"mesh vertex {dist.max():.3g} voxel off the analytic surface"
         out["surface_max"] = float(dist.max())
+    if colour:
+        assert col is not None and col.shape == pos.shape and col.min() >= 0.0 and col.max() <= 1.0
+        if m.colour is not None:
+            x = pos.reshape(-1, 3).astype(np.float64)
+            gvox = np.abs(m.colour_grad).sum(0) * m.vs
+            lim_c = 1.0 + gvox[None, :] * scale(0.0, C_MESH_SURFACE) + 1e-4
+            dc = np.abs(col.reshape(-1, 3).astype(np.float64) * 255.0 - m.colour(x))
+            assert (dc <= lim_c).all(), f"mesh colours {dc.max():.3g} / 255 from the analytic colour field"
+            out["colour_max"] = float(dc.max())
     return out
 
 

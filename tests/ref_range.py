@@ -43,7 +43,8 @@ def project_blocks(pos, M, intr, vs, W, H, T=F, skip_below=1e-6):
     in_front [n] bool: not (zmax < VERY_CLOSE)).  `skip_below` is the law's 1e-6; a fixture passes another value only to
     show that the threshold decides cells of its image."""
     pos = np.asarray(pos, np.int64).reshape(-1, 3)
-    assert np.abs(pos).max(initial=0) <= 32766, "block coordinate at the end of the short range"
+    # (the corner offset is added in 16 bits: only 32767 + 1 wraps, -32768 is as good a block as any)
+    assert pos.min(initial=0) >= -32768 and pos.max(initial=0) <= 32766, "block coordinate at the end of the short range"
     n = len(pos)
     M = np.asarray(M, F).astype(T)
     fx, fy, cx, cy = (T(F(v)) for v in intr)

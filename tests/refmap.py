@@ -133,7 +133,7 @@ class Walk:
         valid = np.arange(smax)[None, :] < s32[:, None]
         self.pix, self.step = (a.astype(np.int64) for a in np.nonzero(valid))
         self.block = b32[valid]
-        assert np.abs(self.block).max(initial=0) < 32768, "block coordinate outside int16"
+        assert self.block.min(initial=0) >= -32768 and self.block.max(initial=0) <= 32767, "block coordinate outside int16"
         self.key_stride = smax + 1
         self.key = self.pix * self.key_stride + self.step
         self.gate_ties = int((g32 != g64).sum())

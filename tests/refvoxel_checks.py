@@ -39,13 +39,18 @@ PRED_TIE_LIMIT = 1e-3
 REACH_MIN = 512
 
 
-def pose(k):
-    """World -> camera: the identity or a quarter turn about y, x or z, then a translation of whole voxels."""
+def pose(k, D=(0, 0, 0)):
+    """World -> camera: the identity or a quarter turn about y, x or z, then a translation of whole voxels.  `D`: the
+    world moved by that many blocks (D / 8 m each: every entry stays a dyadic number float32 holds exactly)."""
     R = [np.eye(3), [[0, 0, -1], [0, 1, 0], [1, 0, 0]], [[1, 0, 0], [0, 0, -1], [0, 1, 0]], [[0, -1, 0], [1, 0, 0], [0, 0, 1]]][k % 4]
-    M = np.eye(4, dtype=np.float32)
+    M = np.eye(4)
     M[:3, :3] = R
     M[:3, 3] = np.array([3, -5, 2]) * VS
-    return M
+    T = np.eye(4)
+    T[:3, 3] = -8.0 * VS * np.asarray(D, np.float64)
+    out = (M @ T).astype(np.float32)
+    assert np.array_equal(out.astype(np.float64), M @ T), "the moved pose is not exact in float32"
+    return out
 
 
 def rgb_camera(M):
@@ -152,13 +157,13 @@ def _entries(api, scene, rs):
 class Case:
     """One scene with its crafted measurement, allocated and overwritten; `expect` is the reference's answer to a call."""
 
-    def __init__(self, api, pkg, max_w, mu_steps, form, pose_k=0, **scene_kw):
+    def __init__(self, api, pkg, max_w, mu_steps, form, pose_k=0, D=(0, 0, 0), **scene_kw):
         self.api, self.form, self.max_w, self.mu_steps = api, form, max_w, mu_steps
         self.deint = form.startswith("deprocess")
         self.stop = form.endswith("stop")
         self.wp = (WP_DEINT[pose_k % 4] if self.deint else WP) if form.endswith("depth_weights") else None
         self.mu = mu_steps * STEP
-        self.M = pose(pose_k)
+        self.M = pose(pose_k, D)
         self.M_rgb = rgb_camera(self.M) if "two_cameras" in form else None
         kw = dict(voxel_size=VS, mu=self.mu, max_w=max_w, frustum_min=0.2, frustum_max=3.0, num_local_blocks=0x800,
                   num_buckets=0x1000, num_excess=0x400, stop_integrating_at_max_w=int(self.stop))
@@ -307,11 +312,11 @@ class Batch:
     of those lists overwritten with crafted voxels.  `loop` corrects the keyframes one by one and checks every step;
     `batch` corrects them in one reintegrate_batch call."""
 
-    def __init__(self, api, pkg, mode, max_w, mu_steps, pose_k):
+    def __init__(self, api, pkg, mode, max_w, mu_steps, pose_k, D=(0, 0, 0)):
         self.api, self.pkg, self.mode, self.max_w, self.mu_steps = api, pkg, mode, max_w, mu_steps
         self.wp, self.sharded = BATCH_MODES[mode]
         self.mu = mu_steps * STEP
-        self.old = [_shift(pose(pose_k), t) for t in KEYFRAME_SHIFTS]
+        self.old = [_shift(pose(pose_k, D), t) for t in KEYFRAME_SHIFTS]
         self.new = [corrected(M, k) for k, M in enumerate(self.old)]
         self.seed = 7000 * max_w + 10 * mu_steps + pose_k
         self.frames = [images(mu_steps, self.seed + 100 * k) for k in range(3)]
@@ -416,11 +421,11 @@ class Batch:
             self._weights(False)
 
 
-def run_batch(api, pkg, mode, max_w, mu_steps, pose_k):
+def run_batch(api, pkg, mode, max_w, mu_steps, pose_k, D=(0, 0, 0)):
     """Two copies of one state; the checked loop on the first, one batch call on the second; the two must be equal byte
     for byte (map, table, free lists, render state).  Returns (batch rig, the second copy, figures)."""
     import scenarios
-    b = Batch(api, pkg, mode, max_w, mu_steps, pose_k)
+    b = Batch(api, pkg, mode, max_w, mu_steps, pose_k, D)
     h1, h2 = b.build(), b.build()
     assert h1["state"].tobytes() == h2["state"].tobytes() and all(np.array_equal(x[0], y[0]) for x, y in zip(h1["lists"], h2["lists"]))
     figures = b.loop(h1)

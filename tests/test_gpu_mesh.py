@@ -13,11 +13,7 @@ def _both(gpu, oracle):
     return (("gpu", gpu), ("oracle", oracle))
 
 
-def _same_mesh(a, b, what):
-    assert a[0].shape == b[0].shape, f"{what}: {a[0].shape[0]} vs {b[0].shape[0]} triangles"
-    assert np.array_equal(a[0], b[0]), f"{what}: positions"
-    if a[1] is not None or b[1] is not None:
-        assert np.array_equal(a[1], b[1]), f"{what}: colours"
+_same_mesh = util.assert_same_mesh
 
 
 @pytest.mark.parametrize("colour", [False, True])

@@ -40,6 +40,14 @@ def assert_same_state(a, b, what="", ignore_stats=()):
         raise AssertionError(f"{what}: {len(bad)} voxels differ, first at block/voxel {tuple(bad[0])}: {x} vs {y}")
 
 
+def assert_same_mesh(a, b, what):
+    """Two (positions, colours) results of mesh_scene, bit for bit, order included."""
+    assert a[0].shape == b[0].shape, f"{what}: {a[0].shape[0]} vs {b[0].shape[0]} triangles"
+    assert np.array_equal(a[0], b[0]), f"{what}: positions"
+    if a[1] is not None or b[1] is not None:
+        assert np.array_equal(a[1], b[1]), f"{what}: colours"
+
+
 def check_invariants(snap, params):
     """Structural invariants of the hash table + pools, independent of any oracle."""
     h = snap["hash"]
