@@ -574,6 +574,12 @@ class CApi:
         self._call("debug_front_end_counts", self._engine, C.byref(computed), C.byref(adopted))
         return computed.value, adopted.value
 
+    def debug_mark_overlap_counts(self):
+        """(allocation passes whose k_mark ran beside the previous GetImage's march, passes whose k_mark ran in the stream)"""
+        overlapped, in_stream = C.c_longlong(0), C.c_longlong(0)
+        self._call("debug_mark_overlap_counts", self._engine, C.byref(overlapped), C.byref(in_stream))
+        return overlapped.value, in_stream.value
+
     def reintegrate_batch_stats(self, scene):
         """(blocks the last batch loaded, its block-operations: (block, keyframe) pairs de-integrated or re-fused) -- HIP engine"""
         b, o = C.c_int32(0), C.c_int32(0)

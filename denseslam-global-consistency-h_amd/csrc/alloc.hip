@@ -58,9 +58,13 @@ __global__ __launch_bounds__(256) void k_reset_tables(HashEntry *hash, int n_ent
 }
 
 // test hook (dslam_debug_inject_device_error): a kernel that reports exactly what a failing pass would
-__global__ void k_inject_error(SceneCounters *cnt, int bits) { report_error(cnt, bits); }
+// (bit 1 is k_mark's alone and travels in k_mark's own word, report_error_own; bit 2 the way every other kernel reports)
+__global__ void k_inject_error(SceneCounters *cnt, int *mark_word, int bits) {
+  if (bits & 1) report_error_own(cnt, mark_word, 1);
+  if (bits & 2) report_error(cnt, 2);
+}
 int launch_inject_error(dslam_engine *e, dslam_scene *s, int bits) {
-  hipLaunchKernelGGL(k_inject_error, dim3(1), dim3(1), 0, e->stream, s->counters, bits);
+  hipLaunchKernelGGL(k_inject_error, dim3(1), dim3(1), 0, e->stream, s->counters, e->err_host.get() + 1, bits);
   DSLAM_HIP(hipGetLastError());
   return DSLAM_OK;
 }
@@ -177,6 +181,7 @@ struct MarkParams {
   unsigned gen;        // this pass' generation bit (0 or 0x80)
   int step_cap;
   SceneCounters *cnt;
+  int *err_word;               // this kernel's own page-locked error word (report_error_own)
   unsigned char *alloc_type;   // allocType bytes of the previous pass are cleared through its request bits
   unsigned *q1, *q2, *mark;    // this pass' bitmaps (all zero when the pass starts)
   const unsigned *old_q1, *old_q2;  // the previous pass' request bits
@@ -292,7 +297,7 @@ __global__ __launch_bounds__(256) void k_mark(MarkParams p) {
   int no_steps = ray_segment(d, x, y, p.invM, p.inv_fx, p.inv_fy, p.cx, p.cy, p.mu, p.one_over_block, pt, dir);
   if (!valid) no_steps = 0;
   if (no_steps > p.step_cap) {  // the order key cannot encode later steps: report instead of mis-ordering
-    report_error(p.cnt, 1);
+    report_error_own(p.cnt, p.err_word, 1);
     no_steps = p.step_cap;
   }
   int wave_steps = no_steps;
@@ -931,10 +936,19 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   mp.hash = s->hash; mp.mask = (unsigned)(s->p.num_buckets - 1); mp.num_buckets = s->p.num_buckets;
   mp.keys = e->order_keys; mp.vis_type = r->visible_type;
   mp.cnt = s->counters;
+  mp.err_word = e->err_host ? e->err_host.get() + 1 : nullptr;
   mp.alloc_type = e->alloc_type;
   if ((rc = alloc_step_cap(s, W, H, &mp.step_cap))) return rc;
   int cap_shift = 0;
   while ((1 << cap_shift) < mp.step_cap) cap_shift++;
+
+  // May this pass' k_mark run beside what the stream still holds?  Only if the last thing enqueued that it
+  // could collide with is a stamped GetImage (EngineStream: the permission goes with the first use of the stream, so it is
+  // asked for before any), on an asynchronous engine, without swapping (whose passes change the table behind the fusion),
+  // and with none of the diagnostics that wait for the stream around the launch.
+  static DiagDump mark_dump("DSLAM_DBG_MARK", 60);
+  bool overlap = e->stream.take() && e->overlap_mark && e->async_mode && !e->stream_lent && !s->p.use_swapping &&
+                 !mark_dump.enabled() && !dbg_sync_on();
 
   // this pass' generation bit; what the previous pass left visible carries the other one
   const unsigned old_gen = r->gen;
@@ -942,6 +956,7 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   mp.gen = r->gen;
   const int n_words = bit_tiles(N) * kBitTileWords, n_tiles = n_words / kSweepWords;
   if (!r->types_follow_list) {
+    overlap = false;   // (k_mark reads what these two write)
     hipLaunchKernelGGL(k_types_keep, dim3(n_words / 256), dim3(256), 0, e->stream, r->visible_type, r->vis_bits, n_words, (unsigned)r->gen);
     hipLaunchKernelGGL(k_types_rearm, dim3(64), dim3(256), 0, e->stream, r->visible_ids, r->counters, r->visible_type, r->vis_bits, old_gen);
     r->types_follow_list = true;
@@ -952,6 +967,7 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   e->alloc_pass++;
   if (e->bits_dirty[oth] > n_words) {  // the pass that dirtied `oth` ran on a larger table than this one
     const int lo = n_words, hi = e->bits_dirty[oth];
+    overlap = false;
     hipLaunchKernelGGL(k_clean_bits_tail, dim3((hi - lo + 255) / 256), dim3(256), 0, e->stream, e->bits_q1[oth], e->bits_q2[oth],
                        e->bits_mark[oth], e->alloc_type, lo, hi);
   }
@@ -966,9 +982,25 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   mp.fx = intr[0]; mp.fy = intr[1]; mp.voxel_size = s->p.voxel_size;
   mp.swapping = s->p.use_swapping ? 1 : 0;
   const int pix_blocks = (W * H + 255) / 256;
-  static DiagDump mark_dump("DSLAM_DBG_MARK", 60);
   mp.dbg = mark_dump.arm(mp.retest_wgs + pix_blocks, 32);
-  hipLaunchKernelGGL(k_mark, dim3(mp.retest_wgs + pix_blocks), dim3(256), 0, e->stream, mp);
+  if (overlap) {
+    // The stamped range pass has started, so all that was enqueued in front of it -- the previous frame's sweep and fusion, which
+    // k_mark's buffers depend on -- is complete; what is left in the stream shares no buffer with k_mark.  The host orders the
+    // three steps, as upload_view_pipelined does (capi.hip): wait for the stamp, run k_mark on the auxiliary stream, wait for
+    // it, and only then enqueue the sweep that reads what it wrote.  Both waits end with GPU progress; if the stream
+    // drains without the stamp having arrived (a failed launch), everything is complete all the same.
+    volatile unsigned *stamp = e->start_stamp;
+    for (unsigned spins = 1; *stamp != e->stamp_seq; spins++)
+      if ((spins & 0xfffu) == 0 && hipStreamQuery(e->stream.peek()) != hipErrorNotReady) break;
+    (void)hipGetLastError();  // (hipErrorNotReady is an answer, not a failure)
+    hipLaunchKernelGGL(k_mark, dim3(mp.retest_wgs + pix_blocks), dim3(256), 0, e->aux_stream, mp);
+    DSLAM_HIP(hipGetLastError());
+    DSLAM_HIP(hipStreamSynchronize(e->aux_stream));
+    e->mark_overlapped++;
+  } else {
+    hipLaunchKernelGGL(k_mark, dim3(mp.retest_wgs + pix_blocks), dim3(256), 0, e->stream, mp);
+    e->mark_in_stream++;
+  }
   dbg_sync(e, "k_mark");
   DSLAM_TRY(mark_dump.write(e));
   v->depth_dirty = false;

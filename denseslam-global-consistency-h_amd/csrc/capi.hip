@@ -85,13 +85,18 @@ unsigned long long next_map_version() {
 // the call itself on a synchronous engine, the next synchronising call (fence wait, read-back, dslam_engine_synchronize)
 // on an asynchronous one.  Told once per occurrence; the scene's own flags stay set for dslam_get_stats.
 int sync_check(dslam_engine *e) {
+  // (taking the stream withdraws the permission to overlap k_mark, EngineStream, and that is meant: once the stream has drained
+  // there is nothing left to run beside, and the auxiliary stream would only cost its launch and its wait)
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   return device_errors(e);
 }
+// Two words: [0] report_error's, [1] k_mark's own (dslam_device.h report_error_own: k_mark may run beside another kernel of
+// the engine, and two kernels must not update one word with a load and a store each).
 int device_errors(dslam_engine *e) {
   int *h = e->err_host;
-  if (!h || __atomic_load_n(h, __ATOMIC_RELAXED) == 0) return DSLAM_OK;
-  const int flags = __atomic_exchange_n(h, 0, __ATOMIC_RELAXED);   // (taken in one step: a report that lands now is the next call's)
+  if (!h || (__atomic_load_n(h, __ATOMIC_RELAXED) | __atomic_load_n(h + 1, __ATOMIC_RELAXED)) == 0) return DSLAM_OK;
+  // (each taken in one step: a report that lands now is the next call's)
+  const int flags = __atomic_exchange_n(h, 0, __ATOMIC_RELAXED) | __atomic_exchange_n(h + 1, 0, __ATOMIC_RELAXED);
   if (flags == 0) return DSLAM_OK;
   if (flags & 2) {
     set_last_error("a tile count of an ordered compaction never arrived (device made no progress?): the map state is undefined");
@@ -206,7 +211,8 @@ static void engine_free(dslam_engine *e) {
   (void)hipSetDevice(e->device);
   engine_detach_fences(e);
   if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
+  if (e->aux_stream) (void)hipStreamDestroy(e->aux_stream);
+  if (e->stream.peek()) (void)hipStreamDestroy(e->stream.peek());
   delete e;
   g_live_engines.fetch_sub(1, std::memory_order_relaxed);
 }
@@ -215,8 +221,11 @@ static void engine_release(dslam_engine *e) {
 }
 
 static int engine_allocate(dslam_engine *e) {
-  DSLAM_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+  DSLAM_HIP(hipStreamCreateWithFlags(e->stream.create_into(), hipStreamNonBlocking));
   DSLAM_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+  DSLAM_HIP(hipStreamCreateWithFlags(&e->aux_stream, hipStreamNonBlocking));
+  DSLAM_TRY(e->start_stamp.alloc(16, hipHostMallocCoherent));
+  *e->start_stamp = 0;
   e->pinned_bytes = 64 * 1024;
   DSLAM_TRY(e->pinned.alloc(e->pinned_bytes));
   memset(e->pinned, 0, e->pinned_bytes);
@@ -227,7 +236,7 @@ static int engine_allocate(dslam_engine *e) {
   e->ticket_base = 0;
   e->hip_failures_seen = hip_failure_count();
   DSLAM_TRY(e->err_host.alloc(16));
-  *e->err_host = 0;
+  e->err_host[0] = 0; e->err_host[1] = 0;
   return DSLAM_OK;
 }
 
@@ -267,6 +276,7 @@ int dslam_engine_create(int device_index, dslam_engine **out) {
   g_live_engines.fetch_add(1, std::memory_order_relaxed);
   e->device = device_index;
   if (const char *v = getenv("DSLAM_SPECULATIVE_FRONT_END")) e->speculate_front = atoi(v) != 0;
+  if (const char *v = getenv("DSLAM_OVERLAP_MARK")) e->overlap_mark = atoi(v) != 0;
   const int rc = engine_allocate(e);
   if (rc) {
     (void)dslam_engine_destroy(e);
@@ -282,8 +292,9 @@ int dslam_engine_destroy(dslam_engine *e) {
   if (!e) return DSLAM_OK;
   (void)hipSetDevice(e->device);
   if (e->closed) return DSLAM_OK;   // (a second destroy of an engine its handles keep alive: nothing left to do)
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
+  if (e->stream.peek()) (void)hipStreamSynchronize(e->stream.peek());
   if (e->copy_stream) (void)hipStreamSynchronize(e->copy_stream);
+  if (e->aux_stream) (void)hipStreamSynchronize(e->aux_stream);
   if (e->children > 0) {   // handles are left: their destroy calls need the object and its streams
     engine_detach_fences(e);
     e->closed = true;
@@ -332,6 +343,12 @@ int dslam_debug_front_end_counts(dslam_engine *e, long long *computed_out, long 
   DSLAM_REQUIRE(e && computed_out && adopted_out, "null argument");
   *computed_out = e->front_launches;
   *adopted_out = e->front_adoptions;
+  return DSLAM_OK;
+}
+int dslam_debug_mark_overlap_counts(dslam_engine *e, long long *overlapped_out, long long *in_stream_out) {
+  DSLAM_REQUIRE(e && overlapped_out && in_stream_out, "null argument");
+  *overlapped_out = e->mark_overlapped;
+  *in_stream_out = e->mark_in_stream;
   return DSLAM_OK;
 }
 int dslam_debug_icp_sums(dslam_engine *e, double out[29]) {
@@ -390,7 +407,7 @@ int dslam_fence_destroy(dslam_fence *f) {
 }
 int dslam_fence_record(dslam_engine *e, dslam_fence *f) {
   DSLAM_REQUIRE(e && f && f->engine == e, "fence belongs to a different engine");
-  DSLAM_HIP(hipEventRecord(f->ev, e->stream));
+  DSLAM_HIP(hipEventRecord(f->ev, e->stream.peek()));   // (a marker touches no buffer: EngineStream)
   f->recorded = true;
   f->view_reads_at_record = e->view_reads;
   e->last_fence = f;
@@ -411,7 +428,13 @@ int dslam_fence_query(dslam_fence *f, int *done) {
   }
   return DSLAM_OK;
 }
-void *dslam_engine_stream(dslam_engine *e) { return e ? (void *)e->stream : nullptr; }
+// (a caller that has the stream may order work of its own by it, which a k_mark on another queue would not respect: no overlap
+// on this engine from here on)
+void *dslam_engine_stream(dslam_engine *e) {
+  if (!e) return nullptr;
+  e->stream_lent = true;
+  return (void *)static_cast<hipStream_t>(e->stream);
+}
 
 // ---- scene ---------------------------------------------------------------------------------------------------
 // Every device / pinned allocation of a handle lives in an owner (dslam_memory.h) that is a member of the handle: deleting the
@@ -803,7 +826,7 @@ static int upload_view_pipelined(dslam_engine *e, dslam_view *v, const uint8_t *
       v->up_lender[b ^ 1] = f;
       v->up_consumed_by[b ^ 1] = f->ev;
     } else {
-      DSLAM_HIP(hipEventRecord(v->up_consumed[b ^ 1], e->stream));
+      DSLAM_HIP(hipEventRecord(v->up_consumed[b ^ 1], e->stream.peek()));   // (a marker touches no buffer: EngineStream)
       v->up_consumed_by[b ^ 1] = v->up_consumed[b ^ 1];
     }
   }
@@ -1726,8 +1749,15 @@ int dslam_get_image(dslam_engine *e, const dslam_scene *s, dslam_render_state *r
   DSLAM_REQUIRE(e && s && r && M && intr, "null argument");
   DSLAM_REQUIRE(type >= 0 && type <= DSLAM_IMAGE_DEPTH, "unknown image type");
   void *direct = direct_image(r, type, out_rgba, out_float);
+  const unsigned stamp_before = e->stamp_seq;
   DSLAM_TRY(get_image_on_device(e, s, r, M, intr, type, direct));
-  return deliver_image(e, r, type, out_rgba, out_float, direct);
+  DSLAM_TRY(deliver_image(e, r, type, out_rgba, out_float, direct));
+  // Everything this call enqueued from its stamped range pass on -- that pass and the march -- shares no buffer with k_mark
+  // (hazard table): the next allocation pass may run its k_mark beside them.  Not if the call waited for its
+  // image (a synchronous engine, an output buffer that is not page-locked): the stream is empty then.
+  const bool enqueued_only = e->async_mode && (direct || (!out_rgba && !out_float));
+  if (e->stamp_seq != stamp_before && enqueued_only) e->stream.grant();
+  return DSLAM_OK;
 }
 
 int dslam_get_image_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,

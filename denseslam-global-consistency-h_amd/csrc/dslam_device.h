@@ -97,6 +97,16 @@ __device__ __forceinline__ void report_error(SceneCounters *cnt, int bits) {
   if (h) __hip_atomic_store(h, bits | __hip_atomic_load(h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// k_mark's form: the engine's SECOND error word (dslam_engine::err_host[1]), which no other kernel writes, and a plain store.
+// k_mark may run beside another kernel of its engine; two kernels that each update one word with a load and
+// a store can lose a bit or deliver it twice.  A word of its own was chosen over one system-scope fetch_or on the shared
+// word: an atomic read-modify-write on page-locked host memory needs PCIe atomics end to end, which not every host
+// bridge passes on, while a store always arrives.  k_mark reports one condition only, so the store carries no old bits.
+__device__ __forceinline__ void report_error_own(SceneCounters *cnt, int *own_word, int bits) {
+  atomicOr(&cnt->error_flags, bits);
+  if (own_word) __hip_atomic_store(own_word, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 struct RenderCounters {
   int no_visible;       // ITMRenderState_VH::noVisibleEntries
   int count_result;     // CountVisibleBlocks result

@@ -177,9 +177,37 @@ constexpr size_t kMapDescriptorBytes = 80;
 
 using dslam::DeviceBuffer, dslam::Event, dslam::PinnedBuffer;
 
+// The engine's compute stream, and with it the permission to run the next allocation pass' k_mark beside what the stream still
+// holds.  dslam_get_image grants it once its stamped range pass and everything behind it are enqueued; whoever
+// takes the stream to enqueue anything else -- a launch, a copy, a memset, the caller through dslam_engine_stream -- withdraws
+// it by the act of taking it, so no launch site has to remember to.  Waits and event records, which touch no buffer, look at
+// the stream through peek() and leave the permission alone.
+class EngineStream {
+ public:
+  EngineStream() = default;
+  EngineStream(const EngineStream &) = delete;
+  EngineStream &operator=(const EngineStream &) = delete;
+  operator hipStream_t() const { stamped_last_ = false; return s_; }
+  hipStream_t peek() const { return s_; }
+  hipStream_t *create_into() { return &s_; }
+  void grant() { stamped_last_ = true; }
+  bool take() { const bool had = stamped_last_; stamped_last_ = false; return had; }   // (the permission is good for one pass)
+
+ private:
+  hipStream_t s_ = nullptr;
+  mutable bool stamped_last_ = false;   // the last thing enqueued that k_mark could collide with is a stamped GetImage
+};
+
 struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   int device = 0;
-  hipStream_t stream = nullptr;
+  EngineStream stream;
+  // k_mark beside the previous GetImage's march; DSLAM_OVERLAP_MARK=0 turns it off
+  hipStream_t aux_stream = nullptr;   // holds nothing but that k_mark; the host waits for it before the sweep is enqueued
+  bool overlap_mark = true;
+  bool stream_lent = false;           // dslam_engine_stream handed the compute stream out: the caller may order its own work by it
+  PinnedBuffer<unsigned> start_stamp; // page-locked, fine-grained: the stamp of the last stamped range pass that has STARTED
+  unsigned stamp_seq = 0;             // the stamp given to the last range pass enqueued with one (0: none yet)
+  long long mark_overlapped = 0, mark_in_stream = 0;   // allocation passes whose k_mark ran on aux_stream / in the stream (test hook)
   // Handles made from this engine that still exist (scenes, render states, views, frame stores: everything that keeps a
   // pointer to it and reads it in its destroy call).  dslam_engine_destroy with children left only closes the engine:
   // object and streams stay until the last child's destroy call (capi.hip engine_adopt / engine_release).
@@ -460,12 +488,15 @@ struct DSLAM_INTERNAL dslam_frame_store {
 namespace dslam {
 // diagnostics (DSLAM_DEBUG_SYNC=1): wait for the stream after a launch and say which one it was -- finds the kernel that
 // hangs or faults without a profiler
-inline void dbg_sync(dslam_engine *e, const char *what) {
+inline bool dbg_sync_on() {
   static const bool on = getenv("DSLAM_DEBUG_SYNC") != nullptr;
-  if (!on) return;
+  return on;
+}
+inline void dbg_sync(dslam_engine *e, const char *what) {
+  if (!dbg_sync_on()) return;
   fprintf(stderr, "[dslam] %s ...", what);
   fflush(stderr);
-  const hipError_t err = hipStreamSynchronize(e->stream);
+  const hipError_t err = hipStreamSynchronize(e->stream.peek());
   fprintf(stderr, " %s\n", err == hipSuccess ? "ok" : hipGetErrorString(err));
   fflush(stderr);
 }
@@ -478,6 +509,7 @@ inline void dbg_sync(dslam_engine *e, const char *what) {
 class DiagDump {
  public:
   DiagDump(const char *env, int ordinal) : file_(getenv(env)), ordinal_(ordinal) {}
+  bool enabled() const { return file_ != nullptr; }
   // the pointer the kernel stores its records through, or null: not this launch (or the allocation failed: write says so)
   unsigned long long *arm(size_t records, size_t bytes_per_record) {
     if (!file_ || ++calls_ != ordinal_) return nullptr;

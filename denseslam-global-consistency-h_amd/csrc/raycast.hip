@@ -110,9 +110,13 @@ __global__ __launch_bounds__(256) void k_fill_range_tiles(const RenderCounters *
                                                           const float2 *__restrict__ zr, const int *__restrict__ req,
                                                           float2 *range, int W, int tiles_x,
                                                           const int *__restrict__ wg_tiles, int n_wg_tiles, int budget,
-                                                          int capacity) {
+                                                          int capacity, unsigned *start_stamp, unsigned stamp) {
   __shared__ int s_min[kRangeTile * kRangeTile], s_max[kRangeTile * kRangeTile];
   __shared__ int red[4];
+  // GetImage's range pass tells the host that it has STARTED (one lane, one ordinary store to a page-locked word): the stream
+  // runs its launches in order, so everything enqueued in front of this one is complete
+  if (start_stamp && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
+    __hip_atomic_store(start_stamp, stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   // The visible count, the per-workgroup tile totals and this lane's first list entry are all fetched before anything
   // waits: four dependent round trips become one (the entry is read speculatively -- the index is inside the
   // buffers whatever the count turns out to be).
@@ -242,13 +246,19 @@ __global__ __launch_bounds__(256) void k_fill_range_tiles(const RenderCounters *
 
 constexpr int kProjectGrid = 512;
 
-static int launch_fill_range(dslam_engine *e, dslam_render_state *r, int n_wg_tiles) {
+// stamped: the pass is GetImage's, and an asynchronous engine that overlaps k_mark wants to hear of its start
+static int launch_fill_range(dslam_engine *e, dslam_render_state *r, int n_wg_tiles, bool stamped = false) {
   // corner = the tiles covering ceil(W/8) x ceil(H/8) cells (clamped to the image); chunks sized for the pool
   const int cw = (r->w + 7) / 8, ch = (r->h + 7) / 8;
   const int tiles_x = (cw + kRangeTile - 1) / kRangeTile, tiles_y = (ch + kRangeTile - 1) / kRangeTile;
+  unsigned *stamp_word = nullptr;
+  if (stamped && e->overlap_mark && e->async_mode) {
+    stamp_word = e->start_stamp;
+    if (++e->stamp_seq == 0) e->stamp_seq = 1;   // (0 is the word's value before the first stamp)
+  }
   hipLaunchKernelGGL(k_fill_range_tiles, dim3(tiles_x * tiles_y, kRangeSlices), dim3(256), 0, e->stream, r->counters,
                      r->proj_boxes, r->proj_z, r->proj_req, r->range, r->w, tiles_x, r->proj_wg_tiles, n_wg_tiles,
-                     e->render_tile_budget, r->n_local);
+                     e->render_tile_budget, r->n_local, stamp_word, e->stamp_seq);
   DSLAM_HIP(hipGetLastError());
   return DSLAM_OK;
 }
@@ -285,12 +295,12 @@ int launch_find_visible_and_depths(dslam_engine *e, const dslam_scene *s, dslam_
       std::swap(r->range, f->range);
       f->valid = false;
       e->front_adoptions++;
-      return launch_fill_range(e, r, select_tiles(N));
+      return launch_fill_range(e, r, select_tiles(N), true);
     }
   }
   SelFrustum<true> sel{s->hash, make_frustum_params(s, r, M, intr), r->proj_boxes, r->proj_z, r->proj_req, r->range, r->w * r->h};
   DSLAM_TRY(launch_bits_select(e, s->alloc_bits, N, sel, r->visible_ids, r->n_local, &r->counters->no_visible, s->counters, r->proj_wg_tiles));
-  return launch_fill_range(e, r, select_tiles(N));
+  return launch_fill_range(e, r, select_tiles(N), true);
 }
 
 

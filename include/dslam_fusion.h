@@ -202,6 +202,15 @@ int dslam_debug_stream_launches(dslam_engine *e, long long *count_out);
 /* Test hook: how many fusion launches of this engine also computed GetImage's front end for their pose (ProcessFrame,
  * unless DSLAM_SPECULATIVE_FRONT_END=0), and how many GetImage calls took such a result instead of computing it. */
 int dslam_debug_front_end_counts(dslam_engine *e, long long *computed_out, long long *adopted_out);
+/* Test hook: of this engine's allocation passes so far, how many ran their marking kernel beside the previous
+ * dslam_get_image's ray march on the engine's auxiliary stream, and how many ran it in the engine's stream.  A pass takes
+ * the first way only on an asynchronous engine, for a scene without swapping, when the last call before it that enqueued
+ * anything was a dslam_get_image that computed a range image (not one answered from its memo) and returned without
+ * waiting for the image (no output buffer, or a page-locked one), when no call has waited for the engine's stream since
+ * (dslam_engine_synchronize, a read-back; a dslam_fence_wait does not count), and dslam_engine_stream was never asked
+ * for; DSLAM_OVERLAP_MARK=0 in the environment of dslam_engine_create selects the second way always.  Both ways
+ * compute the same bytes. */
+int dslam_debug_mark_overlap_counts(dslam_engine *e, long long *overlapped_out, long long *in_stream_out);
 /* Test hook: a one-thread kernel reports the given device-side error bits for the scene (1: allocation ray longer than the
  * order key encodes, 2: a tile count never arrived) exactly as a failing pass would (report_error, csrc/dslam_device.h), so
  * that the way such an error reaches the caller can be tested: returned by this very call on a synchronous engine, by the
