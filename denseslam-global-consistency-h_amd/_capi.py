@@ -580,6 +580,13 @@ class CApi:
         self._call("debug_mark_overlap_counts", self._engine, C.byref(overlapped), C.byref(in_stream))
         return overlapped.value, in_stream.value
 
+    def debug_sweep_overlap_counts(self):
+        """(allocation passes whose sweep ran on the auxiliary stream with its table writes published later, passes whose sweep
+        ran in the stream)"""
+        overlapped, in_stream = C.c_longlong(0), C.c_longlong(0)
+        self._call("debug_sweep_overlap_counts", self._engine, C.byref(overlapped), C.byref(in_stream))
+        return overlapped.value, in_stream.value
+
     def reintegrate_batch_stats(self, scene):
         """(blocks the last batch loaded, its block-operations: (block, keyframe) pairs de-integrated or re-fused) -- HIP engine"""
         b, o = C.c_int32(0), C.c_int32(0)

@@ -383,6 +383,17 @@ __global__ __launch_bounds__(256) void k_mark(MarkParams p) {
 }
 #undef MARK_STAMP
 
+// Table writes of a sweep that ran beside the previous GetImage's march, waiting for k_publish_entries:
+// `entry[i]` goes to table entry `entry_idx[i]` whole, `offset[i].y` into the offset field of entry `offset[i].x`;
+// count[0] / count[1] records of each kind.
+struct PendingWrites {
+  unsigned *count;
+  u32x4 *entry;
+  int *entry_idx;
+  int2 *offset;
+  int entry_cap, offset_cap;
+};
+
 struct SweepParams {
   HashEntry *hash;
   int n_entries, num_buckets, n_tiles, n_words;   // n_words: whole tiles
@@ -419,6 +430,9 @@ struct SweepParams {
   float inv_fx, inv_fy, cx, cy, mu, one_over_block;
   int cap_shift;  // step_cap = 1 << cap_shift
   unsigned long long *dbg;  // diagnostics (DSLAM_DBG_SWEEP=<file>): per tile 8 timestamps (s_memtime)
+  // the DEFER instantiation: the table stores go to the engine's pending lists, errors to a word of its own
+  PendingWrites pend;
+  int *err_word;
 };
 
 // Pools that run out during the pass (rare): which requests get a block is the sequential rule over ALL requests in
@@ -483,7 +497,44 @@ __device__ __forceinline__ short4 replay_request(const SweepParams &p, int t, bo
 }
 
 // ... and the half that needs its ranks (k1, k2: type-1 / type-2 requests in front of it in hash-index order)
-template <bool SWAPPING>
+// The three table stores of a commit.  DEFER: appended to the engine's pending lists instead (k_publish_entries scatters them
+// behind the march that still reads the table); all targets of a pass are distinct, so their order is free.
+// A record that does not fit (it always does: every success takes a voxel-block slot, and the lists hold one record per slot)
+// is reported, never written.
+__device__ __forceinline__ u32x4 pack_entry(int px, int py, int pz, int offset, int ptr) {
+  u32x4 raw;
+  raw.x = ((unsigned)px & 0xffffu) | ((unsigned)py << 16);
+  raw.y = ((unsigned)pz & 0xffffu);
+  raw.z = (unsigned)offset;
+  raw.w = (unsigned)ptr;
+  return raw;
+}
+template <bool DEFER>
+__device__ __forceinline__ void table_store_entry(const SweepParams &p, int idx, short4 bc, int slot) {
+  if (!DEFER) {
+    store_entry(p.hash, idx, bc.x, bc.y, bc.z, 0, slot);
+  } else {
+    const unsigned i = atomicAdd(&p.pend.count[0], 1u);
+    if (i < (unsigned)p.pend.entry_cap) {
+      p.pend.entry_idx[i] = idx;
+      p.pend.entry[i] = pack_entry(bc.x, bc.y, bc.z, 0, slot);
+    } else {
+      report_error_own(p.cnt, p.err_word, 2);
+    }
+  }
+}
+template <bool DEFER>
+__device__ __forceinline__ void table_store_offset(const SweepParams &p, int idx, int offset) {
+  if (!DEFER) {
+    p.hash[idx].offset = offset;
+  } else {
+    const unsigned i = atomicAdd(&p.pend.count[1], 1u);
+    if (i < (unsigned)p.pend.offset_cap) p.pend.offset[i] = make_int2(idx, offset);
+    else report_error_own(p.cnt, p.err_word, 2);
+  }
+}
+
+template <bool SWAPPING, bool DEFER>
 __device__ __forceinline__ void commit_request(const SweepParams &p, int tile_first, int rel, bool is2, int k1, int k2, short4 bc, int base_free,
                                                int base_free_ex, int avail_vba, int avail_ex, unsigned *s_qv, unsigned *s_qf) {
   const int t = tile_first + rel;
@@ -493,7 +544,7 @@ __device__ __forceinline__ void commit_request(const SweepParams &p, int tile_fi
     const bool ok = p.do_commit && vr < avail_vba;
     if (ok) {
       const int slot = p.alloc_list[base_free - vr];
-      store_entry(p.hash, t, bc.x, bc.y, bc.z, 0, slot);
+      table_store_entry<DEFER>(p, t, bc, slot);
       bit_set(p.alloc_bits, t);
       if (p.born) p.born[slot] = p.born_stamp;
     }
@@ -508,8 +559,8 @@ __device__ __forceinline__ void commit_request(const SweepParams &p, int tile_fi
   } else if (p.do_commit && k2 < avail_ex && vr < avail_vba) {
     const int ex_off = p.excess_list[base_free_ex - k2];
     const int slot = p.alloc_list[base_free - vr];
-    p.hash[t].offset = ex_off + 1;
-    store_entry(p.hash, p.num_buckets + ex_off, bc.x, bc.y, bc.z, 0, slot);
+    table_store_offset<DEFER>(p, t, ex_off + 1);
+    table_store_entry<DEFER>(p, p.num_buckets + ex_off, bc, slot);
     bit_set(p.alloc_bits, p.num_buckets + ex_off);
     if (p.born) p.born[slot] = p.born_stamp;
     // (its type byte and its place in the visible list are the business of the tile that owns the new entry)
@@ -524,7 +575,7 @@ __device__ __forceinline__ void commit_request(const SweepParams &p, int tile_fi
 constexpr int kSweepWpt = 1;
 constexpr int kSweepWords = 256 * kSweepWpt;
 
-template <bool SWAPPING, int WPT>
+template <bool SWAPPING, int WPT, bool DEFER = false>
 __global__ __launch_bounds__(256) void k_alloc_sweep(SweepParams p) {
   constexpr int TW = 256 * WPT, TE = TW * 32;
   __shared__ int red[16];
@@ -653,7 +704,10 @@ __global__ __launch_bounds__(256) void k_alloc_sweep(SweepParams p) {
     }
     STAMP(3);
     int pre[4];  // requests (type 1, type 2) and visible entries (retest | mark; new type-1 requests) in front of this tile
-    if (!lookback2(p.agg_req, p.agg_vis, b, p.epoch, red, pre) && threadIdx.x == 0) report_error(p.cnt, 2);
+    if (!lookback2(p.agg_req, p.agg_vis, b, p.epoch, red, pre) && threadIdx.x == 0) {
+      if (DEFER) report_error_own(p.cnt, p.err_word, 2);   // (it may run beside another kernel of the engine, like k_mark)
+      else report_error(p.cnt, 2);
+    }
     STAMP(4);
     int lv[4] = {later2, 0, 0, 0};
     if (has_excess) block_sum4(lv, red);
@@ -691,12 +745,12 @@ __global__ __launch_bounds__(256) void k_alloc_sweep(SweepParams p) {
           const int rel = (int)(rq.x & 0x7fffffffu);
           const bool is2 = rq.x >> 31;
           const short4 bc = replay_request(p, tile_first + rel, is2);
-          commit_request<SWAPPING>(p, tile_first, rel, is2, pre[0] + (int)(rq.y & 0xffffu), pre[1] + (int)(rq.y >> 16), bc, base_free, base_free_ex,
+          commit_request<SWAPPING, DEFER>(p, tile_first, rel, is2, pre[0] + (int)(rq.y & 0xffffu), pre[1] + (int)(rq.y >> 16), bc, base_free, base_free_ex,
                                    avail_vba, avail_ex, s_qv, s_qf);
         }
       }
     } else if (st_has) {
-      commit_request<SWAPPING>(p, tile_first, (int)(st_rq.x & 0x7fffffffu), st_rq.x >> 31, pre[0] + (int)(st_rq.y & 0xffffu), pre[1] + (int)(st_rq.y >> 16),
+      commit_request<SWAPPING, DEFER>(p, tile_first, (int)(st_rq.x & 0x7fffffffu), st_rq.x >> 31, pre[0] + (int)(st_rq.y & 0xffffu), pre[1] + (int)(st_rq.y >> 16),
                                st_bc, base_free, base_free_ex, avail_vba, avail_ex, s_qv, s_qf);
     }
     __syncthreads();
@@ -917,8 +971,44 @@ int alloc_step_cap(const dslam_scene *s, int W, int H, int *cap_out) {
   return DSLAM_OK;
 }
 
+// The table writes a deferring sweep left on the pending lists, scattered into the table: behind the march the sweep ran
+// beside, in front of the fusion launch.  A small fixed grid; the counts are clamped to the lists and every
+// target is checked against the table.  `next`: the other pair of counts, zeroed for the next overlapped pass (nothing
+// appends through it before this kernel has ended: that pass starts behind a stamp that is enqueued behind this kernel).
+constexpr int kPublishWgs = 16;
+__global__ __launch_bounds__(256) void k_publish_entries(HashEntry *hash, int n_entries, PendingWrites pend, unsigned *next) {
+  const unsigned n_e = min(pend.count[0], (unsigned)pend.entry_cap), n_o = min(pend.count[1], (unsigned)pend.offset_cap);
+  const unsigned tid = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+  for (unsigned i = tid; i < n_e; i += stride) {
+    const int t = pend.entry_idx[i];
+    if ((unsigned)t < (unsigned)n_entries) *reinterpret_cast<u32x4 *>(hash + t) = pend.entry[i];
+  }
+  for (unsigned i = tid; i < n_o; i += stride) {
+    const int2 o = pend.offset[i];
+    if ((unsigned)o.x < (unsigned)n_entries) hash[o.x].offset = o.y;
+  }
+  if (tid == 0) { next[0] = 0; next[1] = 0; }
+}
+
+// The rest of an allocation pass whose sweep went to aux_stream: the host waits for that stream (k_mark and the sweep), then
+// the pending table writes go into the engine stream.  Called by launch_allocate itself, or later by the caller that asked
+// to (dslam_process_frame's deferred tail, capi.hip).
+int finish_overlapped_allocate(dslam_engine *e, dslam_scene *s) {
+  if (!e->publish_due) return DSLAM_OK;
+  e->publish_due = false;
+  DSLAM_HIP(hipStreamSynchronize(e->aux_stream));
+  const unsigned pair = (e->pend_pass - 1u) & 1u;   // (the pass that is being finished)
+  PendingWrites pw{e->pend_count + 2 * pair, reinterpret_cast<u32x4 *>(e->pend_entry.get()), e->pend_entry_idx, e->pend_offset,
+                   e->pend_cap, e->pend_cap};
+  hipLaunchKernelGGL(k_publish_entries, dim3(kPublishWgs), dim3(256), 0, e->stream, s->hash, s->n_entries, pw,
+                     e->pend_count + 2 * (pair ^ 1u));
+  DSLAM_HIP(hipGetLastError());
+  return DSLAM_OK;
+}
+
 int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_render_state *r, const float *M_d,
-                    const float *intr, int only_update_visible_list, int *list_out, void *count_out) {
+                    const float *intr, int only_update_visible_list, int *list_out, void *count_out, bool *publish_left) {
+  if (publish_left) *publish_left = false;
   const int W = v->w_d, H = v->h_d, N = s->n_entries;
   DSLAM_REQUIRE(r->n_entries == N, "render state was created for a different scene size");
   DSLAM_REQUIRE((N & 15) == 0, "num_buckets + num_excess must be a multiple of 16");
@@ -947,6 +1037,8 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   // asked for before any), on an asynchronous engine, without swapping (whose passes change the table behind the fusion),
   // and with none of the diagnostics that wait for the stream around the launch.
   static DiagDump mark_dump("DSLAM_DBG_MARK", 60);
+  static DiagDump sweep_dump("DSLAM_DBG_SWEEP", 60);
+  bool overlap_sweep = false;
   bool overlap = e->stream.take() && e->overlap_mark && e->async_mode && !e->stream_lent && !s->p.use_swapping &&
                  !mark_dump.enabled() && !dbg_sync_on();
 
@@ -987,15 +1079,20 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
     // The stamped range pass has started, so all that was enqueued in front of it -- the previous frame's sweep and fusion, which
     // k_mark's buffers depend on -- is complete; what is left in the stream shares no buffer with k_mark.  The host orders the
     // three steps, as upload_view_pipelined does (capi.hip): wait for the stamp, run k_mark on the auxiliary stream, wait for
-    // it, and only then enqueue the sweep that reads what it wrote.  Both waits end with GPU progress; if the stream
-    // drains without the stamp having arrived (a failed launch), everything is complete all the same.
+    // it, and only then enqueue the sweep that reads what it wrote (or: launch the deferring sweep behind it on the same
+    // stream and wait for both later, below).  Both waits end with GPU progress; if the stream drains without the stamp
+    // having arrived (a failed launch), everything is complete all the same.
     volatile unsigned *stamp = e->start_stamp;
     for (unsigned spins = 1; *stamp != e->stamp_seq; spins++)
       if ((spins & 0xfffu) == 0 && hipStreamQuery(e->stream.peek()) != hipErrorNotReady) break;
     (void)hipGetLastError();  // (hipErrorNotReady is an answer, not a failure)
+    e->view_reads_done = e->stamp_view_reads;   // (what the stamp proves about the views' landing buffers, capi.hip)
     hipLaunchKernelGGL(k_mark, dim3(mp.retest_wgs + pix_blocks), dim3(256), 0, e->aux_stream, mp);
     DSLAM_HIP(hipGetLastError());
-    DSLAM_HIP(hipStreamSynchronize(e->aux_stream));
+    // The sweep follows k_mark on the auxiliary stream, its table writes deferred, if this is the plain pass into the render
+    // state's own list; otherwise the host waits for k_mark here and the sweep goes into the stream.
+    overlap_sweep = e->overlap_sweep && !list_out && !count_out && !s->alloc_born && !sweep_dump.enabled() && e->pend_cap > 0;
+    if (!overlap_sweep) DSLAM_HIP(hipStreamSynchronize(e->aux_stream));
     e->mark_overlapped++;
   } else {
     hipLaunchKernelGGL(k_mark, dim3(mp.retest_wgs + pix_blocks), dim3(256), 0, e->stream, mp);
@@ -1025,15 +1122,35 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   sp.epoch = e->epoch;
   const int grid = n_tiles;   // one tile per workgroup, one ticket each
   (void)tickets_ok(e);
-  sp.ticket = e->ticket; sp.ticket_base = e->ticket_base;
-  e->ticket_base += (unsigned)grid;
+  if (overlap_sweep) {   // (a ticket word no launch of the engine stream shares)
+    sp.ticket = e->ticket + 2; sp.ticket_base = e->ticket_base3;
+    e->ticket_base3 += (unsigned)grid;
+  } else {
+    sp.ticket = e->ticket; sp.ticket_base = e->ticket_base;
+    e->ticket_base += (unsigned)grid;
+  }
   sp.gen = r->gen;
   sp.do_commit = only_update_visible_list ? 0 : 1;
   sp.depth = v->depth; sp.W = W; sp.H = H;
   sp.invM = mp.invM; sp.inv_fx = mp.inv_fx; sp.inv_fy = mp.inv_fy; sp.cx = mp.cx; sp.cy = mp.cy;
   sp.mu = mp.mu; sp.one_over_block = mp.one_over_block; sp.cap_shift = cap_shift;
-  static DiagDump sweep_dump("DSLAM_DBG_SWEEP", 60);
   sp.dbg = sweep_dump.arm(n_tiles, 64);
+  sp.pend = PendingWrites{nullptr, nullptr, nullptr, nullptr, 0, 0};
+  sp.err_word = nullptr;
+  if (overlap_sweep) {
+    // (never with swapping: `overlap` excludes it)
+    sp.pend = PendingWrites{e->pend_count + 2 * (e->pend_pass & 1u), reinterpret_cast<u32x4 *>(e->pend_entry.get()), e->pend_entry_idx,
+                            e->pend_offset, e->pend_cap, e->pend_cap};
+    e->pend_pass++;
+    sp.err_word = e->err_host ? e->err_host.get() + 2 : nullptr;
+    hipLaunchKernelGGL((k_alloc_sweep<false, kSweepWpt, true>), dim3(grid), dim3(256), 0, e->aux_stream, sp);
+    DSLAM_HIP(hipGetLastError());
+    e->publish_due = true;
+    e->sweep_overlapped++;
+    if (publish_left) { *publish_left = true; return DSLAM_OK; }
+    return finish_overlapped_allocate(e, s);
+  }
+  e->sweep_in_stream++;
   if (s->p.use_swapping) hipLaunchKernelGGL((k_alloc_sweep<true, kSweepWpt>), dim3(grid), dim3(256), 0, e->stream, sp);
   else hipLaunchKernelGGL((k_alloc_sweep<false, kSweepWpt>), dim3(grid), dim3(256), 0, e->stream, sp);
   dbg_sync(e, "k_alloc_sweep");

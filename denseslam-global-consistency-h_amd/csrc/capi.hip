@@ -92,11 +92,22 @@ int sync_check(dslam_engine *e) {
 }
 // Two words: [0] report_error's, [1] k_mark's own (dslam_device.h report_error_own: k_mark may run beside another kernel of
 // the engine, and two kernels must not update one word with a load and a store each).
+// [2] is the word of the allocation sweep that runs on the auxiliary stream, for the same reason.  A call whose
+// body the engine held back (dslam_engine::deferred) and that failed when it ran is told here too, once, in front of what
+// kernels reported: it happened first.
 int device_errors(dslam_engine *e) {
+  if (e->deferred_rc) {
+    const int rc = e->deferred_rc;
+    e->deferred_rc = 0;
+    set_last_error(e->deferred_error);
+    return rc;
+  }
   int *h = e->err_host;
-  if (!h || (__atomic_load_n(h, __ATOMIC_RELAXED) | __atomic_load_n(h + 1, __ATOMIC_RELAXED)) == 0) return DSLAM_OK;
+  if (!h || (__atomic_load_n(h, __ATOMIC_RELAXED) | __atomic_load_n(h + 1, __ATOMIC_RELAXED) | __atomic_load_n(h + 2, __ATOMIC_RELAXED)) == 0)
+    return DSLAM_OK;
   // (each taken in one step: a report that lands now is the next call's)
-  const int flags = __atomic_exchange_n(h, 0, __ATOMIC_RELAXED) | __atomic_exchange_n(h + 1, 0, __ATOMIC_RELAXED);
+  const int flags = __atomic_exchange_n(h, 0, __ATOMIC_RELAXED) | __atomic_exchange_n(h + 1, 0, __ATOMIC_RELAXED) |
+                    __atomic_exchange_n(h + 2, 0, __ATOMIC_RELAXED);
   if (flags == 0) return DSLAM_OK;
   if (flags & 2) {
     set_last_error("a tile count of an ordered compaction never arrived (device made no progress?): the map state is undefined");
@@ -106,6 +117,31 @@ int device_errors(dslam_engine *e) {
   return DSLAM_ERR_UNSUPPORTED;
 }
 
+// Calls the engine holds back.  The caller's thread runs them, in call order, with the stream's hook
+// disarmed; a body that fails does not stop the ones behind it (a caller that ignored the call's return value would have
+// made them too), and the first failure waits in deferred_rc for the late-error path (device_errors).
+static void run_held_calls(void *engine) { (void)flush_deferred(static_cast<dslam_engine *>(engine)); }
+int flush_deferred(dslam_engine *e) {
+  if (!e || e->flushing || e->deferred.empty()) return DSLAM_OK;
+  e->flushing = true;
+  e->stream.disarm();
+  std::vector<std::function<int()>> bodies;
+  bodies.swap(e->deferred);
+  for (auto &body : bodies) {
+    const int rc = body();
+    if (rc != DSLAM_OK && e->deferred_rc == DSLAM_OK) {
+      e->deferred_rc = rc;
+      e->deferred_error = g_last_error;
+    }
+  }
+  e->flushing = false;
+  return DSLAM_OK;
+}
+void defer_call(dslam_engine *e, std::function<int()> body) {
+  e->deferred.push_back(std::move(body));
+  e->stream.arm(run_held_calls, e);
+}
+
 int finish_call(dslam_engine *e) {
   if (!e->async_mode) return sync_check(e);
   return DSLAM_OK;
@@ -113,7 +149,7 @@ int finish_call(dslam_engine *e) {
 
 int tickets_resync(dslam_engine *e) {
   const unsigned long long seen = hip_failure_count();
-  unsigned host[2] = {0, 0};
+  unsigned host[3] = {0, 0, 0};
   if (hipStreamSynchronize(e->stream) != hipSuccess || hipMemcpy(host, e->ticket, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess) {
     (void)hipGetLastError();
     set_last_error("ticket counters could not be read back after a HIP failure");
@@ -121,6 +157,7 @@ int tickets_resync(dslam_engine *e) {
   }
   e->ticket_base = host[0];
   e->ticket_base2 = host[1];
+  e->ticket_base3 = host[2];
   e->hip_failures_seen = seen;
   return DSLAM_OK;
 }
@@ -149,6 +186,9 @@ int ensure_scratch(dslam_engine *e, int entries, int local_blocks) {
   if (tiles < bit_tiles(N) * (kBitTileWords / 32)) tiles = bit_tiles(N) * (kBitTileWords / 32);  // (room for tiles as small as 1024 entries)
   DSLAM_TRY(n.agg.alloc_zeroed((size_t)tiles * 3, e->stream));
   n.agg_tiles = tiles;
+  n.pend_cap = N < L ? N : L;
+  DSLAM_TRY(n.pend_entry.alloc(n.pend_cap)); DSLAM_TRY(n.pend_entry_idx.alloc(n.pend_cap)); DSLAM_TRY(n.pend_offset.alloc(n.pend_cap));
+  DSLAM_TRY(n.pend_count.alloc_zeroed(4, e->stream));
   DSLAM_TRY(n.tile_counts.alloc((size_t)tiles * 2)); DSLAM_TRY(n.tile_offsets.alloc((size_t)tiles * 2));
   const size_t list_len = (size_t)(N > L ? N : L);
   DSLAM_TRY(n.list_a.alloc(list_len)); DSLAM_TRY(n.list_b.alloc(list_len));
@@ -236,7 +276,7 @@ static int engine_allocate(dslam_engine *e) {
   e->ticket_base = 0;
   e->hip_failures_seen = hip_failure_count();
   DSLAM_TRY(e->err_host.alloc(16));
-  e->err_host[0] = 0; e->err_host[1] = 0;
+  e->err_host[0] = 0; e->err_host[1] = 0; e->err_host[2] = 0;
   return DSLAM_OK;
 }
 
@@ -277,6 +317,8 @@ int dslam_engine_create(int device_index, dslam_engine **out) {
   e->device = device_index;
   if (const char *v = getenv("DSLAM_SPECULATIVE_FRONT_END")) e->speculate_front = atoi(v) != 0;
   if (const char *v = getenv("DSLAM_OVERLAP_MARK")) e->overlap_mark = atoi(v) != 0;
+  if (const char *v = getenv("DSLAM_OVERLAP_SWEEP")) e->overlap_sweep = atoi(v) != 0;
+  if (!e->overlap_mark) e->overlap_sweep = false;
   const int rc = engine_allocate(e);
   if (rc) {
     (void)dslam_engine_destroy(e);
@@ -291,6 +333,7 @@ int dslam_engine_create(int device_index, dslam_engine **out) {
 int dslam_engine_destroy(dslam_engine *e) {
   if (!e) return DSLAM_OK;
   (void)hipSetDevice(e->device);
+  flush_deferred(e);   // (on its own device: held calls launch kernels)
   if (e->closed) return DSLAM_OK;   // (a second destroy of an engine its handles keep alive: nothing left to do)
   if (e->stream.peek()) (void)hipStreamSynchronize(e->stream.peek());
   if (e->copy_stream) (void)hipStreamSynchronize(e->copy_stream);
@@ -311,6 +354,7 @@ int dslam_debug_live_engines(int *out) {
 }
 
 int dslam_selftest_division(dslam_engine *e, long long samples, long long *mismatches_out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && mismatches_out && samples > 0, "bad argument");
   unsigned long long *dev = reinterpret_cast<unsigned long long *>(e->misc_counter + 4);  // 8-byte aligned slot
   int rc = launch_selftest_division(e, samples, dev);
@@ -322,42 +366,56 @@ int dslam_selftest_division(dslam_engine *e, long long samples, long long *misma
 }
 
 int dslam_debug_set_render_tile_budget(dslam_engine *e, int budget) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && budget > 0, "bad argument");
   e->render_tile_budget = budget;
   return DSLAM_OK;
 }
 
 int dslam_debug_set_push_job_min(dslam_engine *e, int min_visible_blocks) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && min_visible_blocks >= 0, "bad argument");
   e->push_job_min = min_visible_blocks;
   return DSLAM_OK;
 }
 
 int dslam_debug_stream_launches(dslam_engine *e, long long *count_out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && count_out, "bad argument");
   *count_out = e->stream_launches;
   return DSLAM_OK;
 }
 
 int dslam_debug_front_end_counts(dslam_engine *e, long long *computed_out, long long *adopted_out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && computed_out && adopted_out, "null argument");
   *computed_out = e->front_launches;
   *adopted_out = e->front_adoptions;
   return DSLAM_OK;
 }
 int dslam_debug_mark_overlap_counts(dslam_engine *e, long long *overlapped_out, long long *in_stream_out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && overlapped_out && in_stream_out, "null argument");
   *overlapped_out = e->mark_overlapped;
   *in_stream_out = e->mark_in_stream;
   return DSLAM_OK;
 }
+int dslam_debug_sweep_overlap_counts(dslam_engine *e, long long *overlapped_out, long long *in_stream_out) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && overlapped_out && in_stream_out, "null argument");
+  *overlapped_out = e->sweep_overlapped;
+  *in_stream_out = e->sweep_in_stream;
+  return DSLAM_OK;
+}
 int dslam_debug_icp_sums(dslam_engine *e, double out[29]) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && out, "null argument");
   DSLAM_REQUIRE(e->icp_have_sums, "no tracker evaluation has run on this engine");
   memcpy(out, e->icp_last_sums, sizeof e->icp_last_sums);
   return DSLAM_OK;
 }
 int dslam_debug_inject_device_error(dslam_engine *e, dslam_scene *s, int bits) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && s->engine == e && (bits == 1 || bits == 2 || bits == 3), "bad argument");
   int rc = launch_inject_error(e, s, bits);
   if (rc) return rc;
@@ -365,17 +423,20 @@ int dslam_debug_inject_device_error(dslam_engine *e, dslam_scene *s, int bits) {
 }
 
 int dslam_engine_set_async(dslam_engine *e, int async_mode) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e, "null engine");
   e->async_mode = async_mode != 0;
   return DSLAM_OK;
 }
 int dslam_engine_synchronize(dslam_engine *e) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e, "null engine");
   return sync_check(e);  // (every pipelined upload is waited for by a kernel of this stream)
 }
 
 // ---- fences --------------------------------------------------------------------------------------------------
 int dslam_fence_create(dslam_engine *e, dslam_fence **out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && out, "null argument");
   *out = nullptr;
   dslam_fence *f = new dslam_fence();
@@ -399,28 +460,40 @@ static void release_lender(dslam_view *v, int b) {
   if (f && --f->lent_count == 0 && f->zombie) fence_free(f);
 }
 int dslam_fence_destroy(dslam_fence *f) {
+  if (f) flush_deferred(f->engine);   // (a record of this fence may still be held back)
   if (!f) return DSLAM_OK;
   if (f->engine && f->engine->last_fence == f) f->engine->last_fence = nullptr;
   if (f->engine && f->lent_count > 0) { f->zombie = true; return DSLAM_OK; }  // (a view still waits on its event)
   fence_free(f);
   return DSLAM_OK;
 }
-int dslam_fence_record(dslam_engine *e, dslam_fence *f) {
-  DSLAM_REQUIRE(e && f && f->engine == e, "fence belongs to a different engine");
+static int fence_record_now(dslam_engine *e, dslam_fence *f) {
+  f->record_held = false;
   DSLAM_HIP(hipEventRecord(f->ev, e->stream.peek()));   // (a marker touches no buffer: EngineStream)
   f->recorded = true;
   f->view_reads_at_record = e->view_reads;
   e->last_fence = f;
   return DSLAM_OK;
 }
+// Behind calls the engine holds back the record is held back too: the fence must sit behind their kernels.
+// Waiting for such a fence, or asking it, hands everything to the GPU first.
+int dslam_fence_record(dslam_engine *e, dslam_fence *f) {
+  DSLAM_REQUIRE(e && f && f->engine == e, "fence belongs to a different engine");
+  if (e->deferred.empty()) return fence_record_now(e, f);
+  f->record_held = true;
+  defer_call(e, [e, f]() { return fence_record_now(e, f); });
+  return DSLAM_OK;
+}
 int dslam_fence_wait(dslam_fence *f) {
   DSLAM_REQUIRE(f, "null fence");
+  if (f->record_held) flush_deferred(f->engine);
   if (f->recorded) DSLAM_HIP(hipEventSynchronize(f->ev));
   return f->engine ? device_errors(f->engine) : DSLAM_OK;   // (what kernels in front of the fence reported, see sync_check)
 }
 int dslam_fence_query(dslam_fence *f, int *done) {
   DSLAM_REQUIRE(f && done, "null argument");
   *done = 1;
+  if (f->record_held) flush_deferred(f->engine);
   if (f->recorded) {
     const hipError_t err = hipEventQuery(f->ev);
     if (err == hipErrorNotReady) *done = 0;
@@ -431,6 +504,7 @@ int dslam_fence_query(dslam_fence *f, int *done) {
 // (a caller that has the stream may order work of its own by it, which a k_mark on another queue would not respect: no overlap
 // on this engine from here on)
 void *dslam_engine_stream(dslam_engine *e) {
+  flush_deferred(e);
   if (!e) return nullptr;
   e->stream_lent = true;
   return (void *)static_cast<hipStream_t>(e->stream);
@@ -466,6 +540,7 @@ static int scene_allocate(dslam_engine *e, dslam_scene *s, void *ext_voxels) {
 }
 
 int dslam_scene_create(dslam_engine *e, const dslam_scene_params *p, void *ext_voxels, dslam_scene **out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && p && out, "null argument");
   *out = nullptr;
   DSLAM_HIP(hipSetDevice(e->device));
@@ -533,6 +608,7 @@ static int front_end_for(dslam_engine *e, dslam_scene *s, const dslam_render_sta
 int dslam_scene_destroy(dslam_scene *s) {
   if (!s) return DSLAM_OK;
   (void)hipSetDevice(s->engine->device);
+  flush_deferred(s->engine);   // (on its own device: held calls launch kernels)
   (void)hipStreamSynchronize(s->engine->stream);
   dslam_engine *e = s->engine;
   delete s;
@@ -547,6 +623,7 @@ static void reset_host_cursors(dslam_scene *s) {
 }
 
 int dslam_scene_reset(dslam_engine *e, dslam_scene *s) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s, "null argument");
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   int rc = launch_scene_reset(e, s);
@@ -568,6 +645,7 @@ int dslam_scene_get_params(const dslam_scene *s, dslam_scene_params *out) {
 }
 
 int dslam_scene_set_shard(dslam_scene *s, int shard, int num_shards, int chunk_blocks) {
+  if (s) flush_deferred(s->engine);
   DSLAM_REQUIRE(s && num_shards >= 1 && shard >= 0 && shard < num_shards && chunk_blocks >= 1, "bad shard spec");
   // A rank that does not own a block still swaps its (stale) copy of it out to ITS host store during the batch, and
   // the exchange moves device blocks only: the ranks' global caches would drift apart.  Refused, not silently wrong.
@@ -577,6 +655,7 @@ int dslam_scene_set_shard(dslam_scene *s, int shard, int num_shards, int chunk_b
 }
 
 int dslam_scene_set_shard_range(dslam_scene *s, int first_block, int num_blocks) {
+  if (s) flush_deferred(s->engine);
   DSLAM_REQUIRE(s && first_block >= 0, "bad shard range");
   DSLAM_REQUIRE(!(s->p.use_swapping && num_blocks >= 0), "a scene with host swapping cannot be sharded (the host store is per rank)");
   s->shard_first = first_block; s->shard_count = num_blocks;
@@ -585,6 +664,7 @@ int dslam_scene_set_shard_range(dslam_scene *s, int first_block, int num_blocks)
 
 // ---- which blocks a sharded batch touched, and moving exactly those (csrc/shard.hip) ------------------------------
 int dslam_scene_track_dirty(dslam_engine *e, dslam_scene *s, int enable) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s, "null argument");
   if (enable) {
     const size_t n = (size_t)s->p.num_local_blocks;
@@ -601,11 +681,13 @@ int dslam_scene_track_dirty(dslam_engine *e, dslam_scene *s, int enable) {
 }
 
 int dslam_shard_dirty_plan(dslam_engine *e, dslam_scene *s, int num_shards, int chunk_blocks, int32_t *counts_out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && counts_out, "null argument");
   return launch_dirty_plan(e, s, num_shards, chunk_blocks, counts_out);
 }
 
 int dslam_shard_dirty_pack(dslam_engine *e, const dslam_scene *s, int shard, void *send_dev, int capacity_blocks) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s, "null argument");
   int rc = launch_dirty_pack(e, s, shard, send_dev, capacity_blocks);
   if (rc) return rc;
@@ -613,6 +695,7 @@ int dslam_shard_dirty_pack(dslam_engine *e, const dslam_scene *s, int shard, voi
 }
 
 int dslam_shard_dirty_unpack(dslam_engine *e, dslam_scene *s, int skip_shard, const void *recv_dev, int stride_blocks) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s, "null argument");
   s->version = next_map_version();  // the map changes: GetImage memos of this scene are stale
   int rc = launch_dirty_unpack(e, s, skip_shard, recv_dev, stride_blocks);
@@ -638,6 +721,7 @@ static int render_state_allocate(dslam_engine *e, dslam_render_state *r) {
 }
 
 int dslam_render_state_create(dslam_engine *e, const dslam_scene *s, int w, int h, dslam_render_state **out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && out && w > 0 && h > 0, "bad argument");
   *out = nullptr;
   dslam_render_state *r = new dslam_render_state();
@@ -654,6 +738,7 @@ int dslam_render_state_create(dslam_engine *e, const dslam_scene *s, int w, int 
 int dslam_render_state_destroy(dslam_render_state *r) {
   if (!r) return DSLAM_OK;
   (void)hipSetDevice(r->engine->device);
+  flush_deferred(r->engine);   // (on its own device: held calls launch kernels)
   (void)hipStreamSynchronize(r->engine->stream);
   dslam_engine *e = r->engine;
   delete r;
@@ -678,6 +763,7 @@ static int view_allocate(dslam_engine *e, dslam_view *v) {
 }
 
 int dslam_view_create(dslam_engine *e, int w_rgb, int h_rgb, int w_d, int h_d, dslam_view **out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && out && w_rgb > 0 && h_rgb > 0 && w_d > 0 && h_d > 0, "bad argument");
   *out = nullptr;
   dslam_view *v = new dslam_view();
@@ -694,6 +780,7 @@ int dslam_view_create(dslam_engine *e, int w_rgb, int h_rgb, int w_d, int h_d, d
 int dslam_view_destroy(dslam_view *v) {
   if (!v) return DSLAM_OK;
   (void)hipSetDevice(v->engine->device);
+  flush_deferred(v->engine);   // (on its own device: held calls launch kernels)
   (void)hipStreamSynchronize(v->engine->stream);
   if (v->engine->copy_stream) (void)hipStreamSynchronize(v->engine->copy_stream);
   for (int b = 0; b < 2; b++) release_lender(v, b);
@@ -817,6 +904,34 @@ static int upload_view_pipelined(dslam_engine *e, dslam_view *v, const uint8_t *
   }
   const int b = v->up_next;
   v->up_next ^= 1;
+  // Calls the engine holds back (a ProcessFrame's tail, the GetImage and the fence record behind it) are handed
+  // to the GPU HERE, in front of the copy: the thread has nothing else to do until the copy's target is free and the copy
+  // has landed, and the GPU gets the frame's fusion launch while the previous march still runs.  The copy then starts when
+  // the auxiliary stream's pass is over -- beside that pass (k_mark above all) it lengthens the march, measured.
+  // DSLAM_COPY_BEFORE_HELD_CALLS=1, a measurement's switch, enqueues the copy first and runs the held calls while it is in
+  // flight (the thread sits out the upload and the auxiliary stream together; 3 % slower on the bench).
+  // Either way the copy's target must be free.  The event that says so sits behind the previous GetImage's march; the stamp
+  // the last allocation pass saw arrive proves the same earlier (every kernel that read a view and was called for by then
+  // is complete), so in the steady state nobody waits for the march here.
+  static const bool copy_first = getenv("DSLAM_COPY_BEFORE_HELD_CALLS") && atoi(getenv("DSLAM_COPY_BEFORE_HELD_CALLS")) != 0;
+  if (stream_waits || !copy_first) flush_deferred(e);
+  if (v->up_used[b] && v->up_reads[b] > e->view_reads_done) {
+    if (stream_waits) {
+      DSLAM_HIP(hipStreamWaitEvent(e->copy_stream, v->up_consumed_by[b], 0));
+    } else {
+      flush_deferred(e);   // (the GPU is never kept waiting for the thread's wait)
+      DSLAM_HIP(hipEventSynchronize(v->up_consumed_by[b]));
+    }
+  }
+  if (reinterpret_cast<const uint8_t *>(depth_host) == rgba_host + c_bytes) {
+    DSLAM_HIP(hipMemcpyAsync(v->up_rgba[b], rgba_host, c_bytes + d_bytes, hipMemcpyHostToDevice, e->copy_stream));
+  } else {
+    DSLAM_HIP(hipMemcpyAsync(v->up_rgba[b], rgba_host, c_bytes, hipMemcpyHostToDevice, e->copy_stream));
+    DSLAM_HIP(hipMemcpyAsync(v->up_raw[b], depth_host, d_bytes, hipMemcpyHostToDevice, e->copy_stream));
+  }
+  flush_deferred(e);   // (copy_first: now)
+  // The other buffer's "consumed" mark, behind the held calls: the fusion launch that reads that buffer and the caller's
+  // fence the mark borrows are only enqueued by them.
   if (v->up_used[b ^ 1]) {
     dslam_fence *f = e->last_fence;
     release_lender(v, b ^ 1);
@@ -829,16 +944,7 @@ static int upload_view_pipelined(dslam_engine *e, dslam_view *v, const uint8_t *
       DSLAM_HIP(hipEventRecord(v->up_consumed[b ^ 1], e->stream.peek()));   // (a marker touches no buffer: EngineStream)
       v->up_consumed_by[b ^ 1] = v->up_consumed[b ^ 1];
     }
-  }
-  if (v->up_used[b]) {
-    if (stream_waits) DSLAM_HIP(hipStreamWaitEvent(e->copy_stream, v->up_consumed_by[b], 0));
-    else DSLAM_HIP(hipEventSynchronize(v->up_consumed_by[b]));
-  }
-  if (reinterpret_cast<const uint8_t *>(depth_host) == rgba_host + c_bytes) {
-    DSLAM_HIP(hipMemcpyAsync(v->up_rgba[b], rgba_host, c_bytes + d_bytes, hipMemcpyHostToDevice, e->copy_stream));
-  } else {
-    DSLAM_HIP(hipMemcpyAsync(v->up_rgba[b], rgba_host, c_bytes, hipMemcpyHostToDevice, e->copy_stream));
-    DSLAM_HIP(hipMemcpyAsync(v->up_raw[b], depth_host, d_bytes, hipMemcpyHostToDevice, e->copy_stream));
+    v->up_reads[b ^ 1] = e->view_reads;
   }
   if (stream_waits) {
     DSLAM_HIP(hipEventRecord(v->up_done[b], e->copy_stream));
@@ -893,6 +999,7 @@ int dslam_view_update(dslam_engine *e, dslam_view *v, const uint8_t *rgba_host, 
     if (rc) return rc;
     return finish_view_update(e, v, rgba_dev, raw_dev, a, b, timestamp, use_bilateral);
   }
+  flush_deferred(e);
   int rc = upload_view_host(e, v, rgba_host, 4, depth_host);
   if (rc) return rc;
   return finish_view_update(e, v, v->rgba, v->raw_depth, a, b, timestamp, use_bilateral);
@@ -900,12 +1007,14 @@ int dslam_view_update(dslam_engine *e, dslam_view *v, const uint8_t *rgba_host, 
 
 int dslam_view_update_device(dslam_engine *e, dslam_view *v, const void *rgba_dev, const void *depth_dev, float a,
                              float b, double timestamp, int use_bilateral) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && v && rgba_dev && depth_dev, "null argument");
   return finish_view_update(e, v, rgba_dev, depth_dev, a, b, timestamp, use_bilateral);
 }
 
 int dslam_view_update_bgr(dslam_engine *e, dslam_view *v, const uint8_t *bgr_host, const int16_t *depth_host, float a,
                           float b, double timestamp, int use_bilateral) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && v && bgr_host && depth_host, "null argument");
   int rc = upload_view_host(e, v, bgr_host, 3, depth_host);
   if (rc) return rc;
@@ -914,6 +1023,7 @@ int dslam_view_update_bgr(dslam_engine *e, dslam_view *v, const uint8_t *bgr_hos
 
 int dslam_view_update_bgr_device(dslam_engine *e, dslam_view *v, const void *bgr_dev, const void *depth_dev, float a,
                                  float b, double timestamp, int use_bilateral) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && v && bgr_dev && depth_dev, "null argument");
   DSLAM_REQUIRE(((uintptr_t)bgr_dev & 3) == 0, "bgr image must be 4-byte aligned");
   int rc = launch_bgr_to_rgba(e, bgr_dev, v->rgba, v->w_rgb * v->h_rgb);
@@ -924,6 +1034,7 @@ int dslam_view_update_bgr_device(dslam_engine *e, dslam_view *v, const void *bgr
 int dslam_view_update_dataset(dslam_engine *e, dslam_view *v, const uint8_t *colour_host, int channels,
                               const int16_t *depth_raw_host, int depth_format, float max_depth_m, float a, float b,
                               double timestamp, int use_bilateral) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && v && colour_host && depth_raw_host, "null argument");
   DSLAM_REQUIRE(channels == 3 || channels == 4, "colour_channels must be 3 (BGR) or 4 (RGBA)");
   DSLAM_REQUIRE(depth_format >= DSLAM_DEPTH_MM && depth_format <= DSLAM_DEPTH_RGBD_X5, "unknown depth format");
@@ -934,6 +1045,7 @@ int dslam_view_update_dataset(dslam_engine *e, dslam_view *v, const uint8_t *col
 }
 
 int dslam_download_view_raw_depth(dslam_engine *e, const dslam_view *v, int16_t *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && v && out, "null argument");
   e->view_reads++;  // (see dslam_engine::last_fence)
   DSLAM_HIP(hipMemcpyAsync(out, v->raw_src, (size_t)v->w_d * v->h_d * 2, hipMemcpyDeviceToHost, e->stream));
@@ -942,6 +1054,7 @@ int dslam_download_view_raw_depth(dslam_engine *e, const dslam_view *v, int16_t 
 }
 
 int dslam_download_view_rgba(dslam_engine *e, const dslam_view *v, uint8_t *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && v && out, "null argument");
   e->view_reads++;  // (see dslam_engine::last_fence)
   DSLAM_HIP(hipMemcpyAsync(out, v->rgba_src, (size_t)v->w_rgb * v->h_rgb * 4, hipMemcpyDeviceToHost, e->stream));
@@ -951,6 +1064,7 @@ int dslam_download_view_rgba(dslam_engine *e, const dslam_view *v, uint8_t *out)
 
 // ---- keyframe store (fusion-frame database payload resident in HBM) -------------------------------------------
 int dslam_frame_store_create(dslam_engine *e, int w_rgb, int h_rgb, int w_d, int h_d, int capacity, dslam_frame_store **out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && out && w_rgb > 0 && h_rgb > 0 && w_d > 0 && h_d > 0 && capacity > 0, "bad argument");
   std::unique_ptr<dslam_frame_store> fs(new dslam_frame_store());
   fs->engine = e; fs->w_rgb = w_rgb; fs->h_rgb = h_rgb; fs->w_d = w_d; fs->h_d = h_d; fs->capacity = capacity;
@@ -966,6 +1080,7 @@ int dslam_frame_store_create(dslam_engine *e, int w_rgb, int h_rgb, int w_d, int
 int dslam_frame_store_destroy(dslam_frame_store *fs) {
   if (!fs) return DSLAM_OK;
   (void)hipSetDevice(fs->engine->device);
+  flush_deferred(fs->engine);   // (on its own device: held calls launch kernels)
   (void)hipStreamSynchronize(fs->engine->stream);
   dslam_engine *e = fs->engine;
   delete fs;
@@ -996,13 +1111,16 @@ static int store_put_host(dslam_engine *e, dslam_frame_store *fs, int slot, cons
 }
 
 int dslam_frame_store_put(dslam_engine *e, dslam_frame_store *fs, int slot, const uint8_t *rgba_host, const int16_t *depth_host) {
+  flush_deferred(e);
   return store_put_host(e, fs, slot, rgba_host, 4, depth_host);
 }
 int dslam_frame_store_put_bgr(dslam_engine *e, dslam_frame_store *fs, int slot, const uint8_t *bgr_host, const int16_t *depth_host) {
+  flush_deferred(e);
   return store_put_host(e, fs, slot, bgr_host, 3, depth_host);
 }
 
 int dslam_frame_store_put_view(dslam_engine *e, dslam_frame_store *fs, int slot, const dslam_view *v) {
+  flush_deferred(e);
   int rc = store_slot_ok(e, fs, slot);
   if (rc) return rc;
   DSLAM_REQUIRE(v && v->engine == e, "null argument");
@@ -1014,6 +1132,7 @@ int dslam_frame_store_put_view(dslam_engine *e, dslam_frame_store *fs, int slot,
 }
 
 int dslam_frame_store_get(dslam_engine *e, const dslam_frame_store *fs, int slot, uint8_t *rgba_out, int16_t *depth_out) {
+  flush_deferred(e);
   int rc = store_slot_ok(e, fs, slot);
   if (rc) return rc;
   if (rgba_out) DSLAM_HIP(hipMemcpyAsync(rgba_out, fs->rgba + fs->rgba_bytes * slot, (size_t)fs->w_rgb * fs->h_rgb * 4, hipMemcpyDeviceToHost, e->stream));
@@ -1031,6 +1150,7 @@ int dslam_frame_store_device_ptrs(const dslam_frame_store *fs, int slot, void **
 
 int dslam_view_update_from_store(dslam_engine *e, dslam_view *v, const dslam_frame_store *fs, int slot, float a, float b,
                                  double timestamp, int use_bilateral) {
+  flush_deferred(e);
   int rc = store_slot_ok(e, fs, slot);
   if (rc) return rc;
   DSLAM_REQUIRE(v && v->engine == e, "null argument");
@@ -1042,6 +1162,7 @@ int dslam_view_update_from_store(dslam_engine *e, dslam_view *v, const dslam_fra
 static const size_t kListHeader = 64;  // (a RenderCounters-shaped count block, padded)
 
 int dslam_frame_store_enable_lists(dslam_engine *e, dslam_frame_store *fs, const dslam_scene *s) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && fs && s && fs->engine == e, "bad argument");
   if (fs->lists && fs->list_cap >= s->p.num_local_blocks && fs->list_entries == s->n_entries) return DSLAM_OK;
   DSLAM_HIP(hipStreamSynchronize(e->stream));
@@ -1065,6 +1186,7 @@ static unsigned char *list_slot(const dslam_frame_store *fs, int slot) { return 
 
 int dslam_frame_store_put_visible_list(dslam_engine *e, dslam_frame_store *fs, int slot, const dslam_scene *s,
                                        const dslam_render_state *r) {
+  flush_deferred(e);
   int rc = store_slot_ok(e, fs, slot);
   if (rc) return rc;
   DSLAM_REQUIRE(s && r && fs->lists, "dslam_frame_store_enable_lists has not been called");
@@ -1080,6 +1202,7 @@ int dslam_frame_store_put_visible_list(dslam_engine *e, dslam_frame_store *fs, i
 
 int dslam_deprocess_frame_stored(dslam_engine *e, dslam_scene *s, const dslam_view *v, const dslam_frame_store *fs, int slot,
                                  const float M_d[16], const float intr_d[4], const float M_rgb[16], const float intr_rgb[4]) {
+  flush_deferred(e);
   int rc = store_slot_ok(e, fs, slot);
   if (rc) return rc;
   DSLAM_REQUIRE(s && v && M_d && intr_d && s->engine == e && v->engine == e, "bad argument");
@@ -1148,6 +1271,7 @@ static int batch_scratch(dslam_engine *e, dslam_scene *s, dslam_frame_store *fs)
 int dslam_reintegrate_batch(dslam_engine *e, dslam_scene *s, dslam_view *v, dslam_render_state *r, dslam_frame_store *fs,
                             int n, const int32_t *slots, const float *old_M, const float *new_M, const float intr[4],
                             float affine_a, float affine_b) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && v && r && fs && intr && n >= 0 && (n == 0 || (slots && old_M && new_M)), "null argument");
   DSLAM_REQUIRE(s->engine == e && v->engine == e && r->engine == e && fs->engine == e, "objects belong to a different engine");
   DSLAM_REQUIRE(fs->lists, "dslam_frame_store_enable_lists has not been called");
@@ -1254,6 +1378,7 @@ int dslam_reintegrate_batch(dslam_engine *e, dslam_scene *s, dslam_view *v, dsla
 }
 
 int dslam_reintegrate_batch_stats(dslam_engine *e, const dslam_scene *s, int32_t *blocks_out, int32_t *block_operations_out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && s->engine == e, "null argument");
   DSLAM_REQUIRE(s->batch_counters, "no batch has run on this scene");
   int host[16];
@@ -1278,6 +1403,7 @@ static int depth_post_args(dslam_engine *e, const void *curr, const void *prev, 
 int dslam_depth_post_processing_device(dslam_engine *e, void *curr_dev, const void *prev_dev, int w, int h,
                                        const float Tpc[16], const float intr[4], float threshold, float area,
                                        int *count_out) {
+  flush_deferred(e);
   int rc = depth_post_args(e, curr_dev, prev_dev, w, h, Tpc, intr);
   if (rc) return rc;
   int *count_dev = e->misc_counter;
@@ -1294,6 +1420,7 @@ int dslam_depth_post_processing_device(dslam_engine *e, void *curr_dev, const vo
 int dslam_depth_post_processing(dslam_engine *e, int16_t *curr_host, const int16_t *prev_host, int w, int h,
                                 const float Tpc[16], const float intr[4], float threshold, float area,
                                 int *count_out) {
+  flush_deferred(e);
   int rc = depth_post_args(e, curr_host, prev_host, w, h, Tpc, intr);
   if (rc) return rc;
   const size_t d_bytes = (size_t)w * h * 2;
@@ -1316,6 +1443,7 @@ int dslam_depth_post_processing(dslam_engine *e, int16_t *curr_host, const int16
 
 // ---- fusion --------------------------------------------------------------------------------------------------
 int dslam_set_fusion_weight_params(dslam_engine *e, const dslam_weight_params *w) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && w, "null argument");
   // newW <= 255: the voxel weight is one byte and k_integrate indexes its reciprocal table with w_depth + newW <= 510
   DSLAM_REQUIRE(!w->depth_weighting || (w->max_distance > 0 && w->max_new_w >= 1 && w->max_new_w <= 255),
@@ -1334,6 +1462,7 @@ static int check_frame_args(dslam_engine *e, dslam_scene *s, const dslam_view *v
 
 int dslam_allocate_scene_from_depth(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_render_state *r,
                                     const float M_d[16], const float intr[4], int only_visible) {
+  flush_deferred(e);
   int rc = check_frame_args(e, s, v, r, M_d, intr);
   if (rc) return rc;
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
@@ -1346,6 +1475,7 @@ int dslam_allocate_scene_from_depth(dslam_engine *e, dslam_scene *s, const dslam
 int dslam_integrate_into_scene(dslam_engine *e, dslam_scene *s, const dslam_view *v, const dslam_render_state *r,
                                const float M_d[16], const float intr_d[4], const float M_rgb[16],
                                const float intr_rgb[4]) {
+  flush_deferred(e);
   int rc = check_frame_args(e, s, v, r, M_d, intr_d);
   if (rc) return rc;
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
@@ -1354,9 +1484,41 @@ int dslam_integrate_into_scene(dslam_engine *e, dslam_scene *s, const dslam_view
   return finish_call(e);
 }
 
+// What is left of a ProcessFrame behind its allocation pass, with its arguments by value: it may run after the call has
+// returned (dslam_engine::deferred), when the caller's arrays are gone.
+namespace {
+struct FrameTail {
+  dslam_engine *e; dslam_scene *s; const dslam_view *v; dslam_render_state *r;
+  float M_d[16], intr_d[4], M_rgb[16], intr_rgb[4];
+  bool has_M_rgb, has_intr_rgb;
+  int is_defusion;
+  FrontEndRecord *front;
+  unsigned long long version;   // the scene's version for this call
+};
+int frame_tail(const FrameTail &t) {
+  dslam_engine *e = t.e;
+  int rc;
+  if ((rc = finish_overlapped_allocate(e, t.s))) return rc;
+  if ((rc = launch_integrate(e, t.s, t.v, t.r, t.M_d, t.intr_d, t.has_M_rgb ? t.M_rgb : nullptr, t.has_intr_rgb ? t.intr_rgb : nullptr, false,
+                             t.is_defusion, t.front)))
+    return rc;
+  if (t.front && t.front->valid) {
+    t.front->version = t.version;
+    memcpy(t.front->M, t.M_d, sizeof(t.front->M));
+    memcpy(t.front->intr, t.intr_d, sizeof(t.front->intr));
+  }
+  if (t.s->p.use_swapping) {
+    if ((rc = launch_swap_in(e, t.s, t.r))) return rc;
+    if ((rc = launch_swap_out(e, t.s, t.r, false))) return rc;
+  }
+  return finish_call(e);
+}
+}  // namespace
+
 int dslam_process_frame(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_render_state *r,
                         const float M_d[16], const float intr_d[4], const float M_rgb[16], const float intr_rgb[4],
                         int only_visible, int is_defusion) {
+  flush_deferred(e);
   int rc = check_frame_args(e, s, v, r, M_d, intr_d);
   if (rc) return rc;
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
@@ -1365,22 +1527,25 @@ int dslam_process_frame(dslam_engine *e, dslam_scene *s, const dslam_view *v, ds
   FrontEndRecord *front = nullptr;
   if (s->front) s->front->valid = false;
   if (e->speculate_front && !s->p.use_swapping && r->n_entries == s->n_entries && (rc = front_end_for(e, s, r, &front))) return rc;
-  if ((rc = launch_allocate(e, s, v, r, M_d, intr_d, only_visible))) return rc;
-  if ((rc = launch_integrate(e, s, v, r, M_d, intr_d, M_rgb, intr_rgb, false, is_defusion ? 1 : 0, front))) return rc;
-  if (front && front->valid) {
-    front->version = s->version;
-    memcpy(front->M, M_d, sizeof(front->M));
-    memcpy(front->intr, intr_d, sizeof(front->intr));
+  bool publish_left = false;
+  if ((rc = launch_allocate(e, s, v, r, M_d, intr_d, only_visible, nullptr, nullptr, &publish_left))) return rc;
+  FrameTail tail{e, s, v, r, {}, {}, {}, {}, M_rgb != nullptr, intr_rgb != nullptr, is_defusion ? 1 : 0, front, s->version};
+  memcpy(tail.M_d, M_d, sizeof(tail.M_d));
+  memcpy(tail.intr_d, intr_d, sizeof(tail.intr_d));
+  if (M_rgb) memcpy(tail.M_rgb, M_rgb, sizeof(tail.M_rgb));
+  if (intr_rgb) memcpy(tail.intr_rgb, intr_rgb, sizeof(tail.intr_rgb));
+  if (publish_left) {
+    // k_mark and the sweep run on the auxiliary stream beside the previous GetImage's march; the call returns,
+    // and the thread comes back for the rest when it has something to sit out (upload_view_pipelined) or touches the engine.
+    defer_call(e, [tail]() { return frame_tail(tail); });
+    return DSLAM_OK;
   }
-  if (s->p.use_swapping) {
-    if ((rc = launch_swap_in(e, s, r))) return rc;
-    if ((rc = launch_swap_out(e, s, r, false))) return rc;
-  }
-  return finish_call(e);
+  return frame_tail(tail);
 }
 
 int dslam_deprocess_frame(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_render_state *r,
                           const float M_d[16], const float intr_d[4], const float M_rgb[16], const float intr_rgb[4]) {
+  flush_deferred(e);
   int rc = check_frame_args(e, s, v, r, M_d, intr_d);
   if (rc) return rc;
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
@@ -1394,6 +1559,7 @@ int dslam_deprocess_frame(dslam_engine *e, dslam_scene *s, const dslam_view *v, 
 int dslam_track_camera(dslam_engine *e, const dslam_view *v, dslam_render_state *r, const float scene_pose_M[16],
                        float pose_M[16], const float intr[4], const dslam_tracker_params *params,
                        dslam_tracker_result *result) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && v && r && scene_pose_M && pose_M && intr && params, "null argument");
   e->view_reads++;  // (see dslam_engine::last_fence)
   DSLAM_REQUIRE(v->engine == e && r->engine == e, "objects belong to a different engine");
@@ -1507,6 +1673,7 @@ int copy_sums(const SumChannel &ch, const char *none, double out[33]) {
 int dslam_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T_map_from_world,
                            int num_maps, float pose_M[16], const float intr[4], const dslam_track_sdf_params *params,
                            dslam_track_sdf_result *result) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && v && scenes && T_map_from_world && pose_M && intr && result, "null argument");
   DSLAM_TRY(check_map_list(e, "dslam_track_camera_sdf", scenes, T_map_from_world, num_maps, 1, true));
   DSLAM_REQUIRE(v->engine == e, "the view belongs to another engine");
@@ -1520,6 +1687,7 @@ int dslam_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_sce
 }
 
 int dslam_debug_track_sdf_sums(dslam_engine *e, double out[33]) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && out, "null argument");
   return copy_sums(e->track_sdf_sums, "no depth-to-SDF tracking evaluation has run on this engine", out);
 }
@@ -1529,6 +1697,7 @@ int dslam_debug_track_sdf_sums(dslam_engine *e, double out[33]) {
 int dslam_score_camera_poses(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T_map_from_world,
                              int num_maps, const float *poses_M, int num_poses, const float intr[4], int level,
                              float residual_gate, dslam_pose_score *scores_out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && v && scenes && T_map_from_world && poses_M && intr && scores_out, "null argument");
   DSLAM_TRY(check_pose_list_call(e, "dslam_score_camera_poses", v, scenes, T_map_from_world, num_maps, poses_M, num_poses, intr));
   DSLAM_REQUIRE(level >= 0 && level < DSLAM_TRACKER_MAX_LEVELS && (v->w_d >> level) > 0 && (v->h_d >> level) > 0,
@@ -1543,6 +1712,7 @@ int dslam_score_camera_poses(dslam_engine *e, const dslam_view *v, const dslam_s
 int dslam_track_camera_sdf_starts(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes,
                                   const float *T_map_from_world, int num_maps, float *poses_M, int num_starts, const float intr[4],
                                   const dslam_track_sdf_params *params, dslam_track_sdf_result *results) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && v && scenes && T_map_from_world && poses_M && intr && results, "null argument");
   DSLAM_TRY(check_pose_list_call(e, "dslam_track_camera_sdf_starts", v, scenes, T_map_from_world, num_maps, poses_M, num_starts, intr));
   dslam_track_sdf_params tp;
@@ -1552,6 +1722,7 @@ int dslam_track_camera_sdf_starts(dslam_engine *e, const dslam_view *v, const ds
 }
 
 int dslam_debug_track_sdf_start_sums(dslam_engine *e, int start, double out[33]) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && out, "null argument");
   const std::vector<double> &last = e->track_starts.last_sums;
   DSLAM_REQUIRE(!last.empty(), "no dslam_track_camera_sdf_starts has run on this engine");
@@ -1590,6 +1761,7 @@ int dslam_camera_pose_lattice(const float pose_M[16], const dslam_pose_lattice *
 
 // ---- decay / sliding window ----------------------------------------------------------------------------------
 int dslam_decay(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int max_weight, int min_age, int force_all) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s, "null argument");
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   if (r) r->memo_valid = false;
@@ -1599,6 +1771,7 @@ int dslam_decay(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int max_
 }
 int dslam_decay_defusion_part(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int max_weight, int min_age,
                               int force_all) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s, "null argument");
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   if (r) r->memo_valid = false;
@@ -1607,6 +1780,7 @@ int dslam_decay_defusion_part(dslam_engine *e, dslam_scene *s, dslam_render_stat
   return finish_call(e);
 }
 int dslam_slide_window(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int max_age) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s, "null argument");
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   if (r) r->memo_valid = false;
@@ -1618,6 +1792,7 @@ int dslam_slide_window(dslam_engine *e, dslam_scene *s, dslam_render_state *r, i
   return finish_call(e);
 }
 int dslam_slide_window_defusion_part(dslam_engine *e, dslam_scene *s, dslam_render_state *r, int max_age, int max_size) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s, "null argument");
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   if (r) r->memo_valid = false;
@@ -1632,6 +1807,7 @@ int dslam_slide_window_defusion_part(dslam_engine *e, dslam_scene *s, dslam_rend
 
 // ---- swapping ------------------------------------------------------------------------------------------------
 int dslam_swap_in(dslam_engine *e, dslam_scene *s, dslam_render_state *r) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && s->p.use_swapping, "scene was created without swapping");
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   if (r) r->memo_valid = false;
@@ -1640,6 +1816,7 @@ int dslam_swap_in(dslam_engine *e, dslam_scene *s, dslam_render_state *r) {
   return finish_call(e);
 }
 int dslam_swap_out(dslam_engine *e, dslam_scene *s, dslam_render_state *r) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && r && s->p.use_swapping, "scene was created without swapping");
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   if (r) r->memo_valid = false;
@@ -1648,6 +1825,7 @@ int dslam_swap_out(dslam_engine *e, dslam_scene *s, dslam_render_state *r) {
   return finish_call(e);
 }
 int dslam_save_to_global_memory(dslam_engine *e, dslam_scene *s) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && s->p.use_swapping, "scene was created without swapping");
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   int rc = launch_save_to_global(e, s);
@@ -1661,6 +1839,7 @@ static void drop_memo(dslam_render_state *r) { r->memo_valid = false; }
 
 int dslam_find_visible_blocks(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
                               const float intr[4]) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && r && M && intr, "null argument");
   drop_memo(r);
   r->types_follow_list = false;
@@ -1670,11 +1849,13 @@ int dslam_find_visible_blocks(dslam_engine *e, const dslam_scene *s, dslam_rende
 }
 int dslam_count_visible_blocks(dslam_engine *e, const dslam_scene *s, const dslam_render_state *r, int min_id,
                                int max_id, int *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && r && out, "null argument");
   return launch_count_visible(e, s, r, min_id, max_id, out);
 }
 int dslam_create_expected_depths(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
                                  const float intr[4]) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && r && M && intr, "null argument");
   drop_memo(r);
   int rc = launch_expected_depths(e, s, r, M, intr);
@@ -1700,6 +1881,7 @@ static int image_out(dslam_engine *e, dslam_render_state *r, int type, uint8_t *
 
 int dslam_render_image(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
                        const float intr[4], int type, uint8_t *out_rgba, float *out_float) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && r && M && intr, "null argument");
   drop_memo(r);
   DSLAM_REQUIRE(type >= 0 && type <= DSLAM_IMAGE_DEPTH, "unknown image type");
@@ -1744,25 +1926,49 @@ static int deliver_image(dslam_engine *e, dslam_render_state *r, int type, uint8
   return image_out(e, r, type, out_rgba, out_float);
 }
 
+namespace {
+struct ImageCall {
+  dslam_engine *e; const dslam_scene *s; dslam_render_state *r;
+  float M[16], intr[4];
+  int type;
+  uint8_t *out_rgba; float *out_float;
+  void *direct;
+};
+int get_image_body(const ImageCall &c) {
+  dslam_engine *e = c.e;
+  const unsigned stamp_before = e->stamp_seq;
+  DSLAM_TRY(get_image_on_device(e, c.s, c.r, c.M, c.intr, c.type, c.direct));
+  DSLAM_TRY(deliver_image(e, c.r, c.type, c.out_rgba, c.out_float, c.direct));
+  // Everything this call enqueued from its stamped range pass on -- that pass and the march -- shares no buffer with k_mark
+  // (DESIGN.md 4g, hazard table): the next allocation pass may run its k_mark beside them.  Not if the call waited for its
+  // image (a synchronous engine, an output buffer that is not page-locked): the stream is empty then.
+  const bool enqueued_only = e->async_mode && (c.direct || (!c.out_rgba && !c.out_float));
+  if (e->stamp_seq != stamp_before && enqueued_only) e->stream.grant();
+  return DSLAM_OK;
+}
+}  // namespace
+
 int dslam_get_image(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
                     const float intr[4], int type, uint8_t *out_rgba, float *out_float) {
   DSLAM_REQUIRE(e && s && r && M && intr, "null argument");
   DSLAM_REQUIRE(type >= 0 && type <= DSLAM_IMAGE_DEPTH, "unknown image type");
-  void *direct = direct_image(r, type, out_rgba, out_float);
-  const unsigned stamp_before = e->stamp_seq;
-  DSLAM_TRY(get_image_on_device(e, s, r, M, intr, type, direct));
-  DSLAM_TRY(deliver_image(e, r, type, out_rgba, out_float, direct));
-  // Everything this call enqueued from its stamped range pass on -- that pass and the march -- shares no buffer with k_mark
-  // (DESIGN.md 4g, hazard table): the next allocation pass may run its k_mark beside them.  Not if the call waited for its
-  // image (a synchronous engine, an output buffer that is not page-locked): the stream is empty then.
-  const bool enqueued_only = e->async_mode && (direct || (!out_rgba && !out_float));
-  if (e->stamp_seq != stamp_before && enqueued_only) e->stream.grant();
-  return DSLAM_OK;
+  ImageCall c{e, s, r, {}, {}, type, out_rgba, out_float, direct_image(r, type, out_rgba, out_float)};
+  memcpy(c.M, M, sizeof(c.M));
+  memcpy(c.intr, intr, sizeof(c.intr));
+  // A call that would only enqueue goes behind the calls the engine holds back (a ProcessFrame's tail), with
+  // its arguments by value; one that hands the image over on return runs them first.
+  if (!e->deferred.empty() && e->async_mode && (c.direct || (!out_rgba && !out_float))) {
+    defer_call(e, [c]() { return get_image_body(c); });
+    return DSLAM_OK;
+  }
+  flush_deferred(e);
+  return get_image_body(c);
 }
 
 int dslam_get_image_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
                           dslam_render_state *r, const float M[16], const float intr[4], int type, uint8_t *out_rgba,
                           float *out_float) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && scenes && T_map_from_world && r && M && intr, "null argument");
   DSLAM_REQUIRE(type >= 0 && type <= DSLAM_IMAGE_DEPTH, "unknown image type");
   DSLAM_REQUIRE(r->engine == e, "the render state belongs to another engine");
@@ -1777,6 +1983,7 @@ int dslam_get_image_multi(dslam_engine *e, const dslam_scene *const *scenes, con
 
 int dslam_get_depth_image_int16(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
                                 const float intr[4], int scale, int16_t *out_host) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && r && M && intr && out_host && scale > 0, "bad argument");
   int rc;
   if ((rc = get_image_on_device(e, s, r, M, intr, DSLAM_IMAGE_DEPTH))) return rc;
@@ -1790,6 +1997,7 @@ int dslam_get_depth_image_int16(dslam_engine *e, const dslam_scene *s, dslam_ren
 
 int dslam_create_icp_maps(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, const float M[16],
                           const float intr[4], float *out_points, float *out_normals) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && r && M && intr, "null argument");
   drop_memo(r);
   int rc;
@@ -1803,6 +2011,7 @@ int dslam_create_icp_maps(dslam_engine *e, const dslam_scene *s, dslam_render_st
 }
 
 int dslam_download_raycast_image(dslam_engine *e, const dslam_render_state *r, uint8_t *out_rgba) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && r && out_rgba, "null argument");
   DSLAM_REQUIRE(r->raycast_image, "dslam_create_icp_maps has not run on this render state");
   DSLAM_HIP(hipMemcpyAsync(out_rgba, r->raycast_image, (size_t)r->w * r->h * 4, hipMemcpyDeviceToHost, e->stream));
@@ -1810,6 +2019,7 @@ int dslam_download_raycast_image(dslam_engine *e, const dslam_render_state *r, u
 }
 
 int dslam_download_icp_maps(dslam_engine *e, const dslam_render_state *r, float *out_points, float *out_normals) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && r, "null argument");
   DSLAM_REQUIRE(r->icp_points && r->icp_normals, "dslam_create_icp_maps has not run on this render state");
   const size_t bytes = (size_t)r->w * r->h * sizeof(float4);
@@ -1820,6 +2030,7 @@ int dslam_download_icp_maps(dslam_engine *e, const dslam_render_state *r, float 
 
 // ---- meshing export --------------------------------------------------------------------------------------------
 int dslam_mesh_scene(dslam_engine *e, const dslam_scene *s, int max_triangles, int with_colour, int *out_num_triangles) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && out_num_triangles, "null argument");
   if (max_triangles <= 0) max_triangles = s->p.num_local_blocks * 32;  // ITMMesh::noMaxTriangles
   int rc = launch_mesh_scene(e, s, max_triangles, with_colour, out_num_triangles);
@@ -1829,6 +2040,7 @@ int dslam_mesh_scene(dslam_engine *e, const dslam_scene *s, int max_triangles, i
 
 int dslam_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
                            int max_triangles, int with_colour, int *out_num_triangles, int32_t *out_map_triangles) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && scenes && T_map_from_world && out_num_triangles, "null argument");
   DSLAM_TRY(check_map_list(e, "dslam_mesh_scene_multi", scenes, T_map_from_world, num_maps, 1, false));
   long long blocks = 0;
@@ -1842,6 +2054,7 @@ int dslam_mesh_scene_multi(dslam_engine *e, const dslam_scene *const *scenes, co
 // ---- map registration ------------------------------------------------------------------------------------------
 int dslam_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_scene *dst, float X_dst_from_src[16],
                         const dslam_register_params *params, dslam_register_result *result) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && src && dst && X_dst_from_src && result, "null argument");
   DSLAM_REQUIRE(src->engine == e && dst->engine == e, "a scene belongs to another engine");
   DSLAM_REQUIRE(src->p.voxel_size == dst->p.voxel_size && src->p.mu == dst->p.mu,
@@ -1855,6 +2068,7 @@ int dslam_register_maps(dslam_engine *e, const dslam_scene *src, const dslam_sce
 }
 
 int dslam_debug_register_sums(dslam_engine *e, double out[33]) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && out, "null argument");
   return copy_sums(e->reg_sums, "no registration evaluation has run on this engine", out);
 }
@@ -1862,6 +2076,7 @@ int dslam_debug_register_sums(dslam_engine *e, double out[33]) {
 int dslam_register_graph(dslam_engine *e, const dslam_scene *const *scenes, float *T_map_from_world, int num_maps,
                          const int32_t *pairs, int num_pairs, int anchor, const dslam_register_params *params,
                          dslam_register_graph_result *result, dslam_register_pair_result *pair_results) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && scenes && T_map_from_world && pairs && result, "null argument");
   DSLAM_TRY(check_map_list(e, "dslam_register_graph", scenes, T_map_from_world, num_maps, 2, true));
   DSLAM_REQUIRE(num_pairs >= 1 && num_pairs <= DSLAM_MAX_REGISTER_PAIRS, "num_pairs must be 1 .. DSLAM_MAX_REGISTER_PAIRS");
@@ -1878,6 +2093,7 @@ int dslam_register_graph(dslam_engine *e, const dslam_scene *const *scenes, floa
 }
 
 int dslam_debug_register_graph_sums(dslam_engine *e, int pair, double out[33]) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && out, "null argument");
   DSLAM_REQUIRE(!e->reg_graph_sums.empty(), "no joint registration has run on this engine");
   DSLAM_REQUIRE(pair >= 0 && (size_t)pair < e->reg_graph_sums.size() / 33, "the pair index is out of range");
@@ -1888,6 +2104,7 @@ int dslam_debug_register_graph_sums(dslam_engine *e, int pair, double out[33]) {
 // ---- overlap survey and pair selection ------------------------------------------------------------------------------
 int dslam_survey_overlaps(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
                           int32_t *live_blocks_out, int32_t *shared_blocks_out, int32_t *shared_octants_out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && scenes && T_map_from_world && live_blocks_out && shared_octants_out, "null argument");
   DSLAM_TRY(check_map_list(e, "dslam_survey_overlaps", scenes, T_map_from_world, num_maps, 2, true));
   return launch_survey_overlaps(e, scenes, T_map_from_world, num_maps, live_blocks_out, shared_blocks_out, shared_octants_out);
@@ -1937,6 +2154,7 @@ int dslam_view_frustum_planes(const dslam_survey_view *view, float voxel_size, f
 int dslam_survey_views(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
                        const dslam_survey_view *views, int num_views, const dslam_view_survey_params *params,
                        int32_t *live_blocks_out, int32_t *reach_blocks_out, int32_t *nearest_out, int32_t *farthest_out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && scenes && T_map_from_world && views && live_blocks_out && reach_blocks_out, "null argument");
   DSLAM_TRY(check_map_list(e, "dslam_survey_views", scenes, T_map_from_world, num_maps, 1, true, 0, DSLAM_MAX_SURVEY_MAPS));
   DSLAM_REQUIRE(num_views >= 1 && num_views <= DSLAM_MAX_SURVEY_VIEWS, "num_views must be 1 .. DSLAM_MAX_SURVEY_VIEWS");
@@ -1953,6 +2171,7 @@ int dslam_survey_views(dslam_engine *e, const dslam_scene *const *scenes, const 
 }
 
 int dslam_debug_survey_views_launches(dslam_engine *e, long long *count_out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && count_out, "null argument");
   *count_out = e->view_survey_launches;
   return DSLAM_OK;
@@ -2008,6 +2227,7 @@ void map_changed(dslam_scene *dst) {
 
 int dslam_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_dst_from_src[16],
                      const dslam_merge_params *params, dslam_merge_result *result) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && src && dst && X_dst_from_src && result, "null argument");
   DSLAM_TRY(check_merge_scenes(e, src, dst));
   DSLAM_TRY(check_rigid_transform(X_dst_from_src, "the transform"));
@@ -2019,6 +2239,7 @@ int dslam_merge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, 
 
 int dslam_unmerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_dst_from_src[16],
                        const dslam_unmerge_params *params, dslam_unmerge_result *result) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && src && dst && X_dst_from_src && result, "null argument");
   DSLAM_TRY(check_merge_scenes(e, src, dst));
   DSLAM_TRY(check_rigid_transform(X_dst_from_src, "the transform"));
@@ -2029,6 +2250,7 @@ int dslam_unmerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst
 int dslam_remerge_maps(dslam_engine *e, const dslam_scene *src, dslam_scene *dst, const float X_old[16],
                        const float X_new[16], const dslam_merge_params *params, dslam_unmerge_result *unmerged,
                        dslam_merge_result *merged) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && src && dst && X_old && X_new && unmerged && merged, "null argument");
   DSLAM_TRY(check_merge_scenes(e, src, dst));
   DSLAM_TRY(check_rigid_transform(X_old, "the old transform"));
@@ -2074,6 +2296,7 @@ static int check_pack_scene(dslam_engine *e, const dslam_scene *s) {
 }
 
 int dslam_device_alloc(dslam_engine *e, size_t bytes, void **out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && out && bytes > 0, "bad argument");
   *out = nullptr;
   DSLAM_HIP(hipSetDevice(e->device));
@@ -2081,6 +2304,7 @@ int dslam_device_alloc(dslam_engine *e, size_t bytes, void **out) {
   return DSLAM_OK;
 }
 int dslam_device_free(dslam_engine *e, void *p) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e, "null engine");
   if (!p) return DSLAM_OK;
   DSLAM_HIP(hipSetDevice(e->device));
@@ -2090,6 +2314,7 @@ int dslam_device_free(dslam_engine *e, void *p) {
 }
 
 int dslam_pack_scene(dslam_engine *e, const dslam_scene *s, void *buf, int64_t capacity, dslam_pack_info *info_out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && info_out, "null argument");
   DSLAM_TRY(check_pack_scene(e, s));
   DSLAM_HIP(hipSetDevice(e->device));
@@ -2101,6 +2326,7 @@ int dslam_pack_scene(dslam_engine *e, const dslam_scene *s, void *buf, int64_t c
 }
 
 int dslam_unpack_scene(dslam_engine *e, dslam_scene *s, const void *buf, int64_t bytes, dslam_pack_info *info_out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && buf, "null argument");
   DSLAM_TRY(check_pack_scene(e, s));
   DSLAM_REQUIRE(bytes >= kPackHeaderBytes, "shorter than the header of a packed map");
@@ -2135,6 +2361,7 @@ int dslam_unpack_scene(dslam_engine *e, dslam_scene *s, const void *buf, int64_t
 }
 
 int dslam_debug_merge_phases(dslam_engine *e, int enable, double out_ms[5]) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e, "null argument");
   if (out_ms) memcpy(out_ms, e->merge_phase_ms, sizeof e->merge_phase_ms);
   e->merge_phases_on = enable != 0;
@@ -2142,6 +2369,7 @@ int dslam_debug_merge_phases(dslam_engine *e, int enable, double out_ms[5]) {
 }
 
 int dslam_mesh_download(dslam_engine *e, float *out_positions, float *out_colours, int capacity_triangles) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && out_positions && capacity_triangles >= 0, "bad argument");
   DSLAM_REQUIRE(capacity_triangles >= e->mesh_triangles, "dslam_mesh_download: buffer smaller than the mesh");
   DSLAM_REQUIRE(!out_colours || e->mesh_has_colour, "dslam_mesh_download: the mesh was made without colours");
@@ -2155,6 +2383,7 @@ int dslam_mesh_download(dslam_engine *e, float *out_positions, float *out_colour
 
 // ---- read-back -----------------------------------------------------------------------------------------------
 int dslam_get_stats(dslam_engine *e, const dslam_scene *s, const dslam_render_state *r, dslam_stats *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && out, "null argument");
   char *host = reinterpret_cast<char *>(e->pinned.get());
   SceneCounters *sc = reinterpret_cast<SceneCounters *>(host);
@@ -2197,22 +2426,27 @@ static int h2d(dslam_engine *e, void *dst, const void *src, size_t bytes) {
 }
 
 int dslam_download_hash_table(dslam_engine *e, const dslam_scene *s, dslam_hash_entry *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && out, "null argument");
   return d2h(e, out, s->hash, (size_t)s->n_entries * sizeof(HashEntry));
 }
 int dslam_download_voxel_blocks(dslam_engine *e, const dslam_scene *s, int first, int n, dslam_voxel *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && out && first >= 0 && n >= 0 && first + n <= s->p.num_local_blocks, "bad block range");
   return d2h(e, out, s->voxels + (size_t)first * kBlock3, (size_t)n * kBlock3 * sizeof(uint2));
 }
 int dslam_download_allocation_list(dslam_engine *e, const dslam_scene *s, int32_t *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && out, "null argument");
   return d2h(e, out, s->alloc_list, (size_t)s->p.num_local_blocks * sizeof(int));
 }
 int dslam_download_excess_list(dslam_engine *e, const dslam_scene *s, int32_t *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && out, "null argument");
   return d2h(e, out, s->excess_list, (size_t)s->p.num_excess * sizeof(int));
 }
 int dslam_download_visible_ids(dslam_engine *e, const dslam_render_state *r, int32_t *out, int capacity, int *count) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && r && out, "null argument");
   RenderCounters *rc = reinterpret_cast<RenderCounters *>(reinterpret_cast<char *>(e->pinned.get()) + 128);
   int st = d2h(e, rc, r->counters, sizeof(RenderCounters));
@@ -2223,20 +2457,24 @@ int dslam_download_visible_ids(dslam_engine *e, const dslam_render_state *r, int
   return DSLAM_OK;
 }
 int dslam_download_visible_types(dslam_engine *e, const dslam_render_state *r, uint8_t *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && r && out, "null argument");
   int rc = d2h(e, out, r->visible_type, r->n_entries);
   for (int i = 0; i < r->n_entries; i++) out[i] &= 0x7f;  // the device bytes carry the pass' generation bit
   return rc;
 }
 int dslam_download_range_image(dslam_engine *e, const dslam_render_state *r, float *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && r && out, "null argument");
   return d2h(e, out, r->range, (size_t)r->w * r->h * sizeof(float2));
 }
 int dslam_download_raycast_result(dslam_engine *e, const dslam_render_state *r, float *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && r && out, "null argument");
   return d2h(e, out, r->raycast, (size_t)r->w * r->h * sizeof(float4));
 }
 int dslam_download_view_depth(dslam_engine *e, const dslam_view *v, float *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && v && out, "null argument");
   e->view_reads++;  // (see dslam_engine::last_fence)
   int rc = ensure_view_depth(e, v);
@@ -2244,14 +2482,17 @@ int dslam_download_view_depth(dslam_engine *e, const dslam_view *v, float *out) 
   return d2h(e, out, v->depth, (size_t)v->w_d * v->h_d * sizeof(float));
 }
 int dslam_download_swap_states(dslam_engine *e, const dslam_scene *s, uint8_t *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && out && s->swap_state, "scene has no swap state");
   return d2h(e, out, s->swap_state, s->n_entries);
 }
 int dslam_download_last_seen(dslam_engine *e, const dslam_scene *s, int32_t *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && out, "null argument");
   return d2h(e, out, s->last_seen, (size_t)s->p.num_local_blocks * sizeof(int));
 }
 int dslam_download_stored_block(dslam_engine *e, const dslam_scene *s, int entry, dslam_voxel *out) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && s->slot_dev && entry >= 0 && entry < s->n_entries, "bad entry / no global cache");
   int slot = -1;  // (d2h waits for the stream: the swap kernels write the host slabs directly)
   int rc = d2h(e, &slot, s->slot_dev + entry, sizeof(int));
@@ -2263,6 +2504,7 @@ int dslam_download_stored_block(dslam_engine *e, const dslam_scene *s, int entry
   return slot >= 0 ? 1 : 0;
 }
 int dslam_download_alloc_scratch(dslam_engine *e, const dslam_scene *s, uint8_t *types, int16_t *coords) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && e->scratch_entries >= s->n_entries, "no allocation pass has run");
   int rc = 0;
   if (types) rc = d2h(e, types, e->alloc_type, s->n_entries);
@@ -2272,6 +2514,7 @@ int dslam_download_alloc_scratch(dslam_engine *e, const dslam_scene *s, uint8_t 
 
 int dslam_upload_scene_state(dslam_engine *e, dslam_scene *s, const dslam_hash_entry *hash, const int32_t *alloc_list,
                              int last_free, const int32_t *excess_list, int last_free_ex) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s, "null argument");
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   int rc = 0;
@@ -2296,11 +2539,13 @@ int dslam_upload_scene_state(dslam_engine *e, dslam_scene *s, const dslam_hash_e
   return rc;
 }
 int dslam_upload_voxel_blocks(dslam_engine *e, dslam_scene *s, int first, int n, const dslam_voxel *host) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && host && first >= 0 && n >= 0 && first + n <= s->p.num_local_blocks, "bad block range");
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
   return h2d(e, s->voxels + (size_t)first * kBlock3, host, (size_t)n * kBlock3 * sizeof(uint2));
 }
 int dslam_upload_visible_ids(dslam_engine *e, dslam_render_state *r, const int32_t *ids, int count) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && r && ids && count >= 0 && count <= r->n_local, "bad visible list");
   drop_memo(r);
   r->types_follow_list = false;
@@ -2314,9 +2559,11 @@ int dslam_upload_visible_ids(dslam_engine *e, dslam_render_state *r, const int32
   return h2d(e, r->counters, rcn, sizeof(RenderCounters));
 }
 
-void *dslam_scene_voxel_blocks_dev(dslam_scene *s) { return s ? s->voxels : nullptr; }
-void *dslam_scene_hash_table_dev(dslam_scene *s) { return s ? s->hash : nullptr; }
+// (a caller that asks for a buffer means to use it: held-back calls that write it are handed to the GPU first)
+void *dslam_scene_voxel_blocks_dev(dslam_scene *s) { if (s) flush_deferred(s->engine); return s ? s->voxels : nullptr; }
+void *dslam_scene_hash_table_dev(dslam_scene *s) { if (s) flush_deferred(s->engine); return s ? s->hash : nullptr; }
 int dslam_scene_table_changed(dslam_engine *e, dslam_scene *s) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e && s && s->engine == e, "null argument");
   s->version = next_map_version();  // the map changed: GetImage memos of this scene are stale
   int rc = launch_build_alloc_bits(e, s);
@@ -2325,12 +2572,14 @@ int dslam_scene_table_changed(dslam_engine *e, dslam_scene *s) {
 }
 void *dslam_render_state_image_dev(dslam_render_state *r, int want_float) {
   if (!r) return nullptr;
+  flush_deferred(r->engine);   // (a held-back GetImage may exchange this render state's buffers with a front-end record's)
   return want_float ? (void *)r->image_float : (void *)r->image_rgba;
 }
 
 // ---- instrumentation -----------------------------------------------------------------------------------------
 int dslam_time_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, const dslam_render_state *r,
                          const float M_d[16], const float intr[4], int iterations, float *out_ms, int *out_blocks) {
+  flush_deferred(e);
   int rc = check_frame_args(e, s, v, r, M_d, intr);
   if (rc) return rc;
   s->version = next_map_version();  // the map may change: GetImage memos of this scene are stale
@@ -2360,6 +2609,7 @@ int dslam_time_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, c
 }
 
 int dslam_kernel_timer_enable(dslam_engine *e, int enable) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e, "null engine");
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   if (enable && e->ev_pool.empty()) {
@@ -2379,6 +2629,7 @@ int dslam_kernel_timer_enable(dslam_engine *e, int enable) {
 }
 
 int dslam_kernel_timer_read(dslam_engine *e, double *out_ms, int64_t *out_launches, int64_t *out_blocks) {
+  flush_deferred(e);
   DSLAM_REQUIRE(e, "null engine");
   DSLAM_HIP(hipStreamSynchronize(e->stream));
   int *counts = reinterpret_cast<int *>(e->pinned.get()) + 64;

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -76,6 +77,15 @@ struct EngineScratch {
   // tags them, so the arrays never need clearing
   DeviceBuffer<unsigned long long> agg;  // [3][agg_tiles]
   int agg_tiles = 0;
+  // table writes of an allocation sweep that ran beside the previous GetImage's march, until k_publish_entries scatters them
+  // (DESIGN.md 4h).  Every committed request takes one voxel-block slot and names one table entry, so a pass appends at
+  // most min(local_blocks, entries) records of each kind: the lists hold that many.  pend_count: [2][2] record counts, the
+  // pair of overlapped pass k at [k & 1]; the publish kernel of a pass zeroes the other pair for the next one.
+  DeviceBuffer<uint4> pend_entry;        // [pend_cap] whole entries ...
+  DeviceBuffer<int> pend_entry_idx;      // [pend_cap] ... and where they go
+  DeviceBuffer<int2> pend_offset;        // [pend_cap] {entry, its new offset field}
+  DeviceBuffer<unsigned> pend_count;     // [4], all zero between passes
+  int pend_cap = 0;
   DeviceBuffer<int> list_d;              // [max(local_blocks, entries)] general purpose scratch (bucket leaders, live flags)
   // release pipeline (decay / sliding window): flags that are ALL ZERO between passes (the kernels that consume a flag
   // clear it), so no pass starts with a memset
@@ -187,14 +197,21 @@ class EngineStream {
   EngineStream() = default;
   EngineStream(const EngineStream &) = delete;
   EngineStream &operator=(const EngineStream &) = delete;
-  operator hipStream_t() const { stamped_last_ = false; return s_; }
-  hipStream_t peek() const { return s_; }
+  operator hipStream_t() const { settle(); stamped_last_ = false; return s_; }
+  hipStream_t peek() const { settle(); return s_; }
   hipStream_t *create_into() { return &s_; }
+  // Calls whose bodies are still held back (dslam_engine::deferred) come first, whoever asks for the stream and
+  // for whatever: the engine arms the hook while it holds any, and the bodies themselves run with it disarmed.
+  void arm(void (*run)(void *), void *owner) { run_held_ = run; owner_ = owner; }
+  void disarm() { run_held_ = nullptr; }
   void grant() { stamped_last_ = true; }
   bool take() { const bool had = stamped_last_; stamped_last_ = false; return had; }   // (the permission is good for one pass)
 
  private:
+  void settle() const { if (run_held_) run_held_(owner_); }
   hipStream_t s_ = nullptr;
+  void (*run_held_)(void *) = nullptr;
+  void *owner_ = nullptr;
   mutable bool stamped_last_ = false;   // the last thing enqueued that k_mark could collide with is a stamped GetImage
 };
 
@@ -202,12 +219,29 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   int device = 0;
   EngineStream stream;
   // k_mark beside the previous GetImage's march; DSLAM_OVERLAP_MARK=0 turns it off
-  hipStream_t aux_stream = nullptr;   // holds nothing but that k_mark; the host waits for it before the sweep is enqueued
+  hipStream_t aux_stream = nullptr;   // holds nothing but that k_mark and, behind it, the pass' deferring sweep (4h); the host waits
+                                      // for it before anything that reads what they wrote is enqueued
   bool overlap_mark = true;
   bool stream_lent = false;           // dslam_engine_stream handed the compute stream out: the caller may order its own work by it
   PinnedBuffer<unsigned> start_stamp; // page-locked, fine-grained: the stamp of the last stamped range pass that has STARTED
   unsigned stamp_seq = 0;             // the stamp given to the last range pass enqueued with one (0: none yet)
   long long mark_overlapped = 0, mark_in_stream = 0;   // allocation passes whose k_mark ran on aux_stream / in the stream (test hook)
+  // ... and the pass' sweep behind it on aux_stream, its table writes deferred to k_publish_entries;
+  // DSLAM_OVERLAP_SWEEP=0 keeps the sweep in the stream
+  bool overlap_sweep = true;
+  long long sweep_overlapped = 0, sweep_in_stream = 0;   // (test hook)
+  unsigned pend_pass = 0;             // overlapped sweeps so far: which pair of pend_count the next one appends through
+  bool publish_due = false;           // aux_stream holds a deferring sweep whose k_publish_entries is not enqueued yet
+  // Calls whose body the caller's thread runs later: the tail of a ProcessFrame whose sweep runs on aux_stream,
+  // and a GetImage / fence record behind it.  Run in order by flush_deferred() -- from the pipelined upload while its copy is
+  // in flight, and otherwise by whatever touches the engine next (every entry point; EngineStream as the backstop).
+  std::vector<std::function<int()>> deferred;
+  bool flushing = false;
+  int deferred_rc = 0;                // first failure of a deferred body, told once by device_errors()
+  std::string deferred_error;
+  // What a stamp that has arrived proves about the views: view_reads when the stamped range pass was enqueued (every kernel
+  // that read a view and was counted by then is complete), and the newest such figure the host has seen arrive.
+  unsigned long long stamp_view_reads = 0, view_reads_done = 0;
   // Handles made from this engine that still exist (scenes, render states, views, frame stores: everything that keeps a
   // pointer to it and reads it in its destroy call).  dslam_engine_destroy with children left only closes the engine:
   // object and streams stay until the last child's destroy call (capi.hip engine_adopt / engine_release).
@@ -230,6 +264,7 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   DeviceBuffer<unsigned> ticket;         // device [16]: counter k is ticket + k
   unsigned ticket_base = 0;           // counter 0
   unsigned ticket_base2 = 0;          // counter 1 (a second, independent chain inside the same launch)
+  unsigned ticket_base3 = 0;          // counter 2: the allocation sweep that runs on aux_stream
   unsigned long long hip_failures_seen = 0;  // ... which is only as good as the launches that were accepted: after any HIP
                                       // failure of the process the bases are read back from the device (tickets_resync)
   // what kernels could not tell anybody (report_error, dslam_device.h): one page-locked word, looked at by every entry
@@ -446,6 +481,7 @@ struct DSLAM_INTERNAL dslam_view : ViewLanding {
   hipEvent_t up_consumed_by[2] = {nullptr, nullptr};  // the event that says so for the current contents: up_consumed[b] or a caller's fence
   dslam_fence *up_lender[2] = {nullptr, nullptr};     // ... the fence that event belongs to, if it is a caller's
   bool up_used[2] = {false, false};
+  unsigned long long up_reads[2] = {0, 0};   // engine->view_reads when buffer b's last reader had been called (see dslam_engine::view_reads_done)
   int up_next = 0;
   float affine_a = 0.001f, affine_b = 0.0f;
   mutable bool depth_dirty = false;  // float depth not yet derived from raw_src (done by the next consumer)
@@ -460,6 +496,7 @@ struct DSLAM_INTERNAL dslam_fence {
   bool recorded = false;
   unsigned long long view_reads_at_record = 0;  // engine->view_reads when it was recorded
   int lent_count = 0;   // views that wait on `ev` as their "landing buffer consumed" mark at the moment
+  bool record_held = false;   // dslam_fence_record was called, the record itself waits in dslam_engine::deferred
   bool zombie = false;  // destroyed by the caller while lent: the object and its event live until the last view lets go
 };
 
@@ -554,7 +591,10 @@ int launch_depth_post(dslam_engine *e, short *curr_dev, const unsigned short *pr
 // list_out / count_out: write the pass' visible list there instead of into the render state's own list (whose bitmap and
 // types follow the pass either way; the re-integration batch keeps the lists of all its passes)
 int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_render_state *r, const float *M_d,
-                    const float *intr, int only_update_visible_list, int *list_out = nullptr, void *count_out = nullptr);
+                    const float *intr, int only_update_visible_list, int *list_out = nullptr, void *count_out = nullptr,
+                    bool *publish_left = nullptr);
+// (publish_left: the caller finishes an overlapped pass itself, later -- finish_overlapped_allocate -- and learns here
+// whether there is one to finish; null: launch_allocate does before it returns)
 // push_ring >= 0: also queue the frame's visible list on that ring (fused into the integrate kernel)
 // front: also compute GetImage's front end for (M_d, intr_d, r's image size) into it, in the same launch, if the fusion
 // runs the plain one-camera kernel (front->valid says whether it did; its buffers are sized for r beforehand)
@@ -669,6 +709,9 @@ int launch_dirty_pack(dslam_engine *e, const dslam_scene *s, int shard, void *se
 int launch_dirty_unpack(dslam_engine *e, dslam_scene *s, int skip_shard, const void *recv_dev, int stride_blocks);
 int ensure_scratch(dslam_engine *e, int entries, int local_blocks);
 int finish_call(dslam_engine *e);  // synchronise unless the engine is in async mode
+int flush_deferred(dslam_engine *e);   // run the calls the engine holds back (dslam_engine::deferred), in order; failures are kept for device_errors()
+void defer_call(dslam_engine *e, std::function<int()> body);
+int finish_overlapped_allocate(dslam_engine *e, dslam_scene *s);   // alloc.hip: wait for aux_stream, enqueue k_publish_entries
 int device_errors(dslam_engine *e);  // report (once) what kernels left in dslam_engine::err_host
 int sync_check(dslam_engine *e);   // wait for the engine's stream, then report what kernels left in dslam_engine::err_host
 // The host advances its copy of the ticket counters when it enqueues a launch.  A launch the runtime rejected never moves the

@@ -255,6 +255,7 @@ static int launch_fill_range(dslam_engine *e, dslam_render_state *r, int n_wg_ti
   if (stamped && e->overlap_mark && e->async_mode) {
     stamp_word = e->start_stamp;
     if (++e->stamp_seq == 0) e->stamp_seq = 1;   // (0 is the word's value before the first stamp)
+    e->stamp_view_reads = e->view_reads;   // (every call that read a view so far has its kernels in front of this pass)
   }
   hipLaunchKernelGGL(k_fill_range_tiles, dim3(tiles_x * tiles_y, kRangeSlices), dim3(256), 0, e->stream, r->counters,
                      r->proj_boxes, r->proj_z, r->proj_req, r->range, r->w, tiles_x, r->proj_wg_tiles, n_wg_tiles,

@@ -211,6 +211,16 @@ int dslam_debug_front_end_counts(dslam_engine *e, long long *computed_out, long 
  * for; DSLAM_OVERLAP_MARK=0 in the environment of dslam_engine_create selects the second way always.  Both ways
  * compute the same bytes. */
 int dslam_debug_mark_overlap_counts(dslam_engine *e, long long *overlapped_out, long long *in_stream_out);
+/* Test hook: allocation passes so far whose sweep (k_alloc_sweep) ran behind that k_mark on the auxiliary stream, its
+ * hash-table writes put on a list that a small kernel publishes behind the previous dslam_get_image's march, and passes
+ * whose sweep ran in the engine's stream.  The first way is taken by a pass whose k_mark overlaps (above) and that writes
+ * the render state's own visible list (no list_out / count_out, no re-integration batch being planned);
+ * DSLAM_OVERLAP_SWEEP=0 in the environment of dslam_engine_create selects the second way always, and so does
+ * DSLAM_OVERLAP_MARK=0.  A dslam_process_frame that takes the first way returns once the two kernels are launched; the
+ * rest of it, and a dslam_get_image / dslam_fence_record behind it that would only enqueue, are handed to the GPU by
+ * the next dslam_view_update (while its copy is in flight) or by whatever other call touches the engine next.  Both ways
+ * compute the same bytes. */
+int dslam_debug_sweep_overlap_counts(dslam_engine *e, long long *overlapped_out, long long *in_stream_out);
 /* Test hook: a one-thread kernel reports the given device-side error bits for the scene (1: allocation ray longer than the
  * order key encodes, 2: a tile count never arrived) exactly as a failing pass would (report_error, csrc/dslam_device.h), so
  * that the way such an error reaches the caller can be tested: returned by this very call on a synchronous engine, by the
