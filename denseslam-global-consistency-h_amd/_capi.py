@@ -764,8 +764,9 @@ class CApi:
         return pose.reshape(4, 4).T.copy(), res
 
     def debug_track_sdf_sums(self):
-        """The 33 double sums of the most recent depth-to-SDF tracking evaluation (pivot at the world origin), laid out as
-        debug_register_sums: 21 Hessian, 6 gradient, sum of b^2, valid count, 3 sum of p, candidate count."""
+        """The 33 double sums of the most recent depth-to-SDF tracking evaluation (rows pivoted at the camera centre of the
+        pose that was evaluated), laid out as debug_register_sums: 21 Hessian, 6 gradient, sum of b^2, valid count, 3 sum of
+        p - t, candidate count."""
         out = np.empty(33, dtype=np.float64)
         self._call("debug_track_sdf_sums", self._engine, out.ctypes.data_as(C.POINTER(C.c_double)))
         return out

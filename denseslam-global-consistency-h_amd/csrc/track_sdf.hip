@@ -8,13 +8,16 @@
 // One evaluation at P~ (camera -> world, the first three rows, row-major, translation in voxels, float32) on level l of
 // the view's depth pyramid: every pixel (x, y) with depth D > 1e-8 (a candidate, counted in N),
 //   camera point     c = (D ((x - cx) / fx), D ((y - cy) / fy), D), each component times (float)(1 / voxel_size);
-//   world point      p = P~ c (to_map's row order);
+//   world point      p = P~ c (to_map's row order); r = R c, the three-term sum before the translation t is added, is kept;
 //   per map i        q = T~_i p (to_map), a miss for a coordinate of magnitude >= 262144; cell floor(q); the 8-tap gate,
 //                    value d_i and gradient g_i of register_body.h; weight w_i: the same three lerp stages on the taps'
 //                    w_depth; g_i^w = R_i^T g_i, each component (r0 gx + r1 gy) + r2 gz;
 //   combine          Blend / Blend3 of multimap_device.h in list order (one map: its values unchanged);
-//   gate             |d| > residual_gate is a miss; else valid with b = -d and the row A = [p x g, g];
-//   sums             the 33 doubles of register_body.h with p in place of q.
+//   gate             |d| > residual_gate is a miss; else valid with b = -d and the row A = [r x g, g]: pivoted at the camera
+//                    centre, so that no float32 product has an operand of the size of the camera's position (DESIGN.md
+//                    section 28: with p x g the conditioning is wrong from block 8000 on and the track is lost at the
+//                    table's ends);
+//   sums             the 33 doubles of register_body.h with r in place of q; the host adds t back (pivot_sums_at_camera).
 //
 // Device work per evaluation: k_track_sdf, a fixed grid of kTrackSdfGrid workgroups, one lane per pixel in a grid-stride
 // loop.  The map descriptors live in an engine-owned device table (64 of them do not fit in kernel arguments); the loop
@@ -122,7 +125,7 @@ int launch_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_sc
     cost_first = good.gated_cost(gate2);
     DSLAM_TRY(lm_iterate(
         6, good.valid >= tp->min_valid, tp->max_evaluations, (double)tp->term_rotation, (double)tp->term_translation_voxels,
-        [&](double *H, double *g) { pivot_sums(good.sums, c, H, g); },
+        [&](double *H, double *g) { pivot_sums_at_camera(good.sums, P, c, H, g); },
         [&](const double *y) -> int {
           double trial[12];
           Evaluation33 ev;

@@ -36,10 +36,15 @@
     c.x = (D * (((float)x - p.cx) / p.fx)) * p.inv_vs;
     c.y = (D * (((float)y - p.cy) / p.fy)) * p.inv_vs;
     c.z = D * p.inv_vs;
-    Vec3 pw;
-    pw.x = ((DSLAM_TRACK_SDF_POSE(0) * c.x + DSLAM_TRACK_SDF_POSE(1) * c.y) + DSLAM_TRACK_SDF_POSE(2) * c.z) + DSLAM_TRACK_SDF_POSE(3);
-    pw.y = ((DSLAM_TRACK_SDF_POSE(4) * c.x + DSLAM_TRACK_SDF_POSE(5) * c.y) + DSLAM_TRACK_SDF_POSE(6) * c.z) + DSLAM_TRACK_SDF_POSE(7);
-    pw.z = ((DSLAM_TRACK_SDF_POSE(8) * c.x + DSLAM_TRACK_SDF_POSE(9) * c.y) + DSLAM_TRACK_SDF_POSE(10) * c.z) + DSLAM_TRACK_SDF_POSE(11);
+    // R c, the point relative to the camera centre t: what the rotation part of the row and sums 29..31 are formed from, so
+    // that neither has an operand of the size of the camera's position; p = R c + t is what the maps are read at
+    Vec3 rc, pw;
+    rc.x = (DSLAM_TRACK_SDF_POSE(0) * c.x + DSLAM_TRACK_SDF_POSE(1) * c.y) + DSLAM_TRACK_SDF_POSE(2) * c.z;
+    rc.y = (DSLAM_TRACK_SDF_POSE(4) * c.x + DSLAM_TRACK_SDF_POSE(5) * c.y) + DSLAM_TRACK_SDF_POSE(6) * c.z;
+    rc.z = (DSLAM_TRACK_SDF_POSE(8) * c.x + DSLAM_TRACK_SDF_POSE(9) * c.y) + DSLAM_TRACK_SDF_POSE(10) * c.z;
+    pw.x = rc.x + DSLAM_TRACK_SDF_POSE(3);
+    pw.y = rc.y + DSLAM_TRACK_SDF_POSE(7);
+    pw.z = rc.z + DSLAM_TRACK_SDF_POSE(11);
     Blend bd = {0, 0.0f, 0.0f, 0.0f};
     Blend3 bg = {0, 0.0f, 0.0f, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f}};
     for (int i = 0; i < p.num_maps; i++) {   // (i is the same in every lane: the descriptor is read by scalar loads)
@@ -94,13 +99,13 @@
     if (fabsf(d) > p.residual_gate) continue;
     const float r = -d;
     float A[6];
-    A[0] = pw.y * g.z - pw.z * g.y;
-    A[1] = pw.z * g.x - pw.x * g.z;
-    A[2] = pw.x * g.y - pw.y * g.x;
+    A[0] = rc.y * g.z - rc.z * g.y;
+    A[1] = rc.z * g.x - rc.x * g.z;
+    A[2] = rc.x * g.y - rc.y * g.x;
     A[3] = g.x; A[4] = g.y; A[5] = g.z;
     valid++;
     sF += (double)(r * r);
-    sQx += (double)pw.x; sQy += (double)pw.y; sQz += (double)pw.z;
+    sQx += (double)rc.x; sQy += (double)rc.y; sQz += (double)rc.z;
 #pragma unroll
     for (int k = 0, c2 = 0; k < 6; k++) {
       sN[k] += (double)(r * A[k]);

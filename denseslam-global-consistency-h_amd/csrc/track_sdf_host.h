@@ -4,6 +4,7 @@
 // Host only: nothing here is device code, and both kernels' parameter structs stay where they are.
 #pragma once
 #include "dslam_internal.h"
+#include "register_host.h"
 
 namespace dslam {
 
@@ -29,6 +30,16 @@ struct TrackSdfPyramid {
     kp.fx = lintr[level][0]; kp.fy = lintr[level][1]; kp.cx = lintr[level][2]; kp.cy = lintr[level][3];
   }
 };
+
+// The system of an evaluation's sums at its centroid.  The kernels form the rotation part of a row and sums 29..31 from
+// R c = p - t, the point relative to the camera centre t (the float32 translation of the P~ that was evaluated; P is the
+// double it was rounded from): pivot_sums' centroid is therefore relative to t, and H_c, g_c are what they would be had the
+// rows been formed at the world origin in exact arithmetic.  c: the centroid in the world (voxels, double), the pivot
+// apply_increment turns about.
+inline void pivot_sums_at_camera(const double sums[kRegSums], const double P[12], double c[3], double Hc[36], double gc[6]) {
+  pivot_sums(sums, c, Hc, gc);
+  for (int i = 0; i < 3; i++) c[i] += (double)(float)P[i * 4 + 3];
+}
 
 // the result of one tracked pose: evaluations over all levels, the levels that took a step; of the last level its outcome,
 // its accepted evaluation, the cost it started with and the cost it ended with

@@ -251,7 +251,7 @@ int launch_track_camera_sdf_starts(dslam_engine *e, const dslam_view *v, const d
       active.clear();
       for (int k = 0; k < num_starts; k++) {
         Start &s = starts[k];
-        if (!s.lm.propose([&](double *H, double *g) { pivot_sums(s.good.sums, s.c, H, g); })) continue;
+        if (!s.lm.propose([&](double *H, double *g) { pivot_sums_at_camera(s.good.sums, s.P, s.c, H, g); })) continue;
         apply_increment(s.lm.increment(), s.c, s.P, s.trial);
         active.push_back(k);
       }
@@ -269,7 +269,7 @@ int launch_track_camera_sdf_starts(dslam_engine *e, const dslam_view *v, const d
     }
     for (int k = 0; k < num_starts; k++) {
       Start &s = starts[k];
-      s.lm.finish([&](double *H, double *g) { pivot_sums(s.good.sums, s.c, H, g); });
+      s.lm.finish([&](double *H, double *g) { pivot_sums_at_camera(s.good.sums, s.P, s.c, H, g); });
       s.total_evaluations += s.lm.out.evaluations;
       if (s.lm.out.accepted_any) { s.accepted_any = true; s.levels_stepped |= 1 << level; }
       s.cost_last = s.good.gated_cost(gate2);

@@ -1051,7 +1051,8 @@ int dslam_debug_icp_sums(dslam_engine *e, double out[29]);
  *   1. candidate: D = depth_l[x, y] > 1e-8f; candidates are counted in N;
  *   2. camera point in voxel units: c = (D ((x - cx) / fx), D ((y - cy) / fy), D) in float32, each component then
  *      multiplied by (float)(1.0 / (double)voxel_size);
- *   3. world point p = P~ c, rows evaluated as ((a x + b y) + c z) + d in float32;
+ *   3. world point p = P~ c, rows evaluated as ((a x + b y) + c z) + d in float32; the three-term sum before d is added,
+ *      r = R c, is kept: it is p relative to the camera centre t (the translation of P~), free of t's rounding;
  *   4. per map i, in list order: q_i = T~_i p in the same row order (a T_i that is exactly the identity reads at p
  *      itself); a q_i with a coordinate of magnitude >= 262144 is a miss for that map; cell floor(q_i), fractions
  *      c = q_i - floor(q_i); items 3 and 4 of dslam_register_maps apply unchanged: all 8 taps resident, each with
@@ -1065,11 +1066,15 @@ int dslam_debug_icp_sums(dslam_engine *e, double out[29]);
  *      float32, in list order (sum w > 0 always: every tap weighs at least 1) -- the camera is tracked against the
  *      field the composite raycast draws;
  *   6. gate: |d| > residual_gate is a miss;
- *   7. a valid pixel has b = -d and the row A = [p x g, g] (rotation about the world origin, then translation);
- *   8. the 33 sums of dslam_register_maps' item 6 with p in place of q: [29..31] sum p over the valid pixels, [32] N;
+ *   7. a valid pixel has b = -d and the row A = [r x g, g] (rotation about the camera centre t, then translation): no
+ *      operand of the row has the size of the camera's position, so the products, which are float32, keep their
+ *      relative precision however far from the world origin the camera is;
+ *   8. the 33 sums of dslam_register_maps' item 6 with r in place of q: [29..31] sum r over the valid pixels, [32] N;
  *   9. cost = (sum b^2 + (N - valid) residual_gate^2) / N (residual_gate^2 for N = 0).
  * Iteration: the levels run from no_hierarchy_levels - 1 down to run_till_level.  Each level runs dslam_register_maps'
- * iteration word for word on P~: pivot at the centroid c = sum p / valid, (H_c + lambda diag H_c) y = g_c, the step
+ * iteration word for word on P~: pivot at the centroid -- sum r / valid is the centroid relative to t, H_c and g_c are the
+ * sums re-pivoted by it, and c = t + sum r / valid in double, t the float32 translation that was evaluated, is the centroid
+ * in the world --, (H_c + lambda diag H_c) y = g_c, the step
  * applied on the left of P~ as p' = c + R(y0..2)(p - c) + y3..5, accepted on valid >= min_valid and a lower cost, the
  * lambda rules and stop reasons 0 - 3 unchanged.  Each level starts at lambda = 1 from the pose the level above returned;
  * max_evaluations is per level; a level that stops with reason 3 changes nothing and the next level starts from the same
@@ -1109,7 +1114,9 @@ int dslam_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_sce
                            const float *T_map_from_world /* [num_maps][16] */, int num_maps,
                            float pose_M[16] /* world -> camera; in: start, out: estimate */, const float intrinsics_d[4],
                            const dslam_track_sdf_params *params /* NULL: defaults */, dslam_track_sdf_result *result);
-/* Test hook: the 33 raw sums (pivot at the world origin) of the engine's most recent evaluation.  Error if none has run. */
+/* Test hook: the 33 raw sums of the engine's most recent evaluation.  The rows are pivoted at the camera centre of the P~
+ * that was evaluated: [0..20] and [21..23] hold r x g where they held p x g with p in world voxels, and [29..31] sum r where
+ * they held sum p (items 7 and 8 above); [24..28] and [32] do not depend on the pivot.  Error if none has run. */
 int dslam_debug_track_sdf_sums(dslam_engine *e, double out[33]);
 
 /* ---- depth-to-SDF tracking from many start poses at once ---------------------------------------- */
@@ -1153,7 +1160,8 @@ int dslam_track_camera_sdf_starts(dslam_engine *e, const dslam_view *v, const ds
                                   const float intrinsics_d[4], const dslam_track_sdf_params *params /* NULL: defaults */,
                                   dslam_track_sdf_result *results /* [num_starts] */);
 /* Test hook: the 33 raw sums of the last evaluation of start `start` in the engine's most recent
- * dslam_track_camera_sdf_starts -- what dslam_debug_track_sdf_sums gives after the single call from that start.  Error if
+ * dslam_track_camera_sdf_starts -- what dslam_debug_track_sdf_sums gives after the single call from that start, its
+ * entries pivoted at that evaluation's camera centre as stated there.  Error if
  * no such call has run or `start` is not one of its starts. */
 int dslam_debug_track_sdf_start_sums(dslam_engine *e, int start, double out[33]);
 

@@ -9,13 +9,15 @@ pyramid.  Every pixel (x, y) with depth D > 1e-8:
                           not +-32767, else the map is a miss; d_i, g_i the trilinear interpolant of raw / 32767 and its
                           analytic gradient, w_i the trilinear interpolant of the taps' w_depth, g_i^w = R_i^T g_i;
   combine                 no map: a miss; one: its d, g; several: d = sum w_i d_i / sum w_i, g = sum w_i g_i^w / sum w_i;
-  |d| > gate is a miss, else valid with b = -d and row A = [p x g, g];
-  sums                    21 lower-triangle entries of sum A^T A, 6 of sum b A, sum b^2, valid, sum p (3), N.
+  |d| > gate is a miss, else valid with b = -d and row A = [(p - t) x g, g], t the translation of P~ and p - t = R c the
+                          three products of c with P~'s rotation, before t is added: the row is pivoted at the camera
+                          centre and has no operand of the size of the camera's position;
+  sums                    21 lower-triangle entries of sum A^T A, 6 of sum b A, sum b^2, valid, sum (p - t) (3), N.
 
 What the engine may differ by: it evaluates the same expressions in float32 (u = 2^-24 per operation) and accumulates the
 float32 products in double.  The first-order propagation of u, per valid pixel, extends ref64_register.py's over
   the camera point   dc = 4 u |c| (a difference, a quotient and two products on the longest path);
-  the product with P~ dp = |P~| dc + 3 u (|a x| + |b y| + |c z| + |d|) per row;
+  the product with P~ dr = |R| dc + 3 u (|a x| + |b y| + |c z|) per row for r = p - t, and dp = dr + 3 u |d| for p;
   each map           dq = |T~| dp + 3 u (...) per row (dq = dp under the identity); fractions dc' = dq + 2 u; with M the
                      largest |s| of the taps, D the largest first difference along a cell edge, H2 the largest mixed second
                      difference over a face:  dd = sum_axis |g_axis| dc' + 10 u M,  dg = 16 u M + 8 u D + 2 H2 max dc';
@@ -23,12 +25,13 @@ float32 products in double.  The first-order propagation of u, per valid pixel, 
   the rotation back  dg^w = |R^T| dg + 3 u |R^T| |g| per component;
   the blend of k > 1 maps: numerators sum w_i v_i: sum (w_i dv_i + |v_i| dw_i + u |w_i v_i|) + (k - 1) u sum |w_i v_i|;
                      denominator: sum dw_i + (k - 1) u sum w_i; quotient: dnum / den + |num| dden / den^2 + u |v|;
-  the row            rotation i: sum over its two products |p| dg + |g| dp + 2 u |p g|; translation: dg;
+  the row            rotation i: sum over its two products |r| dg + |g| dr + 2 u |r g|; translation: dg;
   products x y       |x| dy + |y| dx + u |x y|.
 They are added over the pixels (no cancellation assumed).
 
-Ties.  A pixel whose q has a coordinate within TIE_Q of an integer in any map may fall into the neighbouring cell there in
-float32 (the value is continuous across the boundary, the gradient, the weight's slope and the 8-tap gate are not); a pixel
+Ties.  A pixel whose q has a coordinate within max(TIE_Q, dq) of an integer in any map -- dq the bound derived above for
+that pixel, map and axis: 4e-5 at the origin, the spacing of float32 at q far from it -- may fall into the neighbouring cell
+there in float32 (the value is continuous across the boundary, the gradient, the weight's slope and the 8-tap gate are not); a pixel
 with | |d| - gate | < TIE_B may fall on the other side of the gate.  For those the alternatives are evaluated (the cell
 moved on the tied axes, in all tied maps together and in each alone; valid or a miss) and each sum is compared as an
 interval over them; counts are exact up to the number of tie pixels.
@@ -142,7 +145,7 @@ def read_map(pm, q, cell, dq, weight_law="trilinear"):
 
 
 def _pixel_terms(maps, qs, dqs, cells, p, dp, gate, weight_law="trilinear"):
-    """Pixels with world point p [n, 3], per map the point qs[i], its bound dqs[i] and the cell to read it in:
+    """Pixels with camera-relative point p [n, 3] = R c (the rows' and sum 29..31's operand), per map the point qs[i], its bound dqs[i] and the cell to read it in:
     (valid [n], terms [n, 32], bounds [n, 32], d [n], holders [n]: the maps that passed their gate)."""
     n = len(p)
     k = np.zeros(n, np.int64)
@@ -241,8 +244,9 @@ class Evaluation:
         return float(used)
 
 
-def world_points(depth, intr, Pt, vs):
-    """Of one pyramid level: (pixel index [n] of the candidates, p [n, 3], dp [n, 3]) under P~ (rounded to float32 here)."""
+def camera_points(depth, intr, Pt, vs):
+    """Of one pyramid level under P~ (rounded to float32 here): (pixel index [n] of the candidates, r [n, 3] = R c, dr, p = r + t,
+    dp)."""
     P = _r32(Pt)
     depth = np.asarray(depth, F)
     h, w = depth.shape
@@ -253,8 +257,14 @@ def world_points(depth, intr, Pt, vs):
     inv_vs = float(F(1.0 / float(vs)))
     c = np.stack([D * ((x - cx) / fx), D * ((y - cy) / fy), D], 1) * inv_vs
     dc = 4 * U * np.abs(c)
-    p = c @ P[:, :3].T + P[:, 3]
-    dp = dc @ np.abs(P[:, :3]).T + 3 * U * (np.abs(c) @ np.abs(P[:, :3]).T + np.abs(P[:, 3]))
+    r = c @ P[:, :3].T
+    dr = dc @ np.abs(P[:, :3]).T + 3 * U * (np.abs(c) @ np.abs(P[:, :3]).T)
+    return cand, r, dr, r + P[:, 3], dr + 3 * U * np.abs(P[:, 3])
+
+
+def world_points(depth, intr, Pt, vs):
+    """Of one pyramid level: (pixel index [n] of the candidates, p [n, 3], dp [n, 3]) under P~ (rounded to float32 here)."""
+    cand, _, _, p, dp = camera_points(depth, intr, Pt, vs)
     return cand, p, dp
 
 
@@ -262,10 +272,10 @@ def evaluate(maps, depth, intr, Pt, gate=0.75, weight_law="trilinear"):
     """One evaluation of one pyramid level (float32 depth image [h, w], its float32 intrinsics) at Pt [3, 4]."""
     gate = float(F(gate))
     vs = maps[0].data.vs
-    cand, p, dp = world_points(depth, intr, Pt, vs)
+    cand, r, dr, p, dp = camera_points(depth, intr, Pt, vs)
     ev = Evaluation()
     ev.gate, ev.candidates = gate, len(cand)
-    qs, dqs, cells, tie_axes = [], [], [], []
+    qs, dqs, cells, tie_axes, windows = [], [], [], [], []
     for pm in maps:
         if pm.identity:
             q, dq = p, dp
@@ -276,13 +286,15 @@ def evaluate(maps, depth, intr, Pt, gate=0.75, weight_law="trilinear"):
         cell = np.floor(q)
         frac = q - cell
         qs.append(q); dqs.append(dq); cells.append(cell.astype(np.int64))
-        tie_axes.append(np.minimum(frac, 1 - frac) < TIE_Q)
-    valid, terms, bounds, d, holders = _pixel_terms(maps, qs, dqs, cells, p, dp, gate, weight_law)
+        windows.append(np.maximum(TIE_Q, dq))
+        tie_axes.append(np.minimum(frac, 1 - frac) < windows[-1])
+    valid, terms, bounds, d, holders = _pixel_terms(maps, qs, dqs, cells, r, dr, gate, weight_law)
     tie = np.any([t.any(1) for t in tie_axes], axis=0) | (np.abs(np.abs(d) - gate) < TIE_B) if len(cand) else np.zeros(0, bool)
     sums = np.zeros(NSUMS)
     sums[:32] = terms.sum(0)
     sums[32] = ev.candidates
     lo, hi = np.zeros(NSUMS), np.zeros(NSUMS)
+    ev.tie_lo, ev.tie_hi, ev.sums_no_tie = np.zeros(NSUMS), np.zeros(NSUMS), np.zeros(NSUMS)
     nt = ~tie
     lo[:32] = terms[nt].sum(0) - bounds[nt].sum(0)
     hi[:32] = terms[nt].sum(0) + bounds[nt].sum(0)
@@ -291,23 +303,28 @@ def evaluate(maps, depth, intr, Pt, gate=0.75, weight_law="trilinear"):
     if len(ti):
         alt_lo, alt_hi = terms[ti] - bounds[ti], terms[ti] + bounds[ti]
         sub_q, sub_dq = [q[ti] for q in qs], [dq[ti] for dq in dqs]
+        sub_win = [w[ti] * a[ti] for w, a in zip(windows, tie_axes)]
         shifts = {(0, 0, 0)} | {tuple(s * (((combo >> a) & 1) * 2 - 1) for a in range(3)) for combo in range(8) for s in (1, -1)}
         movers = [list(range(len(maps)))] + ([[i] for i in range(len(maps))] if len(maps) > 1 else [])
         for moved in movers:
             for shift in sorted(shifts):
-                c2 = [np.floor(sub_q[i] + (np.array(shift) * TIE_Q * tie_axes[i][ti] if i in moved else 0.0)).astype(np.int64)
+                c2 = [np.floor(sub_q[i] + (np.array(shift) * sub_win[i] if i in moved else 0.0)).astype(np.int64)
                       for i in range(len(maps))]
-                _, t2, b2, d2, _ = _pixel_terms(maps, sub_q, sub_dq, c2, p[ti], dp[ti], gate, weight_law)
+                _, t2, b2, d2, _ = _pixel_terms(maps, sub_q, sub_dq, c2, r[ti], dr[ti], gate, weight_law)
                 alt_lo, alt_hi = np.minimum(alt_lo, t2 - b2), np.maximum(alt_hi, t2 + b2)
                 on_gate = np.abs(np.abs(d2) - gate) < TIE_B   # either side of the gate: valid, or a miss
                 if on_gate.any():
-                    _, t3, b3, _, _ = _pixel_terms(maps, sub_q, sub_dq, c2, p[ti], dp[ti], 1e30, weight_law)
+                    _, t3, b3, _, _ = _pixel_terms(maps, sub_q, sub_dq, c2, r[ti], dr[ti], 1e30, weight_law)
                     g_ = on_gate[:, None]
                     alt_lo = np.where(g_, np.minimum(alt_lo, np.minimum(t3 - b3, 0.0)), alt_lo)
                     alt_hi = np.where(g_, np.maximum(alt_hi, np.maximum(t3 + b3, 0.0)), alt_hi)
         lo[:32] += alt_lo.sum(0)
         hi[:32] += alt_hi.sum(0)
+        ev.tie_lo[:32], ev.tie_hi[:32] = alt_lo.sum(0), alt_hi.sum(0)
     ev.sums, ev.lo, ev.hi = sums, lo, hi
+    ev.sums_no_tie[:32] = terms[nt].sum(0)   # the pixels that are no tie, alone; the tie pixels' share lies in tie_lo .. tie_hi
+    ev.sums_no_tie[32] = ev.candidates
+    ev.tie, ev.t = tie, _r32(Pt)[:, 3]
     ev.valid, ev.ties = int(sums[28]), int(tie.sum())
     ev.tie_share = ev.ties / max(ev.candidates, 1)
     ev.cost = ev.cost_of(sums, gate)
@@ -320,15 +337,16 @@ def evaluate(maps, depth, intr, Pt, gate=0.75, weight_law="trilinear"):
 # ---------------------------------------------------------------------------------------------------------------------
 # the iteration
 # ---------------------------------------------------------------------------------------------------------------------
-def pivot(sums):
-    """(c, H_c, g_c): the sums re-pivoted to the centroid c = sum p / valid."""
+def pivot(sums, t):
+    """(c, H_c, g_c): the sums, whose rows are pivoted at the camera centre t, re-pivoted to the centroid; c = t + sum (p - t)
+    / valid is the centroid in the world."""
     H = np.zeros((6, 6))
     for col, (k, j) in enumerate(_TRI):
         H[k, j] = H[j, k] = sums[col]
     c = sums[29:32] / sums[28] if sums[28] > 0 else np.zeros(3)
     S = np.eye(6)
     S[:3, 3:] = np.array([[0, c[2], -c[1]], [-c[2], 0, c[0]], [c[1], -c[0], 0]])
-    return c, S @ H @ S.T, S @ sums[21:27]
+    return np.asarray(t, np.float64) + c, S @ H @ S.T, S @ sums[21:27]
 
 
 def conditioning(Hc):
@@ -357,12 +375,14 @@ def moved(y, c, Pt):
     return out
 
 
-def track(maps, depth0, intr, pose_M, **params):
+def track(maps, depth0, intr, pose_M, evaluator=None, **params):
     """dslam_track_camera_sdf on PosedMaps.  depth0: the view's float32 depth image; pose_M: 4 x 4 world -> camera in metres
     (its entries are taken as float32).  Returns (pose 4 x 4 float32 -- pose_M's own bytes if no step was accepted --, result
     dict as dslam_track_sdf_result plus `per_level`: level -> dict(evaluations, stop_reason, trace) and `last`: the finest
     level's last accepted Evaluation; a trace holds one dict per evaluation with cost, valid, tie_share and, for trial
-    evaluations, accepted, lam, margin and cost_slack as ref64_register.register's)."""
+    evaluations, accepted, lam, margin and cost_slack as ref64_register.register's).  evaluator: what stands in for `evaluate`
+    (ref32_track_sdf.py: the same iteration on float32 sums)."""
+    evaluate_ = evaluator or evaluate
     pr = dict(DEFAULTS)
     pr.update({k: v for k, v in params.items() if v})
     pose_M = np.asarray(pose_M, F)
@@ -373,7 +393,7 @@ def track(maps, depth0, intr, pose_M, **params):
     accepted_any, total, stepped, per_level = False, 0, 0, {}
     for level in range(pr["no_hierarchy_levels"] - 1, pr["run_till_level"] - 1, -1):
         depth, k = levels[level]
-        good = evaluate(maps, depth, k, Pt, gate)
+        good = evaluate_(maps, depth, k, Pt, gate)
         trace = [dict(cost=good.cost, valid=good.valid, tie_share=good.tie_share, ev=good)]
         evaluations, stop, lam, accepted_here = 1, -1, 1.0, False
         cost_first = good.cost
@@ -383,10 +403,10 @@ def track(maps, depth0, intr, pose_M, **params):
             if evaluations >= pr["max_evaluations"]:
                 stop = 1
                 break
-            c, Hc, gc = pivot(good.sums)
+            c, Hc, gc = pivot(good.sums, good.t)
             y = damped_step(Hc, gc, lam)
             trial = moved(y, c, Pt)
-            ev = evaluate(maps, depth, k, trial, gate)
+            ev = evaluate_(maps, depth, k, trial, gate)
             evaluations += 1
             accept = ev.valid >= pr["min_valid"] and ev.cost < good.cost
             (l1, h1), (l2, h2) = ev.cost_interval(), good.cost_interval()
@@ -407,7 +427,7 @@ def track(maps, depth0, intr, pose_M, **params):
         if accepted_here:
             accepted_any = True
             stepped |= 1 << level
-        cond = 0.0 if stop == 3 else conditioning(pivot(good.sums)[1])
+        cond = 0.0 if stop == 3 else conditioning(pivot(good.sums, good.t)[1])
         per_level[level] = dict(evaluations=evaluations, stop_reason=stop, trace=trace)
         res = dict(stop_reason=stop, candidates=good.candidates, valid_last=good.valid, cost_first=cost_first,
                    cost_last=good.cost, conditioning=cond, last=good)

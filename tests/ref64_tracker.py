@@ -105,15 +105,58 @@ def inverse_error(M):
     return e
 
 
+def _transform(M, p, e_p, e_M):
+    """M p with its float32 rounding bound: a product and up to three additions per term, the input's error e_p and the
+    matrix's entry-wise error e_M."""
+    out = p @ M[:3, :3].T + M[:3, 3]
+    mag = np.abs(p) @ np.abs(M[:3, :3]).T + np.abs(M[:3, 3])
+    e = 4.0 * EPS * mag + e_p @ np.abs(M[:3, :3]).T
+    if e_M is not None:
+        e = e + np.abs(p) @ e_M[:3, :3].T + e_M[:3, 3]
+    return out, e
+
+
+def _chain(d, x, y, k, Minv, S, si, e_inv):
+    """The float64 chain from a pixel to its projection into the scene image, each value with its float32 rounding bound:
+    (p, e_p, q, e_q, uv [2], e_uv [2])."""
+    pc = np.stack([d * ((x - k[2]) / k[0]), d * ((y - k[3]) / k[1]), d], -1)
+    e_pc = np.abs(pc) * np.array([3.0 * EPS, 3.0 * EPS, 0.0])  # subtract, divide, multiply; z is the input itself
+    p, e_p = _transform(Minv, pc, e_pc, e_inv)
+    q, e_q = _transform(S, p, e_p, None)
+    uv, e_uv = [], []
+    with np.errstate(all="ignore"):
+        for a in (0, 1):
+            r = si[a] * q[:, a] / q[:, 2]
+            uv.append(r + si[2 + a])
+            e_uv.append(EPS * (2.0 * np.abs(r) + np.abs(uv[-1]))
+                        + abs(si[a]) * (e_q[:, a] / np.abs(q[:, 2]) + np.abs(q[:, a]) * e_q[:, 2] / q[:, 2] ** 2))
+    return p, e_p, q, e_q, uv, e_uv
+
+
+def _bilinear(img, ix, iy, dx, dy, e_u, e_v):
+    """Bilinear interpolant of img's cell (ix, iy) at fractions dx, dy [n, 1] and its bound: 1 - dx, two products, up to
+    three additions are 6 roundings on each weighted corner; the fractions' errors enter through the slopes."""
+    a, b, c, dd = (t.astype(np.float64) for t in _corners(img, ix, iy))
+    val = a * (1 - dx) * (1 - dy) + b * dx * (1 - dy) + c * (1 - dx) * dy + dd * dx * dy
+    mag = (np.abs(a) * np.abs((1 - dx) * (1 - dy)) + np.abs(b) * np.abs(dx * (1 - dy)) + np.abs(c) * np.abs((1 - dx) * dy)
+           + np.abs(dd) * np.abs(dx * dy))
+    du = np.abs((b - a) * (1 - dy) + (dd - c) * dy)
+    dv = np.abs((c - a) * (1 - dx) + (dd - b) * dx)
+    return val, 6.0 * EPS * mag + du * e_u[:, None] + dv * e_v[:, None]
+
+
 def evaluate(depth_level, view_intr_level, points, normals, scene_intr, approx_inv_pose, scene_pose, dist_thresh,
-             type, inv_err=None):
+             type, inv_err=None, derived_ties=False):
     """One evaluation at one level.  depth_level [h, w] float32; points / normals [H, W, 4] float32 (w < 0: hole);
     approx_inv_pose (camera -> world) and scene_pose (world -> scene camera) 4x4; `inv_err`: entry-wise bound on the
     error of approx_inv_pose as the engine holds it (it inverts in float32).
     Returns dict: sums[29], bound[29], max_term[29], valid [h, w] bool, tie [h, w] bool, projected (pixels that
     reached the distance gate), gated (those it rejected), b / A / p / n / cp per valid pixel (float64), and the numbers
     of pixels that fell behind the scene camera, outside the projection bounds and onto a cell with a hole (one_hole:
-    of those, per corner a / b / c / d, the pixels whose cell has that corner as its only hole)."""
+    of those, per corner a / b / c / d, the pixels whose cell has that corner as its only hole).
+    derived_ties: a predicate's tie window is the larger of the fixed one and the bound this function derives for the
+    predicate's operand at that pixel (q.z, u, v, the squared distance) -- for poses far from the origin, where a float32
+    projection moves by more than 1e-5 pixel; at the origin's cases the fixed windows stay as they are."""
     depth = np.asarray(depth_level, F)
     h, w = depth.shape
     H, W = points.shape[:2]
@@ -124,6 +167,14 @@ def evaluate(depth_level, view_intr_level, points, normals, scene_intr, approx_i
     vfx, vfy, vcx, vcy = (F(v) for v in view_intr_level)
     sfx, sfy, scx, scy = (F(v) for v in scene_intr)
     tie = np.zeros((h, w), bool)
+    k = [float(v) for v in (vfx, vfy, vcx, vcy)]
+    si = [float(v) for v in (sfx, sfy, scx, scy)]
+    e_inv = inverse_error(np.linalg.inv(Minv)) if inv_err is None else np.asarray(inv_err, np.float64)
+    win = None
+    if derived_ties:   # the chain's bounds on every pixel, as images
+        _, e_p_all, _, e_q_all, _, e_uv_all = _chain(np.where(depth > F(1e-8), depth, F(1)).astype(np.float64).reshape(-1),
+                                                     xs.reshape(-1).astype(np.float64), ys.reshape(-1).astype(np.float64), k, Minv, S, si, e_inv)
+        win = dict(qz=e_q_all[:, 2].reshape(h, w), u=e_uv_all[0].reshape(h, w), v=e_uv_all[1].reshape(h, w), p=e_p_all.reshape(h, w, 3))
 
     ok = depth > F(1e-8)
     tie |= np.abs(depth.astype(np.float64) - 1e-8) <= TIE * 1e-8
@@ -137,16 +188,19 @@ def evaluate(depth_level, view_intr_level, points, normals, scene_intr, approx_i
         front = q32[2] > F(0)
         qscale = np.abs(S[2, :3]) @ np.abs(np.stack([t.astype(np.float64) for t in p32]).reshape(3, -1)) + abs(S[2, 3])
         tie |= ok & (np.abs(q32[2].astype(np.float64)) <= TIE * qscale.reshape(h, w))
+        if win is not None:
+            tie |= ok & (np.abs(q32[2].astype(np.float64)) <= win["qz"])
         n_behind = int((ok & ~front).sum())
         ok &= front
         qz = np.where(ok, q32[2], F(1))
         u32 = sfx * q32[0] / qz + scx
         v32 = sfy * q32[1] / qz + scy
         inside = (u32 >= F(0)) & (u32 <= F(W - 2)) & (v32 >= F(0)) & (v32 <= F(H - 2))
-        for t, hi in ((u32, W - 2), (v32, H - 2)):
+        for t, hi, axis in ((u32, W - 2, "u"), (v32, H - 2, "v")):
             t64 = t.astype(np.float64)
-            tie |= ok & ((np.abs(t64) <= TIE) | (np.abs(t64 - hi) <= TIE))
-            tie |= ok & inside & (np.abs(t64 - np.round(t64)) <= TIE)  # the cell (and its hole test) could change
+            e_t = TIE if win is None else np.maximum(TIE, win[axis])
+            tie |= ok & ((np.abs(t64) <= e_t) | (np.abs(t64 - hi) <= e_t))
+            tie |= ok & inside & (np.abs(t64 - np.round(t64)) <= e_t)  # the cell (and its hole test) could change
         n_outside = int((ok & ~inside).sum())
         # pixels only q.z <= 0 rejects: behind the scene camera, yet projecting inside the bounds onto a cell without holes
         bi = np.nonzero((depth > F(1e-8)) & ~front & (q32[2] < F(0)))
@@ -177,6 +231,13 @@ def evaluate(depth_level, view_intr_level, points, normals, scene_intr, approx_i
     thr = F(dist_thresh)
     gate = dist32 > thr
     t_gate = np.abs(dist32.astype(np.float64) - float(thr)) <= TIE * float(thr)
+    if win is not None:   # the squared distance's own bound: cp from the cell the float32 chain chose, p, their difference
+        e_u, e_v = win["u"][idx], win["v"][idx]
+        cp_g, e_cp_g = _bilinear(pts[..., :3], ix, iy, (u32.astype(np.float64) - ix)[:, None], (v32.astype(np.float64) - iy)[:, None], e_u, e_v)
+        dd_g = cp32.astype(np.float64) - pw32.astype(np.float64)
+        e_dd_g = e_cp_g + win["p"][idx] + EPS * np.abs(dd_g)
+        e_dist = np.sum(2.0 * np.abs(dd_g) * e_dd_g, -1) + 5.0 * EPS * dist32.astype(np.float64)
+        t_gate |= np.abs(dist32.astype(np.float64) - float(thr)) <= e_dist
     tie[tuple(t[t_gate] for t in idx)] = True
     projected = np.zeros((h, w), bool)
     projected[idx] = True
@@ -191,38 +252,11 @@ def evaluate(depth_level, view_intr_level, points, normals, scene_intr, approx_i
     # ---- float64 chain on the valid pixels, each value with its float32 rounding bound ----------------------------
     d = depth[idx].astype(np.float64)
     x, y = xs[idx].astype(np.float64), ys[idx].astype(np.float64)
-    k = [float(v) for v in (vfx, vfy, vcx, vcy)]
-    pc = np.stack([d * ((x - k[2]) / k[0]), d * ((y - k[3]) / k[1]), d], -1)
-    e_pc = np.abs(pc) * np.array([3.0 * EPS, 3.0 * EPS, 0.0])  # subtract, divide, multiply; z is the input itself
-    e_inv = inverse_error(np.linalg.inv(Minv)) if inv_err is None else np.asarray(inv_err, np.float64)
-
-    def transform(M, p, e_p, e_M):
-        out = p @ M[:3, :3].T + M[:3, 3]
-        mag = np.abs(p) @ np.abs(M[:3, :3]).T + np.abs(M[:3, 3])
-        e = 4.0 * EPS * mag + e_p @ np.abs(M[:3, :3]).T  # a product and up to three additions per term
-        if e_M is not None:
-            e = e + np.abs(p) @ e_M[:3, :3].T + e_M[:3, 3]
-        return out, e
-
-    p, e_p = transform(Minv, pc, e_pc, e_inv)
-    q, e_q = transform(S, p, e_p, None)
-    si = [float(v) for v in (sfx, sfy, scx, scy)]
-    uv, e_uv = [], []
-    for a in (0, 1):
-        r = si[a] * q[:, a] / q[:, 2]
-        uv.append(r + si[2 + a])
-        e_uv.append(EPS * (2.0 * np.abs(r) + np.abs(uv[-1])) + abs(si[a]) * (e_q[:, a] / q[:, 2] + np.abs(q[:, a]) * e_q[:, 2] / q[:, 2] ** 2))
+    p, e_p, q, e_q, uv, e_uv = _chain(d, x, y, k, Minv, S, si, e_inv)
     dx, dy = (uv[0] - ix)[:, None], (uv[1] - iy)[:, None]
 
     def bilinear(img):
-        a, b, c, dd = (t.astype(np.float64) for t in _corners(img, ix, iy))
-        val = a * (1 - dx) * (1 - dy) + b * dx * (1 - dy) + c * (1 - dx) * dy + dd * dx * dy
-        mag = (np.abs(a) * np.abs((1 - dx) * (1 - dy)) + np.abs(b) * np.abs(dx * (1 - dy)) + np.abs(c) * np.abs((1 - dx) * dy)
-               + np.abs(dd) * np.abs(dx * dy))
-        du = np.abs((b - a) * (1 - dy) + (dd - c) * dy)
-        dv = np.abs((c - a) * (1 - dx) + (dd - b) * dx)
-        # 1 - dx, two products, up to three additions: 6 roundings on each weighted corner
-        return val, 6.0 * EPS * mag + du * e_uv[0][:, None] + dv * e_uv[1][:, None]
+        return _bilinear(img, ix, iy, dx, dy, e_uv[0], e_uv[1])
 
     cp, e_cp = bilinear(pts[..., :3])
     n, e_n = bilinear(nrm[..., :3])
@@ -323,8 +357,8 @@ def _full(sums, npara):
 
 
 def track(depth, intr, points, normals, scene_pose, pose, levels=5, run_till_level=0, dist_thresh=0.01,
-          termination_threshold=1e-3, regime=(3, 3, 1, 1, 1)):
-    """The whole coarse-to-fine loop in float64.  Returns (pose M, list of per-iteration records)."""
+          termination_threshold=1e-3, regime=(3, 3, 1, 1, 1), derived_ties=False):
+    """The whole coarse-to-fine loop in float64.  Returns (pose M, list of per-iteration records).  derived_ties: evaluate's."""
     pyr = pyramid(depth, intr, levels)
     iters, dist = level_schedule(levels, dist_thresh)
     regime = (list(regime) + [NONE] * 8)[:8]
@@ -340,7 +374,7 @@ def track(depth, intr, points, normals, scene_pose, pose, levels=5, run_till_lev
         good_M, f_old, lam = M.copy(), 1e20, 1.0
         for _ in range(iters[level]):
             ev = evaluate(pyr[level][0], pyr[level][1], points, normals, pyr[0][1], inv, scene_pose, dist[level], type,
-                          inv_err=None)
+                          inv_err=None, derived_ties=derived_ties)
             valid = int(ev["sums"][28])
             f_new = error_value(ev["sums"][27], valid)
             rejected = valid <= 0 or f_new > f_old

@@ -12,6 +12,7 @@ import math
 import numpy as np
 
 import analytic_maps as am
+import placement_fixtures as pf
 import ref64_checks as rc
 import ref64_tracker as rt
 
@@ -71,11 +72,17 @@ def keep_sparse(mm, every=6):
 class Setup:
     """A loaded analytic map with its ICP maps rendered from `M_map`, and a view of the geometry from `M_true`."""
 
-    def __init__(self, api, pkg, m, W, H, map_cam, true_off=(1.0, 0.01), view_edit=None, M_true=None, fy_scale=1.0):
+    def __init__(self, api, pkg, m, W, H, map_cam, true_off=(1.0, 0.01), view_edit=None, M_true=None, fy_scale=1.0, D=None):
+        """D: a placement (placement_fixtures.py, whole blocks): the map's blocks and geometry moved by shift_map, `M_map`
+        and `M_true` by shift_pose; `self.D`, and `self.place(M)` moves any other pose of the origin's (a start) likewise."""
+        self.D = None if D is None else tuple(int(v) for v in D)
+        if D is not None:
+            m = pf.shift_map(m, D)
         self.api, self.pkg, self.m, self.W, self.H = api, pkg, m, W, H
         self.M_map, self.intr = rc.camera(W, H, **map_cam)
         self.intr[1] *= np.float32(fy_scale)  # rc.camera gives fy = fx
         self.M_true = perturbed(self.M_map, *true_off) if M_true is None else np.asarray(M_true, np.float32)
+        self.M_map, self.M_true = self.place(self.M_map), self.place(self.M_true)
         self.scene, self.rs = rc.load_map(api, pkg, m, W, H)
         api.get_image(self.scene, self.rs, self.M_map, self.intr, pkg.IMAGE_DEPTH)
         api.find_visible_blocks(self.scene, self.rs, self.M_map, self.intr)
@@ -88,6 +95,9 @@ class Setup:
         self.view = api.create_view(W, H)
         api.view_update(self.view, np.zeros((H, W, 4), np.uint8), mm)
         self.depth = api.download_view_depth(self.view)
+
+    def place(self, M):
+        return np.asarray(M, np.float32) if self.D is None else pf.shift_pose(M, self.D, self.m.vs)
 
     def track(self, start, **kw):
         return self.api.track_camera(self.view, self.rs, self.M_map, start, self.intr, self.pkg.TrackerParams(**kw))
@@ -141,20 +151,22 @@ def evaluation_cases():
     }
 
 
-def _setup_case(api, pkg, c):
+def _setup_case(api, pkg, c, D=None):
     M_true = None
     if "true_yaw" in c:  # the view camera yawed away from the scene camera, about the scene camera's own position
         cam = dict(c["map_cam"])
         cam["yaw"] = cam.get("yaw", 0.0) + c["true_yaw"]
         M_true = perturbed(rc.camera(c["W"], c["H"], **cam)[0], 0.3, 0.003)
     return Setup(api, pkg, c["map"](), c["W"], c["H"], c["map_cam"], c.get("true_off", (1.0, 0.01)), c.get("view_edit"), M_true,
-                 c.get("fy_scale", 1.0))
+                 c.get("fy_scale", 1.0), D=D)
 
 
-def check_evaluations(api, pkg, case):
-    """Every level and iteration type of one case.  Returns the figures (tie share, worst |got - ref| / bound)."""
+def check_evaluations(api, pkg, case, D=None, tie_cap=TIE_SHARE):
+    """Every level and iteration type of one case.  Returns the figures (tie share, worst |got - ref| / bound).
+    D: the case moved by D blocks (Setup); the reference then derives its tie windows from its own bound, and tie_cap is the
+    share of tie pixels the placement may have (placement_fixtures.TIE_CAP)."""
     c = evaluation_cases()[case]
-    s = _setup_case(api, pkg, c)
+    s = _setup_case(api, pkg, c, D)
     # the pose to evaluate at: the true view pose for the yawed cases (the scene pose is what differs); else a pose off
     # both the map pose (where every pixel would project onto an integer scene pixel: all ties) and the true one
     start = s.M_true if "true_yaw" in c else perturbed(s.M_map, 0.23, 0.0019, axis=(-0.31, 0.52, 0.8), tdir=(-0.4, 0.7, 0.59))
@@ -168,11 +180,12 @@ def check_evaluations(api, pkg, case):
                                 dist_thresh=c["dist_thresh"], termination_threshold=ONE_EVALUATION)
             assert res.iterations == 1, f"{case} level {level} type {type}: {res.iterations} evaluations"
             got = api.debug_icp_sums()
-            ev = rt.evaluate(lv_depth, lv_intr, s.points, s.normals, s.intr, inv, s.M_map, c["dist_thresh"], type)
+            ev = rt.evaluate(lv_depth, lv_intr, s.points, s.normals, s.intr, inv, s.M_map, c["dist_thresh"], type,
+                             derived_ties=D is not None)
             ref, ties = ev["sums"], int(ev["tie"].sum())
             valid = int(ref[28])
             what = f"{case} level {level} ({lv_depth.shape[1]}x{lv_depth.shape[0]}) type {type}"
-            assert ties <= TIE_SHARE * valid, f"{what}: {ties} tie pixels for {valid} valid ones"
+            assert ties <= tie_cap * valid, f"{what}: {ties} tie pixels for {valid} valid ones"
             assert abs(got[28] - valid) <= ties, f"{what}: {int(got[28])} valid points, float64 reference {valid}"
             assert res.valid_points_last == int(got[28])
             npara = 6 if type == rt.BOTH else 3
@@ -411,3 +424,82 @@ def assert_truth_within_limit(case, e, e_start):
     assert e[0] <= lim[0] and e[1] <= lim[1], f"{case}: {e} from the truth, limits {lim}"
     if not case.startswith("plane"):
         assert e[0] < 0.25 * e_start[0] and e[1] < 0.25 * e_start[1], f"{case}: error {e}, start error {e_start}"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# away from the world origin.  The law is the reference's and is not changed.
+# ---------------------------------------------------------------------------------------------------------------------
+PLACED_CASES = ("box_64x48_small_perturbation", "box_70x45_fy_not_fx")
+PLACEMENTS = ("near+-+", "near-+-", "far+", "far-", "edge_pos", "edge_neg")
+# One evaluation.  The reference's bound propagates with the magnitudes of the coordinates (26 eps |t|_1 for the pose's
+# float32 inverse alone), and with the tie windows derived from it (ref64_tracker.evaluate, derived_ties) a projection is a
+# tie over ever more of the image: 37 % of the valid pixels at block 1000, all of them from block 4000 on.  The caps are
+# placement_fixtures.TIE_CAP's; D is halved until the reference meets the cap on every level and iteration type.  Times
+# halved, per case and placement (test_oracle_tracker_placement.py asserts the cap there and that one halving fewer misses
+# it, which is also the statement that the unhalved placements cannot be judged):
+EVALUATION_HALVINGS = {
+    ("box_64x48_small_perturbation", "near+-+"): 6, ("box_64x48_small_perturbation", "near-+-"): 6,
+    ("box_64x48_small_perturbation", "far+"): 8, ("box_64x48_small_perturbation", "far-"): 8,
+    ("box_64x48_small_perturbation", "edge_pos"): 8, ("box_64x48_small_perturbation", "edge_neg"): 8,
+    ("box_70x45_fy_not_fx", "near+-+"): 4, ("box_70x45_fy_not_fx", "near-+-"): 4,
+    ("box_70x45_fy_not_fx", "far+"): 6, ("box_70x45_fy_not_fx", "far-"): 6,
+    ("box_70x45_fy_not_fx", "edge_pos"): 6, ("box_70x45_fy_not_fx", "edge_neg"): 6,
+}
+
+
+def placed_evaluation(case, pname, fewer=0):
+    """(tie cap, D) of a placed single-evaluation case; fewer: that many halvings fewer than recorded."""
+    cls, D = pf.placements(evaluation_cases()[case]["map"]().block_pos)[pname]
+    return pf.TIE_CAP[cls], pf.halved(D, EVALUATION_HALVINGS[case, pname] - fewer)
+
+
+def check_placed_evaluations(api, pkg, case, pname):
+    """check_evaluations, every level and iteration type, with the case moved to its placement."""
+    cap, D = placed_evaluation(case, pname)
+    return check_evaluations(api, pkg, case, D=D, tie_cap=cap)
+
+
+# Whole runs: the default five-level run on the box corner, from the map pose (1 degree and 1 cm from the true one).
+PLACED_RUNS = {"origin": None, "block_100": (100, -70, 130), "near+-+": (1000, -700, 1300), "near-+-": (-1000, 700, -1300)}
+# what a pose far out may differ by, whatever computed it: the float32 inverse of a pose carries 26 eps per rotation entry
+# and 26 eps |t|_1 in its translation (ref64_tracker.inverse_error), and |t|_1 <= 3 P vs, eps P <= u(P): 78 u(P) vs
+POSE_U = 78.0
+
+
+def check_placed_run(api, pkg, name, D=None):
+    """The run on the map moved by D (default PLACED_RUNS[name]) blocks against ref64_tracker.track, with derived tie
+    windows, on the ICP maps the engine rendered there.  Returns (engine's error, reference's error, start error, u), the
+    errors (rotation rad, translation m) from the true pose and u = u(P) vs in metres, or None where the reference flags
+    an accept / reject decision as a tie."""
+    D = PLACED_RUNS[name] if D is None and name in PLACED_RUNS else D
+    s = Setup(api, pkg, am.box_corner(num_buckets=0x80), RUN_W, RUN_H, dict(yaw=0.27, pitch=-0.19, roll=0.1), (1.0, 0.01), D=D)
+    tp = pkg.TrackerParams()
+    M_ref, log = rt.track(s.depth, s.intr, s.points, s.normals, s.M_map, s.M_map, levels=tp.no_hierarchy_levels,
+                          run_till_level=tp.no_icp_run_till_level, dist_thresh=tp.dist_thresh,
+                          termination_threshold=tp.termination_threshold, regime=list(tp.regime), derived_ties=D is not None)
+    e_start, e_ref = pose_error(s.M_map, s.M_true), pose_error(M_ref, s.M_true)
+    u = pf.u(pf.P(s.m)) * s.m.vs
+    print(f"{name}: reference runs {len(log)} evaluations on levels {[r['level'] for r in log]}; start {e_start}, reference {e_ref}")
+    if any(r["accept_tie"] for r in log):
+        print(f"{name}: the reference's accept / reject decision is a tie; not judged")
+        return None
+    pose, res = s.track(s.M_map)
+    assert_rigid(pose, name)
+    e = pose_error(pose, s.M_true)
+    last = log[-1]
+    print(f"{name}: engine {res.iterations} evaluations, {e}; last valid {res.valid_points_last}, reference {last['valid']} "
+          f"with {last['ties']} ties")
+    assert res.iterations == len(log), f"{name}: {res.iterations} evaluations, reference {len(log)}"
+    assert abs(res.valid_points_last - last["valid"]) <= last["ties"], f"{name}: last valid {res.valid_points_last}, reference {last['valid']}"
+    return e, e_ref, e_start, u
+
+
+def assert_placed_run(name, e, e_ref, e_start, u):
+    """Tier (b)'s rule with what the coordinates' size adds: an engine's error to the truth is within the larger of the
+    origin's limit (TRUTH_LIMIT_FACTOR x the reference's error at the origin) and the reference's error on the same input
+    plus POSE_U u(P) (translation, metres) or 3 x 26 eps (rotation, the three entries of a row of the inverse)."""
+    lim = [TRUTH_LIMIT_FACTOR * v for v in REFERENCE_TRUTH_ERROR["box_default_5_levels"]]
+    assert e[0] <= max(lim[0], e_ref[0] + 78.0 * rt.EPS), f"{name}: rotation {e[0]} from the truth, reference {e_ref[0]}"
+    assert e[1] <= max(lim[1], e_ref[1] + POSE_U * u), f"{name}: translation {e[1]} from the truth, reference {e_ref[1]}"
+    if PLACED_RUNS[name] is None:
+        assert e_ref[0] < 0.25 * e_start[0] and e_ref[1] < 0.25 * e_start[1]

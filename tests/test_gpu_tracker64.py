@@ -33,6 +33,22 @@ def test_tracked_pose_against_the_truth(pkg, gpu, case):
     tc.assert_truth_within_limit(case, e, e_start)
 
 
+@pytest.mark.parametrize("pname", tc.PLACEMENTS)
+@pytest.mark.parametrize("case", tc.PLACED_CASES)
+def test_one_evaluation_away_from_the_origin(pkg, gpu, case, pname):
+    """the 29 sums on maps moved by whole blocks, as far out as the reference can judge them."""
+    print(f"{case} at {pname}: {tc.check_placed_evaluations(gpu, pkg, case, pname)}")
+
+
+@pytest.mark.parametrize("name", sorted(tc.PLACED_RUNS))
+def test_whole_run_away_from_the_origin(pkg, gpu, name):
+    """the engine runs the float64 reference's iteration on maps moved by whole blocks and ends as
+    close to the truth as the reference does."""
+    out = tc.check_placed_run(gpu, pkg, name)
+    assert out is not None, f"{name}: the reference calls a decision a tie, so the case judges nothing"
+    tc.assert_placed_run(name, *out)
+
+
 def test_icp_sums_need_an_evaluation(pkg, gpu):
     fresh = pkg.open_engine(0)  # `gpu` has tracked by now or will; a new engine has not
     with pytest.raises(pkg.DslamError):
