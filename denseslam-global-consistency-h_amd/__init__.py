@@ -14,7 +14,8 @@ from ._capi import (BLOCK_SIZE3, HASH_ENTRY_DTYPE, IMAGE_COLOUR_FROM_NORMAL, IMA
                     IMAGE_SHADED, MAX_REGISTER_PAIRS, MAX_RENDER_MAPS, MAX_SURVEY_MAPS, MAX_SURVEY_VIEWS, VOXEL_DTYPE, CApi, DslamError, MergeParams, MergeResult, PackInfo,
                     MAX_TRACK_STARTS, PoseLattice, PoseScore, PairSelectParams, PairSelectResult, RegisterGraphResult, RegisterPairResult, RegisterParams, RegisterResult,
                     SceneParams, Stats, SurveyView, TrackerParams, TrackerResult, TrackSdfParams, TrackSdfResult, UnmergeParams,
-                    UnmergeResult, ViewSelectParams, ViewSelectResult, ViewSurveyParams, WeightParams, mat_to_abi)
+                    UnmergeResult, ViewSelectParams, ViewSelectResult, ViewSurveyParams, WeightParams, mat_to_abi,
+                    FERN_CODE_DWORDS, FERN_MATCH_DTYPE, FERN_MAX_MATCHES, FERN_MAX_QUERIES, FernMatch, FernParams)
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")

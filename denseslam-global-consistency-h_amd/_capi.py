@@ -213,6 +213,30 @@ assert C.sizeof(SurveyView) == 96 and C.sizeof(ViewSurveyParams) == 16  # the he
 assert C.sizeof(ViewSelectParams) == 16 and C.sizeof(ViewSelectResult) == 8
 
 
+FERN_MAX_MATCHES, FERN_MAX_QUERIES, FERN_CODE_DWORDS = 64, 64, 64   # DSLAM_FERN_MAX_MATCHES, _MAX_QUERIES, _CODE_DWORDS
+
+
+class FernParams(C.Structure):
+    """dslam_fern_params; a field left at 0 selects its default (seed has none)."""
+    _fields_ = [("num_ferns", C.c_int32), ("cell", C.c_int32), ("channels", C.c_int32), ("depth_min_mm", C.c_int32),
+                ("depth_max_mm", C.c_int32), ("seed", C.c_uint32)]
+
+    def __init__(self, num_ferns=0, cell=0, channels=0, depth_min_mm=0, depth_max_mm=0, seed=0):
+        super().__init__(num_ferns, cell, channels, depth_min_mm, depth_max_mm, seed)
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class FernMatch(C.Structure):
+    """dslam_fern_match."""
+    _fields_ = [("id", C.c_int32), ("dissimilarity", C.c_int32)]
+
+
+FERN_MATCH_DTYPE = np.dtype([("id", "<i4"), ("dissimilarity", "<i4")])
+assert C.sizeof(FernParams) == 24 and C.sizeof(FernMatch) == 8 and FERN_MATCH_DTYPE.itemsize == 8  # the header's layouts
+
+
 class MergeParams(C.Structure):
     """dslam_merge_params; max_passes = 0 selects its default."""
     _fields_ = [("max_passes", C.c_int32), ("with_colour", C.c_int32)]
@@ -333,6 +357,10 @@ class View(_Handle):
 
 
 class FrameStore(_Handle):
+    pass
+
+
+class FernIndex(_Handle):
     pass
 
 
@@ -1022,6 +1050,75 @@ class CApi:
         self._call("select_view_maps", reach.ctypes.data_as(i32), nearest.ctypes.data_as(i32), C.c_int(nv), C.c_int(n),
                    C.byref(params) if params is not None else None, maps.ctypes.data_as(i32), C.byref(res))
         return maps[:res.selected].copy(), res
+
+    # -- fern keyframe index ---------------------------------------------------------------------------
+    def create_fern_index(self, width_d, height_d, capacity, params=None):
+        """dslam_fern_index_create: an index of `capacity` codes for depth images of width_d x height_d."""
+        h = C.c_void_p()
+        self._call("fern_index_create", self._engine, C.c_int(width_d), C.c_int(height_d),
+                   C.byref(params) if params is not None else None, C.c_int(capacity), C.byref(h))
+        idx = FernIndex(self, h, self._fn("fern_index_destroy"))
+        idx.width_d, idx.height_d, idx.capacity = width_d, height_d, capacity
+        return idx
+
+    def fern_index_count(self, idx):
+        n = C.c_int32(-1)
+        self._call("fern_index_count", idx.ptr, C.byref(n))
+        return n.value
+
+    def fern_index_table(self, idx):
+        """dslam_fern_index_table: (the FernParams with defaults filled in, the table int32 [F, 4, 3])."""
+        p = FernParams()
+        self._call("fern_index_table", idx.ptr, C.byref(p), None)
+        table = np.zeros((p.num_ferns, 4, 3), dtype=np.int32)
+        self._call("fern_index_table", idx.ptr, None, table.ctypes.data_as(C.POINTER(C.c_int32)))
+        return p, table
+
+    def fern_index_reset(self, idx):
+        self._call("fern_index_reset", self._engine, idx.ptr)
+
+    def fern_encode(self, idx, view):
+        """dslam_fern_encode: the view's code, uint32 [64]."""
+        code = np.zeros(FERN_CODE_DWORDS, dtype=np.uint32)
+        self._call("fern_encode", self._engine, idx.ptr, view.ptr, code.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return code
+
+    def fern_query(self, idx, view, first_id, last_id, k):
+        """dslam_fern_query: the first k candidates of the window as a FERN_MATCH_DTYPE array (id, dissimilarity)."""
+        matches = np.zeros(max(k, 1), dtype=FERN_MATCH_DTYPE)
+        n = C.c_int32(0)
+        self._call("fern_query", self._engine, idx.ptr, view.ptr, C.c_int(first_id), C.c_int(last_id), C.c_int(k),
+                   _vptr(matches), C.byref(n))
+        return matches[:n.value].copy()
+
+    def fern_process(self, idx, view, harvest_min_dissimilarity, first_id, last_id, k):
+        """dslam_fern_process: (matches, the id the view's code was appended under or -1, full).  full: the code should have
+        been appended but the index is full (DSLAM_ERR_UNSUPPORTED: the matches are delivered all the same)."""
+        matches = np.zeros(max(k, 1), dtype=FERN_MATCH_DTYPE)
+        n, added = C.c_int32(0), C.c_int32(-1)
+        rc = self._fn("fern_process")(self._engine, idx.ptr, view.ptr, C.c_int(harvest_min_dissimilarity), C.c_int(first_id),
+                                      C.c_int(last_id), C.c_int(k), _vptr(matches), C.byref(n), C.byref(added))
+        full = rc == -3 and self.fern_index_count(idx) == idx.capacity
+        if not full:
+            self._check(rc, "fern_process")
+        return matches[:n.value].copy(), added.value, full
+
+    def fern_add_from_store(self, idx, fs, first_slot, num_slots):
+        """dslam_fern_add_from_store: the id of the first of the num_slots codes appended."""
+        first = C.c_int32(-1)
+        self._call("fern_add_from_store", self._engine, idx.ptr, fs.ptr, C.c_int(first_slot), C.c_int(num_slots), C.byref(first))
+        return first.value
+
+    def fern_query_stored(self, idx, query_ids, first_id, last_id, k):
+        """dslam_fern_query_stored: one list of matches (FERN_MATCH_DTYPE) per query id."""
+        ids = np.ascontiguousarray(np.asarray(query_ids, dtype=np.int32))
+        nq = len(ids)
+        matches = np.zeros((max(nq, 1), max(k, 1)), dtype=FERN_MATCH_DTYPE)
+        nums = np.zeros(max(nq, 1), dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._call("fern_query_stored", self._engine, idx.ptr, ids.ctypes.data_as(i32), C.c_int(nq), C.c_int(first_id),
+                   C.c_int(last_id), C.c_int(k), _vptr(matches), nums.ctypes.data_as(i32))
+        return [matches[q, :nums[q]].copy() for q in range(nq)]
 
     # -- map merge -------------------------------------------------------------------------------------
     def merge_maps(self, src, dst, X, params=None):

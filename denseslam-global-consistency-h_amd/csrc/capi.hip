@@ -2193,6 +2193,148 @@ int dslam_select_view_maps(const int32_t *reach_blocks, const int32_t *nearest, 
   return DSLAM_OK;
 }
 
+// ---- fern keyframe index --------------------------------------------------------------------------------------------
+namespace {
+
+// what every dslam_fern_* call that takes a window rejects
+int check_fern_window(int first_id, int last_id, int k) {
+  DSLAM_REQUIRE(k >= 1 && k <= DSLAM_FERN_MAX_MATCHES, "k must be 1 .. DSLAM_FERN_MAX_MATCHES");
+  DSLAM_REQUIRE(first_id >= 0 && last_id >= 0 && first_id <= last_id, "the id window must satisfy 0 <= first_id <= last_id");
+  return DSLAM_OK;
+}
+
+int check_fern_view(const dslam_engine *e, const dslam_fern_index *idx, const dslam_view *v) {
+  DSLAM_REQUIRE(idx->engine == e, "the fern index belongs to another engine");
+  DSLAM_REQUIRE(v->engine == e, "the view belongs to another engine");
+  DSLAM_REQUIRE(v->updated, "the view was never updated");
+  DSLAM_REQUIRE(v->w_d == idx->w && v->h_d == idx->h, "the view's depth size is not the fern index's");
+  DSLAM_REQUIRE(idx->p.channels == 1 || (v->w_rgb == idx->w && v->h_rgb == idx->h),
+                "a fern index with a grey channel needs the view's RGB size to equal its depth size");
+  return DSLAM_OK;
+}
+
+}  // namespace
+
+int dslam_fern_index_create(dslam_engine *e, int width_d, int height_d, const dslam_fern_params *params, int capacity,
+                            dslam_fern_index **out) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && out, "null argument");
+  DSLAM_REQUIRE(width_d > 0 && height_d > 0 && (long long)width_d * height_d < (1ll << 30), "bad image size");
+  DSLAM_REQUIRE(capacity >= 1 && capacity <= (1 << 22), "capacity must be 1 .. 4194304");
+  dslam_fern_params p = {0, 0, 0, 0, 0, 0u};
+  if (params) p = *params;
+  DSLAM_REQUIRE(p.num_ferns >= 0 && p.cell >= 0 && p.channels >= 0 && p.depth_min_mm >= 0 && p.depth_max_mm >= 0,
+                "a fern parameter is negative");
+  if (p.num_ferns == 0) p.num_ferns = 512;
+  if (p.cell == 0) p.cell = 8;
+  if (p.channels == 0) p.channels = 1;
+  if (p.depth_min_mm == 0) p.depth_min_mm = 300;
+  if (p.depth_max_mm == 0) p.depth_max_mm = 10000;
+  DSLAM_REQUIRE(p.num_ferns % 8 == 0 && p.num_ferns <= 512, "num_ferns must be a multiple of 8 in 8 .. 512");
+  DSLAM_REQUIRE(p.cell <= 32, "cell must be 1 .. 32");
+  DSLAM_REQUIRE(p.channels <= 2, "channels must be 1 or 2");
+  DSLAM_REQUIRE(p.depth_min_mm <= p.depth_max_mm && p.depth_max_mm <= 32767, "need depth_min_mm <= depth_max_mm <= 32767");
+  DSLAM_REQUIRE(width_d / p.cell >= 1 && height_d / p.cell >= 1, "the cell is larger than the image");
+  std::unique_ptr<dslam_fern_index> idx(new dslam_fern_index());
+  idx->engine = e; idx->w = width_d; idx->h = height_d; idx->p = p; idx->capacity = capacity;
+  idx->tw = width_d / p.cell; idx->th = height_d / p.cell;
+  fern_build_table(p, idx->tw, idx->th, idx->table);
+  DSLAM_TRY(fern_index_allocate(e, idx.get()));
+  engine_adopt(e);   // (only a complete index is a handle, as a frame store)
+  *out = idx.release();
+  return DSLAM_OK;
+}
+
+int dslam_fern_index_destroy(dslam_fern_index *idx) {
+  if (!idx) return DSLAM_OK;
+  (void)hipSetDevice(idx->engine->device);
+  flush_deferred(idx->engine);   // (on its own device: held calls launch kernels)
+  (void)hipStreamSynchronize(idx->engine->stream);
+  dslam_engine *e = idx->engine;
+  delete idx;
+  engine_release(e);
+  return DSLAM_OK;
+}
+
+int dslam_fern_index_count(const dslam_fern_index *idx, int32_t *count_out) {
+  DSLAM_REQUIRE(idx && count_out, "null argument");
+  *count_out = idx->count;
+  return DSLAM_OK;
+}
+
+int dslam_fern_index_table(const dslam_fern_index *idx, dslam_fern_params *params_out, int32_t *table_out) {
+  DSLAM_REQUIRE(idx, "null argument");
+  if (params_out) *params_out = idx->p;
+  if (table_out) memcpy(table_out, idx->table.data(), idx->table.size() * sizeof(int32_t));
+  return DSLAM_OK;
+}
+
+int dslam_fern_index_reset(dslam_engine *e, dslam_fern_index *idx) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && idx, "null argument");
+  DSLAM_REQUIRE(idx->engine == e, "the fern index belongs to another engine");
+  idx->count = 0;
+  return DSLAM_OK;
+}
+
+int dslam_fern_encode(dslam_engine *e, dslam_fern_index *idx, const dslam_view *v, uint32_t code_out[DSLAM_FERN_CODE_DWORDS]) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && idx && v && code_out, "null argument");
+  DSLAM_TRY(check_fern_view(e, idx, v));
+  e->view_reads++;  // (see dslam_engine::last_fence)
+  return fern_encode_view(e, idx, v, code_out);
+}
+
+int dslam_fern_query(dslam_engine *e, dslam_fern_index *idx, const dslam_view *v, int first_id, int last_id, int k,
+                     dslam_fern_match *matches_out, int32_t *num_out) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && idx && v && matches_out && num_out, "null argument");
+  DSLAM_TRY(check_fern_view(e, idx, v));
+  DSLAM_TRY(check_fern_window(first_id, last_id, k));
+  e->view_reads++;  // (see dslam_engine::last_fence)
+  return fern_query_view(e, idx, v, -1, first_id, last_id, k, matches_out, num_out, nullptr);
+}
+
+int dslam_fern_process(dslam_engine *e, dslam_fern_index *idx, const dslam_view *v, int harvest_min_dissimilarity, int first_id,
+                       int last_id, int k, dslam_fern_match *matches_out, int32_t *num_out, int32_t *added_id_out) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && idx && v && matches_out && num_out && added_id_out, "null argument");
+  DSLAM_TRY(check_fern_view(e, idx, v));
+  DSLAM_TRY(check_fern_window(first_id, last_id, k));
+  DSLAM_REQUIRE(harvest_min_dissimilarity >= 0, "the harvest threshold is negative");
+  e->view_reads++;  // (see dslam_engine::last_fence)
+  return fern_query_view(e, idx, v, harvest_min_dissimilarity, first_id, last_id, k, matches_out, num_out, added_id_out);
+}
+
+int dslam_fern_add_from_store(dslam_engine *e, dslam_fern_index *idx, const dslam_frame_store *fs, int first_slot, int num_slots,
+                              int32_t *first_id_out) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && idx && fs && first_id_out, "null argument");
+  DSLAM_REQUIRE(idx->engine == e, "the fern index belongs to another engine");
+  DSLAM_REQUIRE(fs->engine == e, "frame store belongs to a different engine");
+  DSLAM_REQUIRE(fs->w_d == idx->w && fs->h_d == idx->h, "the frame store's depth size is not the fern index's");
+  DSLAM_REQUIRE(idx->p.channels == 1 || (fs->w_rgb == idx->w && fs->h_rgb == idx->h),
+                "a fern index with a grey channel needs the store's RGB size to equal its depth size");
+  DSLAM_REQUIRE(num_slots >= 1 && first_slot >= 0 && first_slot <= fs->capacity - num_slots, "the slots are not all in the frame store");
+  DSLAM_REQUIRE(num_slots <= idx->capacity - idx->count, "the fern index has no room for that many codes");
+  const int first_id = idx->count;
+  DSLAM_TRY(fern_add_from_store(e, idx, fs, first_slot, num_slots));
+  *first_id_out = first_id;
+  return DSLAM_OK;
+}
+
+int dslam_fern_query_stored(dslam_engine *e, dslam_fern_index *idx, const int32_t *query_ids, int num_queries, int first_id,
+                            int last_id, int k, dslam_fern_match *matches_out, int32_t *num_out) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && idx && query_ids && matches_out && num_out, "null argument");
+  DSLAM_REQUIRE(idx->engine == e, "the fern index belongs to another engine");
+  DSLAM_REQUIRE(num_queries >= 1 && num_queries <= DSLAM_FERN_MAX_QUERIES, "num_queries must be 1 .. DSLAM_FERN_MAX_QUERIES");
+  DSLAM_TRY(check_fern_window(first_id, last_id, k));
+  for (int q = 0; q < num_queries; q++)
+    DSLAM_REQUIRE(query_ids[q] >= 0 && query_ids[q] < idx->count, "a query id is not a stored code");
+  return fern_query_stored(e, idx, query_ids, num_queries, first_id, last_id, k, matches_out, num_out);
+}
+
 // ---- map merge --------------------------------------------------------------------------------------------------
 namespace {
 

@@ -522,7 +522,44 @@ struct DSLAM_INTERNAL dslam_frame_store {
   std::vector<unsigned char *> batch_list_ptr;
 };
 
+// The fern keyframe index (fern.hip): the codes of all keyframes, the fern table and the index's own
+// scratch.  The scratch groups exist whole or not at all (built aside, move-assigned).
+struct FernThumbs {
+  DeviceBuffer<unsigned short> thumbs;   // [thumb_slots][2][TW TH]: D and G of the images being encoded
+  int thumb_slots = 0;
+};
+struct FernRows {
+  DeviceBuffer<unsigned short> dist;     // [rows][dist_stride]: the dissimilarity of query q to stored id i at [q][i]
+  DeviceBuffer<unsigned> partial;        // [rows][kFernMaxSlices][64]: the best keys of each slice of the window
+  int rows = 0;                          // 1, or DSLAM_FERN_MAX_QUERIES from the first dslam_fern_query_stored with more than one
+};
+struct DSLAM_INTERNAL dslam_fern_index : FernThumbs, FernRows {
+  dslam_engine *engine = nullptr;
+  int w = 0, h = 0, tw = 0, th = 0, capacity = 0, count = 0;
+  dslam_fern_params p{};                 // defaults filled in
+  std::vector<int32_t> table;            // [F][4][3] as dslam_fern_index_table gives it
+  DeviceBuffer<int2> table_dev;          // [F][4] {2 cell + channel, threshold}
+  DeviceBuffer<unsigned> codes;          // [capacity][64]
+  DeviceBuffer<unsigned> qcode;          // [64]: the code of the view a call encodes
+  size_t dist_stride = 0;                // capacity rounded up to 64
+  DeviceBuffer<unsigned> result;         // what a call reads back (fern.hip FernResult) ...
+  PinnedBuffer<unsigned> result_host;    // ... and where
+  PinnedBuffer<int> query_ids;           // mapped: [DSLAM_FERN_MAX_QUERIES] the stored codes a scan compares against
+};
+
 namespace dslam {
+// dslam_fern_* (fern.hip); everything already checked by the entry points (capi.hip).  All wait for the stream; the
+// outputs are written only when everything has succeeded.
+void fern_build_table(const dslam_fern_params &p, int tw, int th, std::vector<int32_t> &table);
+int fern_index_allocate(dslam_engine *e, dslam_fern_index *idx);
+int fern_encode_view(dslam_engine *e, dslam_fern_index *idx, const dslam_view *v, uint32_t *code_out);
+// harvest < 0: the query alone; otherwise dslam_fern_process (*added_out: the new id or -1; DSLAM_ERR_UNSUPPORTED: full)
+int fern_query_view(dslam_engine *e, dslam_fern_index *idx, const dslam_view *v, int harvest, int first_id, int last_id, int k,
+                    dslam_fern_match *matches_out, int32_t *num_out, int32_t *added_out);
+int fern_add_from_store(dslam_engine *e, dslam_fern_index *idx, const dslam_frame_store *fs, int first_slot, int num_slots);
+int fern_query_stored(dslam_engine *e, dslam_fern_index *idx, const int32_t *query_ids, int num_queries, int first_id, int last_id,
+                      int k, dslam_fern_match *matches_out, int32_t *num_out);
+
 // diagnostics (DSLAM_DEBUG_SYNC=1): wait for the stream after a launch and say which one it was -- finds the kernel that
 // hangs or faults without a profiler
 inline bool dbg_sync_on() {

@@ -828,6 +828,94 @@ int dslam_select_view_maps(const int32_t *reach_blocks /* [V][N] */, const int32
                            int num_maps, const dslam_view_select_params *params /* NULL: defaults */,
                            int32_t *maps_out /* [max_maps] */, dslam_view_select_result *result);
 
+/* ---- fern keyframe index: which stored keyframe does this frame look like? ------------------
+ * Upstream's relocaliser (FernRelocLib: randomised ferns over a thumbnail of the frame, Glocker et al.) with the codes of
+ * all keyframes in HBM.  The reference ships the submodule empty, so the law is this project's own; it is all-integer, so
+ * the device gives the same bytes as any other statement of it.
+ *   parameters   dslam_fern_params below (every field int32 except seed; 0 selects the default).  F = num_ferns, c = cell.
+ *   thumbnail    the index is created for one depth image size W x H.  TW = W / c, TH = H / c (floor); the columns
+ *                x >= TW c and the rows y >= TH c are never read.  For cell (tx, ty), over its c x c pixels of the raw
+ *                int16 millimetre image as the kernels see it (what dslam_download_view_raw_depth returns) and of the
+ *                view's RGBA:  n = the pixels with mm > 0 (a negative value is invalid like 0), S = the int32 sum of
+ *                those mm, D = S / n (floor) if 2 n >= c c, else 0 -- a hole;  G = (sum over all c c pixels of
+ *                r + 2 g + b) / (4 c c), in 0 .. 255.
+ *   fern table   F ferns x 4 decisions, drawn in the order f, then j, from splitmix64 whose state starts at
+ *                (uint64_t)seed: next() is  state += 0x9E3779B97F4A7C15; z = state; z = (z ^ z >> 30) *
+ *                0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31.  A decision draws
+ *                cell = next() % (TW TH);  channel = next() & 1 (drawn only when channels == 2, otherwise 0);  threshold =
+ *                depth_min_mm + next() % (depth_max_mm - depth_min_mm + 1) for channel 0, next() % 255 for channel 1.
+ *                dslam_fern_index_table gives it as int32 [F][4][3] = (cell, channel, threshold), cell = ty TW + tx.
+ *   code         decision bit = value(cell, channel) > threshold, the value being D for channel 0 (a hole is 0 and never
+ *                passes) and G for channel 1;  nibble of fern f = sum_j bit_j << j.  A code is 64 uint32 (256 bytes): fern f
+ *                sits in dword f / 8 at bits 4 (f % 8) .. 4 (f % 8) + 3; the dwords of ferns >= F are zero.
+ *   dissimilarity of two codes: the ferns f < F whose nibbles differ, 0 .. F.
+ *   index        `capacity` codes in HBM with ids 0, 1, ... in the order of insertion; count = how many are stored.  What
+ *                else belongs to a keyframe (pose, timestamp, map) stays in the caller's containers keyed by id, as slot
+ *                bookkeeping does for the frame store.
+ *   query        the candidates are the ids in [first_id, last_id) n [0, count), ordered by (dissimilarity ascending, id
+ *                ascending); the first k (k <= DSLAM_FERN_MAX_MATCHES) go to matches_out, their number -- possibly 0 --
+ *                to num_out.  Entries of matches_out past that number are not written.
+ * With channels == 2 the grey channel is read at the depth image's pixel positions, so a view or frame store whose RGB
+ * size differs from its depth size counts as one of another size.  An index may be destroyed before or after its engine's
+ * other handles, and before or after dslam_engine_destroy (the lifetime rule of DESIGN.md section 21).  Every call below
+ * that takes the engine waits for the stream on synchronous and asynchronous engines, as dslam_survey_views does; none
+ * touches a scene, a render state, a view's images, a GetImage memo or a map version.
+ * DSLAM_ERR_INVALID with all outputs untouched (and the index unchanged): a NULL argument other than params; a view, store
+ * or index of another engine; a view never updated, or a view or store of another size than the index; k outside
+ * 1 .. DSLAM_FERN_MAX_MATCHES; first_id > last_id or a negative id; a query id outside [0, count); num_queries outside
+ * 1 .. DSLAM_FERN_MAX_QUERIES; a negative harvest threshold; parameters outside their ranges. */
+#define DSLAM_FERN_MAX_MATCHES 64
+#define DSLAM_FERN_MAX_QUERIES 64
+#define DSLAM_FERN_CODE_DWORDS 64
+typedef struct dslam_fern_index dslam_fern_index;
+typedef struct {
+  int32_t num_ferns;               /* 0 -> 512; a multiple of 8 in 8 .. 512 */
+  int32_t cell;                    /* 0 -> 8; 1 .. 32 */
+  int32_t channels;                /* 0 -> 1; 1 = depth, 2 = depth + grey */
+  int32_t depth_min_mm;            /* 0 -> 300 */
+  int32_t depth_max_mm;            /* 0 -> 10000; depth_min_mm <= depth_max_mm <= 32767 */
+  uint32_t seed;
+} dslam_fern_params;
+typedef struct {
+  int32_t id;
+  int32_t dissimilarity;
+} dslam_fern_match;
+/* capacity: 1 .. 4194304 codes (256 bytes each).  TW TH >= 1, i.e. cell <= min(W, H). */
+int dslam_fern_index_create(dslam_engine *e, int width_d, int height_d, const dslam_fern_params *params /* NULL: defaults */,
+                            int capacity, dslam_fern_index **out);
+int dslam_fern_index_destroy(dslam_fern_index *idx);
+int dslam_fern_index_count(const dslam_fern_index *idx, int32_t *count_out);
+/* the parameters with their defaults filled in (params_out may be NULL) and the table, int32 [F][4][3] (table_out may be NULL) */
+int dslam_fern_index_table(const dslam_fern_index *idx, dslam_fern_params *params_out, int32_t *table_out);
+/* count = 0; the ids start again at 0 */
+int dslam_fern_index_reset(dslam_engine *e, dslam_fern_index *idx);
+/* The view's code, to the host.  Two launches: the thumbnails (the view's images read once), the ferns. */
+int dslam_fern_encode(dslam_engine *e, dslam_fern_index *idx, const dslam_view *v, uint32_t code_out[DSLAM_FERN_CODE_DWORDS]);
+/* The query of the view's code; the index is only read. */
+int dslam_fern_query(dslam_engine *e, dslam_fern_index *idx, const dslam_view *v, int first_id, int last_id, int k,
+                     dslam_fern_match *matches_out /* [k] */, int32_t *num_out);
+/* Upstream's ProcessFrame in one device round trip: the query's result, and the view's code is appended (its id to
+ * added_id_out, -1 when nothing was added) when the index is empty or the smallest dissimilarity over ALL stored ids --
+ * whatever the window -- is >= harvest_min_dissimilarity; 0 always appends.  The decision is taken on the device.  A full
+ * index that should append returns DSLAM_ERR_UNSUPPORTED: the matches and their number are still delivered, added_id_out
+ * is -1 and the index is unchanged. */
+int dslam_fern_process(dslam_engine *e, dslam_fern_index *idx, const dslam_view *v, int harvest_min_dissimilarity, int first_id,
+                       int last_id, int k, dslam_fern_match *matches_out /* [k] */, int32_t *num_out, int32_t *added_id_out);
+/* Encodes and appends the stored keyframes of the slots first_slot .. first_slot + num_slots - 1 straight from the store's
+ * device images: ids in slot order, the first to first_id_out; the same codes as dslam_view_update_from_store +
+ * dslam_fern_process(..., 0, ...) per slot.  Two launches per batch of slots whose thumbnails fit the index's scratch
+ * (64 MiB: 3495 keyframes of 640 x 480 at cell 8), never one per slot.  DSLAM_ERR_INVALID with nothing written: num_slots
+ * < 1, a range that does not fit the store or the remaining capacity, a store of another size. */
+int dslam_fern_add_from_store(dslam_engine *e, dslam_fern_index *idx, const dslam_frame_store *fs, int first_slot, int num_slots,
+                              int32_t *first_id_out);
+/* The queries are stored codes (num_queries in 1 .. DSLAM_FERN_MAX_QUERIES); the stored codes of the window are read once
+ * for all of them.  Row q of matches_out / num_out is what dslam_fern_query gives for a view with the code of
+ * query_ids[q]; a query id inside the window is a candidate like any other and matches itself at 0.  Rows are num_queries
+ * x k: entry j of row q is matches_out[q k + j]. */
+int dslam_fern_query_stored(dslam_engine *e, dslam_fern_index *idx, const int32_t *query_ids, int num_queries, int first_id,
+                            int last_id, int k, dslam_fern_match *matches_out /* [num_queries][k] */,
+                            int32_t *num_out /* [num_queries] */);
+
 /* Fuse one local map into another on the device (no counterpart in the reference; the law is this project's own,
  * DESIGN.md section 14).  X is what dslam_register_maps takes and returns: source frame -> destination frame, metres,
  * column-major.  X~ is X with its translation in voxel units, Y~ its inverse (R^T, -R^T t); both are formed on the host
