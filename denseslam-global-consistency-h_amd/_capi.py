@@ -615,6 +615,12 @@ class CApi:
         self._call("debug_sweep_overlap_counts", self._engine, C.byref(overlapped), C.byref(in_stream))
         return overlapped.value, in_stream.value
 
+    def debug_front_overlap_counts(self):
+        """(front ends computed on the auxiliary stream beside the fusion launch, front ends computed inside the fusion launch)"""
+        on_aux, in_launch = C.c_longlong(0), C.c_longlong(0)
+        self._call("debug_front_overlap_counts", self._engine, C.byref(on_aux), C.byref(in_launch))
+        return on_aux.value, in_launch.value
+
     def reintegrate_batch_stats(self, scene):
         """(blocks the last batch loaded, its block-operations: (block, keyframe) pairs de-integrated or re-fused) -- HIP engine"""
         b, o = C.c_int32(0), C.c_int32(0)

@@ -433,6 +433,7 @@ struct SweepParams {
   // the DEFER instantiation: the table stores go to the engine's pending lists, errors to a word of its own
   PendingWrites pend;
   int *err_word;
+  short4 *hidden_pos;   // [entries]: the position of every entry the pass creates, for a selection that runs before the publish (4i)
 };
 
 // Pools that run out during the pass (rare): which requests get a block is the sequential rule over ALL requests in
@@ -518,6 +519,7 @@ __device__ __forceinline__ void table_store_entry(const SweepParams &p, int idx,
     if (i < (unsigned)p.pend.entry_cap) {
       p.pend.entry_idx[i] = idx;
       p.pend.entry[i] = pack_entry(bc.x, bc.y, bc.z, 0, slot);
+      if ((unsigned)idx < (unsigned)p.n_entries) p.hidden_pos[idx] = bc;   // (idx names a table entry: a bucket head of this tile or num_buckets + an excess-list slot)
     } else {
       report_error_own(p.cnt, p.err_word, 2);
     }
@@ -996,7 +998,20 @@ __global__ __launch_bounds__(256) void k_publish_entries(HashEntry *hash, int n_
 int finish_overlapped_allocate(dslam_engine *e, dslam_scene *s) {
   if (!e->publish_due) return DSLAM_OK;
   e->publish_due = false;
-  DSLAM_HIP(hipStreamSynchronize(e->aux_stream));
+  // (where the front end follows the sweep on aux_stream, DESIGN.md 4i, only the sweep is waited for: the event behind it)
+  if (e->sweep_done_recorded) {
+    DSLAM_HIP(hipEventSynchronize(e->sweep_done));
+  } else if (e->sweep_done_seq) {
+    // (bounded by GPU progress, as the wait for the start stamp: it also ends when the stream has drained)
+    volatile unsigned *word = e->start_stamp.get() + 1;
+    for (unsigned spins = 1; *word != e->sweep_done_seq; spins++)
+      if ((spins & 0xfffu) == 0 && hipStreamQuery(e->aux_stream) != hipErrorNotReady) break;
+    (void)hipGetLastError();  // (hipErrorNotReady is an answer, not a failure)
+  } else {
+    DSLAM_HIP(hipStreamSynchronize(e->aux_stream));
+  }
+  e->sweep_done_recorded = false;
+  e->sweep_done_seq = 0;
   const unsigned pair = (e->pend_pass - 1u) & 1u;   // (the pass that is being finished)
   PendingWrites pw{e->pend_count + 2 * pair, reinterpret_cast<u32x4 *>(e->pend_entry.get()), e->pend_entry_idx, e->pend_offset,
                    e->pend_cap, e->pend_cap};
@@ -1007,7 +1022,7 @@ int finish_overlapped_allocate(dslam_engine *e, dslam_scene *s) {
 }
 
 int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_render_state *r, const float *M_d,
-                    const float *intr, int only_update_visible_list, int *list_out, void *count_out, bool *publish_left) {
+                    const float *intr, int only_update_visible_list, int *list_out, void *count_out, bool *publish_left, FrontEndRecord *front_aux) {
   if (publish_left) *publish_left = false;
   const int W = v->w_d, H = v->h_d, N = s->n_entries;
   DSLAM_REQUIRE(r->n_entries == N, "render state was created for a different scene size");
@@ -1137,6 +1152,7 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
   sp.dbg = sweep_dump.arm(n_tiles, 64);
   sp.pend = PendingWrites{nullptr, nullptr, nullptr, nullptr, 0, 0};
   sp.err_word = nullptr;
+  sp.hidden_pos = e->hidden_pos;
   if (overlap_sweep) {
     // (never with swapping: `overlap` excludes it)
     sp.pend = PendingWrites{e->pend_count + 2 * (e->pend_pass & 1u), reinterpret_cast<u32x4 *>(e->pend_entry.get()), e->pend_entry_idx,
@@ -1147,6 +1163,22 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
     DSLAM_HIP(hipGetLastError());
     e->publish_due = true;
     e->sweep_overlapped++;
+    e->front_at_pass = false;
+    if (publish_left && front_aux && e->overlap_front && !e->front_behind_tail && e->sweep_done && front_aux->n_entries == N &&
+        front_aux->n_local == r->n_local && front_aux->w == r->w && front_aux->h == r->h) {
+      // GetImage's front end for this pose directly behind the sweep: it needs the table as the sweep leaves it
+      // -- the entries still on the pending lists it sees through hidden_pos -- and nothing of the fusion launch.  The event
+      // between the two, or the selection's own start, is what the held tail waits for.
+      if (e->sweep_done_by_event) {
+        DSLAM_HIP(hipEventRecord(e->sweep_done, e->aux_stream));
+        e->sweep_done_recorded = true;
+      } else {
+        if (++e->front_seq == 0) e->front_seq = 1;   // (0: no selection to hear of)
+        e->sweep_done_seq = e->front_seq;
+      }
+      DSLAM_TRY(launch_front_end_aux(e, s, r, M_d, intr, front_aux));
+      e->front_at_pass = true;
+    }
     if (publish_left) { *publish_left = true; return DSLAM_OK; }
     return finish_overlapped_allocate(e, s);
   }

@@ -103,11 +103,12 @@ int device_errors(dslam_engine *e) {
     return rc;
   }
   int *h = e->err_host;
-  if (!h || (__atomic_load_n(h, __ATOMIC_RELAXED) | __atomic_load_n(h + 1, __ATOMIC_RELAXED) | __atomic_load_n(h + 2, __ATOMIC_RELAXED)) == 0)
+  if (!h || (__atomic_load_n(h, __ATOMIC_RELAXED) | __atomic_load_n(h + 1, __ATOMIC_RELAXED) | __atomic_load_n(h + 2, __ATOMIC_RELAXED) |
+             __atomic_load_n(h + 3, __ATOMIC_RELAXED)) == 0)
     return DSLAM_OK;
   // (each taken in one step: a report that lands now is the next call's)
   const int flags = __atomic_exchange_n(h, 0, __ATOMIC_RELAXED) | __atomic_exchange_n(h + 1, 0, __ATOMIC_RELAXED) |
-                    __atomic_exchange_n(h + 2, 0, __ATOMIC_RELAXED);
+                    __atomic_exchange_n(h + 2, 0, __ATOMIC_RELAXED) | __atomic_exchange_n(h + 3, 0, __ATOMIC_RELAXED);
   if (flags == 0) return DSLAM_OK;
   if (flags & 2) {
     set_last_error("a tile count of an ordered compaction never arrived (device made no progress?): the map state is undefined");
@@ -122,13 +123,35 @@ int device_errors(dslam_engine *e) {
 // made them too), and the first failure waits in deferred_rc for the late-error path (device_errors).
 static void run_held_calls(void *engine) { (void)flush_deferred(static_cast<dslam_engine *>(engine)); }
 int flush_deferred(dslam_engine *e) {
-  if (!e || e->flushing || e->deferred.empty()) return DSLAM_OK;
+  if (!e || e->flushing) return DSLAM_OK;
+  if (e->deferred.empty()) {
+    // (a ProcessFrame that failed behind its launches holds no tail, but may have left a front end on aux_stream: DESIGN.md 4i)
+    if (e->front_pending) (void)settle_front(e);
+    return DSLAM_OK;
+  }
   e->flushing = true;
   e->stream.disarm();
   std::vector<std::function<int()>> bodies;
   bodies.swap(e->deferred);
   for (auto &body : bodies) {
-    const int rc = body();
+    int rc = body();
+    // A ProcessFrame's tail has left GetImage's front end on aux_stream.  The pipelined upload wants its copy
+    // enqueued here: behind the fusion launch, in front of the GetImage that sits the auxiliary stream out.
+    if (e->front_pending && e->after_tail) {
+      const std::function<void()> hook = std::move(e->after_tail);
+      e->after_tail = nullptr;
+      hook();
+    }
+    if (rc != DSLAM_OK && e->deferred_rc == DSLAM_OK) {
+      e->deferred_rc = rc;
+      e->deferred_error = g_last_error;
+    }
+  }
+  // ... and if no GetImage among the held calls waited for that front end, the thread does now: whatever comes next --
+  // Decay, SlideWindow, a reset, DeProcessFrame, a wait, the batch, the caller with the engine's stream in its hands --
+  // finds the record complete, never half-written, and the auxiliary stream empty.
+  if (e->front_pending) {
+    const int rc = settle_front(e);
     if (rc != DSLAM_OK && e->deferred_rc == DSLAM_OK) {
       e->deferred_rc = rc;
       e->deferred_error = g_last_error;
@@ -189,6 +212,7 @@ int ensure_scratch(dslam_engine *e, int entries, int local_blocks) {
   n.pend_cap = N < L ? N : L;
   DSLAM_TRY(n.pend_entry.alloc(n.pend_cap)); DSLAM_TRY(n.pend_entry_idx.alloc(n.pend_cap)); DSLAM_TRY(n.pend_offset.alloc(n.pend_cap));
   DSLAM_TRY(n.pend_count.alloc_zeroed(4, e->stream));
+  DSLAM_TRY(n.hidden_pos.alloc(N));
   DSLAM_TRY(n.tile_counts.alloc((size_t)tiles * 2)); DSLAM_TRY(n.tile_offsets.alloc((size_t)tiles * 2));
   const size_t list_len = (size_t)(N > L ? N : L);
   DSLAM_TRY(n.list_a.alloc(list_len)); DSLAM_TRY(n.list_b.alloc(list_len));
@@ -265,7 +289,7 @@ static int engine_allocate(dslam_engine *e) {
   DSLAM_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
   DSLAM_HIP(hipStreamCreateWithFlags(&e->aux_stream, hipStreamNonBlocking));
   DSLAM_TRY(e->start_stamp.alloc(16, hipHostMallocCoherent));
-  *e->start_stamp = 0;
+  e->start_stamp[0] = 0; e->start_stamp[1] = 0;   // ([1]: the start of the selection behind a sweep on aux_stream)
   e->pinned_bytes = 64 * 1024;
   DSLAM_TRY(e->pinned.alloc(e->pinned_bytes));
   memset(e->pinned, 0, e->pinned_bytes);
@@ -276,7 +300,8 @@ static int engine_allocate(dslam_engine *e) {
   e->ticket_base = 0;
   e->hip_failures_seen = hip_failure_count();
   DSLAM_TRY(e->err_host.alloc(16));
-  e->err_host[0] = 0; e->err_host[1] = 0; e->err_host[2] = 0;
+  DSLAM_TRY(e->sweep_done.create());
+  e->err_host[0] = 0; e->err_host[1] = 0; e->err_host[2] = 0; e->err_host[3] = 0;
   return DSLAM_OK;
 }
 
@@ -319,6 +344,10 @@ int dslam_engine_create(int device_index, dslam_engine **out) {
   if (const char *v = getenv("DSLAM_OVERLAP_MARK")) e->overlap_mark = atoi(v) != 0;
   if (const char *v = getenv("DSLAM_OVERLAP_SWEEP")) e->overlap_sweep = atoi(v) != 0;
   if (!e->overlap_mark) e->overlap_sweep = false;
+  if (const char *v = getenv("DSLAM_OVERLAP_FRONT")) e->overlap_front = atoi(v) != 0;
+  if (!e->overlap_sweep) e->overlap_front = false;
+  if (const char *v = getenv("DSLAM_FRONT_BEHIND_TAIL")) e->front_behind_tail = atoi(v) != 0;
+  if (const char *v = getenv("DSLAM_SWEEP_DONE_EVENT")) e->sweep_done_by_event = atoi(v) != 0;
   const int rc = engine_allocate(e);
   if (rc) {
     (void)dslam_engine_destroy(e);
@@ -405,6 +434,13 @@ int dslam_debug_sweep_overlap_counts(dslam_engine *e, long long *overlapped_out,
   DSLAM_REQUIRE(e && overlapped_out && in_stream_out, "null argument");
   *overlapped_out = e->sweep_overlapped;
   *in_stream_out = e->sweep_in_stream;
+  return DSLAM_OK;
+}
+int dslam_debug_front_overlap_counts(dslam_engine *e, long long *on_aux_out, long long *in_launch_out) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && on_aux_out && in_launch_out, "null argument");
+  *on_aux_out = e->front_on_aux;
+  *in_launch_out = e->front_in_launch;
   return DSLAM_OK;
 }
 int dslam_debug_icp_sums(dslam_engine *e, double out[29]) {
@@ -910,24 +946,49 @@ static int upload_view_pipelined(dslam_engine *e, dslam_view *v, const uint8_t *
   // the auxiliary stream's pass is over -- beside that pass (k_mark above all) it lengthens the march, measured.
   // DSLAM_COPY_BEFORE_HELD_CALLS=1, a measurement's switch, enqueues the copy first and runs the held calls while it is in
   // flight (the thread sits out the upload and the auxiliary stream together; 3 % slower on the bench).
+  // (Where the held tail leaves GetImage's front end on the auxiliary stream the copy goes BETWEEN the held calls: below.)
   // Either way the copy's target must be free.  The event that says so sits behind the previous GetImage's march; the stamp
   // the last allocation pass saw arrive proves the same earlier (every kernel that read a view and was called for by then
   // is complete), so in the steady state nobody waits for the march here.
   static const bool copy_first = getenv("DSLAM_COPY_BEFORE_HELD_CALLS") && atoi(getenv("DSLAM_COPY_BEFORE_HELD_CALLS")) != 0;
-  if (stream_waits || !copy_first) flush_deferred(e);
-  if (v->up_used[b] && v->up_reads[b] > e->view_reads_done) {
-    if (stream_waits) {
-      DSLAM_HIP(hipStreamWaitEvent(e->copy_stream, v->up_consumed_by[b], 0));
+  auto enqueue_copy = [&]() -> int {
+    if (reinterpret_cast<const uint8_t *>(depth_host) == rgba_host + c_bytes) {
+      DSLAM_HIP(hipMemcpyAsync(v->up_rgba[b], rgba_host, c_bytes + d_bytes, hipMemcpyHostToDevice, e->copy_stream));
     } else {
-      flush_deferred(e);   // (the GPU is never kept waiting for the thread's wait)
-      DSLAM_HIP(hipEventSynchronize(v->up_consumed_by[b]));
+      DSLAM_HIP(hipMemcpyAsync(v->up_rgba[b], rgba_host, c_bytes, hipMemcpyHostToDevice, e->copy_stream));
+      DSLAM_HIP(hipMemcpyAsync(v->up_raw[b], depth_host, d_bytes, hipMemcpyHostToDevice, e->copy_stream));
     }
+    return DSLAM_OK;
+  };
+  // Where the held ProcessFrame's tail leaves GetImage's front end on aux_stream, the copy is enqueued right
+  // behind that tail -- the fusion launch is enqueued, k_mark and the sweep are over -- and the held GetImage sits out the
+  // auxiliary stream and enqueues its march and the fence record while the copy is in flight.  Only if the target is known to
+  // be free without a wait (the stamp's proof, above); otherwise, and on every other path, the copy follows the held calls.
+  // DSLAM_COPY_BEHIND_HELD_CALLS=1, a measurement's switch, keeps it behind them always.
+  static const bool copy_behind = getenv("DSLAM_COPY_BEHIND_HELD_CALLS") && atoi(getenv("DSLAM_COPY_BEHIND_HELD_CALLS")) != 0;
+  bool copied = false;
+  int copy_rc = DSLAM_OK;
+  if (stream_waits || !copy_first) {
+    if (!stream_waits && !copy_behind)
+      e->after_tail = [&]() {
+        if (v->up_used[b] && v->up_reads[b] > e->view_reads_done) return;
+        copy_rc = enqueue_copy();
+        copied = true;
+      };
+    flush_deferred(e);
+    e->after_tail = nullptr;
   }
-  if (reinterpret_cast<const uint8_t *>(depth_host) == rgba_host + c_bytes) {
-    DSLAM_HIP(hipMemcpyAsync(v->up_rgba[b], rgba_host, c_bytes + d_bytes, hipMemcpyHostToDevice, e->copy_stream));
-  } else {
-    DSLAM_HIP(hipMemcpyAsync(v->up_rgba[b], rgba_host, c_bytes, hipMemcpyHostToDevice, e->copy_stream));
-    DSLAM_HIP(hipMemcpyAsync(v->up_raw[b], depth_host, d_bytes, hipMemcpyHostToDevice, e->copy_stream));
+  if (copy_rc) return copy_rc;
+  if (!copied) {
+    if (v->up_used[b] && v->up_reads[b] > e->view_reads_done) {
+      if (stream_waits) {
+        DSLAM_HIP(hipStreamWaitEvent(e->copy_stream, v->up_consumed_by[b], 0));
+      } else {
+        flush_deferred(e);   // (the GPU is never kept waiting for the thread's wait)
+        DSLAM_HIP(hipEventSynchronize(v->up_consumed_by[b]));
+      }
+    }
+    DSLAM_TRY(enqueue_copy());
   }
   flush_deferred(e);   // (copy_first: now)
   // The other buffer's "consumed" mark, behind the held calls: the fusion launch that reads that buffer and the caller's
@@ -1498,9 +1559,14 @@ struct FrameTail {
 int frame_tail(const FrameTail &t) {
   dslam_engine *e = t.e;
   int rc;
+  // The sweep of this pass ran on aux_stream (4h) and the engine may put the front end there as well (4i): the fusion launch
+  // is then the plain one.  Only as a held call: flush_deferred sees to it that the front end is waited for.
+  // Either the pass launched it behind its sweep (front_at_pass), or -- the measurement's order -- it goes behind this launch.
+  const int front_on_aux = !(e->overlap_front && e->publish_due && e->flushing && t.front != nullptr) ? 0 : e->front_at_pass ? 2 : 1;
+  e->front_at_pass = false;
   if ((rc = finish_overlapped_allocate(e, t.s))) return rc;
   if ((rc = launch_integrate(e, t.s, t.v, t.r, t.M_d, t.intr_d, t.has_M_rgb ? t.M_rgb : nullptr, t.has_intr_rgb ? t.intr_rgb : nullptr, false,
-                             t.is_defusion, t.front)))
+                             t.is_defusion, t.front, front_on_aux)))
     return rc;
   if (t.front && t.front->valid) {
     t.front->version = t.version;
@@ -1528,7 +1594,7 @@ int dslam_process_frame(dslam_engine *e, dslam_scene *s, const dslam_view *v, ds
   if (s->front) s->front->valid = false;
   if (e->speculate_front && !s->p.use_swapping && r->n_entries == s->n_entries && (rc = front_end_for(e, s, r, &front))) return rc;
   bool publish_left = false;
-  if ((rc = launch_allocate(e, s, v, r, M_d, intr_d, only_visible, nullptr, nullptr, &publish_left))) return rc;
+  if ((rc = launch_allocate(e, s, v, r, M_d, intr_d, only_visible, nullptr, nullptr, &publish_left, front))) return rc;
   FrameTail tail{e, s, v, r, {}, {}, {}, {}, M_rgb != nullptr, intr_rgb != nullptr, is_defusion ? 1 : 0, front, s->version};
   memcpy(tail.M_d, M_d, sizeof(tail.M_d));
   memcpy(tail.intr_d, intr_d, sizeof(tail.intr_d));

@@ -60,6 +60,10 @@ struct TileChain {
   unsigned ticket_base;
   int n_tiles;
   unsigned long long *dbg;   // diagnostics (DSLAM_DBG_SELECT=<file>): 8 timestamps per tile
+  int *err_word;             // non-null: the launch may run beside another kernel of its engine and reports through this
+                             // page-locked word of its own (report_error_own); null: report_error
+  unsigned *start_word;      // non-null: a page-locked word that hears of the launch's START (start_value), as the engine's
+  unsigned start_value;      // start stamp does: a stream runs its launches in order, so what was enqueued in front is complete
 };
 
 // single-channel look-back: a 32-bit count per tile ({epoch, count} in one word); bounded spin
@@ -96,6 +100,8 @@ static __device__ __forceinline__ void publish1(unsigned long long *agg, int til
 inline TileChain next_chain(dslam_engine *e, int n_tiles, int *grid_out, bool second = false) {
   TileChain ch;
   ch.dbg = nullptr;
+  ch.err_word = nullptr;
+  ch.start_word = nullptr; ch.start_value = 0;
   (void)tickets_ok(e);   // (after a HIP failure anywhere in the process: bases re-read from the device)
   if (++e->epoch == 0) e->epoch = 1;
   ch.agg = second ? e->agg + e->agg_tiles : e->agg;
@@ -148,6 +154,8 @@ __device__ __forceinline__ void bits_select_tile(const unsigned *__restrict__ sr
   constexpr int kTileEntries = SelLds::kTileEntries;
   constexpr int kRounds = (kTileEntries + kSelThreads * BATCH - 1) / (kSelThreads * BATCH);
   const unsigned long long t_start = ch.dbg ? __builtin_amdgcn_s_memtime() : 0ull;
+  if (ch.start_word && blockIdx.x == 0 && threadIdx.x == 0)
+    __hip_atomic_store(ch.start_word, ch.start_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   const int b = take_ticket(ch.ticket, ch.ticket_base, s_ticket);
   if ((unsigned)b >= (unsigned)ch.n_tiles) return;   // (unsigned: a ticket in front of the host's base must not index anything)
 #define DSLAM_SEL_STAMP(i) do { if (ch.dbg && threadIdx.x == 0) ch.dbg[(size_t)b * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -232,7 +240,10 @@ __device__ __forceinline__ void bits_select_tile(const unsigned *__restrict__ sr
     }
   }
   int before;
-  if (!lookback1<kSelThreads>(ch.agg, b, ch.epoch, red, before) && tid == 0 && err_cnt) report_error(err_cnt, 2);
+  if (!lookback1<kSelThreads>(ch.agg, b, ch.epoch, red, before) && tid == 0 && err_cnt) {
+    if (ch.err_word) report_error_own(err_cnt, ch.err_word, 2);
+    else report_error(err_cnt, 2);
+  }
   DSLAM_SEL_STAMP(6);
   // ---- emit -----------------------------------------------------------------------------------------------------------------
   int sum = 0;

@@ -86,6 +86,10 @@ struct EngineScratch {
   DeviceBuffer<int2> pend_offset;        // [pend_cap] {entry, its new offset field}
   DeviceBuffer<unsigned> pend_count;     // [4], all zero between passes
   int pend_cap = 0;
+  // ... and, by table entry, the block position of every entry such a sweep creates (bucket and excess alike): what a
+  // selection that runs before k_publish_entries reads in place of the still empty table entry.  Only the
+  // slots of entries created by the pass in flight mean anything.
+  DeviceBuffer<short4> hidden_pos;       // [entries]
   DeviceBuffer<int> list_d;              // [max(local_blocks, entries)] general purpose scratch (bucket leaders, live flags)
   // release pipeline (decay / sliding window): flags that are ALL ZERO between passes (the kernels that consume a flag
   // clear it), so no pass starts with a memset
@@ -219,8 +223,8 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   int device = 0;
   EngineStream stream;
   // k_mark beside the previous GetImage's march; DSLAM_OVERLAP_MARK=0 turns it off
-  hipStream_t aux_stream = nullptr;   // holds nothing but that k_mark and, behind it, the pass' deferring sweep (4h); the host waits
-                                      // for it before anything that reads what they wrote is enqueued
+  hipStream_t aux_stream = nullptr;   // holds nothing but that k_mark and, behind it, the pass' deferring sweep (4h) and GetImage's front
+                                      // end for the pass' pose (4i); the host waits for it before anything that reads what they wrote is enqueued
   bool overlap_mark = true;
   bool stream_lent = false;           // dslam_engine_stream handed the compute stream out: the caller may order its own work by it
   PinnedBuffer<unsigned> start_stamp; // page-locked, fine-grained: the stamp of the last stamped range pass that has STARTED
@@ -232,6 +236,28 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   long long sweep_overlapped = 0, sweep_in_stream = 0;   // (test hook)
   unsigned pend_pass = 0;             // overlapped sweeps so far: which pair of pend_count the next one appends through
   bool publish_due = false;           // aux_stream holds a deferring sweep whose k_publish_entries is not enqueued yet
+  // ... and behind the sweep GetImage's front end for the pass' pose -- selection and range pass -- on aux_stream as well,
+  // beside the publish kernel and the plain fusion launch; DSLAM_OVERLAP_FRONT=0 keeps it in the fusion launch
+  bool overlap_front = true;
+  long long front_on_aux = 0, front_in_launch = 0;   // front ends computed on aux_stream / in the fusion launch (test hook)
+  bool front_pending = false;         // aux_stream holds such a front end the host has not waited for yet (settle_front)
+  // Host order ("Host order"): the front end is launched at ProcessFrame time directly behind the sweep, and the
+  // held tail waits for the sweep alone, not for the whole stream, so that the publish kernel and the fusion launch are
+  // enqueued as soon as the sweep is complete.  What tells it is the selection's own start: one lane stores the pass' number
+  // into start_stamp[1] (a stream runs its launches in order), and the host polls the word as it polls the start stamp.
+  // DSLAM_SWEEP_DONE_EVENT=1, a measurement's switch, records an event between the two kernels and waits for that instead.
+  // DSLAM_FRONT_BEHIND_TAIL=1, another, launches the front end from the tail, behind the fusion launch (the order that lost).
+  bool front_behind_tail = false;
+  bool sweep_done_by_event = false;
+  Event sweep_done;
+  bool sweep_done_recorded = false;   // the sweep in flight has sweep_done behind it (the event, or:)
+  unsigned sweep_done_seq = 0;        // ... the value start_stamp[1] takes when the selection behind the sweep has started (0: none)
+  unsigned front_seq = 0;             // front ends launched behind a sweep so far
+  bool front_at_pass = false;         // the pass in flight launched its front end itself (frame_tail: nothing left to launch)
+  bool stamp_due = false;             // GetImage adopted a complete record: its march carries the start stamp (raycast.hip)
+  // The pipelined upload enqueues its copy between the held calls: behind a ProcessFrame tail that left a front end on
+  // aux_stream, in front of the GetImage that has to sit that stream out (capi.hip upload_view_pipelined).  Called once.
+  std::function<void()> after_tail;
   // Calls whose body the caller's thread runs later: the tail of a ProcessFrame whose sweep runs on aux_stream,
   // and a GetImage / fence record behind it.  Run in order by flush_deferred() -- from the pipelined upload while its copy is
   // in flight, and otherwise by whatever touches the engine next (every entry point; EngineStream as the backstop).
@@ -332,10 +358,12 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
 
 // GetImage's front end for the pose of the last ProcessFrame: FindVisibleBlocks with the projections of its blocks and a reset
 // range image, computed by workgroups at the front of that ProcessFrame's fusion launch (they read the table, not the
-// voxels).  A GetImage of the same scene version, pose, intrinsics and image size adopts the buffers -- their pointers
-// are exchanged with the render state's -- and runs only the range pass and the march (raycast.hip).
+// voxels) -- or, where the pass' sweep ran on aux_stream, behind that sweep with the range pass as well.
+// A GetImage of the same scene version, pose, intrinsics and image size adopts the buffers -- their pointers are exchanged
+// with the render state's -- and runs only the range pass and the march, or the march alone (raycast.hip).
 struct FrontEndRecord {
   bool valid = false;
+  bool range_filled = false;          // computed on aux_stream, range pass included: GetImage runs the march alone
   unsigned long long version = 0;     // the scene's version after the ProcessFrame
   float M[16] = {0}, intr[4] = {0};
   int w = 0, h = 0, n_local = 0, n_entries = 0;   // the sizes of the buffers (= those of the render states they may go to)
@@ -629,7 +657,9 @@ int launch_depth_post(dslam_engine *e, short *curr_dev, const unsigned short *pr
 // types follow the pass either way; the re-integration batch keeps the lists of all its passes)
 int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_render_state *r, const float *M_d,
                     const float *intr, int only_update_visible_list, int *list_out = nullptr, void *count_out = nullptr,
-                    bool *publish_left = nullptr);
+                    bool *publish_left = nullptr, FrontEndRecord *front_aux = nullptr);
+// (front_aux: where the sweep goes to aux_stream and the caller finishes the pass later, GetImage's front end for this pose
+// follows the sweep there, into this record -- DESIGN.md 4i; dslam_engine::front_at_pass says whether it did)
 // (publish_left: the caller finishes an overlapped pass itself, later -- finish_overlapped_allocate -- and learns here
 // whether there is one to finish; null: launch_allocate does before it returns)
 // push_ring >= 0: also queue the frame's visible list on that ring (fused into the integrate kernel)
@@ -637,7 +667,9 @@ int launch_allocate(dslam_engine *e, dslam_scene *s, const dslam_view *v, dslam_
 // runs the plain one-camera kernel (front->valid says whether it did; its buffers are sized for r beforehand)
 int launch_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, const dslam_render_state *r,
                      const float *M_d, const float *intr_d, const float *M_rgb, const float *intr_rgb,
-                     bool deintegrate, int push_ring = -1, FrontEndRecord *front = nullptr);
+                     bool deintegrate, int push_ring = -1, FrontEndRecord *front = nullptr, int front_on_aux = 0);
+// (front_on_aux, DESIGN.md 4i: the front end belongs on aux_stream behind the pass' deferring sweep and the fusion launch
+// stays the plain one -- 1: launch it there now, behind this launch (launch_front_end_aux); 2: the pass has launched it)
 // the same kernel over a stored list (count header, ids, expected block positions) instead of a render state's
 int launch_integrate_list(dslam_engine *e, dslam_scene *s, const dslam_view *v, const void *count_header, const int *ids,
                           const short4 *expect_pos, const float *M_d, const float *intr_d, const float *M_rgb,
@@ -749,6 +781,11 @@ int finish_call(dslam_engine *e);  // synchronise unless the engine is in async 
 int flush_deferred(dslam_engine *e);   // run the calls the engine holds back (dslam_engine::deferred), in order; failures are kept for device_errors()
 void defer_call(dslam_engine *e, std::function<int()> body);
 int finish_overlapped_allocate(dslam_engine *e, dslam_scene *s);   // alloc.hip: wait for aux_stream, enqueue k_publish_entries
+// raycast.hip: GetImage's front end for (M, intr, r's image size) into `front` on aux_stream -- selection over alloc_bits that
+// sees the entries the deferring sweep created (hidden_pos), then the range pass -- and the wait that ends it
+int launch_front_end_aux(dslam_engine *e, const dslam_scene *s, const dslam_render_state *r, const float *M, const float *intr,
+                         FrontEndRecord *front);
+int settle_front(dslam_engine *e);
 int device_errors(dslam_engine *e);  // report (once) what kernels left in dslam_engine::err_host
 int sync_check(dslam_engine *e);   // wait for the engine's stream, then report what kernels left in dslam_engine::err_host
 // The host advances its copy of the ticket counters when it enqueues a launch.  A launch the runtime rejected never moves the

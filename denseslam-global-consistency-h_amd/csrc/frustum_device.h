@@ -72,7 +72,14 @@ __device__ __forceinline__ int project_single_block(const HashEntry &e, const Pr
 // PROJECT: the lane that lists visible entry number r also projects it (CreateExpectedDepths' ProjectSingleBlock; GetImage
 // runs both with one pose), the compaction launch resets the range image, and every compaction tile leaves its
 // render-tile total for k_fill_range_tiles.
-template <bool PROJECT>
+// HIDDEN: the selection runs on the auxiliary stream behind a deferring allocation sweep whose table stores k_publish_entries
+// has not scattered yet.  The sweep has set alloc_bits for the entries it created and left their positions in
+// hidden_pos.  A selection only loads entries whose bit is set, and without swapping a set bit over a table entry that is
+// still empty (ptr < 0) can only mean "created by this pass": every other path that sets the bit stores the entry in the same
+// launch, and every path that empties an entry clears the bit.  Such an entry is taken as resident at its hidden position; the
+// slot is not known yet and nothing here reads it (test and project_single_block look at the sign of ptr alone).  An entry
+// the publish kernel has already stored carries the same position in the table.  Scenes with swapping never take this path.
+template <bool PROJECT, bool HIDDEN = false>
 struct SelFrustum {
   const HashEntry *hash;
   FrustumParams fp;
@@ -81,12 +88,23 @@ struct SelFrustum {
   int *req_out;
   float2 *range;
   int npix;
+  const short4 *hidden_pos = nullptr;   // (HIDDEN only)
   __device__ void prologue() const {
     if (PROJECT)   // (independent job) reset the range image to (FAR_AWAY, VERY_CLOSE)
       for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) range[i] = make_float2(kFarAway, kVeryClose);
   }
   typedef HashEntry Payload;
-  __device__ HashEntry load(int t) const { return load_entry(hash, t); }
+  __device__ HashEntry load(int t) const {
+    HashEntry e = load_entry(hash, t);
+    if constexpr (HIDDEN) {
+      if (e.ptr < 0) {
+        const short4 p = hidden_pos[t];
+        e.pos[0] = p.x; e.pos[1] = p.y; e.pos[2] = p.z;
+        e.ptr = 0;
+      }
+    }
+    return e;
+  }
   __device__ bool test(int, const HashEntry &e) const {
     if (e.ptr < 0) return false;
     bool vis, vis_enl;

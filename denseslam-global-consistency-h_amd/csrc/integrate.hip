@@ -1033,7 +1033,7 @@ static int launch_integrate_params(dslam_engine *e, IntegrateParams &ip, bool de
 
 int launch_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, const dslam_render_state *r,
                      const float *M_d, const float *intr_d, const float *M_rgb, const float *intr_rgb,
-                     bool deintegrate, int push_ring, FrontEndRecord *front) {
+                     bool deintegrate, int push_ring, FrontEndRecord *front, int front_on_aux) {
   int rc = ensure_view_depth(e, v);
   if (rc) return rc;
   IntegrateParams ip;
@@ -1049,9 +1049,13 @@ int launch_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, const
   // a streaming launch is hundreds of microseconds long and the selection's 12 us do not matter there.  (Not with the
   // per-wave timeline of DSLAM_DBG_INTEGRATE either: that launch is the plain kernel alone.)
   static const bool dbg_integrate = getenv("DSLAM_DBG_INTEGRATE") != nullptr;
-  if (front) front->valid = false;
-  if (front && !deintegrate && plain_fusion(ip) && !stream && !dbg_integrate && r->n_entries == s->n_entries &&
-      front->n_entries == s->n_entries && front->n_local == r->n_local && front->w == r->w && front->h == r->h) {
+  if (front && front_on_aux != 2) { front->valid = false; front->range_filled = false; }
+  const bool wants_front = front && !deintegrate && plain_fusion(ip) && !stream && !dbg_integrate && r->n_entries == s->n_entries &&
+                           front->n_entries == s->n_entries && front->n_local == r->n_local && front->w == r->w && front->h == r->h;
+  // Where the pass' sweep ran on aux_stream the front end follows it there, beside this launch (below), and the launch is
+  // the plain one.
+  const bool aux_front = wants_front && front_on_aux == 1;
+  if (wants_front && front_on_aux == 0) {
     if ((rc = ensure_scratch(e, s->n_entries, s->p.num_local_blocks))) return rc;
     int grid;
     const TileChain ch = next_chain(e, select_tiles(s->n_entries), &grid);
@@ -1063,8 +1067,16 @@ int launch_integrate(dslam_engine *e, dslam_scene *s, const dslam_view *v, const
     ip.fe.total_out = &front->counters->no_visible; ip.fe.tile_sum_out = front->proj_wg_tiles; ip.fe.ch = ch;
     ip.fe.err_cnt = s->counters; ip.fe.wgs = grid;
     front->valid = true;
+    e->front_in_launch++;
   }
-  return launch_integrate_params(e, ip, deintegrate, stream);
+  if ((rc = launch_integrate_params(e, ip, deintegrate, stream))) return rc;
+  if (aux_front && (rc = launch_front_end_aux(e, s, r, M_d, intr_d, front))) return rc;
+  if (aux_front || (front && front_on_aux == 2)) {
+    front->valid = true;
+    e->front_launches++;   // (a front end computed, wherever: dslam_debug_front_end_counts)
+    e->front_on_aux++;
+  }
+  return DSLAM_OK;
 }
 
 int launch_integrate_list(dslam_engine *e, dslam_scene *s, const dslam_view *v, const void *count_header, const int *ids,

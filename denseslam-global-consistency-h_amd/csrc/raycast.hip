@@ -281,6 +281,9 @@ int launch_find_visible_and_depths(dslam_engine *e, const dslam_scene *s, dslam_
   DSLAM_REQUIRE(r->n_entries == N, "render state was created for a different scene size");
   int rc = ensure_scratch(e, N, s->p.num_local_blocks);
   if (rc) return rc;
+  // A front end still in flight on aux_stream is sat out first, adopted or not: the range image must be
+  // complete before the march is enqueued, and a selection of this call's own would share the per-tile words with it.
+  DSLAM_TRY(settle_front(e));
   // The last ProcessFrame computed this selection already (FrontEndRecord): same map, pose, intrinsics and image size.  The
   // render state takes its buffers -- the list, its count, the projections, the per-tile totals, the reset range image --
   // and gives its own in exchange (the same sizes), all on the engine's one stream.
@@ -296,6 +299,14 @@ int launch_find_visible_and_depths(dslam_engine *e, const dslam_scene *s, dslam_
       std::swap(r->range, f->range);
       f->valid = false;
       e->front_adoptions++;
+      if (f->range_filled) {
+        // A complete record: the range image the render state just took was filled on aux_stream.  The march
+        // may only be enqueued once that stream has drained (settle_front above), and it carries the start stamp, as the
+        // first kernel this call puts on the engine stream behind the fusion launch.
+        f->range_filled = false;
+        e->stamp_due = true;
+        return DSLAM_OK;
+      }
       return launch_fill_range(e, r, select_tiles(N), true);
     }
   }
@@ -305,12 +316,61 @@ int launch_find_visible_and_depths(dslam_engine *e, const dslam_scene *s, dslam_
 }
 
 
+// GetImage's front end for the pose of a ProcessFrame whose sweep ran on aux_stream: the same k_bits_select
+// over alloc_bits as above (4 entries per lane) and the same range pass, into the scene's FrontEndRecord, on aux_stream behind
+// that sweep -- beside k_publish_entries and the plain fusion launch, which the engine stream holds.  The selection reads the
+// table but sees the entries the sweep created through hidden_pos (SelFrustum<true, true>); nothing here writes the table.
+// Tickets come from the auxiliary stream's word (ticket + 2), errors go to a page-locked word of the selection's own
+// (err_host[3]); the range pass carries no stamp.  The host waits for the stream in settle_front.
+int launch_front_end_aux(dslam_engine *e, const dslam_scene *s, const dslam_render_state *r, const float *M, const float *intr,
+                         FrontEndRecord *f) {
+  const int N = s->n_entries;
+  DSLAM_TRY(ensure_scratch(e, N, s->p.num_local_blocks));
+  SelFrustum<true, true> sel{s->hash, make_frustum_params(s, r, M, intr), f->proj_boxes, f->proj_z, f->proj_req, f->range, r->w * r->h,
+                             e->hidden_pos};
+  const int n_tiles = select_tiles(N);
+  TileChain ch;
+  (void)tickets_ok(e);
+  if (++e->epoch == 0) e->epoch = 1;
+  ch.agg = e->agg + 2 * (size_t)e->agg_tiles;   // (the third channel: no launch of the engine stream publishes through it)
+  ch.epoch = e->epoch;
+  ch.ticket = e->ticket + 2; ch.ticket_base = e->ticket_base3;
+  ch.n_tiles = n_tiles;
+  ch.dbg = nullptr;
+  ch.err_word = e->err_host ? e->err_host.get() + 3 : nullptr;
+  ch.start_word = e->sweep_done_seq ? e->start_stamp.get() + 1 : nullptr;   // (the held tail waits for the sweep in front: alloc.hip)
+  ch.start_value = e->sweep_done_seq;
+  const int grid = n_tiles > 0 ? n_tiles : 1;
+  e->ticket_base3 += (unsigned)grid;
+  hipLaunchKernelGGL((k_bits_select<SelFrustum<true, true>>), dim3(grid), dim3(kSelThreads), 0, e->aux_stream, s->alloc_bits.get(), sel,
+                     f->visible_ids.get(), r->n_local, &f->counters->no_visible, f->proj_wg_tiles.get(), ch, s->counters.get());
+  DSLAM_HIP(hipGetLastError());
+  const int cw = (r->w + 7) / 8, chh = (r->h + 7) / 8;
+  const int tiles_x = (cw + kRangeTile - 1) / kRangeTile, tiles_y = (chh + kRangeTile - 1) / kRangeTile;
+  hipLaunchKernelGGL(k_fill_range_tiles, dim3(tiles_x * tiles_y, kRangeSlices), dim3(256), 0, e->aux_stream, f->counters.get(),
+                     f->proj_boxes.get(), f->proj_z.get(), f->proj_req.get(), f->range.get(), r->w, tiles_x, f->proj_wg_tiles.get(), n_tiles,
+                     e->render_tile_budget, r->n_local, (unsigned *)nullptr, 0u);
+  DSLAM_HIP(hipGetLastError());
+  e->front_pending = true;
+  f->range_filled = true;
+  return DSLAM_OK;
+}
+
+int settle_front(dslam_engine *e) {
+  if (!e->front_pending) return DSLAM_OK;
+  e->front_pending = false;
+  DSLAM_HIP(hipStreamSynchronize(e->aux_stream));
+  return DSLAM_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // castRay + shading, one kernel
 // ---------------------------------------------------------------------------------------------------------
 struct RenderParams {
   VolumeRef vol;
   RayCamera cam;
+  unsigned *start_stamp;   // non-null: the march of a GetImage that adopted a complete front-end record -- the
+  unsigned stamp;          // first kernel of the call on the engine stream, so IT tells the host that it has started
   unsigned long long *dbg_waves;  // diagnostics only (env DSLAM_DBG_WAVETIME=<file>): per wave {cycles, max iterations, straddling iterations, their cycles, setup cycles, refinement cycles}
   float split_len;  // > 0: tiles with a longer depth range (voxels) are marched by two wavefronts; the grid is (W/8, 2 H/8)
 };
@@ -425,6 +485,9 @@ __device__ __forceinline__ bool cast_ray(Vec4 &out, int x, int y, const RenderPa
 template <bool SHADE, bool DIAG = false, bool REUSE = false>
 __global__ __launch_bounds__(64, 5) void k_render(RenderParams rp) {
   const RayCamera &p = rp.cam;
+  // (what the stamp proves is what it proved on the range pass, DESIGN.md 4g: everything enqueued in front of this launch is complete)
+  if (rp.start_stamp && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
+    __hip_atomic_store(rp.start_stamp, rp.stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   // one wavefront = one workgroup = an 8x8 pixel tile = exactly one cell of the 1/8-resolution range image.
   // Single-wave workgroups let the dispatcher backfill a SIMD the moment a short tile finishes (ray lengths vary
   // by 10x between tiles), instead of holding 4 waves until the slowest of a 16x16 tile is done.
@@ -507,6 +570,7 @@ static int fill_render_params(RenderParams &rp, const dslam_scene *s, dslam_rend
   rp.vol.num_buckets = s->p.num_buckets;
   DSLAM_TRY(fill_ray_camera(rp.cam, s, r, M, intr, type, image_out_override));
   rp.dbg_waves = nullptr; rp.split_len = 0.0f;
+  rp.start_stamp = nullptr; rp.stamp = 0;
   return DSLAM_OK;
 }
 
@@ -523,6 +587,15 @@ int launch_render(dslam_engine *e, const dslam_scene *s, dslam_render_state *r, 
   static DiagDump dump("DSLAM_DBG_WAVETIME", 30);
   rp.dbg_waves = dump.arm((size_t)((r->w + 7) / 8) * ((r->h + 7) / 8) * 2, 48);   // (6 words per wavefront of the split grid)
   const dim3 grid1 = march_grid(rp, r, !reuse_raycast);
+  if (e->stamp_due) {   // (set by the adoption of a complete record in this very GetImage: launch_find_visible_and_depths)
+    e->stamp_due = false;
+    if (e->overlap_mark && e->async_mode) {
+      rp.start_stamp = e->start_stamp;
+      if (++e->stamp_seq == 0) e->stamp_seq = 1;
+      rp.stamp = e->stamp_seq;
+      e->stamp_view_reads = e->view_reads;   // (as launch_fill_range: every call that read a view so far has its kernels in front)
+    }
+  }
   if (reuse_raycast) {
     if (type == DSLAM_IMAGE_DEPTH || type < 0) hipLaunchKernelGGL((k_render<false, false, true>), grid1, dim3(64), 0, e->stream, rp);
     else hipLaunchKernelGGL((k_render<true, false, true>), grid1, dim3(64), 0, e->stream, rp);

@@ -221,6 +221,13 @@ int dslam_debug_mark_overlap_counts(dslam_engine *e, long long *overlapped_out, 
  * the next dslam_view_update (while its copy is in flight) or by whatever other call touches the engine next.  Both ways
  * compute the same bytes. */
 int dslam_debug_sweep_overlap_counts(dslam_engine *e, long long *overlapped_out, long long *in_stream_out);
+/* Test hook: of the front ends dslam_debug_front_end_counts reports as computed, how many ran on the engine's auxiliary stream
+ * behind such a sweep -- the selection and the range pass both, beside the fusion launch, so that a dslam_get_image that takes
+ * the result runs the ray march alone -- and how many ran inside the fusion launch.  The first way is taken by a
+ * dslam_process_frame whose sweep took the auxiliary stream (above) and that computes a front end at all;
+ * DSLAM_OVERLAP_FRONT=0 in the environment of dslam_engine_create selects the second way always, and so do
+ * DSLAM_OVERLAP_SWEEP=0 and DSLAM_OVERLAP_MARK=0.  Both ways compute the same bytes. */
+int dslam_debug_front_overlap_counts(dslam_engine *e, long long *on_aux_out, long long *in_launch_out);
 /* Test hook: a one-thread kernel reports the given device-side error bits for the scene (1: allocation ray longer than the
  * order key encodes, 2: a tile count never arrived) exactly as a failing pass would (report_error, csrc/dslam_device.h), so
  * that the way such an error reaches the caller can be tested: returned by this very call on a synchronous engine, by the
