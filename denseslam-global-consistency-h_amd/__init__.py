@@ -13,7 +13,8 @@ import subprocess
 from ._capi import (BLOCK_SIZE3, HASH_ENTRY_DTYPE, IMAGE_COLOUR_FROM_NORMAL, IMAGE_COLOUR_FROM_VOLUME, IMAGE_DEPTH,
                     IMAGE_SHADED, MAX_REGISTER_PAIRS, MAX_RENDER_MAPS, MAX_SURVEY_MAPS, MAX_SURVEY_VIEWS, VOXEL_DTYPE, CApi, DslamError, MergeParams, MergeResult, PackInfo,
                     MAX_TRACK_STARTS, PoseLattice, PoseScore, PairSelectParams, PairSelectResult, RegisterGraphResult, RegisterPairResult, RegisterParams, RegisterResult,
-                    SceneParams, Stats, SurveyView, TrackerParams, TrackerResult, TrackSdfParams, TrackSdfResult, UnmergeParams,
+                    SceneParams, Stats, SurveyView, TrackerParams, TrackerResult, TrackSdfParams, TrackSdfResult, TrackSdfRgbParams,
+                    TrackSdfRgbResult, UnmergeParams,
                     UnmergeResult, ViewSelectParams, ViewSelectResult, ViewSurveyParams, WeightParams, mat_to_abi,
                     FERN_CODE_DWORDS, FERN_MATCH_DTYPE, FERN_MAX_MATCHES, FERN_MAX_QUERIES, FernMatch, FernParams)
 

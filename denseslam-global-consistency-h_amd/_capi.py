@@ -79,6 +79,28 @@ class TrackSdfResult(C.Structure):
 assert C.sizeof(TrackSdfParams) == 32 and C.sizeof(TrackSdfResult) == 32  # the header's layouts
 
 
+class TrackSdfRgbParams(C.Structure):
+    """dslam_track_sdf_rgb_params: dslam_track_sdf_params (its fields are this constructor's too) and the photometric
+    term's colour_weight (0 -> 1), colour_gate (0 -> 0.25), colour_levels (0 -> 1)."""
+    _fields_ = [("base", TrackSdfParams), ("colour_weight", C.c_float), ("colour_gate", C.c_float),
+                ("colour_levels", C.c_int32), ("pad", C.c_int32)]
+
+    def __init__(self, colour_weight=0.0, colour_gate=0.0, colour_levels=0, **base):
+        super().__init__(TrackSdfParams(**base), colour_weight, colour_gate, colour_levels, 0)
+
+
+class TrackSdfRgbResult(C.Structure):
+    """dslam_track_sdf_rgb_result."""
+    _fields_ = [("base", TrackSdfResult), ("colour_valid_last", C.c_int32), ("colour_rms_last", C.c_float),
+                ("cost_depth_last", C.c_float), ("cost_colour_last", C.c_float)]
+
+    def as_dict(self):
+        return dict(self.base.as_dict(), **{n: getattr(self, n) for n, _ in self._fields_[1:]})
+
+
+assert C.sizeof(TrackSdfRgbParams) == 48 and C.sizeof(TrackSdfRgbResult) == 48  # the header's layouts
+
+
 MAX_TRACK_STARTS = 256   # DSLAM_MAX_TRACK_STARTS
 
 
@@ -803,6 +825,33 @@ class CApi:
         p - t, candidate count."""
         out = np.empty(33, dtype=np.float64)
         self._call("debug_track_sdf_sums", self._engine, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
+
+    def track_camera_sdf_rgb(self, view, scenes, map_poses, pose_M, intr, params=None):
+        """dslam_track_camera_sdf_rgb: track_camera_sdf with a photometric term between the maps' colour field and the view's
+        own colour image (which must have the depth image's size).  Arguments as track_camera_sdf, `params` a
+        TrackSdfRgbParams.  Returns (the estimate as a 4x4 float32 array -- the start's own bytes if no step was accepted --,
+        TrackSdfRgbResult)."""
+        n, ptrs, t_abi = self._map_list(scenes, map_poses)
+        pose, k = self._mi(pose_M, intr)
+        pose = pose.copy()
+        res = TrackSdfRgbResult()
+        self._call("track_camera_sdf_rgb", self._engine, view.ptr, ptrs, _fptr(t_abi), C.c_int(n), _fptr(pose), _fptr(k),
+                   C.byref(params) if params is not None else None, C.byref(res))
+        return pose.reshape(4, 4).T.copy(), res
+
+    def debug_track_sdf_rgb_sums(self):
+        """The 35 double sums of the most recent track_camera_sdf_rgb evaluation: the 33 of debug_track_sdf_sums (depth and
+        colour rows together in the first 27), the sum of e^2 over the colour-valid pixels, the colour-valid count."""
+        out = np.empty(35, dtype=np.float64)
+        self._call("debug_track_sdf_rgb_sums", self._engine, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
+
+    def debug_track_sdf_rgb_grey(self, view, level):
+        """Level `level` of the grey pyramid the most recent track_camera_sdf_rgb built on `view`: float32 [h >> level, w >> level]."""
+        h, w = view.height >> level, view.width >> level
+        out = np.empty((max(h, 0), max(w, 0)), dtype=np.float32)
+        self._call("debug_track_sdf_rgb_grey", self._engine, view.ptr, C.c_int(level), _fptr(out.reshape(-1)))
         return out
 
     @staticmethod

@@ -1758,6 +1758,48 @@ int dslam_debug_track_sdf_sums(dslam_engine *e, double out[33]) {
   return copy_sums(e->track_sdf_sums, "no depth-to-SDF tracking evaluation has run on this engine", out);
 }
 
+// ---- depth-to-SDF tracker with a photometric term -------------------------------------------------------------------
+
+int dslam_track_camera_sdf_rgb(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T_map_from_world,
+                               int num_maps, float pose_M[16], const float intr[4], const dslam_track_sdf_rgb_params *params,
+                               dslam_track_sdf_rgb_result *result) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && v && scenes && T_map_from_world && pose_M && intr && result, "null argument");
+  DSLAM_TRY(check_map_list(e, "dslam_track_camera_sdf_rgb", scenes, T_map_from_world, num_maps, 1, true));
+  DSLAM_REQUIRE(v->engine == e, "the view belongs to another engine");
+  DSLAM_REQUIRE(v->updated, "the view was never updated");
+  DSLAM_REQUIRE(v->w_rgb == v->w_d && v->h_rgb == v->h_d, "the view's colour and depth images differ in size");
+  DSLAM_TRY(check_rigid_transform(pose_M, "the start pose"));
+  for (int k = 0; k < 4; k++) DSLAM_REQUIRE(std::isfinite(intr[k]), "the intrinsics are not finite");
+  dslam_track_sdf_rgb_params rp;
+  memset(&rp, 0, sizeof rp);
+  if (params) rp = *params;
+  DSLAM_TRY(default_track_sdf_params(v, params ? &params->base : nullptr, &rp.base));
+  DSLAM_REQUIRE(rp.colour_weight >= 0.0f && rp.colour_gate >= 0.0f, "colour_weight or colour_gate is negative (or not a number)");
+  DSLAM_REQUIRE(rp.colour_levels >= 0 && rp.colour_levels <= rp.base.no_hierarchy_levels - rp.base.run_till_level,
+                "colour_levels is negative or above the levels run");
+  if (rp.colour_weight == 0.0f) rp.colour_weight = 1.0f;
+  if (rp.colour_gate == 0.0f) rp.colour_gate = 0.25f;
+  if (rp.colour_levels == 0) rp.colour_levels = 1;
+  e->view_reads++;  // (see dslam_engine::last_fence)
+  return launch_track_camera_sdf_rgb(e, v, scenes, T_map_from_world, num_maps, pose_M, intr, &rp, result);
+}
+
+int dslam_debug_track_sdf_rgb_sums(dslam_engine *e, double out[35]) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && out, "null argument");
+  DSLAM_REQUIRE(e->track_sdf_rgb_sums.have_sums, "no photometric depth-to-SDF tracking evaluation has run on this engine");
+  memcpy(out, e->track_sdf_rgb_sums.last_sums, sizeof e->track_sdf_rgb_sums.last_sums);
+  return DSLAM_OK;
+}
+
+int dslam_debug_track_sdf_rgb_grey(dslam_engine *e, const dslam_view *v, int level, float *out_host) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && v && out_host, "null argument");
+  DSLAM_REQUIRE(v->engine == e, "the view belongs to another engine");
+  return download_track_sdf_rgb_grey(e, v, level, out_host);
+}
+
 // ---- depth-to-SDF tracking from many start poses at once -----------------------------------------------------------
 
 int dslam_score_camera_poses(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T_map_from_world,

@@ -169,6 +169,22 @@ struct SumChannel {
     have_sums = true;
   }
 };
+// The reduction channel of dslam_track_camera_sdf_rgb (track_sdf_rgb.hip): SumChannel's with 35 sums per row
+constexpr int kTrackSdfRgbSums = 35;
+struct RgbSumChannel {
+  PinnedBuffer<double> partials;         // mapped: [rows][35], allocated by the first call
+  double last_sums[kTrackSdfRgbSums] = {0};   // the totals of the most recent evaluation (dslam_debug_track_sdf_rgb_sums; test hook)
+  bool have_sums = false;
+  int ensure(int rows) { return partials ? 0 : partials.alloc((size_t)rows * kTrackSdfRgbSums, hipHostMallocMapped); }
+  // rows 0 .. rows of the per-workgroup partials, added in index order
+  void collect(int rows) {
+    const double *row = partials;
+    for (int i = 0; i < kTrackSdfRgbSums; i++) last_sums[i] = 0.0;
+    for (int g = 0; g < rows; g++, row += kTrackSdfRgbSums)
+      for (int i = 0; i < kTrackSdfRgbSums; i++) last_sums[i] += row[i];
+    have_sums = true;
+  }
+};
 // dslam_score_camera_poses / dslam_track_camera_sdf_starts (track_sdf_starts.hip): their own scratch.  The tables exist
 // from the first call on; the rows grow on demand (a larger level or more poses in a round) and are never allocated per call.
 struct TrackStartsScratch {
@@ -340,6 +356,7 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   DeviceBuffer<void> map_table;
   dslam::SumChannel reg_sums;         // dslam_register_maps (register.hip)
   dslam::SumChannel track_sdf_sums;   // dslam_track_camera_sdf (track_sdf.hip)
+  dslam::RgbSumChannel track_sdf_rgb_sums;   // dslam_track_camera_sdf_rgb (track_sdf_rgb.hip)
   dslam::TrackStartsScratch track_starts;   // dslam_score_camera_poses, dslam_track_camera_sdf_starts (track_sdf_starts.hip)
   dslam::MergeScratch merge;          // dslam_merge_maps (merge.hip)
   dslam::LiveLists live_lists;        // dslam_register_graph, dslam_survey_overlaps
@@ -502,6 +519,8 @@ struct DSLAM_INTERNAL dslam_view : ViewLanding {
   DeviceBuffer<float> depth_own;
   short *raw_depth = nullptr;   // (inside rgba's allocation, behind the RGBA image)
   mutable DeviceBuffer<float> pyramid;  // depth tracker: levels 1.. of the depth pyramid (scratch, allocated on first use)
+  mutable DeviceBuffer<float> grey;     // photometric tracker: the grey pyramid of rgba_src (scratch, allocated on first use)
+  mutable int grey_levels = 0;          // ... the levels the most recent dslam_track_camera_sdf_rgb built
   // what the kernels read: own buffers, or the caller's resident frame (dslam_view_update_device: no copy)
   const uchar4 *rgba_src = nullptr;
   const short *raw_src = nullptr;
@@ -702,6 +721,12 @@ int build_depth_pyramid(dslam_engine *e, const dslam_view *v, int levels, const 
 int launch_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T_map_from_world,
                             int num_maps, float *pose_M, const float *intr, const dslam_track_sdf_params *params,
                             dslam_track_sdf_result *result);
+// everything already checked (and params defaulted) by dslam_track_camera_sdf_rgb (track_sdf_rgb.hip)
+int launch_track_camera_sdf_rgb(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes, const float *T_map_from_world,
+                                int num_maps, float *pose_M, const float *intr, const dslam_track_sdf_rgb_params *params,
+                                dslam_track_sdf_rgb_result *result);
+// level `level` of the grey pyramid the most recent dslam_track_camera_sdf_rgb built on this view, to host memory
+int download_track_sdf_rgb_grey(dslam_engine *e, const dslam_view *v, int level, float *out_host);
 // arguments already checked by dslam_select_start_poses / dslam_camera_pose_lattice (host only)
 void select_start_poses(const dslam_pose_score *scores, int num, int min_valid, int max_keep, int32_t *kept_out, int32_t *num_kept_out);
 void camera_pose_lattice(const float pose_M[16], const dslam_pose_lattice &l, float *poses_out);

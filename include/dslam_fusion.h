@@ -1214,6 +1214,74 @@ int dslam_track_camera_sdf(dslam_engine *e, const dslam_view *v, const dslam_sce
  * they held sum p (items 7 and 8 above); [24..28] and [32] do not depend on the pivot.  Error if none has run. */
 int dslam_debug_track_sdf_sums(dslam_engine *e, double out[33]);
 
+/* ---- depth-to-SDF tracker with a photometric term ------------------------------------------------ */
+/* dslam_track_camera_sdf fixes only what the surface's shape fixes: on a road, a facade or a corridor wall it slides
+ * along the plane.  dslam_track_camera_sdf_rgb adds a photometric residual between the maps' colour field at the
+ * back-projected point and the view's own pixel (ITMColorTracker's purpose in the reference).  The
+ * colour comes out of the 8 taps the depth term has already loaded (a voxel's second word), the Jacobian goes through the
+ * maps' trilinear colour field as the SDF's does: no image gradients, no raycast, one 4-byte image read per pixel.
+ * The view's colour and depth images must have the same size (pixel (x, y) of the one is pixel (x, y) of the other).
+ *
+ * One evaluation at level l.  Items 1 - 6 of dslam_track_camera_sdf stand word for word (candidate, camera point, world
+ * point p and r = R c, the per-map read, the blend, the residual gate), and so do b = -d and A = [r x g, g].  Added:
+ *   where     level l carries the photometric term iff l - run_till_level < colour_levels; on the other levels an
+ *             evaluation is dslam_track_camera_sdf's, with sums [33] and [34] zero;
+ *   image     G_0[x, y] = ((0.299f R + 0.587f G) + 0.114f B) * (float)(1.0 / 255.0) of the view's RGBA pixel, alpha
+ *             ignored; G_k[x, y] = ((a + b) + (c + d)) * 0.25f of level k - 1's pixels (2x, 2y), (2x + 1, 2y),
+ *             (2x, 2y + 1), (2x + 1, 2y + 1); level k has the size of level k of the depth pyramid (H / 2, W / 2, an odd
+ *             last row or column dropped).  The pixel's intensity is I = G_l[x, y]: integer pixel, no interpolation;
+ *   map       per map i that passed its 8-tap gate for this pixel, on the same cell and the same 16 words: the map is
+ *             colour-ok iff all 8 taps have w_color > 0; the tap grey y_k is the expression of G_0 on the tap's clr bytes;
+ *             C_i and h_i are the trilinear value and the analytic gradient by the expressions of d_i and g_i with y in
+ *             place of s; w^c_i is the three lerp stages on the taps' w_color; h_i^w = R_i^T h_i as g_i^w; the colour-ok
+ *             maps are combined by item 5's law in list order (one: unchanged; several: C = sum w^c C / sum w^c, h alike):
+ *             dslam_get_image_multi's colour law;
+ *   gate      e = C - I; the pixel is a colour miss if it is a depth miss (item 6), if no map is colour-ok, or if
+ *             |e| > colour_gate;
+ *   rows      with k = colour_weight: b_c = -(k e) and A_c = k [r x h, h] (each of the six entries of [r x h, h] times k),
+ *             pivoted at the camera centre as A;
+ *   sums      35 doubles of float32 products: [0..20] the lower triangle of sum A A^T + sum A_c A_c^T (a pixel adds its
+ *             depth product, then its colour product), [21..26] sum b A + sum b_c A_c, [27] sum b^2, [28] valid,
+ *             [29..31] sum r over the valid pixels, [32] N, [33] sum e^2 over the colour-valid pixels, [34] colour-valid;
+ *   cost      cost = cost_depth + k^2 cost_colour; cost_depth is item 9; cost_colour = (sum e^2 + (N - colour_valid)
+ *             colour_gate^2) / N, colour_gate^2 for N = 0, and absent (0) on a level without the term.
+ * Iteration: dslam_track_camera_sdf's, on the combined sums: the pivot at sum r / valid (the colour rows are pivoted at t
+ * too), a trial accepted on valid >= min_valid and a lower cost; lambda rules, stop reasons and "pose_M untouched byte for
+ * byte if nothing was accepted" unchanged.
+ * colour_weight's default of 1 is a convention and not a tuned value: d is a fraction of mu and e a fraction of 255, so
+ * both residuals are dimensionless on their full scale.
+ * Every map is only read; no render state, version, memo or front-end record changes.  Waits for the stream on synchronous
+ * and asynchronous engines.  dslam_track_camera_sdf is not touched.
+ * DSLAM_ERR_INVALID with pose_M and result untouched: every rejection of dslam_track_camera_sdf; a view whose colour and
+ * depth images differ in size; a negative or NaN colour_weight or colour_gate; colour_levels negative or above the levels
+ * run (no_hierarchy_levels - run_till_level).
+ * Not promised: convergence from farther than the truncation band or a quarter of the texture's period; anything about
+ * exposure changes. */
+typedef struct {
+  dslam_track_sdf_params base;
+  float colour_weight;             /* k; 0 -> 1.0 */
+  float colour_gate;               /* fraction of full scale; 0 -> 0.25 */
+  int32_t colour_levels;           /* finest levels that carry the term; 0 -> 1 */
+  int32_t pad;
+} dslam_track_sdf_rgb_params;
+typedef struct {
+  dslam_track_sdf_result base;     /* cost_first, cost_last: the combined cost */
+  int32_t colour_valid_last;       /* this and the fields below: of the finest level run, at the returned pose */
+  float colour_rms_last;           /* sqrt(sum e^2 / colour_valid), 0 for colour_valid = 0 */
+  float cost_depth_last;
+  float cost_colour_last;          /* before k^2; 0 on a level without the term */
+} dslam_track_sdf_rgb_result;
+int dslam_track_camera_sdf_rgb(dslam_engine *e, const dslam_view *v, const dslam_scene *const *scenes,
+                               const float *T_map_from_world /* [num_maps][16] */, int num_maps,
+                               float pose_M[16] /* world -> camera; in: start, out: estimate */, const float intrinsics_d[4],
+                               const dslam_track_sdf_rgb_params *params /* NULL: defaults */,
+                               dslam_track_sdf_rgb_result *result);
+/* Test hooks: the 35 raw sums of the engine's most recent evaluation of dslam_track_camera_sdf_rgb (error if none has
+ * run), and level `level` of the grey pyramid G as the most recent call on this view built it, (W >> level) x (H >> level)
+ * floats to host memory (error if that call built no such level). */
+int dslam_debug_track_sdf_rgb_sums(dslam_engine *e, double out[35]);
+int dslam_debug_track_sdf_rgb_grey(dslam_engine *e, const dslam_view *v, int level, float *out_host);
+
 /* ---- depth-to-SDF tracking from many start poses at once ---------------------------------------- */
 /* dslam_track_camera_sdf promises nothing from farther away than the truncation band.  After a tracking loss, at a loop
  * closure or against maps dslam_register_graph has just moved, a caller has a region of poses and not a pose; these calls
