@@ -16,7 +16,9 @@ from ._capi import (BLOCK_SIZE3, HASH_ENTRY_DTYPE, IMAGE_COLOUR_FROM_NORMAL, IMA
                     SceneParams, Stats, SurveyView, TrackerParams, TrackerResult, TrackSdfParams, TrackSdfResult, TrackSdfRgbParams,
                     TrackSdfRgbResult, UnmergeParams,
                     UnmergeResult, ViewSelectParams, ViewSelectResult, ViewSurveyParams, WeightParams, mat_to_abi,
-                    FERN_CODE_DWORDS, FERN_MATCH_DTYPE, FERN_MAX_MATCHES, FERN_MAX_QUERIES, FernMatch, FernParams)
+                    FERN_CODE_DWORDS, FERN_MATCH_DTYPE, FERN_MAX_MATCHES, FERN_MAX_QUERIES, FernMatch, FernParams,
+                    POINT_SAMPLE_DTYPE, QUERY_ALL, QUERY_COLOUR, QUERY_GRADIENT, QUERY_MAX_ELEMENTS, QUERY_MAX_RAY_VOXELS,
+                    QUERY_OUTSIDE, QUERY_SDF, RAY_HIT_DTYPE, PointSample, RayHit)
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")

@@ -259,6 +259,31 @@ FERN_MATCH_DTYPE = np.dtype([("id", "<i4"), ("dissimilarity", "<i4")])
 assert C.sizeof(FernParams) == 24 and C.sizeof(FernMatch) == 8 and FERN_MATCH_DTYPE.itemsize == 8  # the header's layouts
 
 
+QUERY_MAX_ELEMENTS, QUERY_MAX_RAY_VOXELS = 1 << 24, 16384   # DSLAM_QUERY_MAX_ELEMENTS, DSLAM_QUERY_MAX_RAY_VOXELS
+QUERY_SDF, QUERY_GRADIENT, QUERY_COLOUR = 1, 2, 4           # DSLAM_QUERY_SDF, _GRADIENT, _COLOUR
+QUERY_ALL = QUERY_SDF | QUERY_GRADIENT | QUERY_COLOUR
+QUERY_OUTSIDE = 1                                           # DSLAM_QUERY_OUTSIDE
+
+
+class PointSample(C.Structure):
+    """dslam_point_sample."""
+    _fields_ = [("sdf", C.c_float), ("weight", C.c_float), ("grad", C.c_float * 3), ("colour", C.c_float * 3),
+                ("found_lo", C.c_uint32), ("found_hi", C.c_uint32), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+class RayHit(C.Structure):
+    """dslam_ray_hit."""
+    _fields_ = [("t", C.c_float), ("point", C.c_float * 3), ("normal", C.c_float * 3), ("colour", C.c_float * 3),
+                ("status", C.c_int32), ("steps", C.c_int32)]
+
+
+POINT_SAMPLE_DTYPE = np.dtype([("sdf", "<f4"), ("weight", "<f4"), ("grad", "<f4", (3,)), ("colour", "<f4", (3,)),
+                               ("found_lo", "<u4"), ("found_hi", "<u4"), ("status", "<i4"), ("pad", "<i4")])
+RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("point", "<f4", (3,)), ("normal", "<f4", (3,)), ("colour", "<f4", (3,)),
+                          ("status", "<i4"), ("steps", "<i4")])
+assert C.sizeof(PointSample) == C.sizeof(RayHit) == POINT_SAMPLE_DTYPE.itemsize == RAY_HIT_DTYPE.itemsize == 48  # the header's layouts
+
+
 class MergeParams(C.Structure):
     """dslam_merge_params; max_passes = 0 selects its default."""
     _fields_ = [("max_passes", C.c_int32), ("with_colour", C.c_int32)]
@@ -1105,6 +1130,41 @@ class CApi:
         self._call("select_view_maps", reach.ctypes.data_as(i32), nearest.ctypes.data_as(i32), C.c_int(nv), C.c_int(n),
                    C.byref(params) if params is not None else None, maps.ctypes.data_as(i32), C.byref(res))
         return maps[:res.selected].copy(), res
+
+    # -- the maps at any point or along any ray --------------------------------------------------------
+    def query_points(self, scenes, map_poses, points, what=QUERY_ALL):
+        """dslam_query_points: the combined reads of `scenes` / `map_poses` (as track_camera_sdf) at world points [n, 3]
+        (metres).  Returns a POINT_SAMPLE_DTYPE array [n]."""
+        n_maps, ptrs, t_abi = self._map_list(scenes, map_poses)
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 3))
+        out = np.zeros(len(pts), dtype=POINT_SAMPLE_DTYPE)
+        self._call("query_points", self._engine, ptrs, _fptr(t_abi), C.c_int(n_maps), _fptr(pts), C.c_int(len(pts)),
+                   C.c_int(what), _vptr(out))
+        return out
+
+    def query_points_device(self, scenes, map_poses, points_dev_ptr, n, out_dev_ptr, what=QUERY_ALL):
+        """dslam_query_points_device: `points_dev_ptr` [n][3] float32 and `out_dev_ptr` [n] x 48 bytes are device addresses;
+        enqueues on the engine's stream."""
+        n_maps, ptrs, t_abi = self._map_list(scenes, map_poses)
+        self._call("query_points_device", self._engine, ptrs, _fptr(t_abi), C.c_int(n_maps), C.c_void_p(points_dev_ptr),
+                   C.c_int(n), C.c_int(what), C.c_void_p(out_dev_ptr))
+
+    def cast_rays(self, scenes, map_poses, rays, max_range=0.0, what=QUERY_ALL):
+        """dslam_cast_rays: `rays` [n, 8] float32 (origin, direction, t_min, t_max; metres); max_range 0: the limit.
+        Returns a RAY_HIT_DTYPE array [n]."""
+        n_maps, ptrs, t_abi = self._map_list(scenes, map_poses)
+        r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32).reshape(-1, 8))
+        out = np.zeros(len(r), dtype=RAY_HIT_DTYPE)
+        self._call("cast_rays", self._engine, ptrs, _fptr(t_abi), C.c_int(n_maps), _fptr(r), C.c_int(len(r)),
+                   C.c_float(max_range), C.c_int(what), _vptr(out))
+        return out
+
+    def cast_rays_device(self, scenes, map_poses, rays_dev_ptr, n, out_dev_ptr, max_range=0.0, what=QUERY_ALL):
+        """dslam_cast_rays_device: `rays_dev_ptr` [n][8] float32 and `out_dev_ptr` [n] x 48 bytes are device addresses;
+        enqueues on the engine's stream."""
+        n_maps, ptrs, t_abi = self._map_list(scenes, map_poses)
+        self._call("cast_rays_device", self._engine, ptrs, _fptr(t_abi), C.c_int(n_maps), C.c_void_p(rays_dev_ptr), C.c_int(n),
+                   C.c_float(max_range), C.c_int(what), C.c_void_p(out_dev_ptr))
 
     # -- fern keyframe index ---------------------------------------------------------------------------
     def create_fern_index(self, width_d, height_d, capacity, params=None):

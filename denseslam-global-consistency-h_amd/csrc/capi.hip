@@ -2301,6 +2301,67 @@ int dslam_select_view_maps(const int32_t *reach_blocks, const int32_t *nearest, 
   return DSLAM_OK;
 }
 
+// ---- the maps at any point or along any ray ---------------------------------------------------------------------------
+namespace {
+
+// what the four query calls check alike; max_range: NULL for points, else in: the caller's, out: the default in place of 0
+int check_query_call(dslam_engine *e, const char *call, const dslam_scene *const *scenes, const float *T, int num_maps,
+                     const void *in, int n, int what, const void *out, float *max_range) {
+  DSLAM_REQUIRE(e && scenes && T, "null argument");
+  DSLAM_TRY(check_map_list(e, call, scenes, T, num_maps, 1, true));
+  DSLAM_REQUIRE(n >= 0 && n <= DSLAM_QUERY_MAX_ELEMENTS, std::string(call) + ": n must be 0 .. DSLAM_QUERY_MAX_ELEMENTS");
+  DSLAM_REQUIRE((what & ~(DSLAM_QUERY_SDF | DSLAM_QUERY_GRADIENT | DSLAM_QUERY_COLOUR)) == 0, std::string(call) + ": unknown bits in `what`");
+  DSLAM_REQUIRE(max_range || (what & DSLAM_QUERY_SDF), std::string(call) + ": `what` must include DSLAM_QUERY_SDF");
+  if (max_range) {
+    const float limit = (float)DSLAM_QUERY_MAX_RAY_VOXELS * scenes[0]->p.voxel_size;
+    DSLAM_REQUIRE(std::isfinite(*max_range) && *max_range >= 0.0f && *max_range <= limit,
+                  std::string(call) + ": max_range must be 0 (the limit) .. DSLAM_QUERY_MAX_RAY_VOXELS x voxel_size");
+    if (*max_range == 0.0f) *max_range = limit;
+  }
+  DSLAM_REQUIRE(n == 0 || (in && out), std::string(call) + ": null array");
+  return DSLAM_OK;
+}
+
+}  // namespace
+
+int dslam_query_points(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                       const float *points_host, int n, int what, dslam_point_sample *out_host) {
+  flush_deferred(e);
+  DSLAM_TRY(check_query_call(e, "dslam_query_points", scenes, T_map_from_world, num_maps, points_host, n, what, out_host, nullptr));
+  if (n == 0) return DSLAM_OK;
+  DSLAM_TRY(launch_query(e, scenes, T_map_from_world, num_maps, false, points_host, n, 0.0f, what, out_host, true));
+  return sync_check(e);
+}
+
+int dslam_query_points_device(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                              const void *points_dev, int n, int what, void *out_dev) {
+  flush_deferred(e);
+  DSLAM_TRY(check_query_call(e, "dslam_query_points_device", scenes, T_map_from_world, num_maps, points_dev, n, what, out_dev, nullptr));
+  DSLAM_REQUIRE(((uintptr_t)points_dev & 3) == 0 && ((uintptr_t)out_dev & 15) == 0, "points must be 4-byte, results 16-byte aligned");
+  if (n == 0) return DSLAM_OK;
+  DSLAM_TRY(launch_query(e, scenes, T_map_from_world, num_maps, false, points_dev, n, 0.0f, what, out_dev, false));
+  return finish_call(e);
+}
+
+int dslam_cast_rays(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                    const float *rays_host, int n, float max_range, int what, dslam_ray_hit *out_host) {
+  flush_deferred(e);
+  DSLAM_TRY(check_query_call(e, "dslam_cast_rays", scenes, T_map_from_world, num_maps, rays_host, n, what, out_host, &max_range));
+  if (n == 0) return DSLAM_OK;
+  DSLAM_TRY(launch_query(e, scenes, T_map_from_world, num_maps, true, rays_host, n, max_range, what, out_host, true));
+  return sync_check(e);
+}
+
+int dslam_cast_rays_device(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                           const void *rays_dev, int n, float max_range, int what, void *out_dev) {
+  flush_deferred(e);
+  DSLAM_TRY(check_query_call(e, "dslam_cast_rays_device", scenes, T_map_from_world, num_maps, rays_dev, n, what, out_dev, &max_range));
+  DSLAM_REQUIRE(((uintptr_t)rays_dev & 15) == 0 && ((uintptr_t)out_dev & 15) == 0, "rays and results must be 16-byte aligned");
+  if (n == 0) return DSLAM_OK;
+  DSLAM_TRY(launch_query(e, scenes, T_map_from_world, num_maps, true, rays_dev, n, max_range, what, out_dev, false));
+  return finish_call(e);
+}
+
 // ---- fern keyframe index --------------------------------------------------------------------------------------------
 namespace {
 

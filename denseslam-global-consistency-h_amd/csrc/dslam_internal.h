@@ -198,6 +198,12 @@ struct TrackStartsScratch {
   std::vector<double> last_sums;         // [starts][33]: each start's most recent evaluation in the most recent _starts call
                                          // (dslam_debug_track_sdf_start_sums; test hook)
 };
+// dslam_query_points / dslam_cast_rays (query.hip): what the host forms stage a chunk of elements through; grown on demand
+// (to one chunk of 2^20 elements at the most) and released with the engine
+struct QueryScratch {
+  DeviceBuffer<void> in, out;            // a chunk's points or rays, and its 48-byte results
+  size_t in_bytes = 0, out_bytes = 0;    // their capacities
+};
 // bytes of one map descriptor (MultiMap, multimap_device.h) in dslam_engine::map_table
 constexpr size_t kMapDescriptorBytes = 80;
 }  // namespace dslam
@@ -364,6 +370,7 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   dslam::OverlapScratch overlap;      // dslam_survey_overlaps (overlap.hip)
   dslam::ViewSurveyScratch view_survey;   // dslam_survey_views (view_survey.hip)
   long long view_survey_launches = 0; // kernel launches dslam_survey_views has enqueued (test hook)
+  dslam::QueryScratch query;          // dslam_query_points, dslam_cast_rays (query.hip)
   std::vector<double> reg_graph_sums; // [pairs][33]: each pair's totals at the most recent joint evaluation it took part
                                       // in (dslam_debug_register_graph_sums; test hook)
   // dslam_debug_merge_phases (bench hook): wall clock of the last merge's phases, each closed by a wait for the stream --
@@ -770,6 +777,10 @@ void view_frustum_planes(const dslam_survey_view &view, float voxel_size, float 
 int launch_survey_views(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
                         const float *planes, int num_views, float rho, int32_t *live_blocks_out, int32_t *reach_blocks_out,
                         int32_t *nearest_out, int32_t *farthest_out);
+// query.hip: dslam_query_points (rays false) / dslam_cast_rays over n elements, everything already checked (max_range
+// defaulted); host: in / out are host arrays staged in chunks, else device arrays.  Enqueues only
+int launch_query(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps, bool rays,
+                 const void *in, int n, float max_range, int what, void *out, bool host);
 // arguments already checked (and params defaulted) by dslam_select_view_maps: the selection law of DESIGN.md section 20
 void select_view_maps(const int32_t *reach_blocks, const int32_t *nearest, int num_views, int num_maps,
                       const dslam_view_select_params &params, int32_t *maps_out, dslam_view_select_result *result);

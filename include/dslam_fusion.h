@@ -835,6 +835,64 @@ int dslam_select_view_maps(const int32_t *reach_blocks /* [V][N] */, const int32
                            int num_maps, const dslam_view_select_params *params /* NULL: defaults */,
                            int32_t *maps_out /* [max_maps] */, dslam_view_select_result *result);
 
+/* ---- the maps at any point or along any ray (no counterpart in the reference) ---------------
+ * The posed, weighted cross-map reads of dslam_get_image_multi (the law of DESIGN.md section 10) without a camera: at
+ * arbitrary world points, and along arbitrary rays.  scenes / T_map_from_world / num_maps as dslam_track_camera_sdf (1 ..
+ * DSLAM_MAX_RENDER_MAPS scenes of one engine, none twice, one voxel_size and mu, rigid transforms).  Every listed map is
+ * visited for every element, in list order; narrow the list with dslam_survey_views / dslam_select_view_maps.  The
+ * scenes are only read, no render state is taken and no GetImage memo is touched.
+ *
+ * dslam_query_points: per world point p (metres) the combined trilinear sdf (1.0 where no map holds a tap of the cell),
+ * `weight` = the law's sum of the weights of that read (the trilinear w_depth of every map that reported found, float32,
+ * list order; 0 where none did), the combined un-normalised gradient in the world frame, the combined colour in 0 .. 1,
+ * and in found_lo / found_hi bit i set when map i holds a tap of the cell.  status DSLAM_QUERY_OUTSIDE: a coordinate is
+ * not finite or lies beyond +-2^20 voxels; no map is read, sdf is 1 and every other field 0.  `what`: DSLAM_QUERY_SDF,
+ * optionally | DSLAM_QUERY_GRADIENT | DSLAM_QUERY_COLOUR; a field not asked for is written as 0, a field asked for carries
+ * the same bits whatever else was asked.
+ *
+ * dslam_cast_rays: per ray (origin o, direction d of any length > 0, t_min, t_max; metres along the normalised
+ * direction) the march of dslam_get_image_multi from o + t_min d^ to min(t_max, t_min + max_range).  max_range: metres,
+ * 0 -> the limit DSLAM_QUERY_MAX_RAY_VOXELS x voxel_size, above the limit an error: a ray takes at most
+ * DSLAM_QUERY_MAX_RAY_VOXELS iterations whatever its t_max.  status 0: a miss (t_min >= t_max: with steps 0); 1: a hit;
+ * 2: a hit at the first read -- the ray began at or behind a surface, and `point` is where the march's two refinement
+ * steps led from there; -1: an invalid ray (a component not finite, a direction of length 0 or not finite, t_min < 0,
+ * the start beyond +-2^20 voxels), never marched, everything else 0.  At a hit: t = (point - o) . d^, point in world
+ * metres, normal = the combined gradient at the hit point, normalised ((0, 0, 0) when its float32 length is exactly 0),
+ * colour as dslam_query_points gives it there -- both are read at `point` taken back to voxel units as
+ * dslam_query_points takes its points, so a later dslam_query_points at `point` returns the bits the ray carries.  `what`: DSLAM_QUERY_GRADIENT (normal) and DSLAM_QUERY_COLOUR select the shading;
+ * DSLAM_QUERY_SDF is accepted and means nothing more.
+ *
+ * The host forms stage through buffers of the engine in chunks of 2^20 elements and return when the results are in
+ * out_host.  The device forms (points_dev / rays_dev 4-byte aligned, out_dev 16-byte aligned, device memory) enqueue on the
+ * engine's stream and return as every enqueue-only call does (dslam_engine_set_async).  n == 0 is DSLAM_OK.
+ * DSLAM_ERR_INVALID: the map-list errors, n outside 0 .. DSLAM_QUERY_MAX_ELEMENTS, unknown bits in `what` (or no
+ * DSLAM_QUERY_SDF for points), max_range negative, not finite or above the limit, a NULL array with n > 0. */
+#define DSLAM_QUERY_MAX_ELEMENTS (1 << 24)
+#define DSLAM_QUERY_MAX_RAY_VOXELS 16384
+#define DSLAM_QUERY_SDF 1
+#define DSLAM_QUERY_GRADIENT 2
+#define DSLAM_QUERY_COLOUR 4
+#define DSLAM_QUERY_OUTSIDE 1
+typedef struct {
+  float sdf, weight, grad[3], colour[3];
+  uint32_t found_lo, found_hi;
+  int32_t status, pad;
+} dslam_point_sample; /* 48 bytes */
+typedef struct {
+  float t, point[3], normal[3], colour[3];
+  int32_t status, steps;
+} dslam_ray_hit; /* 48 bytes */
+int dslam_query_points(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                       const float *points_host /* [n][3] */, int n, int what, dslam_point_sample *out_host);
+int dslam_query_points_device(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                              const void *points_dev /* [n][3] float */, int n, int what, void *out_dev /* [n] dslam_point_sample */);
+int dslam_cast_rays(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                    const float *rays_host /* [n][8]: o, d, t_min, t_max */, int n, float max_range, int what,
+                    dslam_ray_hit *out_host);
+int dslam_cast_rays_device(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                           const void *rays_dev /* [n][8] float */, int n, float max_range, int what,
+                           void *out_dev /* [n] dslam_ray_hit */);
+
 /* ---- fern keyframe index: which stored keyframe does this frame look like? ------------------
  * Upstream's relocaliser (FernRelocLib: randomised ferns over a thumbnail of the frame, Glocker et al.) with the codes of
  * all keyframes in HBM.  The reference ships the submodule empty, so the law is this project's own; it is all-integer, so
