@@ -284,6 +284,30 @@ RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("point", "<f4", (3,)), ("normal", "<f4"
 assert C.sizeof(PointSample) == C.sizeof(RayHit) == POINT_SAMPLE_DTYPE.itemsize == RAY_HIT_DTYPE.itemsize == 48  # the header's layouts
 
 
+GRID_MAX_CELL, GRID_MAX_DIM, GRID_MAX_CELLS = 64, 1024, 1 << 26   # DSLAM_GRID_MAX_CELL, _MAX_DIM, _MAX_CELLS
+CELL_OBSERVED, CELL_OCCUPIED = 1, 2                              # DSLAM_CELL_OBSERVED, _OCCUPIED
+SEED_OCCUPIED, SEED_UNKNOWN = 1, 2                               # DSLAM_SEED_OCCUPIED, _UNKNOWN
+DIST_SQUARED_CELLS, DIST_METRES = 0, 1                           # DSLAM_DIST_SQUARED_CELLS, _METRES
+DIST_MAX_CELLS, DIST_FAR = 1774, 0x7FFFFFFF                      # DSLAM_DIST_MAX_CELLS, DSLAM_DIST_FAR
+
+
+class Grid(C.Structure):
+    """dslam_grid: a world-aligned box of cells in world voxel units."""
+    _fields_ = [("origin", C.c_int32 * 3), ("cell", C.c_int32), ("dims", C.c_int32 * 3), ("pad", C.c_int32)]
+
+    @classmethod
+    def of(cls, origin, cell, dims, pad=0):
+        return cls((C.c_int32 * 3)(*[int(v) for v in origin]), int(cell), (C.c_int32 * 3)(*[int(v) for v in dims]), int(pad))
+
+    @property
+    def cells(self):
+        return int(self.dims[0]) * int(self.dims[1]) * int(self.dims[2])
+
+
+GRID_DTYPE = np.dtype([("origin", "<i4", (3,)), ("cell", "<i4"), ("dims", "<i4", (3,)), ("pad", "<i4")])
+assert C.sizeof(Grid) == GRID_DTYPE.itemsize == 32  # the header's layout
+
+
 class MergeParams(C.Structure):
     """dslam_merge_params; max_passes = 0 selects its default."""
     _fields_ = [("max_passes", C.c_int32), ("with_colour", C.c_int32)]
@@ -1165,6 +1189,75 @@ class CApi:
         n_maps, ptrs, t_abi = self._map_list(scenes, map_poses)
         self._call("cast_rays_device", self._engine, ptrs, _fptr(t_abi), C.c_int(n_maps), C.c_void_p(rays_dev_ptr), C.c_int(n),
                    C.c_float(max_range), C.c_int(what), C.c_void_p(out_dev_ptr))
+
+    # -- occupancy and exact distance grids --------------------------------------------------------------
+    def grid_from_box(self, lo_m, hi_m, voxel_size, cell):
+        """dslam_grid_from_box: the Grid of cell edge `cell` (voxels) that covers the metric box lo_m .. hi_m."""
+        lo, hi = np.asarray(lo_m, np.float32).reshape(3), np.asarray(hi_m, np.float32).reshape(3)
+        g = Grid()
+        self._call("grid_from_box", _fptr(lo), _fptr(hi), C.c_float(voxel_size), C.c_int(cell), C.byref(g))
+        return g
+
+    @staticmethod
+    def _dist_dtype(fmt):
+        return np.float32 if fmt == DIST_METRES else np.int32
+
+    def mark_occupancy(self, scenes, map_poses, grid, min_weight=0, occupied_below=0.0, out=None):
+        """dslam_mark_occupancy: one state byte per cell of `grid` (0 unknown, 1 observed free, 3 occupied) from `scenes` /
+        `map_poses` (as query_points).  out: a uint8 array [cells] to write into."""
+        n_maps, ptrs, t_abi = self._map_list(scenes, map_poses)
+        out = np.zeros(grid.cells, np.uint8) if out is None else out
+        self._call("mark_occupancy", self._engine, ptrs, _fptr(t_abi), C.c_int(n_maps), C.byref(grid), C.c_int(min_weight),
+                   C.c_float(occupied_below), _vptr(out))
+        return out
+
+    def mark_occupancy_device(self, scenes, map_poses, grid, states_dev_ptr, min_weight=0, occupied_below=0.0):
+        """dslam_mark_occupancy_device: `states_dev_ptr` [cells] bytes is a device address; enqueues on the engine's stream."""
+        n_maps, ptrs, t_abi = self._map_list(scenes, map_poses)
+        self._call("mark_occupancy_device", self._engine, ptrs, _fptr(t_abi), C.c_int(n_maps), C.byref(grid), C.c_int(min_weight),
+                   C.c_float(occupied_below), C.c_void_p(states_dev_ptr))
+
+    def distance_transform(self, grid, states, seeds=SEED_OCCUPIED, max_cells=0, fmt=DIST_SQUARED_CELLS, voxel_size=0.0, out=None):
+        """dslam_distance_transform: the exact squared distance (int32, cells) or the distance in metres (float32) of every
+        cell of `grid` to the nearest seed cell of `states` (uint8 [cells]); DIST_FAR / +inf beyond max_cells or without a seed."""
+        states = None if states is None else np.ascontiguousarray(states, dtype=np.uint8)
+        out = np.zeros(grid.cells, self._dist_dtype(fmt)) if out is None else out
+        self._call("distance_transform", self._engine, C.byref(grid), _vptr(states), C.c_int(seeds), C.c_int(max_cells), C.c_int(fmt),
+                   C.c_float(voxel_size), _vptr(out))
+        return out
+
+    def distance_transform_device(self, grid, states_dev_ptr, dist_dev_ptr, seeds=SEED_OCCUPIED, max_cells=0, fmt=DIST_SQUARED_CELLS,
+                                  voxel_size=0.0):
+        """dslam_distance_transform_device: `states_dev_ptr` [cells] bytes and `dist_dev_ptr` [cells] x 4 bytes are device addresses."""
+        self._call("distance_transform_device", self._engine, C.byref(grid), C.c_void_p(states_dev_ptr), C.c_int(seeds),
+                   C.c_int(max_cells), C.c_int(fmt), C.c_float(voxel_size), C.c_void_p(dist_dev_ptr))
+
+    def distance_field(self, scenes, map_poses, grid, min_weight=0, occupied_below=0.0, seeds=SEED_OCCUPIED, max_cells=0,
+                       fmt=DIST_SQUARED_CELLS, want_states=True, want_dist=True, states_out=None, dist_out=None):
+        """dslam_distance_field: mark_occupancy, then distance_transform on its states, on the device.  Returns (states or
+        None, distances or None)."""
+        n_maps, ptrs, t_abi = self._map_list(scenes, map_poses)
+        if want_states and states_out is None:
+            states_out = np.zeros(grid.cells, np.uint8)
+        if want_dist and dist_out is None:
+            dist_out = np.zeros(grid.cells, self._dist_dtype(fmt))
+        self._call("distance_field", self._engine, ptrs, _fptr(t_abi), C.c_int(n_maps), C.byref(grid), C.c_int(min_weight),
+                   C.c_float(occupied_below), C.c_int(seeds), C.c_int(max_cells), C.c_int(fmt), _vptr(states_out), _vptr(dist_out))
+        return states_out, dist_out
+
+    def distance_field_device(self, scenes, map_poses, grid, states_dev_ptr, dist_dev_ptr, min_weight=0, occupied_below=0.0,
+                              seeds=SEED_OCCUPIED, max_cells=0, fmt=DIST_SQUARED_CELLS):
+        """dslam_distance_field_device: `states_dev_ptr` / `dist_dev_ptr` are device addresses, either may be 0 (not wanted)."""
+        n_maps, ptrs, t_abi = self._map_list(scenes, map_poses)
+        self._call("distance_field_device", self._engine, ptrs, _fptr(t_abi), C.c_int(n_maps), C.byref(grid), C.c_int(min_weight),
+                   C.c_float(occupied_below), C.c_int(seeds), C.c_int(max_cells), C.c_int(fmt), C.c_void_p(states_dev_ptr or None),
+                   C.c_void_p(dist_dev_ptr or None))
+
+    def distance_field_phases(self, enable=-1, read=True):
+        """dslam_debug_distance_field_phases (bench hook): [states, x pass, y pass, last pass] of the most recent call in ms."""
+        ms = (C.c_float * 4)()
+        self._call("debug_distance_field_phases", self._engine, C.c_int(enable), ms if read else None)
+        return list(ms)
 
     # -- fern keyframe index ---------------------------------------------------------------------------
     def create_fern_index(self, width_d, height_d, capacity, params=None):

@@ -2362,6 +2362,121 @@ int dslam_cast_rays_device(dslam_engine *e, const dslam_scene *const *scenes, co
   return finish_call(e);
 }
 
+// ---- occupancy and exact distance grids ---------------------------------------------------------------------------------
+int dslam_grid_from_box(const float *lo_m, const float *hi_m, float voxel_size, int cell, dslam_grid *out) {
+  DSLAM_REQUIRE(lo_m && hi_m && out, "null argument");
+  DSLAM_REQUIRE(std::isfinite(voxel_size) && voxel_size > 0.0f, "dslam_grid_from_box: voxel_size must be finite and positive");
+  DSLAM_REQUIRE(cell >= 1 && cell <= DSLAM_GRID_MAX_CELL, "dslam_grid_from_box: cell must be 1 .. DSLAM_GRID_MAX_CELL");
+  dslam_grid g;
+  memset(&g, 0, sizeof g);
+  g.cell = cell;
+  for (int a = 0; a < 3; a++) {
+    DSLAM_REQUIRE(std::isfinite(lo_m[a]) && std::isfinite(hi_m[a]) && hi_m[a] >= lo_m[a], "dslam_grid_from_box: the box must be finite with hi >= lo");
+    const double o = floor((double)lo_m[a] / (double)voxel_size);
+    const double d = std::max(1.0, ceil(((double)hi_m[a] / (double)voxel_size - o) / (double)cell));
+    // (checked as doubles, before any conversion)
+    DSLAM_REQUIRE(o >= -1048576.0 && d <= (double)DSLAM_GRID_MAX_DIM && o + (double)cell * d <= 1048576.0,
+                  "dslam_grid_from_box: the box exceeds the grid's limits");
+    g.origin[a] = (int32_t)o;
+    g.dims[a] = (int32_t)d;
+  }
+  DSLAM_REQUIRE(grid_ok(g), "dslam_grid_from_box: the box exceeds the grid's limits");
+  *out = g;
+  return DSLAM_OK;
+}
+
+namespace {
+
+// what the six grid calls check alike, and the call they make.  scenes NULL: the transform alone; transform false: the marking alone
+int distance_field_call(dslam_engine *e, const char *call, const dslam_scene *const *scenes, const float *T, int num_maps, bool marking,
+                        const dslam_grid *grid, int min_weight, float occupied_below, const void *states_in, bool transform, int seeds,
+                        int max_cells, int format, float voxel_size, void *states_out, void *dist_out, bool host) {
+  flush_deferred(e);
+  auto msg = [call](const char *what) { return std::string(call) + ": " + what; };
+  DSLAM_REQUIRE(e && grid, "null argument");
+  DistanceFieldCall c;
+  memset(&c, 0, sizeof c);
+  if (marking) {
+    DSLAM_REQUIRE(scenes && T, "null argument");
+    DSLAM_TRY(check_map_list(e, call, scenes, T, num_maps, 1, true));
+    DSLAM_REQUIRE(min_weight >= 0 && min_weight <= 255, msg("min_weight must be 0 .. 255"));
+    const float mu = scenes[0]->p.mu;
+    DSLAM_REQUIRE(std::isfinite(occupied_below) && fabsf(occupied_below) < mu, msg("occupied_below must be finite with |occupied_below| < mu"));
+    c.scenes = scenes; c.T = T; c.num_maps = num_maps;
+    c.min_weight = min_weight == 0 ? 1 : min_weight;
+    c.thr = (int)floor((double)occupied_below / (double)mu * 32767.0);
+    voxel_size = scenes[0]->p.voxel_size;
+  }
+  DSLAM_REQUIRE(grid_ok(*grid), msg("the grid is outside the limits (cell, dims, cells, the +-2^20 voxel range) or its pad is not 0"));
+  if (transform) {
+    DSLAM_REQUIRE(seeds >= 1 && seeds <= 3, msg("seeds must be DSLAM_SEED_OCCUPIED, DSLAM_SEED_UNKNOWN or both"));
+    DSLAM_REQUIRE(max_cells >= 0 && max_cells <= DSLAM_DIST_MAX_CELLS, msg("max_cells must be 0 .. DSLAM_DIST_MAX_CELLS"));
+    DSLAM_REQUIRE(format == DSLAM_DIST_SQUARED_CELLS || format == DSLAM_DIST_METRES, msg("unknown format"));
+    DSLAM_REQUIRE(format != DSLAM_DIST_METRES || (std::isfinite(voxel_size) && voxel_size > 0.0f), msg("voxel_size must be finite and positive"));
+  }
+  if (!marking) DSLAM_REQUIRE(states_in && dist_out, msg("null array"));
+  else if (!transform) DSLAM_REQUIRE(states_out, msg("null array"));
+  else DSLAM_REQUIRE(states_out || dist_out, msg("states_out and dist_out are both NULL"));
+  if (!host)
+    DSLAM_REQUIRE(((uintptr_t)states_in & 15) == 0 && ((uintptr_t)states_out & 15) == 0 && ((uintptr_t)dist_out & 15) == 0,
+                  msg("device arrays must be 16-byte aligned"));
+  c.grid = *grid;
+  c.states_in = states_in;
+  c.transform = transform;
+  c.seeds = seeds; c.max_cells = max_cells; c.format = format;
+  c.voxel_size = voxel_size;
+  c.states_out = states_out; c.dist_out = dist_out;
+  c.host = host;
+  DSLAM_TRY(launch_distance_field(e, c));
+  return host ? sync_check(e) : finish_call(e);
+}
+
+}  // namespace
+
+int dslam_mark_occupancy(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                         const dslam_grid *grid, int min_weight, float occupied_below, uint8_t *states_out_host) {
+  return distance_field_call(e, "dslam_mark_occupancy", scenes, T_map_from_world, num_maps, true, grid, min_weight, occupied_below,
+                             nullptr, false, 0, 0, 0, 0.0f, states_out_host, nullptr, true);
+}
+
+int dslam_mark_occupancy_device(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                                const dslam_grid *grid, int min_weight, float occupied_below, void *states_out_dev) {
+  return distance_field_call(e, "dslam_mark_occupancy_device", scenes, T_map_from_world, num_maps, true, grid, min_weight,
+                             occupied_below, nullptr, false, 0, 0, 0, 0.0f, states_out_dev, nullptr, false);
+}
+
+int dslam_distance_transform(dslam_engine *e, const dslam_grid *grid, const uint8_t *states_host, int seeds, int max_cells, int format,
+                             float voxel_size, void *dist_out_host) {
+  return distance_field_call(e, "dslam_distance_transform", nullptr, nullptr, 0, false, grid, 0, 0.0f, states_host, true, seeds,
+                             max_cells, format, voxel_size, nullptr, dist_out_host, true);
+}
+
+int dslam_distance_transform_device(dslam_engine *e, const dslam_grid *grid, const void *states_dev, int seeds, int max_cells,
+                                    int format, float voxel_size, void *dist_out_dev) {
+  return distance_field_call(e, "dslam_distance_transform_device", nullptr, nullptr, 0, false, grid, 0, 0.0f, states_dev, true, seeds,
+                             max_cells, format, voxel_size, nullptr, dist_out_dev, false);
+}
+
+int dslam_distance_field(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                         const dslam_grid *grid, int min_weight, float occupied_below, int seeds, int max_cells, int format,
+                         uint8_t *states_out_host, void *dist_out_host) {
+  return distance_field_call(e, "dslam_distance_field", scenes, T_map_from_world, num_maps, true, grid, min_weight, occupied_below,
+                             nullptr, true, seeds, max_cells, format, 0.0f, states_out_host, dist_out_host, true);
+}
+
+int dslam_distance_field_device(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                                const dslam_grid *grid, int min_weight, float occupied_below, int seeds, int max_cells, int format,
+                                void *states_out_dev, void *dist_out_dev) {
+  return distance_field_call(e, "dslam_distance_field_device", scenes, T_map_from_world, num_maps, true, grid, min_weight,
+                             occupied_below, nullptr, true, seeds, max_cells, format, 0.0f, states_out_dev, dist_out_dev, false);
+}
+
+int dslam_debug_distance_field_phases(dslam_engine *e, int enable, float out_ms[4]) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e, "null argument");
+  return distance_field_phases(e, enable, out_ms);
+}
+
 // ---- fern keyframe index --------------------------------------------------------------------------------------------
 namespace {
 

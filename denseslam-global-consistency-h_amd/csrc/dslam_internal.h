@@ -204,6 +204,20 @@ struct QueryScratch {
   DeviceBuffer<void> in, out;            // a chunk's points or rays, and its 48-byte results
   size_t in_bytes = 0, out_bytes = 0;    // their capacities
 };
+// dslam_mark_occupancy / dslam_distance_transform / dslam_distance_field (distance_field.hip): the packed states of a grid,
+// its int32 line distances, what the host forms stage state bytes through, and the call's map table; each grown on demand
+// and released with the engine
+struct DistanceFieldScratch {
+  DeviceBuffer<unsigned> packed;         // [dims2][dims1][ceil(dims0 / 16)]: 2 bits per cell, 16 cells along x per word
+  DeviceBuffer<int> lines;               // [cells]: the passes work in place; the host forms' distances leave from here
+  DeviceBuffer<unsigned char> bytes;     // [cells]: the host forms' state bytes, in or out
+  DeviceBuffer<void> maps;               // [DSLAM_MAX_RENDER_MAPS] map descriptors of a marking call
+  size_t packed_words = 0, lines_cells = 0, bytes_cells = 0;   // their capacities
+  // dslam_debug_distance_field_phases (bench hook): events recorded at the phase boundaries of a call while `timing` is set
+  bool timing = false;
+  Event events[5];
+  unsigned recorded = 0;                 // bit k: events[k] was recorded by the most recent call
+};
 // bytes of one map descriptor (MultiMap, multimap_device.h) in dslam_engine::map_table
 constexpr size_t kMapDescriptorBytes = 80;
 }  // namespace dslam
@@ -371,6 +385,7 @@ struct DSLAM_INTERNAL dslam_engine : dslam::EngineScratch {
   dslam::ViewSurveyScratch view_survey;   // dslam_survey_views (view_survey.hip)
   long long view_survey_launches = 0; // kernel launches dslam_survey_views has enqueued (test hook)
   dslam::QueryScratch query;          // dslam_query_points, dslam_cast_rays (query.hip)
+  dslam::DistanceFieldScratch distance_field;   // dslam_mark_occupancy, dslam_distance_transform, dslam_distance_field
   std::vector<double> reg_graph_sums; // [pairs][33]: each pair's totals at the most recent joint evaluation it took part
                                       // in (dslam_debug_register_graph_sums; test hook)
   // dslam_debug_merge_phases (bench hook): wall clock of the last merge's phases, each closed by a wait for the stream --
@@ -781,6 +796,27 @@ int launch_survey_views(dslam_engine *e, const dslam_scene *const *scenes, const
 // defaulted); host: in / out are host arrays staged in chunks, else device arrays.  Enqueues only
 int launch_query(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps, bool rays,
                  const void *in, int n, float max_range, int what, void *out, bool host);
+// distance_field.hip.  grid_ok: a dslam_grid within the limits of include/dslam_fusion.h (host only).  launch_distance_field:
+// everything already checked; scenes NULL: no marking, the states come from states_in (bytes); dist_out / states_out NULL: not
+// wanted; host: the arrays are host arrays, staged through dslam_engine::distance_field, else device arrays.  Enqueues only
+// (the marking waits once for the live counts)
+bool grid_ok(const dslam_grid &g);
+struct DistanceFieldCall {
+  const dslam_scene *const *scenes;   // NULL: transform only
+  const float *T;
+  int num_maps;
+  dslam_grid grid;
+  int min_weight;                     // already defaulted: 1 .. 255
+  int thr;                            // occupied: (int16)sdf <= thr
+  const void *states_in;              // transform only
+  bool transform;
+  int seeds, max_cells, format;
+  float voxel_size;
+  void *states_out, *dist_out;
+  bool host;
+};
+int launch_distance_field(dslam_engine *e, const DistanceFieldCall &c);
+int distance_field_phases(dslam_engine *e, int enable, float *ms_out);   // dslam_debug_distance_field_phases
 // arguments already checked (and params defaulted) by dslam_select_view_maps: the selection law of DESIGN.md section 20
 void select_view_maps(const int32_t *reach_blocks, const int32_t *nearest, int num_views, int num_maps,
                       const dslam_view_select_params &params, int32_t *maps_out, dslam_view_select_result *result);

@@ -893,6 +893,86 @@ int dslam_cast_rays_device(dslam_engine *e, const dslam_scene *const *scenes, co
                            const void *rays_dev /* [n][8] float */, int n, float max_range, int what,
                            void *out_dev /* [n] dslam_ray_hit */);
 
+/* ---- occupancy and exact distance grids (no counterpart in the reference) --------------------
+ * What a planner reads next to the truncated distances of dslam_query_points: over a world-aligned box of cells, which
+ * cells the listed maps have observed, which hold a surface, and the exact Euclidean distance of every cell to the
+ * nearest occupied (or never observed) cell.  Everything behind one float32 transform per voxel is integer arithmetic, so
+ * the results are the same bits on every run and equal tests/ref_distance_field.py bit for bit.
+ *
+ * dslam_grid: the box in world VOXEL units.  origin: the world voxel coordinate of the low corner of cell (0, 0, 0); cell:
+ * the edge of a cell in voxels, 1 .. DSLAM_GRID_MAX_CELL; dims: cells per axis, each 1 .. DSLAM_GRID_MAX_DIM, their
+ * product at most DSLAM_GRID_MAX_CELLS; origin[a] >= -2^20 and origin[a] + cell * dims[a] <= 2^20; pad 0.  Every per-cell
+ * array is x-fastest: cell (x, y, z) at index x + dims[0] * (y + dims[1] * z).  dslam_grid_from_box (host only) makes the
+ * grid of cell edge `cell` that covers the metric box lo_m .. hi_m: origin = floor((double)lo / (double)voxel_size), dims =
+ * max(1, ceil((hi / voxel_size - origin) / cell)); DSLAM_ERR_INVALID (and *out untouched) where a limit is exceeded, hi <
+ * lo, or an input is not finite.
+ *
+ * dslam_mark_occupancy (law 1).  scenes / T_map_from_world / num_maps as dslam_query_points.  For every listed map i,
+ * every hash entry with ptr >= 0 and each of its 512 voxels at integer position p of the map's own frame:
+ *   1. w_depth >= min_weight (0 -> 1, else 1 .. 255), or the voxel is ignored;
+ *   2. w = B_i p, B_i = float32(rigid_inverse(voxel_pose(T_i, (double)voxel_size))) (csrc/register_host.h, in double, the
+ *      12 entries then rounded), p as float32, each row ((a x + b y) + c z) + d in float32 without contraction; a voxel
+ *      with a coordinate of w not finite or |w| > 2^20 is ignored;
+ *   3. g = (int)floorf(w) per axis, c = floor_div(g - origin, cell); a voxel whose c lies outside dims is ignored;
+ *   4. the cell's byte gets DSLAM_CELL_OBSERVED, and DSLAM_CELL_OCCUPIED as well when (int16)sdf <= thr, thr =
+ *      (int)floor((double)occupied_below / (double)mu * 32767.0); occupied_below: metres, |occupied_below| < mu, 0 = the
+ *      shell behind the surface.
+ * A cell's byte is the OR over all voxels of all maps that land in it: 0 unknown, 1 observed and free, 3 occupied -- so
+ * the order of the list, and of anything else, does not matter.  Two consequences: with cell = 1 under a rotation not
+ * every world cell of the shell receives a lattice point of the map (the shell is mu deep, so it stays closed; a caller
+ * who needs every cell of it filled uses cell >= 2), and blocks that are swapped out (ptr == -1) are not resident and
+ * mark nothing.
+ *
+ * dslam_distance_transform (law 2).  states: one byte per cell, of which bits 0 and 1 are read.  seeds:
+ * DSLAM_SEED_OCCUPIED (byte & 2), DSLAM_SEED_UNKNOWN ((byte & 3) == 0), or both (either).  d2[c] = the smallest |c - s|^2
+ * over the seed cells s, an exact integer.  max_cells R: 0 no bound; 1 .. DSLAM_DIST_MAX_CELLS: a cell with d2 > R^2 is
+ * far (d2 == R^2 is kept).  A grid without a seed is far everywhere.  format DSLAM_DIST_SQUARED_CELLS: int32 d2, far =
+ * DSLAM_DIST_FAR; DSLAM_DIST_METRES: float32 sqrtf((float)d2) * ((float)cell * voxel_size) (one correctly rounded root,
+ * the cell size computed first), far = +inf; voxel_size is read for this format only (finite, > 0).
+ *
+ * dslam_distance_field: law 1, then law 2 on its states, without leaving the device; states_out and dist_out are each
+ * optional, not both NULL.
+ *
+ * The host forms stage through buffers of the engine (grown on demand, released with it) and return when the results
+ * are in the caller's arrays.  The device forms (states: bytes; distances: 4 bytes per cell; both 16-byte aligned device
+ * memory) enqueue on the engine's stream and return as every enqueue-only call does (dslam_engine_set_async).  The scenes
+ * are only read, no render state is taken and no GetImage memo is touched.  DSLAM_ERR_INVALID, with nothing written: the
+ * map-list errors, a grid outside the limits or with pad != 0, min_weight outside 0 .. 255, occupied_below not finite or
+ * |occupied_below| >= mu, seeds outside 1 .. 3, max_cells outside 0 .. DSLAM_DIST_MAX_CELLS, an unknown format, a NULL
+ * array that is needed, a misaligned device pointer. */
+#define DSLAM_GRID_MAX_CELL 64
+#define DSLAM_GRID_MAX_DIM 1024
+#define DSLAM_GRID_MAX_CELLS (1 << 26)
+#define DSLAM_CELL_OBSERVED 1
+#define DSLAM_CELL_OCCUPIED 2
+#define DSLAM_SEED_OCCUPIED 1
+#define DSLAM_SEED_UNKNOWN 2
+#define DSLAM_DIST_SQUARED_CELLS 0
+#define DSLAM_DIST_METRES 1
+#define DSLAM_DIST_MAX_CELLS 1774
+#define DSLAM_DIST_FAR 0x7fffffff
+typedef struct { int32_t origin[3]; int32_t cell; int32_t dims[3]; int32_t pad; } dslam_grid; /* 32 bytes */
+int dslam_grid_from_box(const float *lo_m /* [3] */, const float *hi_m /* [3] */, float voxel_size, int cell, dslam_grid *out);
+int dslam_mark_occupancy(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                         const dslam_grid *grid, int min_weight, float occupied_below, uint8_t *states_out_host);
+int dslam_mark_occupancy_device(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                                const dslam_grid *grid, int min_weight, float occupied_below, void *states_out_dev);
+int dslam_distance_transform(dslam_engine *e, const dslam_grid *grid, const uint8_t *states_host, int seeds, int max_cells,
+                             int format, float voxel_size, void *dist_out_host /* [cells] int32 or float */);
+int dslam_distance_transform_device(dslam_engine *e, const dslam_grid *grid, const void *states_dev, int seeds, int max_cells,
+                                    int format, float voxel_size, void *dist_out_dev);
+int dslam_distance_field(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                         const dslam_grid *grid, int min_weight, float occupied_below, int seeds, int max_cells, int format,
+                         uint8_t *states_out_host /* or NULL */, void *dist_out_host /* or NULL */);
+int dslam_distance_field_device(dslam_engine *e, const dslam_scene *const *scenes, const float *T_map_from_world, int num_maps,
+                                const dslam_grid *grid, int min_weight, float occupied_below, int seeds, int max_cells,
+                                int format, void *states_out_dev /* or NULL */, void *dist_out_dev /* or NULL */);
+/* bench hook: enable 1 / 0 switches events at the phase boundaries of the calls above on or off (-1: leaves it as it is);
+ * out_ms (or NULL): waits for the stream, then the device time of the most recent call's phases -- [0] the packed states
+ * (memset and k_df_mark, or the packing of the caller's bytes), [1] the x pass, [2] the y pass, [3] the last pass (or the
+ * expansion of the states when no distance was asked for); -1 for a phase that did not run or was not timed */
+int dslam_debug_distance_field_phases(dslam_engine *e, int enable, float out_ms[4]);
+
 /* ---- fern keyframe index: which stored keyframe does this frame look like? ------------------
  * Upstream's relocaliser (FernRelocLib: randomised ferns over a thumbnail of the frame, Glocker et al.) with the codes of
  * all keyframes in HBM.  The reference ships the submodule empty, so the law is this project's own; it is all-integer, so
