@@ -20,7 +20,9 @@ from ._capi import (BLOCK_SIZE3, HASH_ENTRY_DTYPE, IMAGE_COLOUR_FROM_NORMAL, IMA
                     POINT_SAMPLE_DTYPE, QUERY_ALL, QUERY_COLOUR, QUERY_GRADIENT, QUERY_MAX_ELEMENTS, QUERY_MAX_RAY_VOXELS,
                     QUERY_OUTSIDE, QUERY_SDF, RAY_HIT_DTYPE, PointSample, RayHit,
                     CELL_OBSERVED, CELL_OCCUPIED, DIST_FAR, DIST_MAX_CELLS, DIST_METRES, DIST_SQUARED_CELLS, GRID_DTYPE,
-                    GRID_MAX_CELL, GRID_MAX_CELLS, GRID_MAX_DIM, SEED_OCCUPIED, SEED_UNKNOWN, Grid)
+                    GRID_MAX_CELL, GRID_MAX_CELLS, GRID_MAX_DIM, SEED_OCCUPIED, SEED_UNKNOWN, Grid,
+                    STEREO_CALIB_DTYPE, STEREO_CENSUS_LEFT, STEREO_CENSUS_RIGHT, STEREO_COST_OUT, STEREO_INVALID, STEREO_MAX_P2,
+                    STEREO_MAX_SIZE, STEREO_PARAMS_DTYPE, STEREO_S, StereoCalib, StereoParams)
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")

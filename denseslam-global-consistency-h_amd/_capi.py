@@ -308,6 +308,42 @@ GRID_DTYPE = np.dtype([("origin", "<i4", (3,)), ("cell", "<i4"), ("dims", "<i4",
 assert C.sizeof(Grid) == GRID_DTYPE.itemsize == 32  # the header's layout
 
 
+STEREO_INVALID, STEREO_COST_OUT, STEREO_MAX_SIZE, STEREO_MAX_P2 = 0xFFFF, 63, 4096, 192   # DSLAM_STEREO_INVALID, _COST_OUT, _MAX_SIZE, _MAX_P2
+STEREO_CENSUS_LEFT, STEREO_CENSUS_RIGHT, STEREO_S = 0, 1, 2                              # DSLAM_STEREO_CENSUS_LEFT, _CENSUS_RIGHT, _S
+
+
+class StereoParams(C.Structure):
+    """dslam_stereo_params in the header's encoding: a field left at 0 selects its default; uniqueness -1 = off; lr_max -1 =
+    check off, -2 = exact.  effective(): what the law takes (uniqueness 0 = off, lr_max -1 = off, 0 = exact)."""
+    _fields_ = [("max_disparity", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("uniqueness", C.c_int32),
+                ("lr_max", C.c_int32), ("channels", C.c_int32), ("pad", C.c_int32 * 2)]
+
+    def __init__(self, max_disparity=0, p1=0, p2=0, uniqueness=0, lr_max=0, channels=0):
+        super().__init__(max_disparity, p1, p2, uniqueness, lr_max, channels)
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+    def effective(self):
+        d = self.as_dict()
+        d["uniqueness"] = max(d["uniqueness"], 0)
+        d["lr_max"] = 0 if d["lr_max"] == -2 else d["lr_max"]
+        return d
+
+
+class StereoCalib(C.Structure):
+    """dslam_stereo_calib."""
+    _fields_ = [("focal_length_px", C.c_float), ("baseline_m", C.c_float), ("scale", C.c_float), ("min_depth_m", C.c_float),
+                ("max_depth_m", C.c_float)]
+
+
+STEREO_PARAMS_DTYPE = np.dtype([("max_disparity", "<i4"), ("p1", "<i4"), ("p2", "<i4"), ("uniqueness", "<i4"), ("lr_max", "<i4"),
+                                ("channels", "<i4"), ("pad", "<i4", (2,))])
+STEREO_CALIB_DTYPE = np.dtype([("focal_length_px", "<f4"), ("baseline_m", "<f4"), ("scale", "<f4"), ("min_depth_m", "<f4"),
+                               ("max_depth_m", "<f4")])
+assert C.sizeof(StereoParams) == STEREO_PARAMS_DTYPE.itemsize == 32 and C.sizeof(StereoCalib) == STEREO_CALIB_DTYPE.itemsize == 20
+
+
 class MergeParams(C.Structure):
     """dslam_merge_params; max_passes = 0 selects its default."""
     _fields_ = [("max_passes", C.c_int32), ("with_colour", C.c_int32)]
@@ -432,6 +468,10 @@ class FrameStore(_Handle):
 
 
 class FernIndex(_Handle):
+    pass
+
+
+class Stereo(_Handle):
     pass
 
 
@@ -1257,6 +1297,91 @@ class CApi:
         """dslam_debug_distance_field_phases (bench hook): [states, x pass, y pass, last pass] of the most recent call in ms."""
         ms = (C.c_float * 4)()
         self._call("debug_distance_field_phases", self._engine, C.c_int(enable), ms if read else None)
+        return list(ms)
+
+    # -- semi-global stereo matching -------------------------------------------------------------------
+    def create_stereo(self, width, height, params=None):
+        """dslam_stereo_create: a matcher for rectified pairs of width x height; .params: its StereoParams, defaults filled in."""
+        h = C.c_void_p()
+        self._call("stereo_create", self._engine, C.c_int(width), C.c_int(height), C.byref(params) if params is not None else None,
+                   C.byref(h))
+        st = Stereo(self, h, self._fn("stereo_destroy"))
+        st.width, st.height, st.params = width, height, self.stereo_get_params(st)
+        st.D, st.channels = st.params.max_disparity, st.params.channels
+        return st
+
+    def stereo_get_params(self, st):
+        p = StereoParams()
+        self._call("stereo_get_params", st.ptr, C.byref(p))
+        return p
+
+    @staticmethod
+    def _stereo_image(st, img):
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        assert img.size == st.width * st.height * st.channels
+        return img
+
+    @staticmethod
+    def _stereo_calib(calib):
+        return calib if isinstance(calib, StereoCalib) else StereoCalib(*[float(v) for v in calib])
+
+    def stereo_match(self, st, left, right, out=None):
+        """dslam_stereo_match: the left image's disparity, uint16 [H, W] in 1/16 pixel (STEREO_INVALID: none)."""
+        left, right = self._stereo_image(st, left), self._stereo_image(st, right)
+        out = np.zeros((st.height, st.width), np.uint16) if out is None else out
+        self._call("stereo_match", self._engine, st.ptr, _vptr(left), _vptr(right), _vptr(out))
+        return out
+
+    def stereo_match_device(self, st, left_dev_ptr, right_dev_ptr, disp_dev_ptr):
+        """dslam_stereo_match_device: device addresses; enqueues on the engine's stream."""
+        self._call("stereo_match_device", self._engine, st.ptr, C.c_void_p(left_dev_ptr), C.c_void_p(right_dev_ptr),
+                   C.c_void_p(disp_dev_ptr))
+
+    def disparity_to_depth(self, st, disp, calib, out=None):
+        """dslam_disparity_to_depth: int16 [H, W] millimetres from a uint16 disparity image; calib: a StereoCalib or its 5 values."""
+        disp = np.ascontiguousarray(disp, dtype=np.uint16)
+        assert disp.size == st.width * st.height
+        out = np.zeros((st.height, st.width), np.int16) if out is None else out
+        self._call("disparity_to_depth", self._engine, st.ptr, _vptr(disp), C.byref(self._stereo_calib(calib)), _vptr(out))
+        return out
+
+    def disparity_to_depth_device(self, st, disp_dev_ptr, calib, depth_dev_ptr):
+        self._call("disparity_to_depth_device", self._engine, st.ptr, C.c_void_p(disp_dev_ptr), C.byref(self._stereo_calib(calib)),
+                   C.c_void_p(depth_dev_ptr))
+
+    def stereo_depth(self, st, left, right, calib, want_disp=True, depth_out=None, disp_out=None):
+        """dslam_stereo_depth: (depth int16 [H, W] in millimetres, disparity uint16 [H, W] or None)."""
+        left, right = self._stereo_image(st, left), self._stereo_image(st, right)
+        depth_out = np.zeros((st.height, st.width), np.int16) if depth_out is None else depth_out
+        if want_disp and disp_out is None:
+            disp_out = np.zeros((st.height, st.width), np.uint16)
+        self._call("stereo_depth", self._engine, st.ptr, _vptr(left), _vptr(right), C.byref(self._stereo_calib(calib)),
+                   _vptr(depth_out), _vptr(disp_out))
+        return depth_out, disp_out
+
+    def stereo_depth_device(self, st, left_dev_ptr, right_dev_ptr, calib, depth_dev_ptr, disp_dev_ptr=None):
+        """dslam_stereo_depth_device: device addresses (disp_dev_ptr may be None); the depth image is what view_update_device takes."""
+        self._call("stereo_depth_device", self._engine, st.ptr, C.c_void_p(left_dev_ptr), C.c_void_p(right_dev_ptr),
+                   C.byref(self._stereo_calib(calib)), C.c_void_p(depth_dev_ptr), C.c_void_p(disp_dev_ptr or None))
+
+    def debug_stereo_download(self, st, what):
+        """dslam_debug_stereo_download: STEREO_CENSUS_LEFT / _RIGHT uint64 [H, W], STEREO_S uint16 [H, W, D] of the last match."""
+        out = np.zeros((st.height, st.width, st.D), np.uint16) if what == STEREO_S else np.zeros((st.height, st.width), np.uint64)
+        self._call("debug_stereo_download", self._engine, st.ptr, C.c_int(what), _vptr(out))
+        return out
+
+    def debug_stereo_select(self, st, S, out=None):
+        """dslam_debug_stereo_select: selection, left-right check and sub-pixel step on the caller's S uint16 [H, W, D]."""
+        S = np.ascontiguousarray(S, dtype=np.uint16)
+        assert S.size == st.width * st.height * st.D
+        out = np.zeros((st.height, st.width), np.uint16) if out is None else out
+        self._call("debug_stereo_select", self._engine, st.ptr, _vptr(S), _vptr(out))
+        return out
+
+    def stereo_phases(self, st, enable=-1, read=True):
+        """dslam_debug_stereo_phases (bench hook): [census, aggregation, selection, left-right check, conversion alone] in ms."""
+        ms = (C.c_float * 5)()
+        self._call("debug_stereo_phases", self._engine, st.ptr, C.c_int(enable), ms if read else None)
         return list(ms)
 
     # -- fern keyframe index ---------------------------------------------------------------------------

@@ -2477,6 +2477,129 @@ int dslam_debug_distance_field_phases(dslam_engine *e, int enable, float out_ms[
   return distance_field_phases(e, enable, out_ms);
 }
 
+// ---- semi-global stereo matching ------------------------------------------------------------------------------------
+namespace {
+
+int check_stereo_calib(const dslam_stereo_calib *c) {
+  DSLAM_REQUIRE(std::isfinite(c->focal_length_px) && c->focal_length_px > 0.0f && std::isfinite(c->baseline_m) && c->baseline_m > 0.0f &&
+                    std::isfinite(c->scale) && c->scale > 0.0f,
+                "the calibration's focal_length_px, baseline_m and scale must be finite and positive");
+  DSLAM_REQUIRE(std::isfinite(c->min_depth_m) && std::isfinite(c->max_depth_m) && c->min_depth_m >= 0.0f && c->max_depth_m >= c->min_depth_m,
+                "the calibration needs 0 <= min_depth_m <= max_depth_m");
+  DSLAM_REQUIRE(c->max_depth_m * 1000.0f < 32767.0f, "max_depth_m * 1000 must stay below 32767: the depth image is int16 millimetres");
+  return DSLAM_OK;
+}
+
+// what the stereo calls check alike, and the call they make
+int stereo_call(dslam_engine *e, dslam_stereo *st, const StereoCall &c) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && st, "null argument");
+  DSLAM_REQUIRE(st->engine == e, "the stereo matcher belongs to another engine");
+  const bool match = c.left || c.right, convert = c.calib || c.depth_out;
+  if (c.S_host) DSLAM_REQUIRE(c.disp_out, "null argument");
+  else if (match) DSLAM_REQUIRE(c.left && c.right && (convert || c.disp_out), "null argument");
+  else DSLAM_REQUIRE(c.disp_in, "null argument");
+  if (convert || !(match || c.S_host)) {
+    DSLAM_REQUIRE(c.calib && c.depth_out, "null argument");
+    DSLAM_TRY(check_stereo_calib(c.calib));
+  }
+  if (!c.host)
+    DSLAM_REQUIRE(((uintptr_t)c.left & 15) == 0 && ((uintptr_t)c.right & 15) == 0 && ((uintptr_t)c.disp_in & 15) == 0 &&
+                      ((uintptr_t)c.disp_out & 15) == 0 && ((uintptr_t)c.depth_out & 15) == 0,
+                  "device arrays must be 16-byte aligned");
+  DSLAM_TRY(launch_stereo(e, st, c));
+  return c.host ? sync_check(e) : finish_call(e);
+}
+
+}  // namespace
+
+int dslam_stereo_create(dslam_engine *e, int width, int height, const dslam_stereo_params *params, dslam_stereo **out) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && out, "null argument");
+  DSLAM_REQUIRE(width >= 1 && width <= DSLAM_STEREO_MAX_SIZE && height >= 1 && height <= DSLAM_STEREO_MAX_SIZE,
+                "width and height must be 1 .. DSLAM_STEREO_MAX_SIZE");
+  std::unique_ptr<dslam_stereo> st(new dslam_stereo());
+  DSLAM_TRY(stereo_resolve_params(params, st.get()));
+  st->engine = e; st->w = width; st->h = height;
+  DSLAM_TRY(stereo_allocate(e, st.get()));
+  engine_adopt(e);   // (only a complete matcher is a handle, as a fern index)
+  *out = st.release();
+  return DSLAM_OK;
+}
+
+int dslam_stereo_destroy(dslam_stereo *st) {
+  if (!st) return DSLAM_OK;
+  (void)hipSetDevice(st->engine->device);
+  flush_deferred(st->engine);   // (on its own device: held calls launch kernels)
+  (void)hipStreamSynchronize(st->engine->stream);
+  dslam_engine *e = st->engine;
+  delete st;
+  engine_release(e);
+  return DSLAM_OK;
+}
+
+int dslam_stereo_get_params(const dslam_stereo *st, dslam_stereo_params *params_out) {
+  DSLAM_REQUIRE(st && params_out, "null argument");
+  *params_out = st->p;
+  return DSLAM_OK;
+}
+
+int dslam_stereo_match(dslam_engine *e, dslam_stereo *st, const uint8_t *left_host, const uint8_t *right_host, uint16_t *disp_out_host) {
+  DSLAM_REQUIRE(left_host && right_host && disp_out_host, "null argument");
+  return stereo_call(e, st, StereoCall{left_host, right_host, nullptr, nullptr, nullptr, disp_out_host, nullptr, true});
+}
+
+int dslam_stereo_match_device(dslam_engine *e, dslam_stereo *st, const void *left_dev, const void *right_dev, void *disp_out_dev) {
+  DSLAM_REQUIRE(left_dev && right_dev && disp_out_dev, "null argument");
+  return stereo_call(e, st, StereoCall{left_dev, right_dev, nullptr, nullptr, nullptr, disp_out_dev, nullptr, false});
+}
+
+int dslam_disparity_to_depth(dslam_engine *e, dslam_stereo *st, const uint16_t *disp_host, const dslam_stereo_calib *calib,
+                             int16_t *depth_mm_out_host) {
+  DSLAM_REQUIRE(disp_host && calib && depth_mm_out_host, "null argument");
+  return stereo_call(e, st, StereoCall{nullptr, nullptr, nullptr, disp_host, calib, nullptr, depth_mm_out_host, true});
+}
+
+int dslam_disparity_to_depth_device(dslam_engine *e, dslam_stereo *st, const void *disp_dev, const dslam_stereo_calib *calib,
+                                    void *depth_mm_out_dev) {
+  DSLAM_REQUIRE(disp_dev && calib && depth_mm_out_dev, "null argument");
+  return stereo_call(e, st, StereoCall{nullptr, nullptr, nullptr, disp_dev, calib, nullptr, depth_mm_out_dev, false});
+}
+
+int dslam_stereo_depth(dslam_engine *e, dslam_stereo *st, const uint8_t *left_host, const uint8_t *right_host,
+                       const dslam_stereo_calib *calib, int16_t *depth_mm_out_host, uint16_t *disp_out_host) {
+  DSLAM_REQUIRE(left_host && right_host && calib && depth_mm_out_host, "null argument");
+  return stereo_call(e, st, StereoCall{left_host, right_host, nullptr, nullptr, calib, disp_out_host, depth_mm_out_host, true});
+}
+
+int dslam_stereo_depth_device(dslam_engine *e, dslam_stereo *st, const void *left_dev, const void *right_dev,
+                              const dslam_stereo_calib *calib, void *depth_mm_out_dev, void *disp_out_dev) {
+  DSLAM_REQUIRE(left_dev && right_dev && calib && depth_mm_out_dev, "null argument");
+  return stereo_call(e, st, StereoCall{left_dev, right_dev, nullptr, nullptr, calib, disp_out_dev, depth_mm_out_dev, false});
+}
+
+int dslam_debug_stereo_download(dslam_engine *e, dslam_stereo *st, int what, void *out_host) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && st && out_host, "null argument");
+  DSLAM_REQUIRE(st->engine == e, "the stereo matcher belongs to another engine");
+  DSLAM_REQUIRE(what == DSLAM_STEREO_CENSUS_LEFT || what == DSLAM_STEREO_CENSUS_RIGHT || what == DSLAM_STEREO_S, "unknown `what`");
+  DSLAM_REQUIRE(st->matched, "the stereo matcher has not matched a pair yet");
+  DSLAM_TRY(stereo_download(e, st, what, out_host));
+  return sync_check(e);
+}
+
+int dslam_debug_stereo_select(dslam_engine *e, dslam_stereo *st, const uint16_t *S_host, uint16_t *disp_out_host) {
+  DSLAM_REQUIRE(S_host && disp_out_host, "null argument");
+  return stereo_call(e, st, StereoCall{nullptr, nullptr, S_host, nullptr, nullptr, disp_out_host, nullptr, true});
+}
+
+int dslam_debug_stereo_phases(dslam_engine *e, dslam_stereo *st, int enable, float out_ms[5]) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && st, "null argument");
+  DSLAM_REQUIRE(st->engine == e, "the stereo matcher belongs to another engine");
+  return stereo_phases(e, st, enable, out_ms);
+}
+
 // ---- fern keyframe index --------------------------------------------------------------------------------------------
 namespace {
 

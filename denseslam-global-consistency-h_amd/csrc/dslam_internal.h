@@ -616,7 +616,47 @@ struct DSLAM_INTERNAL dslam_fern_index : FernThumbs, FernRows {
   PinnedBuffer<int> query_ids;           // mapped: [DSLAM_FERN_MAX_QUERIES] the stored codes a scan compares against
 };
 
+// The semi-global stereo matcher (stereo.hip): everything a match of one image size needs.  The
+// buffers exist whole or not at all (built aside, move-assigned).
+struct StereoBuffers {
+  DeviceBuffer<unsigned long long> census;   // [2][H W]: left, right
+  DeviceBuffer<unsigned short> S;            // [H][W][D]: the sum of the eight path costs (D innermost)
+  DeviceBuffer<unsigned> rkey;               // [H W]: min over d of S(y, xr + d, d) << 8 | d
+  DeviceBuffer<unsigned> cand;               // [H W]: d* << 16 | d16 of the left selection, ~0 where rejected
+  DeviceBuffer<unsigned char> images;        // [2][H W channels]: where the host forms' images land
+  DeviceBuffer<unsigned short> disp;         // [H W]: the disparity of the host forms and of a depth call without disp_out
+  DeviceBuffer<short> depth;                 // [H W]: the host forms' depth
+};
+struct DSLAM_INTERNAL dslam_stereo : StereoBuffers {
+  dslam_engine *engine = nullptr;
+  int w = 0, h = 0;
+  dslam_stereo_params p{};                   // as dslam_stereo_get_params gives it
+  int D = 0, p1 = 0, p2 = 0, uniq = 0, lr_max = 0, channels = 0;   // what the kernels take (lr_max < 0: check off)
+  bool matched = false;                      // census and S hold a match (dslam_debug_stereo_download)
+  // dslam_debug_stereo_phases (bench hook): events recorded at the phase boundaries of a call while `timing` is set
+  bool timing = false;
+  Event events[6];
+  int recorded = 0;
+};
+// one call of the dslam_stereo_* family, already checked by its entry point (capi.hip)
+struct StereoCall {
+  const void *left, *right;                  // NULL: no match (conversion alone, or selection on S_host)
+  const unsigned short *S_host;              // dslam_debug_stereo_select
+  const void *disp_in;                       // dslam_disparity_to_depth*
+  const dslam_stereo_calib *calib;           // NULL: no conversion
+  void *disp_out, *depth_out;
+  bool host;
+};
+
 namespace dslam {
+// dslam_stereo_* (stereo.hip); stereo_resolve_params fills st->p and the kernels' values from a caller's block (or NULL).
+// launch_stereo enqueues only (the host forms' copies included).
+int stereo_resolve_params(const dslam_stereo_params *params, dslam_stereo *st);
+int stereo_allocate(dslam_engine *e, dslam_stereo *st);
+int launch_stereo(dslam_engine *e, dslam_stereo *st, const StereoCall &c);
+int stereo_download(dslam_engine *e, dslam_stereo *st, int what, void *out_host);
+int stereo_phases(dslam_engine *e, dslam_stereo *st, int enable, float *ms_out);
+
 // dslam_fern_* (fern.hip); everything already checked by the entry points (capi.hip).  All wait for the stream; the
 // outputs are written only when everything has succeeded.
 void fern_build_table(const dslam_fern_params &p, int tw, int th, std::vector<int32_t> &table);

@@ -973,6 +973,94 @@ int dslam_distance_field_device(dslam_engine *e, const dslam_scene *const *scene
  * expansion of the states when no distance was asked for); -1 for a phase that did not run or was not timed */
 int dslam_debug_distance_field_phases(dslam_engine *e, int enable, float out_ms[4]);
 
+/* ---- semi-global stereo matching: a depth image from a rectified pair ------------------------
+ * A handle is made for one image size W x H (1 .. 4096 each) and one parameter block and owns all working memory.  The law
+ * is all-integer up to the depth conversion, so the device gives the same bytes as tests/ref_stereo.py.  D = max_disparity.
+ *   grey         channels == 1: the byte as it is; channels == 4 (RGBA): (r + 2 g + b) >> 2.
+ *   census       window 9 wide, 7 high, coordinates clamped to the image; 62 bits in a uint64: over the neighbours in
+ *                row-major order (dy = -3 .. 3 outer, dx = -4 .. 4 inner, centre skipped) code = code << 1 | (neighbour <
+ *                centre).
+ *   cost         C(y, x, d) = popcount(censusL(y, x) ^ censusR(y, x - d)) for 0 <= d < D and x - d >= 0, otherwise
+ *                DSLAM_STEREO_COST_OUT.
+ *   aggregation  eight directions r = (dy, dx) in {(0, +-1), (+-1, 0), (+-1, +-1)}, q = p - r.  q outside the image:
+ *                L_r(p, d) = C(p, d).  Otherwise with m = min_k L_r(q, k):  L_r(p, d) = C(p, d) + min(L_r(q, d),
+ *                L_r(q, d - 1) + p1, L_r(q, d + 1) + p1, m + p2) - m, the d +- 1 terms absent at the ends of the range.
+ *                S = the sum of the eight L_r (every L_r <= 63 + 192, S <= 2040).
+ *   selection    d* = argmin_d S(y, x, d), the smallest d on ties; s0 = S(d*); s2 = min S(d) over |d - d*| > 1; with
+ *                uniqueness u (percent) the pixel is rejected iff s2 (100 - u) < 100 s0.
+ *   left-right   dR(y, xr) = argmin_d S(y, xr + d, d) over the d with xr + d < W, the smallest d on ties.  Rejected if
+ *                x - d* < 0, and, unless the check is off, if |dR(y, x - d*) - d*| > lr_max.
+ *   sub-pixel    sm = S(d* - 1), sp = S(d* + 1), den = sm + sp - 2 s0.  If 0 < d* < D - 1 and den > 0: delta =
+ *                floor((16 (sm - sp) + den) / (2 den)), else 0.  d16 = 16 d* + delta (1/16 pixel), DSLAM_STEREO_INVALID
+ *                where rejected.
+ *   depth        float32, in this order: disp = d16 * 0.0625f; z = (focal_length_px * baseline_m) / disp; mm_f =
+ *                (1000.0f * scale) * z; mm = (int32)mm_f.  0 where d16 is DSLAM_STEREO_INVALID or 0, !(mm_f <
+ *                2147483648.0f), mm > (int32)(max_depth_m * 1000.0f) or mm < (int32)(min_depth_m * 1000.0f).
+ * Parameter encoding (dslam_stereo_params, all int32): a field left at 0 selects its default.  Two fields have a meaningful
+ * value 0, which therefore has a code of its own: uniqueness -1 means 0 (the filter is off); lr_max -1 switches the
+ * left-right check off and lr_max -2 means 0 (dR must equal d*).  dslam_stereo_get_params returns the block in the same
+ * encoding with no field left at 0, so it recreates the same matcher.  pad must be 0.
+ * Images are dense rows: left / right uint8 [H][W][channels], disparity uint16 [H][W], depth int16 [H][W] millimetres --
+ * what dslam_view_update_device takes as depth_mm_dev.  The host forms stage through buffers of the handle and wait for the
+ * stream; the _device forms take device addresses (16-byte aligned), enqueue on the engine's stream and return as every
+ * call of a synchronous or asynchronous engine does.  A handle may be destroyed before or after dslam_engine_destroy
+ * (DESIGN.md section 21).  None of the calls touches a scene, a view or a render state.
+ * DSLAM_ERR_INVALID with nothing enqueued and nothing written: a NULL argument other than params / disp_out; a handle of
+ * another engine; width or height outside 1 .. 4096; max_disparity other than 64 or 128; p1 > p2, p2 > 192 or a negative
+ * penalty; uniqueness above 99 or below -1; lr_max above D or below -2; channels other than 1 or 4; a non-zero pad; a
+ * calibration that is not finite and positive in focal_length_px, baseline_m and scale, with min_depth_m < 0, max_depth_m
+ * < min_depth_m or max_depth_m * 1000 >= 32767; a misaligned device address; an unknown `what`; a debug download before
+ * the first match.  DSLAM_ERR_HIP from dslam_stereo_create when the volumes cannot be allocated: no handle is made. */
+#define DSLAM_STEREO_INVALID 0xFFFF
+#define DSLAM_STEREO_COST_OUT 63
+#define DSLAM_STEREO_MAX_SIZE 4096
+#define DSLAM_STEREO_MAX_P2 192
+#define DSLAM_STEREO_CENSUS_LEFT 0
+#define DSLAM_STEREO_CENSUS_RIGHT 1
+#define DSLAM_STEREO_S 2
+typedef struct dslam_stereo dslam_stereo;
+typedef struct {
+  int32_t max_disparity;           /* 0 -> 128; 64 or 128 */
+  int32_t p1;                      /* 0 -> 10; 1 <= p1 <= p2 */
+  int32_t p2;                      /* 0 -> 120; p1 <= p2 <= 192 */
+  int32_t uniqueness;              /* 0 -> 5; percent, 1 .. 99; -1 = off */
+  int32_t lr_max;                  /* 0 -> 1; 1 .. D; -1 = check off; -2 = exact (tolerance 0) */
+  int32_t channels;                /* 0 -> 1; 1 = grey bytes, 4 = RGBA */
+  int32_t pad[2];
+} dslam_stereo_params; /* 32 bytes */
+typedef struct {
+  float focal_length_px;
+  float baseline_m;
+  float scale;
+  float min_depth_m;
+  float max_depth_m;
+} dslam_stereo_calib; /* 20 bytes */
+int dslam_stereo_create(dslam_engine *e, int width, int height, const dslam_stereo_params *params /* NULL: defaults */,
+                        dslam_stereo **out);
+int dslam_stereo_destroy(dslam_stereo *st);
+int dslam_stereo_get_params(const dslam_stereo *st, dslam_stereo_params *params_out);
+/* The disparity of the LEFT image in 1/16 pixel.  Four launches and two memsets: the census of both images, the aggregation of
+ * all eight directions, the selection, the left-right check. */
+int dslam_stereo_match(dslam_engine *e, dslam_stereo *st, const uint8_t *left_host, const uint8_t *right_host, uint16_t *disp_out_host);
+int dslam_stereo_match_device(dslam_engine *e, dslam_stereo *st, const void *left_dev, const void *right_dev, void *disp_out_dev);
+int dslam_disparity_to_depth(dslam_engine *e, dslam_stereo *st, const uint16_t *disp_host, const dslam_stereo_calib *calib,
+                             int16_t *depth_mm_out_host);
+int dslam_disparity_to_depth_device(dslam_engine *e, dslam_stereo *st, const void *disp_dev, const dslam_stereo_calib *calib,
+                                    void *depth_mm_out_dev);
+/* The match and the conversion without leaving the device (the conversion runs inside the last launch of the match). */
+int dslam_stereo_depth(dslam_engine *e, dslam_stereo *st, const uint8_t *left_host, const uint8_t *right_host,
+                       const dslam_stereo_calib *calib, int16_t *depth_mm_out_host, uint16_t *disp_out_host /* or NULL */);
+int dslam_stereo_depth_device(dslam_engine *e, dslam_stereo *st, const void *left_dev, const void *right_dev,
+                              const dslam_stereo_calib *calib, void *depth_mm_out_dev, void *disp_out_dev /* or NULL */);
+/* Test hooks.  download: one intermediate result of the most recent match to the host -- DSLAM_STEREO_CENSUS_LEFT / _RIGHT
+ * uint64 [H][W], DSLAM_STEREO_S uint16 [H][W][D].  select: selection, left-right check and sub-pixel step on the caller's
+ * S (uint16 [H][W][D]; it replaces the handle's).  phases (bench hook): enable >= 0 switches the handle's phase events on
+ * or off; out_ms [5] (or NULL): census, aggregation (with its memset), selection, left-right check (with the conversion),
+ * stand-alone conversion of the most recent call in ms, -1 where a phase did not run. */
+int dslam_debug_stereo_download(dslam_engine *e, dslam_stereo *st, int what, void *out_host);
+int dslam_debug_stereo_select(dslam_engine *e, dslam_stereo *st, const uint16_t *S_host, uint16_t *disp_out_host);
+int dslam_debug_stereo_phases(dslam_engine *e, dslam_stereo *st, int enable, float out_ms[5]);
+
 /* ---- fern keyframe index: which stored keyframe does this frame look like? ------------------
  * Upstream's relocaliser (FernRelocLib: randomised ferns over a thumbnail of the frame, Glocker et al.) with the codes of
  * all keyframes in HBM.  The reference ships the submodule empty, so the law is this project's own; it is all-integer, so
