@@ -22,7 +22,11 @@ from ._capi import (BLOCK_SIZE3, HASH_ENTRY_DTYPE, IMAGE_COLOUR_FROM_NORMAL, IMA
                     CELL_OBSERVED, CELL_OCCUPIED, DIST_FAR, DIST_MAX_CELLS, DIST_METRES, DIST_SQUARED_CELLS, GRID_DTYPE,
                     GRID_MAX_CELL, GRID_MAX_CELLS, GRID_MAX_DIM, SEED_OCCUPIED, SEED_UNKNOWN, Grid,
                     STEREO_CALIB_DTYPE, STEREO_CENSUS_LEFT, STEREO_CENSUS_RIGHT, STEREO_COST_OUT, STEREO_INVALID, STEREO_MAX_P2,
-                    STEREO_MAX_SIZE, STEREO_PARAMS_DTYPE, STEREO_S, StereoCalib, StereoParams)
+                    STEREO_MAX_SIZE, STEREO_PARAMS_DTYPE, STEREO_S, StereoCalib, StereoParams,
+                    SFLOW_CHECKER_BOUND, SFLOW_FEATURE_BYTES, SFLOW_FILTER_DU, SFLOW_FILTER_DV, SFLOW_FILTER_F1, SFLOW_FILTER_F2,
+                    SFLOW_IMAGE_1C, SFLOW_IMAGE_1P, SFLOW_IMAGE_2C, SFLOW_IMAGE_2P, SFLOW_MARGIN, SFLOW_MATCH_WORDS, SFLOW_MAX_BINS,
+                    SFLOW_MAX_COST, SFLOW_MAX_FEATURES, SFLOW_MAX_NMS_N, SFLOW_MAX_SIZE, SFLOW_PARAMS_DTYPE, SFLOW_SOBEL_BOUND,
+                    SflowParams)
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")

@@ -344,6 +344,37 @@ STEREO_CALIB_DTYPE = np.dtype([("focal_length_px", "<f4"), ("baseline_m", "<f4")
 assert C.sizeof(StereoParams) == STEREO_PARAMS_DTYPE.itemsize == 32 and C.sizeof(StereoCalib) == STEREO_CALIB_DTYPE.itemsize == 20
 
 
+# DSLAM_SFLOW_MAX_SIZE, _MAX_NMS_N, _MAX_BINS, _MAX_FEATURES, _MARGIN, _MAX_COST, _SOBEL_BOUND, _CHECKER_BOUND
+SFLOW_MAX_SIZE, SFLOW_MAX_NMS_N, SFLOW_MAX_BINS, SFLOW_MAX_FEATURES, SFLOW_MARGIN, SFLOW_MAX_COST = 4096, 32, 65536, 4194304, 9, 8160
+SFLOW_SOBEL_BOUND, SFLOW_CHECKER_BOUND = 12240, 2040
+SFLOW_FEATURE_BYTES, SFLOW_MATCH_WORDS = 48, 12                                  # DSLAM_SFLOW_FEATURE_BYTES, _MATCH_WORDS
+SFLOW_IMAGE_1C, SFLOW_IMAGE_2C, SFLOW_IMAGE_1P, SFLOW_IMAGE_2P = 0, 1, 2, 3      # DSLAM_SFLOW_IMAGE_*
+SFLOW_FILTER_DU, SFLOW_FILTER_DV, SFLOW_FILTER_F1, SFLOW_FILTER_F2 = 0, 1, 2, 3  # DSLAM_SFLOW_FILTER_*
+
+
+class SflowParams(C.Structure):
+    """dslam_sflow_params in the header's encoding: a field left at 0 selects its default; half_resolution -1 = off.
+    effective(): what the law takes (half_resolution 0 = off)."""
+    _fields_ = [("nms_n", C.c_int32), ("nms_tau", C.c_int32), ("match_binsize", C.c_int32), ("match_radius", C.c_int32),
+                ("match_disp_tolerance", C.c_int32), ("half_resolution", C.c_int32), ("channels", C.c_int32), ("pad", C.c_int32)]
+
+    def __init__(self, nms_n=0, nms_tau=0, match_binsize=0, match_radius=0, match_disp_tolerance=0, half_resolution=0, channels=0):
+        super().__init__(nms_n, nms_tau, match_binsize, match_radius, match_disp_tolerance, half_resolution, channels)
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+    def effective(self):
+        d = self.as_dict()
+        d["half_resolution"] = max(d["half_resolution"], 0)
+        return d
+
+
+SFLOW_PARAMS_DTYPE = np.dtype([("nms_n", "<i4"), ("nms_tau", "<i4"), ("match_binsize", "<i4"), ("match_radius", "<i4"),
+                               ("match_disp_tolerance", "<i4"), ("half_resolution", "<i4"), ("channels", "<i4"), ("pad", "<i4")])
+assert C.sizeof(SflowParams) == SFLOW_PARAMS_DTYPE.itemsize == 32
+
+
 class MergeParams(C.Structure):
     """dslam_merge_params; max_passes = 0 selects its default."""
     _fields_ = [("max_passes", C.c_int32), ("with_colour", C.c_int32)]
@@ -472,6 +503,10 @@ class FernIndex(_Handle):
 
 
 class Stereo(_Handle):
+    pass
+
+
+class Sflow(_Handle):
     pass
 
 
@@ -1382,6 +1417,78 @@ class CApi:
         """dslam_debug_stereo_phases (bench hook): [census, aggregation, selection, left-right check, conversion alone] in ms."""
         ms = (C.c_float * 5)()
         self._call("debug_stereo_phases", self._engine, st.ptr, C.c_int(enable), ms if read else None)
+        return list(ms)
+
+    # -- sparse stereo scene flow ----------------------------------------------------------------------
+    def create_sflow(self, width, height, params=None):
+        """dslam_sflow_create: a scene-flow matcher for frames of width x height; .params: its SflowParams, defaults filled in."""
+        h = C.c_void_p()
+        self._call("sflow_create", self._engine, C.c_int(width), C.c_int(height), C.byref(params) if params is not None else None,
+                   C.byref(h))
+        sf = Sflow(self, h, self._fn("sflow_destroy"))
+        sf.width, sf.height, sf.params = width, height, self.sflow_get_params(sf)
+        sf.channels, sf.scale = sf.params.channels, 2 if sf.params.half_resolution == 1 else 1
+        return sf
+
+    def sflow_get_params(self, sf):
+        p = SflowParams()
+        self._call("sflow_get_params", sf.ptr, C.byref(p))
+        return p
+
+    @staticmethod
+    def _sflow_image(sf, img):
+        if img is None:
+            return None
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        assert img.size == sf.width * sf.height * sf.channels
+        return img
+
+    def sflow_push(self, sf, left, right=None, replace=False):
+        """dslam_sflow_push: a new current frame (right may be None); replace overwrites the current frame instead of rotating."""
+        left, right = self._sflow_image(sf, left), self._sflow_image(sf, right)
+        self._call("sflow_push", self._engine, sf.ptr, _vptr(left), _vptr(right), C.c_int(int(replace)))
+
+    def sflow_push_device(self, sf, left_dev_ptr, right_dev_ptr=None, replace=False):
+        self._call("sflow_push_device", self._engine, sf.ptr, C.c_void_p(left_dev_ptr), C.c_void_p(right_dev_ptr or None),
+                   C.c_int(int(replace)))
+
+    def sflow_match(self, sf, method, which=0, capacity=None, out=None):
+        """dslam_sflow_match: (records int32 [min(count, capacity), 12], count).  capacity None: room for every match."""
+        if capacity is None:
+            count = C.c_int32(0)
+            self._call("sflow_match", self._engine, sf.ptr, C.c_int(method), C.c_int(which), None, C.c_int(0), C.byref(count))
+            capacity = count.value
+        out = np.zeros((capacity, SFLOW_MATCH_WORDS), np.int32) if out is None else out
+        count = C.c_int32(0)
+        self._call("sflow_match", self._engine, sf.ptr, C.c_int(method), C.c_int(which), _vptr(out), C.c_int(capacity), C.byref(count))
+        return out[:min(count.value, capacity)], count.value
+
+    def sflow_match_device(self, sf, method, which, out_dev_ptr, capacity, count_dev_ptr):
+        """dslam_sflow_match_device: records and count stay in device memory; enqueues on the engine's stream."""
+        self._call("sflow_match_device", self._engine, sf.ptr, C.c_int(method), C.c_int(which), C.c_void_p(out_dev_ptr),
+                   C.c_int(capacity), C.c_void_p(count_dev_ptr))
+
+    def sflow_features(self, sf, image, which, capacity=None):
+        """dslam_sflow_features: the records of one image (SFLOW_IMAGE_*) and set as int32 [n, 12] (12 words = 48 bytes)."""
+        count = C.c_int32(0)
+        if capacity is None:
+            self._call("sflow_features", self._engine, sf.ptr, C.c_int(image), C.c_int(which), None, C.c_int(0), C.byref(count))
+            capacity = count.value
+        out = np.zeros((capacity, SFLOW_FEATURE_BYTES // 4), np.int32)
+        self._call("sflow_features", self._engine, sf.ptr, C.c_int(image), C.c_int(which), _vptr(out), C.c_int(capacity), C.byref(count))
+        return out[:min(count.value, capacity)], count.value
+
+    def debug_sflow_download(self, sf, side, which):
+        """dslam_debug_sflow_download: one filter image (SFLOW_FILTER_*) of the current frame's left (0) or right (1) image."""
+        shape = (sf.height // sf.scale, sf.width // sf.scale)
+        out = np.zeros(shape, np.uint8 if which <= SFLOW_FILTER_DV else np.int16)
+        self._call("debug_sflow_download", self._engine, sf.ptr, C.c_int(side), C.c_int(which), _vptr(out))
+        return out
+
+    def sflow_phases(self, sf, enable=-1, read=True):
+        """dslam_debug_sflow_phases (bench hook): [filters, suppression, compaction, bins, matching, match compaction] in ms."""
+        ms = (C.c_float * 6)()
+        self._call("debug_sflow_phases", self._engine, sf.ptr, C.c_int(enable), ms if read else None)
         return list(ms)
 
     # -- fern keyframe index ---------------------------------------------------------------------------

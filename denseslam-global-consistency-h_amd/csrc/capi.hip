@@ -2600,6 +2600,109 @@ int dslam_debug_stereo_phases(dslam_engine *e, dslam_stereo *st, int enable, flo
   return stereo_phases(e, st, enable, out_ms);
 }
 
+// ---- sparse stereo scene flow ---------------------------------------------------------------------------------------
+namespace {
+
+// what every dslam_sflow_* call on a handle checks first
+int check_sflow(dslam_engine *e, dslam_sflow *sf) {
+  DSLAM_REQUIRE(e && sf, "null argument");
+  DSLAM_REQUIRE(sf->engine == e, "the scene-flow matcher belongs to another engine");
+  return DSLAM_OK;
+}
+
+int sflow_push_call(dslam_engine *e, dslam_sflow *sf, const void *left, const void *right, int replace, bool host) {
+  flush_deferred(e);
+  DSLAM_TRY(check_sflow(e, sf));
+  DSLAM_REQUIRE(left, "null argument");
+  if (!host) DSLAM_REQUIRE(((uintptr_t)left & 15) == 0 && ((uintptr_t)right & 15) == 0, "device arrays must be 16-byte aligned");
+  DSLAM_TRY(launch_sflow_push(e, sf, SflowPush{left, right, replace != 0, host}));
+  return host ? sync_check(e) : finish_call(e);
+}
+
+int sflow_match_call(dslam_engine *e, dslam_sflow *sf, int method, int set, void *out, int capacity, void *count, bool host) {
+  flush_deferred(e);
+  DSLAM_TRY(check_sflow(e, sf));
+  DSLAM_REQUIRE(count && (out || capacity == 0), "null argument");
+  DSLAM_REQUIRE(method >= 0 && method <= 2 && (set == 0 || set == 1), "method must be 0, 1 or 2 and set 0 or 1");
+  DSLAM_REQUIRE(capacity >= 0, "capacity must not be negative");
+  if (!host) DSLAM_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)count & 15) == 0, "device arrays must be 16-byte aligned");
+  DSLAM_TRY(launch_sflow_match(e, sf, SflowMatch{method, set, out, count, capacity, host}));
+  return host ? sync_check(e) : finish_call(e);
+}
+
+}  // namespace
+
+int dslam_sflow_create(dslam_engine *e, int width, int height, const dslam_sflow_params *params, dslam_sflow **out) {
+  flush_deferred(e);
+  DSLAM_REQUIRE(e && out, "null argument");
+  std::unique_ptr<dslam_sflow> sf(new dslam_sflow());
+  DSLAM_TRY(sflow_resolve_params(params, width, height, sf.get()));
+  sf->engine = e;
+  DSLAM_TRY(sflow_allocate(e, sf.get()));
+  engine_adopt(e);   // (only a complete matcher is a handle)
+  *out = sf.release();
+  return DSLAM_OK;
+}
+
+int dslam_sflow_destroy(dslam_sflow *sf) {
+  if (!sf) return DSLAM_OK;
+  (void)hipSetDevice(sf->engine->device);
+  flush_deferred(sf->engine);
+  (void)hipStreamSynchronize(sf->engine->stream);
+  dslam_engine *e = sf->engine;
+  delete sf;
+  engine_release(e);
+  return DSLAM_OK;
+}
+
+int dslam_sflow_get_params(const dslam_sflow *sf, dslam_sflow_params *params_out) {
+  DSLAM_REQUIRE(sf && params_out, "null argument");
+  *params_out = sf->p;
+  return DSLAM_OK;
+}
+
+int dslam_sflow_push(dslam_engine *e, dslam_sflow *sf, const uint8_t *left_host, const uint8_t *right_host, int replace) {
+  return sflow_push_call(e, sf, left_host, right_host, replace, true);
+}
+
+int dslam_sflow_push_device(dslam_engine *e, dslam_sflow *sf, const void *left_dev, const void *right_dev, int replace) {
+  return sflow_push_call(e, sf, left_dev, right_dev, replace, false);
+}
+
+int dslam_sflow_match(dslam_engine *e, dslam_sflow *sf, int method, int set, int32_t *out_host, int capacity, int32_t *count_out) {
+  return sflow_match_call(e, sf, method, set, out_host, capacity, count_out, true);
+}
+
+int dslam_sflow_match_device(dslam_engine *e, dslam_sflow *sf, int method, int set, void *out_dev, int capacity, void *count_dev) {
+  return sflow_match_call(e, sf, method, set, out_dev, capacity, count_dev, false);
+}
+
+int dslam_sflow_features(dslam_engine *e, dslam_sflow *sf, int image, int set, void *out_host, int capacity, int32_t *count_out) {
+  flush_deferred(e);
+  DSLAM_TRY(check_sflow(e, sf));
+  DSLAM_REQUIRE(count_out && (out_host || capacity == 0), "null argument");
+  DSLAM_REQUIRE(image >= DSLAM_SFLOW_IMAGE_1C && image <= DSLAM_SFLOW_IMAGE_2P && (set == 0 || set == 1), "unknown image or set");
+  DSLAM_REQUIRE(capacity >= 0, "capacity must not be negative");
+  DSLAM_TRY(sflow_features(e, sf, image, set, out_host, capacity, count_out));
+  return sync_check(e);
+}
+
+int dslam_debug_sflow_download(dslam_engine *e, dslam_sflow *sf, int side, int filter, void *out_host) {
+  flush_deferred(e);
+  DSLAM_TRY(check_sflow(e, sf));
+  DSLAM_REQUIRE(out_host, "null argument");
+  DSLAM_REQUIRE((side == 0 || side == 1) && filter >= DSLAM_SFLOW_FILTER_DU && filter <= DSLAM_SFLOW_FILTER_F2, "unknown side or filter");
+  DSLAM_REQUIRE(sf->pushes > 0, "the scene-flow matcher has not been given a frame yet");
+  DSLAM_TRY(sflow_download(e, sf, side, filter, out_host));
+  return sync_check(e);
+}
+
+int dslam_debug_sflow_phases(dslam_engine *e, dslam_sflow *sf, int enable, float out_ms[6]) {
+  flush_deferred(e);
+  DSLAM_TRY(check_sflow(e, sf));
+  return sflow_phases(e, sf, enable, out_ms);
+}
+
 // ---- fern keyframe index --------------------------------------------------------------------------------------------
 namespace {
 

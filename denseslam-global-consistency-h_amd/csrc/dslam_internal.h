@@ -648,7 +648,49 @@ struct StereoCall {
   bool host;
 };
 
+// The sparse scene-flow matcher (sflow.hip).  A "list" is one feature set: l = (slot * 2 + side) * 2 +
+// set, slot one of the two frames of the ring, side 0 left / 1 right, set 0 sparse / 1 dense.  Every list has its worst-case
+// capacity (4 features per cell) from creation, so nothing can overflow.  The buffers exist whole or not at all.
+struct SflowBuffers {
+  DeviceBuffer<unsigned char> images;        // [2][H W channels]: where the host form's images land
+  DeviceBuffer<unsigned char> sobel;         // [2 sides][du, dv][h w] of the current frame
+  DeviceBuffer<short> corner;                // [2 sides][f1, f2][h w]
+  DeviceBuffer<int4> cell_feat;              // [2 sides][2 sets][cells of the dense set]: u | v << 16 per class, -1 = none
+  DeviceBuffer<int> cell_count, cell_offset; // the same shape: accepted extrema per cell and their exclusive scan
+  DeviceBuffer<int4> feats;                  // [8 lists][capacity of the set][3]: the 48-byte records
+  DeviceBuffer<int> counts;                  // [8 lists] (+ pad): features per list
+  DeviceBuffer<int> bin_fill, bin_start;     // [8 lists][bins], [8 lists][bins + 1]
+  DeviceBuffer<unsigned long long> bin_list; // [8 lists][capacity]: (u_bin VB + v_bin) << 32 | index, grouped by bin
+  DeviceBuffer<int4> stage, packed;          // [dense capacity][3]: a match per driving feature; the matches compacted
+  DeviceBuffer<int> flags, keep, match_offset;   // [dense capacity]
+  DeviceBuffer<int> match_count;             // [4]: the count of the most recent match (16-byte aligned)
+};
+struct DSLAM_INTERNAL dslam_sflow : SflowBuffers {
+  dslam_engine *engine = nullptr;
+  int w = 0, h = 0;                          // the caller's image size
+  dslam_sflow_params p{};                    // as dslam_sflow_get_params gives it
+  int s = 1, mw = 0, mh = 0;                 // scale, matching image size
+  int n[2] = {0, 0}, cx[2] = {0, 0}, cy[2] = {0, 0}, cap[2] = {0, 0};   // per set: nms distance, cells along x / y, capacity
+  int tau = 0, binsize = 0, radius = 0, vtol = 0, channels = 0, ub = 0, vb = 0;
+  int cur = 0, pushes = 0;                   // the ring: slot of the current frame; pushes so far
+  bool timing = false;
+  Event events[8];                           // push: 0 .. 4, match: 5 .. 7
+  int recorded = 0;
+};
+struct SflowPush { const void *left, *right; bool replace, host; };
+struct SflowMatch { int method, set; void *out, *count; int capacity; bool host; };
+
 namespace dslam {
+// dslam_sflow_* (sflow.hip); everything already checked by the entry points (capi.hip).  The launches enqueue only; the host
+// forms of match / features wait for the stream themselves because the number of records to copy is a device result.
+int sflow_resolve_params(const dslam_sflow_params *params, int width, int height, dslam_sflow *sf);
+int sflow_allocate(dslam_engine *e, dslam_sflow *sf);
+int launch_sflow_push(dslam_engine *e, dslam_sflow *sf, const SflowPush &c);
+int launch_sflow_match(dslam_engine *e, dslam_sflow *sf, const SflowMatch &c);
+int sflow_features(dslam_engine *e, dslam_sflow *sf, int image, int set, void *out_host, int capacity, int32_t *count_out);
+int sflow_download(dslam_engine *e, dslam_sflow *sf, int side, int filter, void *out_host);
+int sflow_phases(dslam_engine *e, dslam_sflow *sf, int enable, float *ms_out);
+
 // dslam_stereo_* (stereo.hip); stereo_resolve_params fills st->p and the kernels' values from a caller's block (or NULL).
 // launch_stereo enqueues only (the host forms' copies included).
 int stereo_resolve_params(const dslam_stereo_params *params, dslam_stereo *st);

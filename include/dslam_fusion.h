@@ -1061,6 +1061,122 @@ int dslam_debug_stereo_download(dslam_engine *e, dslam_stereo *st, int what, voi
 int dslam_debug_stereo_select(dslam_engine *e, dslam_stereo *st, const uint16_t *S_host, uint16_t *disp_out_host);
 int dslam_debug_stereo_phases(dslam_engine *e, dslam_stereo *st, int enable, float out_ms[5]);
 
+/* ---- sparse stereo scene flow: feature matches over a stereo pair and over time -------------
+ * What libviso2's Matcher returns from getRawMatches() after two pushBack calls and matchFeatures(method) without a motion
+ * prior: the first matching pass, with no prior, refinement or outlier removal.  The law is all-integer, so the device gives
+ * the same bytes as tests/ref_sflow.py, and both are held to that library's own output (tests/golden/sflow_*.npz).
+ * A handle is made for one image size W x H and one parameter block and keeps two frames: the current one (1c left, 2c
+ * right) and the previous one (1p, 2p).  s = 2 and (w, h) = (W / 2, H / 2) with half_resolution, else s = 1, (w, h) = (W, H).
+ *   grey        channels == 1: the byte as it is; channels == 4 (RGBA): (r + 2 g + b) >> 2.  With half_resolution the
+ *               matching image is m(y, x) = (g(2y, 2x) + g(2y, 2x + 1) + g(2y + 1, 2x) + g(2y + 1, 2x + 1)) >> 2.
+ *   filters     four images of m, stated on the interior 2 <= x <= w - 3, 2 <= y <= h - 3 and 0 outside it.  (The
+ *               reference pads rows to 16 and lets its row passes run across row ends, which only reaches pixels outside
+ *               this interior, and nothing below reads those: the cells and their neighbourhoods stay inside 9 .. w - 10,
+ *               and a descriptor tap is at most 5 from its feature, so every read is inside 4 .. w - 5, rows alike.)
+ *               With column sums over dy = -2 .. 2 and row sums over dx = -2 .. 2 of the weights given:
+ *                 du = sat8(((rows (1, 2, 0, -2, -1) of cols (1, 4, 6, 4, 1)) >> 7) + 128)      left minus right
+ *                 dv = sat8(((rows (1, 4, 6, 4, 1) of cols (1, 2, 0, -2, -1)) >> 7) + 128)      top minus bottom
+ *                 f1 = - (sum of the 5 x 5 window) + 2 (sum of the 3 x 3 window) + 7 m(y, x)     the blob
+ *                 f2 = rows (1, 1, 0, -1, -1) of cols (1, 1, 0, -1, -1)                          the checkerboard
+ *               >> is arithmetic, sat8 clamps to 0 .. 255; du, dv are uint8, f1, f2 int16.  (The reference forms f1 from
+ *               an integral image of inclusive sums; read that way, what it stores at (y, x) is the window y - 2 .. y + 2,
+ *               x - 2 .. x + 2: centred, with no displacement, and the golden files confirm it.)  No intermediate leaves int16, so the reference's wrapping 16-bit
+ *               adds never wrap: a (1, 4, 6, 4, 1) sum is at most 16 * 255 = 4080 and the (1, 2, 0, -2, -1) row of it at
+ *               most 3 * 4080 = 12240 in magnitude (DSLAM_SFLOW_SOBEL_BOUND); a (1, 2, 0, -2, -1) sum is at most 765 and
+ *               its (1, 4, 6, 4, 1) row 16 * 765 = 12240; |f1| <= 16 * 255 = 4080; a (1, 1, 0, -1, -1) sum is at most 510
+ *               and f2 at most 4 * 510 = 2040 (DSLAM_SFLOW_CHECKER_BOUND).
+ *   features    non-maximum suppression with distance n over cells of (n + 1)^2 pixels.  Cell (a, b) starts at
+ *               (i, j) = (n + 9 + a (n + 1), n + 9 + b (n + 1)) and exists while i < w - n - 9 and j < h - n - 9; cells
+ *               are taken with the COLUMN index a outermost.  In a cell the minimum and the maximum of f1 and of f2 are
+ *               found scanning x outer, y inner, with strict comparisons: of equal values the first met wins.  An
+ *               extremum at (u, v) with value e fails if any pixel of u - n .. min(u + n, w - 10), v - n .. min(v + n,
+ *               h - 10) is strictly better (the lower bounds are not clamped and need not be: u - n >= 9); it is
+ *               accepted if e <= -nms_tau (minimum) or e >= nms_tau (maximum).  A cell gives up to four features, in
+ *               class order 0 f1 minimum, 1 f1 maximum, 2 f2 minimum, 3 f2 maximum.  Every image has two sets: set 0
+ *               (sparse) with n = 3 nms_n, replaced by max(nms_n, 10) where that exceeds 10; set 1 (dense) with n = nms_n.
+ *   record      a feature is 48 bytes: int32 u s, v s, 0, class, then 32 descriptor bytes: for the 16 taps (dx, dy) =
+ *               (-3,-1) (-3,1) (-1,-1) (-1,1) (3,-1) (3,1) (1,-1) (1,1) (-1,-5) (-1,5) (1,-5) (1,5) (-5,-3) (-5,3) (5,-3)
+ *               (5,3) in this order du(v + dy, u + dx) then dv(v + dy, u + dx).
+ *   bins        coordinates of records are full-resolution.  UB = ceil(W / match_binsize), VB = ceil(H / match_binsize);
+ *               a feature lies in bin (min(u / match_binsize, UB - 1), min(v / match_binsize, VB - 1)) of its class, with
+ *               integer division.  (The reference takes floor of a float quotient.  The quotient of an integer below 2^24
+ *               by match_binsize is an integer or at least 1 / match_binsize away from one, and the float rounding error
+ *               is below that, so both floors agree.)
+ *   find        the partner of a feature q in another set T: the candidates are the features of T of q's class with
+ *               |u - uq| <= R and |v - vq| <= R (a flow leg) or <= match_disp_tolerance (a stereo leg), R = match_radius,
+ *               halved by integer division with half_resolution.  The cost is the sum of absolute differences of the 32
+ *               descriptor bytes (at most DSLAM_SFLOW_MAX_COST = 8160).  The smallest cost wins; of equal costs the
+ *               candidate met first when the bins that the window touches (clamped to the grid) are visited bin column
+ *               outermost, then bin row, then ascending feature index.  NO candidate gives feature 0 of T: a circle can
+ *               close through feature 0, and does so here as in the reference.
+ *   methods     2 (quad): for every i1p in order 1p -> 2p (stereo) -> 2c (flow) -> 1c (stereo) -> 1p (flow); kept if the
+ *               last leg returns i1p, u1p >= u2p and u1c >= u2c.  1 (stereo): 1c -> 2c -> 1c, kept if it returns and
+ *               u1c >= u2c.  0 (flow): 1c -> 1p -> 1c.  For methods 0 and 1 only the first kept feature, in index order,
+ *               of those on one current-left pixel stays.  If a set the method needs is empty there are no matches; set 0
+ *               also needs the dense sets of the same images non-empty, as the reference checks them before its first
+ *               pass.  A match is int32[12]: u1p, v1p, i1p, u2p, v2p, i2p, u1c, v1c, i1c, u2c, v2c, i2c; the fields a
+ *               method does not fill hold -1.  Matches are in ascending order of the driving feature's index.
+ * Parameter encoding (dslam_sflow_params, all int32): a field left at 0 selects its default; half_resolution has a
+ * meaningful 0, so -1 means off.  dslam_sflow_get_params returns the block with no field left at 0.  pad must be 0.
+ * Images are dense rows, uint8 [H][W][channels].  push is Matcher::pushBack: the current frame becomes the previous one
+ * (or, with replace != 0, is overwritten) and the features and bin lists of the new one are built at once; right may be NULL
+ * (monocular flow: the right sets of that frame are empty).  The host forms stage through buffers of the handle and wait
+ * for the stream; the _device forms take device addresses (16-byte aligned) and enqueue on the engine's stream: match_device
+ * writes min(count, capacity) records to out_dev and the full count to count_dev (one int32) without a host round trip.
+ * count is the full number also where capacity is smaller.  A handle may be destroyed before or after its engine.
+ * DSLAM_ERR_INVALID with nothing enqueued and nothing written: a NULL argument other than params / right; a handle of another
+ * engine; W or H outside s .. DSLAM_SFLOW_MAX_SIZE; nms_n outside 1 .. DSLAM_SFLOW_MAX_NMS_N; nms_tau, match_binsize,
+ * match_radius or match_disp_tolerance below 1 (after defaults); more than DSLAM_SFLOW_MAX_BINS bin lists or
+ * DSLAM_SFLOW_MAX_FEATURES possible dense features; half_resolution other than 0, 1, -1; channels other than 1 or 4; a
+ * non-zero pad; a method, set, image or filter id that does not exist; a negative capacity; a misaligned device address; a
+ * debug download before the first push. */
+#define DSLAM_SFLOW_MAX_SIZE 4096
+#define DSLAM_SFLOW_MAX_NMS_N 32
+#define DSLAM_SFLOW_MAX_BINS 65536
+#define DSLAM_SFLOW_MAX_FEATURES 4194304
+#define DSLAM_SFLOW_MARGIN 9
+#define DSLAM_SFLOW_MAX_COST 8160
+#define DSLAM_SFLOW_SOBEL_BOUND 12240
+#define DSLAM_SFLOW_CHECKER_BOUND 2040
+#define DSLAM_SFLOW_FEATURE_BYTES 48
+#define DSLAM_SFLOW_MATCH_WORDS 12
+#define DSLAM_SFLOW_IMAGE_1C 0
+#define DSLAM_SFLOW_IMAGE_2C 1
+#define DSLAM_SFLOW_IMAGE_1P 2
+#define DSLAM_SFLOW_IMAGE_2P 3
+#define DSLAM_SFLOW_FILTER_DU 0
+#define DSLAM_SFLOW_FILTER_DV 1
+#define DSLAM_SFLOW_FILTER_F1 2
+#define DSLAM_SFLOW_FILTER_F2 3
+typedef struct dslam_sflow dslam_sflow;
+typedef struct {
+  int32_t nms_n;                   /* 0 -> 3; 1 .. 32 */
+  int32_t nms_tau;                 /* 0 -> 50; >= 1 */
+  int32_t match_binsize;           /* 0 -> 50; >= 1 */
+  int32_t match_radius;            /* 0 -> 200; >= 1 */
+  int32_t match_disp_tolerance;    /* 0 -> 2; >= 1 */
+  int32_t half_resolution;         /* 0 -> 1; 1 = on, -1 = off */
+  int32_t channels;                /* 0 -> 1; 1 = grey bytes, 4 = RGBA */
+  int32_t pad;
+} dslam_sflow_params; /* 32 bytes */
+int dslam_sflow_create(dslam_engine *e, int width, int height, const dslam_sflow_params *params /* NULL: defaults */,
+                       dslam_sflow **out);
+int dslam_sflow_destroy(dslam_sflow *sf);
+int dslam_sflow_get_params(const dslam_sflow *sf, dslam_sflow_params *params_out);
+int dslam_sflow_push(dslam_engine *e, dslam_sflow *sf, const uint8_t *left_host, const uint8_t *right_host /* or NULL */, int replace);
+int dslam_sflow_push_device(dslam_engine *e, dslam_sflow *sf, const void *left_dev, const void *right_dev /* or NULL */, int replace);
+/* method 0 flow, 1 stereo, 2 quad; set 0 sparse (getRawMatches), 1 dense matched the same way.  out: int32 [capacity][12]. */
+int dslam_sflow_match(dslam_engine *e, dslam_sflow *sf, int method, int set, int32_t *out_host, int capacity, int32_t *count_out);
+int dslam_sflow_match_device(dslam_engine *e, dslam_sflow *sf, int method, int set, void *out_dev, int capacity, void *count_dev);
+/* the feature records of one image (DSLAM_SFLOW_IMAGE_*) and set: [capacity][48] bytes */
+int dslam_sflow_features(dslam_engine *e, dslam_sflow *sf, int image, int set, void *out_host, int capacity, int32_t *count_out);
+/* Test hooks.  download: one filter image (DSLAM_SFLOW_FILTER_*: du, dv uint8 [h][w]; f1, f2 int16 [h][w]) of the current
+ * frame's left (side 0) or right (side 1) image.  phases (bench hook): enable >= 0 switches the handle's phase events on or
+ * off; out_ms [6] (or NULL): filters, suppression, feature compaction, bin lists of the most recent push and matching, match
+ * compaction of the most recent match in ms, -1 where a phase did not run. */
+int dslam_debug_sflow_download(dslam_engine *e, dslam_sflow *sf, int side, int filter, void *out_host);
+int dslam_debug_sflow_phases(dslam_engine *e, dslam_sflow *sf, int enable, float out_ms[6]);
+
 /* ---- fern keyframe index: which stored keyframe does this frame look like? ------------------
  * Upstream's relocaliser (FernRelocLib: randomised ferns over a thumbnail of the frame, Glocker et al.) with the codes of
  * all keyframes in HBM.  The reference ships the submodule empty, so the law is this project's own; it is all-integer, so
